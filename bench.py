@@ -23,6 +23,11 @@ log_amd.dist.GradientBucket.reduce_scatter_rows_sparse + the sparse all-gather; 
 resident in HBM before the timed region; the timed region contains no host synchronisation (tile-instance capacity
 comes from the warm-up; every forward records itself in the rasterizer's status block, checked afterwards).
 
+A plain run sets up, warms up, times --steps steps and prints the line (value, ms_per_step, the headline's config); every
+other figure described below -- the modes besides `pipelined`, roofline and per-kernel tables, measured roofs, forward_only,
+cpu_baseline, secondary, the one-rank RCCL leg, the exchange-only timing and hint check (N > 1), parity -- is measured with
+--full only.  --dump-outputs DIR: what the last timed step computed (step_outputs()) as DIR/<name>.npy.
+
 The LAST stdout line of rank 0 is the compact contract object (< 4 KB: compact_line()); the FULL result described below goes
 to bench_full.json next to this file (and gpurun_out/bench_full.json; --print-full: also an earlier stdout line):
   value        : the pipelined mode above (what a multi-view training step of this framework runs);
@@ -70,6 +75,14 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: per-kernel timing and roofline, measured copy roofs, the drop-in "
+                         "default mode, CPU baseline, forward-only, opacity = rand and trained-like variants, the C2 / C3 / "
+                         "C5 legs, the one-rank RCCL leg, the exchange-only timing and the hinted-pack check (N > 1), the "
+                         "parity summary.  Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32; fixed, "
+                         "seeded samples of the images, radii and summed gradients: step_outputs())")
     ap.add_argument("--gaussians", type=int, default=30_000_000)
     ap.add_argument("--views", type=int, default=8, help="views per GPU per step")
     ap.add_argument("--width", type=int, default=1920)
@@ -184,7 +197,7 @@ def one_rank_rccl_leg(args, N):
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--gaussians", str(N), "--width", str(args.width),
            "--height", str(args.height), "--views", str(args.views), "--steps", "5", "--warmup", "2", "--no-cpu-baseline",
            "--no-dropin-mode", "--no-secondary", "--no-forward-only", "--no-rand-variant", "--no-trained-like",
-           "--no-one-rank-leg", "--full-out", path]
+           "--no-one-rank-leg", "--full", "--full-out", path]
     try:
         env = dict(os.environ, LOGRAST_DIST_SINGLE_RANK="1", HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
         for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR"):
@@ -260,6 +273,7 @@ class RasterWorkload:
         self.zero_means2d = True
         self.last_radii = None
         self.last_weight = None
+        self.keep = None          # dict: index of the view -> (image, radii) of its latest rendering (--dump-outputs)
 
     def one_view(self, rast, leaves):
         torch = self.torch
@@ -275,13 +289,18 @@ class RasterWorkload:
         out[0].backward(gradient=self.wloss)
         self.last_radii = out[1]
         self.last_weight = out[4] if len(out) > 4 else None     # point_weight: zero exactly where the view touched nothing
+        if self.keep is not None:
+            # (held, so that a captured graph's later captures do not reuse the memory: every replay rewrites it in place)
+            self.keep[self.rasts.index(rast)] = (out[0], out[1])
         return out
 
 
-def measure(args, wl, S, fused, steps, warmup, world, timing, sync_free=True, graphs=False):
+def measure(args, wl, S, fused, steps, warmup, world, timing, sync_free=True, graphs=False, extras=True, dump=None):
     """Times `steps` steps of workload `wl` with S views in flight.  sync_free=False + S=1 + fused=False is the drop-in
     default mode.  graphs: every view (forward + backward, a fixed sequence of ~15 launches once the capacity is fixed)
     is captured into one HIP graph per (stream, camera) after the warm-up and replayed in the timed region.
+    extras (N > 1): after the timed region, also time the exchange alone and check the hinted pack (--full).
+    dump: a dict that receives step_outputs() of the last timed step (wl.keep must be a dict).
     -> dict(elapsed, t_enqueued, V, I, I_rect, prof_timed, prof_serial, bucket_floats, graphs)."""
     import numpy as np
     import torch
@@ -557,6 +576,9 @@ def measure(args, wl, S, fused, steps, warmup, world, timing, sync_free=True, gr
         dist.barrier()
     torch.cuda.synchronize()
     res["elapsed"] = time.perf_counter() - t0
+    if dump is not None and rank == 0:
+        streamed = bool(sparse["on"] and n_parts() > 1)
+        dump.update(step_outputs(wl, ex.buckets[0], gathered["t"] if streamed else None))
     res["prof_timed"] = res["prof_serial"] = None
     if timing:
         if kernel_timing:
@@ -581,52 +603,53 @@ def measure(args, wl, S, fused, steps, warmup, world, timing, sync_free=True, gr
         # The same collectives with nothing to hide under: link time alone, so that a first run on real xGMI separates what
         # the links cost from what the overlap lost (exposed = ms_per_step - rendering; hidden = exchange_only - exposed).
         assert not on_any_rank(ex.compact_overflowed()), "touched-block / row-sparse exchange outgrew its bound inside the timed region: result invalid"
-        xsteps, tsum = 3, 0.0
-        for _ in range(xsteps):
-            step(do_exchange=False)                     # (the rank's own sums again: the exchange leaves the total in bucket 0)
-            torch.cuda.synchronize()
+        if extras:
+            xsteps, tsum = 3, 0.0
+            for _ in range(xsteps):
+                step(do_exchange=False)                     # (the rank's own sums again: the exchange leaves the total in bucket 0)
+                torch.cuda.synchronize()
+                dist.barrier()
+                torch.cuda.synchronize()
+                tx = time.perf_counter()
+                exchange()
+                torch.cuda.synchronize()
+                tsum += time.perf_counter() - tx
             dist.barrier()
-            torch.cuda.synchronize()
-            tx = time.perf_counter()
-            exchange()
-            torch.cuda.synchronize()
-            tsum += time.perf_counter() - tx
-        dist.barrier()
-        txe = torch.tensor([tsum], device=dev, dtype=torch.float64)
-        dist.all_reduce(txe, op=dist.ReduceOp.MAX)
-        res["exchange_only_ms_per_step"] = 1e3 * float(txe.item()) / xsteps
-        if sparse["on"] and n_parts() > 1 and S == 1 and not args.no_pack_hint and gathered["t"] is not None:
-            # self-check of the hinted pack (the views' point_weight tensors live in the graphs' pools): the step's gathered
-            # gradient sum with the hints against the same step with the scanning pack -- the same rows, the same sums up to
-            # the order of the reverse walk's float atomics between two renderings
-            step()
-            torch.cuda.synchronize()
-            with_hint = gathered["t"].clone()
-            args.no_pack_hint = True
-            try:
+            txe = torch.tensor([tsum], device=dev, dtype=torch.float64)
+            dist.all_reduce(txe, op=dist.ReduceOp.MAX)
+            res["exchange_only_ms_per_step"] = 1e3 * float(txe.item()) / xsteps
+            if sparse["on"] and n_parts() > 1 and S == 1 and not args.no_pack_hint and gathered["t"] is not None:
+                # self-check of the hinted pack (the views' point_weight tensors live in the graphs' pools): the step's gathered
+                # gradient sum with the hints against the same step with the scanning pack -- the same rows, the same sums up to
+                # the order of the reverse walk's float atomics between two renderings
                 step()
                 torch.cuda.synchronize()
-            finally:
-                args.no_pack_hint = False
-            scan = gathered["t"]
-            rows_h, rows_s = (with_hint != 0).any(1), (scan != 0).any(1)
-            # asserted on dL/dopacity and dL/dcolour (row slots 10-13: plain sums of the reverse walk); the slots behind the chain
-            # rule are reported only -- on check_gui's uniform scales one needle-shaped Gaussian can carry the tensor's norm and
-            # amplify the reverse walk's summation-order noise to 1e-3 between ANY two renderings (seen: 200 000 Gaussians,
-            # 1.3e-3 in three of five processes with every row present in both; tests/gpu_util.py quantifies that per row)
-            direct = float((with_hint[:, 10:14] - scan[:, 10:14]).norm() / scan[:, 10:14].norm().clamp_min(1e-30))
-            res["exchange_hint_check"] = {
-                "rel_l2": direct, "rel_l2_all_slots": float((with_hint - scan).norm() / scan.norm().clamp_min(1e-30)),
-                "rows_with_hint": int(rows_h.sum()), "rows_scanning": int(rows_s.sum()),
-                "rows_differ": int((rows_h != rows_s).sum())}
-            # (every rank must take the same decision, or the ones that go on hang in the next collective)
-            hc = res["exchange_hint_check"]
-            okf = torch.tensor([1.0 if (hc["rel_l2"] < 1e-4 and hc["rows_with_hint"] > 0
-                                        and hc["rows_differ"] <= 1e-3 * hc["rows_scanning"]) else 0.0], device=dev)
-            dist.all_reduce(okf, op=dist.ReduceOp.MIN)
-            res["exchange_hint_check"]["ok_on_every_rank"] = bool(okf.item() > 0)
-            assert res["exchange_hint_check"]["ok_on_every_rank"], res["exchange_hint_check"]
-            del with_hint, scan
+                with_hint = gathered["t"].clone()
+                args.no_pack_hint = True
+                try:
+                    step()
+                    torch.cuda.synchronize()
+                finally:
+                    args.no_pack_hint = False
+                scan = gathered["t"]
+                rows_h, rows_s = (with_hint != 0).any(1), (scan != 0).any(1)
+                # asserted on dL/dopacity and dL/dcolour (row slots 10-13: plain sums of the reverse walk); the slots behind the chain
+                # rule are reported only -- on check_gui's uniform scales one needle-shaped Gaussian can carry the tensor's norm and
+                # amplify the reverse walk's summation-order noise to 1e-3 between ANY two renderings (seen: 200 000 Gaussians,
+                # 1.3e-3 in three of five processes with every row present in both; tests/gpu_util.py quantifies that per row)
+                direct = float((with_hint[:, 10:14] - scan[:, 10:14]).norm() / scan[:, 10:14].norm().clamp_min(1e-30))
+                res["exchange_hint_check"] = {
+                    "rel_l2": direct, "rel_l2_all_slots": float((with_hint - scan).norm() / scan.norm().clamp_min(1e-30)),
+                    "rows_with_hint": int(rows_h.sum()), "rows_scanning": int(rows_s.sum()),
+                    "rows_differ": int((rows_h != rows_s).sum())}
+                # (every rank must take the same decision, or the ones that go on hang in the next collective)
+                hc = res["exchange_hint_check"]
+                okf = torch.tensor([1.0 if (hc["rel_l2"] < 1e-4 and hc["rows_with_hint"] > 0
+                                            and hc["rows_differ"] <= 1e-3 * hc["rows_scanning"]) else 0.0], device=dev)
+                dist.all_reduce(okf, op=dist.ReduceOp.MIN)
+                res["exchange_hint_check"]["ok_on_every_rank"] = bool(okf.item() > 0)
+                assert res["exchange_hint_check"]["ok_on_every_rank"], res["exchange_hint_check"]
+                del with_hint, scan
         cols = sum(c for _, c in ex.buckets[0].layout) + 1
         frac = 1.0
         if compact["on"] and ex.touched is not None:
@@ -656,6 +679,50 @@ def mode_summary(N, views, world, steps, r):
     return {"ms_per_view": 1e3 * r["elapsed"] / (steps * views), "ms_per_step": 1e3 * r["elapsed"] / steps,
             "value": float(N) * views * world * steps / r["elapsed"],
             "host_enqueue_ms_per_view": 1e3 * r["t_enqueued"] / (steps * views)}
+
+
+DUMP_FLOATS = 4 << 20      # per output group (images, radii, gradients): at most 16 MB each, 48 MB in all
+
+
+def step_outputs(wl, bucket, gathered_rows=None, seed=0):
+    """What a caller of the timed path receives from one step, as float32 numpy arrays: every view's image and radii
+    (wl.keep) and the step's summed gradients (bucket.alias, or the [rows, 16] result of the streamed row-sparse exchange).
+    Larger outputs are represented by fixed samples (indices drawn from `seed`, sorted): the same for every run with the
+    same arguments.
+      images            [views, k]  pixels of the flattened (3, H, W) image, the same k for every view
+      radii             [views, k]  radii of the same k Gaussians for every view
+      grad_<attribute>  [k, c]      dL/d<attribute> summed over the step's views (and ranks), c columns per attribute"""
+    import numpy as np
+    import torch
+    from log_amd.dist import LAYOUT, ROW_COLUMNS
+    rng = np.random.default_rng(seed)
+    views = len(wl.rasts)
+
+    def sample(n, k):
+        idx = np.arange(n) if k >= n else np.sort(rng.choice(n, size=k, replace=False))
+        return torch.from_numpy(idx).to(wl.dev)
+
+    px = 3 * wl.H * wl.W
+    pix = sample(px, max(1, DUMP_FLOATS // views))
+    out = {"images": torch.stack([wl.keep[j][0].detach().reshape(-1)[pix] for j in range(views)]).cpu().numpy()}
+    rad = sample(wl.N, max(1, DUMP_FLOATS // views))
+    out["radii"] = torch.stack([wl.keep[j][1].reshape(-1)[rad] for j in range(views)]).to(torch.float32).cpu().numpy()
+    rows = sample(wl.N, max(1, DUMP_FLOATS // sum(c for _, c in LAYOUT)))
+    for name, _ in LAYOUT:
+        if gathered_rows is not None:
+            a, b = ROW_COLUMNS[name]
+            g = gathered_rows[:wl.N, a:b]
+        else:
+            g = bucket.alias[name]
+        out["grad_" + name] = g[rows].reshape(rows.numel(), -1).to(torch.float32).cpu().numpy()
+    return out
+
+
+def write_outputs(outputs, d):
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def R_forms():
@@ -943,11 +1010,17 @@ def main():
 
     N, W, H = args.gaussians, args.width, args.height
     Px = W * H
-    timing = not args.no_kernel_timing
+    timing = args.full and not args.no_kernel_timing
     fused = not args.no_fused_accumulate
     wl = RasterWorkload(args, N, dev, rank, world, torch, np)
     S = auto_streams(args, N)
-    r = measure(args, wl, S, fused, args.steps, args.warmup, world, timing, graphs=not args.no_graphs)
+    outputs = {} if args.dump_outputs else None
+    wl.keep = {} if args.dump_outputs else None
+    r = measure(args, wl, S, fused, args.steps, args.warmup, world, timing, graphs=not args.no_graphs, extras=args.full,
+                dump=outputs)
+    wl.keep = None
+    if outputs:
+        write_outputs(outputs, args.dump_outputs)
     V, I, I_rect, elapsed = r["V"], r["I"], r["I_rect"], r["elapsed"]
     head = mode_summary(N, args.views, world, args.steps, r)
     op_name = "rand" if args.opacity < 0 else args.opacity
@@ -992,7 +1065,7 @@ def main():
                                         if r.get("exchange_only_ms_per_step") and r.get("exchange_bytes_per_step") else None),
             "rccl_env": {k: os.environ.get(k) for k in ("NCCL_MAX_NCHANNELS", "NCCL_MIN_NCHANNELS", "NCCL_ALGO",
                                                          "NCCL_PROTO", "RCCL_MSCCL_ENABLE") if os.environ.get(k)}}
-    if not args.no_dropin_mode:
+    if args.full and not args.no_dropin_mode:
         # the drop-in default: what LoG's unmodified renderer.py gets -- one stream, the package's default forward (stage 2
         # enqueued speculatively, one read-back per forward that the stream does not wait for), a zero-filled means2D per
         # view, gradients added in place into the leaves' existing .grad
@@ -1007,6 +1080,11 @@ def main():
                  "stream), gradients added in place into the leaves' .grad")
 
     if rank == 0:
+        result["config"]["ms_per_view"] = head["ms_per_view"]
+        if r.get("graphs_error"):
+            result["graphs_error"] = r["graphs_error"]
+    roofs = {}
+    if rank == 0 and args.full:
         best_copy, copy_forms = measured_stream_copy_bandwidth(dev)
         roofs = {"measured_stream_copy": best_copy, "measured_copy": measured_copy_bandwidth(dev)}
         result["measured_stream_copy_GBs"] = roofs["measured_stream_copy"]
@@ -1028,7 +1106,6 @@ def main():
             rf["whole_view"] = whole_view_summary(rep, head["ms_per_view"], best_copy)
             rf["compute_radius"] = compute_radius_leg(wl)
             rf["forms"] = dict(R_forms())
-        result["config"]["ms_per_view"] = head["ms_per_view"]
         for k in ("effective_units_per_view", "algorithmic_bytes_per_view", "algorithmic_bytes_per_view_survey_formula",
                   "algorithmic_GBs_whole_view", "algorithmic_GBs_whole_view_survey_formula",
                   "algorithmic_frac_of_measured_stream_copy", "algorithmic_frac_of_measured_stream_copy_survey_formula",
@@ -1036,18 +1113,14 @@ def main():
                   "algorithmic_frac_of_hbm_peak", "kernels", "roofline", "kernels_timed_region", "roofline_timed_region"):
             if k in rep:
                 result[k] = rep[k]
-        if r.get("graphs_error"):
-            result["graphs_error"] = r["graphs_error"]
         if not args.no_cpu_baseline and world == 1:   # rank 0 at N=1 only: the host cores are shared by all ranks
             result["cpu_baseline"] = cpu_baseline(wl.sc, wl.cams, wl.wloss.cpu().numpy(), N)
-    else:
-        roofs = {}
-    if world == 1 and not args.no_forward_only:
+    if args.full and world == 1 and not args.no_forward_only:
         result["forward_only"] = {"headline": forward_only(args, wl)}
     del wl
     torch.cuda.empty_cache()
 
-    if world == 1 and not args.no_rand_variant and args.opacity >= 0:
+    if args.full and world == 1 and not args.no_rand_variant and args.opacity >= 0:
         # "opacity = 0.999 AND a second run with opacity = rand(N, 1)" -- same harness, same mode
         try:
             args_r = argparse.Namespace(**dict(vars(args), opacity=-1.0))
@@ -1070,7 +1143,7 @@ def main():
             result["modes"]["pipelined_opacity_rand"] = {"error": "%s: %s" % (type(e).__name__, e)}
         torch.cuda.empty_cache()
 
-    if world == 1 and not args.no_trained_like and args.scene == "random":
+    if args.full and world == 1 and not args.no_trained_like and args.scene == "random":
         # Round-4 verdict, missing #4: the same 30 M / 1080p / 8-view step on a scene with the statistics of a TRAINED model
         # (log-normal scales sigma 0.5, anisotropy <= 10, sigmoid-normal opacity; tests/test_gpu_scale.py checks the very
         # same scene against the oracle) -- neither an opaque cube where 93 % of the Gaussians never composite nor uniform
@@ -1095,7 +1168,7 @@ def main():
             result["modes"]["pipelined_trained_like"] = {"error": "%s: %s" % (type(e).__name__, e)}
         torch.cuda.empty_cache()
 
-    if world == 1 and not args.no_secondary:
+    if args.full and world == 1 and not args.no_secondary:
         sec = {}
         try:
             if N != 1_000_000:
@@ -1126,7 +1199,8 @@ def main():
             sec["error"] = "%s: %s" % (type(e).__name__, e)
         result["secondary"] = sec
 
-    if world == 1 and not dist_on(world) and not args.no_one_rank_leg and not args.no_secondary and N >= 1_000_000:
+    if (args.full and world == 1 and not dist_on(world) and not args.no_one_rank_leg and not args.no_secondary
+            and N >= 1_000_000):
         result["multi_gpu_step_one_rank_rccl"] = one_rank_rccl_leg(args, N)
 
     # whatever the libraries left in C stdio buffers (librccl's banner) goes out NOW, on every rank, in front of the line
@@ -1138,7 +1212,8 @@ def main():
     if dist_on(world):
         dist.barrier()
     if rank == 0:
-        result["parity"] = parity_summary()
+        if args.full:
+            result["parity"] = parity_summary()
         flatten_for_the_driver(result)
         emit(result, args)
     if dist_on(world):

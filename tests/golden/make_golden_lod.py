@@ -39,35 +39,94 @@ def reference_env():
     oracle_backend.install(OracleBackend())
 
 
-def build_case(seed, n_roots, n_levels, max_child, split_prob=0.7, remove_prob=0.04, extent=1.0):
-    """A tree grown with the reference's TensorTree, parameters of children derived from their parent."""
+def build_case(seed, n_roots, n_levels, max_child, split_prob=0.7, remove_prob=0.04, extent=1.0, record=None):
+    """A tree grown with the reference's TensorTree, parameters of children derived from their parent.  record (a list):
+    receives the candidate lists the tree handed out, from which replay_case() draws the same parameters."""
     from LoG.model.tensor_tree import TensorTree
-    g = torch.Generator().manual_seed(seed)
     tree = TensorTree(max_child=max_child, max_level=30)
+    return (tree,) + _grow(_Grown(tree, record), seed, n_roots, n_levels, max_child, split_prob, remove_prob, extent)
+
+
+def replay_case(seed, n_roots, n_levels, max_child, cands, split_prob=0.7, remove_prob=0.04, extent=1.0):
+    """The parameters build_case() draws, from the candidate lists it recorded (no tree needed): (xyz, scaling, rotation)."""
+    return _grow(_Replayed(cands), seed, n_roots, n_levels, max_child, split_prob, remove_prob, extent)
+
+
+class _Grown:
+    """The tree operations of _grow() on a reference TensorTree, recording every candidate list."""
+
+    def __init__(self, tree, record):
+        self.tree, self.record = tree, record if record is not None else []
+
+    def initialize(self, xyz):
+        self.tree.initialize(xyz)
+
+    def split_candidates(self, level):
+        return self._note(torch.where((self.tree.node_index == -1) & (self.tree.depth == level))[0])
+
+    def split(self, parent):
+        self.tree.split(parent)
+
+    def remove_candidates(self):
+        return self._note(torch.where((self.tree.node_index == -1) & (self.tree.index_parent > -1))[0])
+
+    def remove(self, rem):
+        self.tree.remove(rem)
+
+    def _note(self, cand):
+        self.record.append(cand.clone())
+        return cand
+
+
+class _Replayed:
+    """The same operations, handing back recorded candidate lists."""
+
+    def __init__(self, cands):
+        self.cands = [torch.as_tensor(c).long() for c in cands]
+
+    def initialize(self, xyz):
+        pass
+
+    def split_candidates(self, level):
+        return self.cands.pop(0)
+
+    def split(self, parent):
+        pass
+
+    def remove_candidates(self):
+        return self.cands.pop(0)
+
+    def remove(self, rem):
+        pass
+
+
+def _grow(ops, seed, n_roots, n_levels, max_child, split_prob, remove_prob, extent):
+    g = torch.Generator().manual_seed(seed)
     xyz = (torch.rand(n_roots, 3, generator=g) - 0.5) * extent
     scaling = torch.log(torch.rand(n_roots, 3, generator=g) * 0.06 + 0.01)
     rotation = torch.randn(n_roots, 4, generator=g)
-    tree.initialize(xyz)
+    ops.initialize(xyz)
     for level in range(n_levels):
-        cand = torch.where((tree.node_index == -1) & (tree.depth == level))[0]
+        cand = ops.split_candidates(level)
         parent = cand[torch.rand(cand.shape[0], generator=g) < split_prob]
         if parent.numel() == 0:
             break
-        tree.split(parent)
+        ops.split(parent)
         rep = parent[:, None].repeat(1, max_child).reshape(-1)
         sig = torch.exp(scaling[rep]).max(dim=-1, keepdim=True).values
         xyz = torch.cat([xyz, xyz[rep] + torch.randn(rep.shape[0], 3, generator=g) * sig])
         scaling = torch.cat([scaling, scaling[rep] - math.log(1.6) + 0.2 * torch.randn(rep.shape[0], 3, generator=g)])
         rotation = torch.cat([rotation, rotation[rep] + 0.3 * torch.randn(rep.shape[0], 4, generator=g)])
     # holes: remove some non-root leaves (tensor_tree.py:92-119); the caller drops the same rows of the parameters
-    cand = torch.where((tree.node_index == -1) & (tree.index_parent > -1))[0]
+    cand = ops.remove_candidates()
     rem = cand[torch.rand(cand.shape[0], generator=g) < remove_prob]
-    keep = torch.ones(tree.num_points, dtype=torch.bool)
+    keep = torch.ones(xyz.shape[0], dtype=torch.bool)
     keep[rem] = False
-    tree.remove(rem)
+    ops.remove(rem)
     xyz, scaling, rotation = xyz[keep], scaling[keep], rotation[keep]
-    assert xyz.shape[0] == tree.num_points
-    return tree, xyz.contiguous(), scaling.contiguous(), rotation.contiguous()
+    if isinstance(ops, _Grown):
+        assert xyz.shape[0] == ops.tree.num_points
+    return xyz.contiguous(), scaling.contiguous(), rotation.contiguous()
 
 
 def camera_and_rasterizer(W, H, focal, theta=30.0, radius=2.5):
@@ -80,6 +139,33 @@ def camera_and_rasterizer(W, H, focal, theta=30.0, radius=2.5):
         viewmatrix=torch.tensor(cam["world_view_transform"]), projmatrix=torch.tensor(cam["full_proj_transform"]),
         sh_degree=0, campos=torch.tensor(cam["camera_center"]), prefiltered=False, debug=False)
     return cam, GaussianRasterizer(raster_settings=rs)
+
+
+def random_tree_case(seed, cands=None, record=None):
+    """Case `seed` of tests/test_lod_cpu.py::test_oracle_and_dropin_follow_reference_on_random_trees: a tree of random
+    arity, depth and removal rate grown by the reference's TensorTree (cands=None; `record` receives its candidate lists)
+    or its parameters replayed from those lists (cands), and a random camera.  -> (rng, tree or None, xyz, scaling,
+    rotation, rast); rng goes on with the draws of the roots and the queries."""
+    rng = np.random.default_rng(seed)
+    mc = int(rng.choice([2, 3, 4, 8]))
+    args = (100 + seed, int(rng.integers(50, 400)), int(rng.integers(1, 5)), mc)
+    kw = dict(split_prob=float(rng.uniform(0.3, 0.95)), remove_prob=float(rng.uniform(0.0, 0.3)))
+    if cands is None:
+        tree, xyz, scaling, rotation = build_case(*args, record=record, **kw)
+    else:
+        tree, (xyz, scaling, rotation) = None, replay_case(*args, cands, **kw)
+    cam, rast = camera_and_rasterizer(320, 240, float(rng.uniform(150, 500)), theta=float(rng.integers(0, 8) * 45))
+    return rng, tree, xyz, scaling, rotation, rast
+
+
+def random_tree_queries(rng, root_index):
+    """The roots handed over (a random 85 %) and three (min_px, max_depth) queries of a random_tree_case()."""
+    roots = root_index[torch.from_numpy(rng.random(root_index.shape[0]) < 0.85)]
+    queries = []
+    for _ in range(3):
+        min_px = float(rng.choice([0.5, 2.0, 3.0, 6.0, 20.0]))
+        queries.append((min_px, int(rng.choice([0, 1, 2, 3, 1000]))))
+    return roots, queries
 
 
 def reference_traverse(tree, xyz, scaling, rotation, root_index, rast, min_px, max_depth):
@@ -116,7 +202,18 @@ def main():
             out[f"index_{qi}"] = idx.numpy().astype(np.int64)
             print(c["name"], "min_px", min_px, "max_depth", max_depth, "->", idx.shape[0], "of", tree.num_points,
                   "points; mean depth", float(tree.depth[idx].float().mean()))
-        np.savez_compressed(os.path.join(HERE, f"lod_{c['name']}.npz"), **out)
+        save_lzma(os.path.join(HERE, f"lod_{c['name']}.npz"), out)
+
+
+def save_lzma(path, arrays):
+    """np.savez with LZMA members (np.load reads them like deflated ones): lod_a stays below 1 MiB, which deflate misses."""
+    import io
+    import zipfile
+    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_LZMA) as z:
+        for name, a in arrays.items():
+            buf = io.BytesIO()
+            np.save(buf, np.asanyarray(a))
+            z.writestr(name + ".npy", buf.getvalue())
 
 
 if __name__ == "__main__":

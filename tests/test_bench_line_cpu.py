@@ -156,3 +156,41 @@ def test_the_one_rank_rccl_leg_reaches_the_line():
     line = bench.compact_line(broken)
     assert line["value"] == pytest.approx(full["value"], rel=1e-6) and len(line["config"]["rccl_one_rank_exchange"]) <= 100
     assert "rccl_one_rank_step_ms" not in line["config"]
+
+
+def test_a_plain_run_is_the_headline_alone(monkeypatch):
+    """Without --full the run times the headline only (every other leg is opt-in) and dumps nothing."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.steps == 7 and a.warmup == 2 and a.full is False and a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "out"
+
+
+def test_dumped_outputs_are_a_fixed_sample_within_64_mb(tmp_path):
+    """--dump-outputs: the same sample for every run with the same arguments, float32, at most 64 MB at any size."""
+    import types
+    import numpy as np
+    import torch
+    from log_amd.dist import GradientBucket
+    N, W, H, V = 2_000_000, 960, 540, 8
+    b = GradientBucket(N, "cpu", row_major=True, track_seen=False)
+    b.flat.copy_(torch.arange(b.flat.numel(), dtype=torch.float32))
+    gen = torch.Generator().manual_seed(0)
+    keep = {j: (torch.rand(3, H, W, generator=gen), torch.randint(0, 50, (N,), dtype=torch.int32, generator=gen))
+            for j in range(V)}
+    wl = types.SimpleNamespace(rasts=list(range(V)), N=N, W=W, H=H, dev=torch.device("cpu"), keep=keep)
+    one, two = bench.step_outputs(wl, b), bench.step_outputs(wl, b)
+    assert set(one) == {"images", "radii", "grad_means3D", "grad_scales", "grad_rotations", "grad_opacities", "grad_colors"}
+    assert all(np.array_equal(one[k], two[k]) for k in one)
+    assert sum(a.nbytes for a in one.values()) <= 64 * 1024 * 1024
+    assert one["images"].shape[0] == V and one["radii"].shape[0] == V
+    # the sampled rows of the summed gradients are the bucket's own rows (row-major: columns 0-2 = dL/dmeans3D)
+    rows, k = b.alias["means3D"], one["grad_means3D"]
+    idx = (k[:, 0] / 16).astype(np.int64)
+    assert (np.diff(idx) > 0).all() and np.array_equal(k, rows[torch.from_numpy(idx)].numpy())
+    bench.write_outputs(one, str(tmp_path))
+    for name, a in one.items():
+        back = np.load(tmp_path / (name + ".npy"))
+        assert back.dtype == np.float32 and np.array_equal(back, a)

@@ -13,10 +13,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _bench(*flags, env=None):
-    """-> the FULL result object (bench.py --print-full: an earlier stdout line), after checking that the LAST stdout line is
-    the compact contract object the driver parses (< 4 KB, the same value)."""
+    """-> the FULL result object (bench.py --full --print-full: an earlier stdout line), after checking that the LAST stdout
+    line is the compact contract object the driver parses (< 4 KB, the same value)."""
     e = dict(os.environ, **(env or {}))
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--print-full"] + list(flags), env=e,
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--print-full"] + list(flags), env=e,
                          capture_output=True, text=True, timeout=600)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert out.returncode == 0 and len(lines) >= 2, (out.returncode, out.stdout[-2000:], out.stderr[-2000:])

@@ -1,17 +1,14 @@
 """Row N2: the packages' native `shs=` input.  CPU: the C oracle's SH basis against the reference's own PyTorch
-twin (LoG/model/sh_utils.py, imported from /root/reference when present) and its hand-written backward against
+twin (LoG/model/sh_utils.py: its results stored in tests/golden/sh_basis.npz) and its hand-written backward against
 float64 autograd.  GPU: the HIP kernels against the oracle, stand-alone and through the rasterizer module."""
 import math
 import os
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 from util import cam_tan, rel_l2, small_case
-
-REF = os.environ.get("LOG_REFERENCE", "/root/reference")
 
 
 def _inputs(n=4000, M=16, seed=0, scale=0.6):
@@ -22,20 +19,15 @@ def _inputs(n=4000, M=16, seed=0, scale=0.6):
     return means, campos, shs
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "LoG")), reason="reference tree not present")
 @pytest.mark.parametrize("degree", [1, 2, 3])
 def test_oracle_basis_matches_reference_sh_utils(oracle_mod, degree):
-    """0.5 + C0*sh0 + eval_sh_wobase(dirs, sh[1:]) == the oracle's unclamped colour (activation.py:27-34)."""
-    if REF not in sys.path:
-        sys.path.insert(0, REF)
-    from LoG.model.sh_utils import SH2RGB, eval_sh_wobase          # reference code
+    """0.5 + C0*sh0 + eval_sh_wobase(dirs, sh[1:]) == the oracle's unclamped colour (activation.py:27-34); the reference's
+    colours are stored in tests/golden/sh_basis.npz (tests/golden/make_golden_sh.py runs its sh_utils on these inputs)."""
     means, campos, shs = _inputs(scale=0.2)                        # small coefficients: nothing reaches the clamp
     col, clamped = oracle_mod.sh_forward(means, campos, shs, degree)
     assert not clamped.any()
-    d = torch.tensor(means - campos[None])
-    d = d / d.norm(dim=-1, keepdim=True)
-    ref = SH2RGB(torch.tensor(shs[:, 0])) + eval_sh_wobase(d, torch.tensor(shs[:, 1:]), degree=degree)
-    np.testing.assert_allclose(col, ref.numpy(), rtol=2e-5, atol=2e-6)
+    ref = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "sh_basis.npz"))["colour_deg%d" % degree]
+    np.testing.assert_allclose(col, ref, rtol=2e-5, atol=2e-6)
 
 
 @pytest.mark.parametrize("degree", [0, 1, 2, 3])

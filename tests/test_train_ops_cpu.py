@@ -140,91 +140,53 @@ def test_installed_on_reference_classes_side_by_side(double):
             del SparseOptimizer._lograst_load_state_dict
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "LoG")), reason="reference tree not present")
 @pytest.mark.parametrize("seed", range(6))
 def test_random_views_and_steps_against_reference_classes(seed, double):
-    """Random sizes, random subsets of keys without gradient, amsgrad on/off, several views / steps: the reference's
-    Counter and SparseOptimizer (unpatched, torch CPU) and the drop-in functions see identical inputs."""
-    if REF not in sys.path:
-        sys.path.insert(0, REF)
+    """Random sizes, random subsets of keys without gradient, amsgrad on/off, several views / steps: the drop-in functions
+    see the inputs the reference's Counter and SparseOptimizer (unpatched, torch CPU) saw, and compute what they computed
+    (tests/golden/train_random_<seed>.npz: tests/golden/make_golden_train_random.py runs the reference classes on
+    train_util.random_case(seed))."""
     import types
-    from LoG.model.counter import Counter
-    from LoG.model.sparse_optimizer import SparseOptimizer
     from log_amd import counter, sparse_optimizer
-    rng = np.random.default_rng(100 + seed)
-    g = torch.Generator().manual_seed(seed)
-    P = int(rng.integers(50, 3000))
-    # ---- counter: views with random visible sets, radii (some 0 = culled), id lists over the visible ones
-    views = []
-    for _ in range(int(rng.integers(1, 4))):
-        nv = int(rng.integers(1, P + 1))
-        vis = rng.permutation(P)[:nv]
-        n_leaf = int(rng.integers(0, nv + 1))
-        radii = rng.integers(0, 40000, nv).astype(np.int32) * (rng.random(nv) < 0.8)       # > int16 range too (.short() wraps)
-        k = int(rng.integers(0, nv + 1))
-        pid = np.sort(rng.permutation(nv)[:k]).astype(np.int32)
-        views.append(dict(index=vis[:n_leaf], index_node=vis[n_leaf:], grad=rng.standard_normal((nv, 3)).astype(np.float32),
-                          radii=radii.astype(np.int32), pw=rng.random(nv).astype(np.float32), pid=pid,
-                          pc=rng.integers(1, 5000, k).astype(np.int64)))
-
-    def output():
-        t = torch.from_numpy
-        return {"render": [None] * len(views),
-                "visibility_flag": [{"index": t(v["index"]), "index_node": t(v["index_node"])} for v in views],
-                "viewspace_points": [types.SimpleNamespace(grad=t(v["grad"])) for v in views],
-                "radii": [t(v["radii"]) for v in views], "point_weight": [t(v["pw"]) for v in views],
-                "point_id": [t(v["pid"]) for v in views], "point_count": [t(v["pc"]) for v in views]}
-
-    c_ref, c_new = Counter(num_points=P), Counter(num_points=P)
-    o_ref, o_new = output(), output()
-    c_ref.update_by_output(o_ref, fix_parent=True)
+    c = U.random_case(seed)
+    ref = U.load("train_random_%d.npz" % seed)
+    P = c["P"]
+    assert int(ref["P"]) == P and int(ref["n_views"]) == len(c["views"]) and int(ref["n_steps"]) == len(c["steps"])
+    # ---- counter
+    c_new = U.fresh_counter(P, "cpu")
+    o_new = U.random_counter_output(c["views"])
     counter.update_by_output(c_new, o_new, fix_parent=True)
     for k in U.COUNTER_DTYPES:
-        a, b = getattr(c_new, k).numpy(), getattr(c_ref, k).numpy()
+        a, b = getattr(c_new, k).numpy(), ref["counter_" + k]
+        assert a.dtype == b.dtype, k
         if a.dtype.kind == "f":
             np.testing.assert_allclose(a, b, rtol=3e-6, atol=1e-12, err_msg=k)
         else:
             np.testing.assert_array_equal(a, b, err_msg=k)
-    for v in range(len(views)):
-        assert torch.equal(o_new["visibility_flag"][v]["flag_vis"], o_ref["visibility_flag"][v]["flag_vis"])
-        assert torch.equal(o_new["visibility_flag"][v]["index_vis"], o_ref["visibility_flag"][v]["index_vis"])
-    # ---- sparse Adam
-    amsgrad = bool(seed % 2)
-    shapes = {"xyz": (3,), "colors": (3,), "scaling": (3,), "opacity": (1,), "rotation": (4,), "shs": (int(rng.integers(1, 16)), 3)}
-    lr = {"xyz": 0.00016, "xyz_final": 0.0000016, "colors": 0.0025, "shs": 0.000125, "scaling": 0.005, "opacity": 0.05,
-          "rotation": 0.001, "max_steps": 30000}
-
-    def make():
-        gg = torch.Generator().manual_seed(seed)
-        model = types.SimpleNamespace(**{k: torch.randn(P, *s, generator=gg) for k, s in shapes.items()})
-        opt = SparseOptimizer(list(shapes), dict(lr), model, device=torch.device("cpu"), xyz_scale=1.0, use_amsgrad=amsgrad)
-        opt.global_steps += int(seed * 7)
-        return model, opt
-
-    (m_ref, op_ref), (m_new, op_new) = make(), make()
-    for _ in range(int(rng.integers(1, 4))):
-        m = int(rng.integers(1, P + 1))
-        index = torch.randperm(P, generator=g)[:m]
-        flag_vis = torch.rand(m, generator=g) < 0.7
-        no_grad = {k for k in shapes if rng.random() < 0.25}
-        grads = {k: torch.randn(m, *s, generator=g) * 10.0 ** float(rng.integers(-6, 1)) for k, s in shapes.items()}
-
-        def params(model):
-            out = {}
-            for k in shapes:
-                p = torch.nn.Parameter(getattr(model, k)[index].clone())
-                if k not in no_grad:
-                    p.grad = grads[k].clone()
-                out[k] = p
-            return out
-
-        op_ref.step(m_ref, index, params(m_ref), flag_vis)
-        sparse_optimizer.step(op_new, m_new, index, params(m_new), flag_vis)
-    assert float(op_ref.global_steps) == float(op_new.global_steps)
+    for v in range(len(c["views"])):
+        assert torch.equal(o_new["visibility_flag"][v]["flag_vis"], torch.from_numpy(ref[f"v{v}_flag_vis"]))
+        assert torch.equal(o_new["visibility_flag"][v]["index_vis"], torch.from_numpy(ref[f"v{v}_index_vis"]))
+    # ---- sparse Adam: what SparseOptimizer.__init__ sets up that step() reads, with the reference's learning rates
+    amsgrad, shapes = c["amsgrad"], c["shapes"]
+    m_new = c["init_model"]()
+    zeros = lambda: {k: torch.zeros_like(getattr(m_new, k)) for k in shapes}
+    lrs = {int(ref[f"s{i}_step"]): (float(ref[f"s{i}_lr_xyz"]), float(ref[f"s{i}_lr_scaling"])) for i in range(len(c["steps"]))}
+    op_new = types.SimpleNamespace(
+        global_steps=torch.tensor(float(ref["start_global_steps"]), dtype=torch.float32),
+        lr_dict={k: float(ref["lr_" + k]) for k in ("colors", "shs", "opacity", "rotation")}, exp_avg=zeros(),
+        exp_avg_sq=zeros(), use_amsgrad=amsgrad, xyz_lr=None, xyz_scheduler_args=lambda step: lrs[step][0],
+        scaling_scheduler_args=lambda step: lrs[step][1])
+    if amsgrad:
+        op_new.max_exp_avg_sq = zeros()
+    for st in c["steps"]:
+        sparse_optimizer.step(op_new, m_new, st["index"], U.random_step_params(m_new, st, shapes), st["flag_vis"])
+    assert float(op_new.global_steps) == float(ref["final_global_steps"])
+    if not np.isnan(float(ref["final_xyz_lr"])):
+        assert op_new.xyz_lr == float(ref["final_xyz_lr"])
     for k in shapes:
-        np.testing.assert_allclose(getattr(m_new, k).numpy(), getattr(m_ref, k).numpy(), rtol=3e-6, atol=2e-8, err_msg=k)
-        np.testing.assert_allclose(op_new.exp_avg[k].numpy(), op_ref.exp_avg[k].numpy(), rtol=3e-6, atol=1e-12, err_msg=k)
-        np.testing.assert_allclose(op_new.exp_avg_sq[k].numpy(), op_ref.exp_avg_sq[k].numpy(), rtol=3e-6, atol=1e-20, err_msg=k)
+        np.testing.assert_allclose(getattr(m_new, k).numpy(), ref["final_" + k], rtol=3e-6, atol=2e-8, err_msg=k)
+        np.testing.assert_allclose(op_new.exp_avg[k].numpy(), ref["final_exp_avg_" + k], rtol=3e-6, atol=1e-12, err_msg=k)
+        np.testing.assert_allclose(op_new.exp_avg_sq[k].numpy(), ref["final_exp_avg_sq_" + k], rtol=3e-6, atol=1e-20, err_msg=k)
         if amsgrad:
-            np.testing.assert_allclose(op_new.max_exp_avg_sq[k].numpy(), op_ref.max_exp_avg_sq[k].numpy(), rtol=3e-6,
+            np.testing.assert_allclose(op_new.max_exp_avg_sq[k].numpy(), ref["final_max_exp_avg_sq_" + k], rtol=3e-6,
                                        atol=1e-20, err_msg=k)

@@ -98,3 +98,67 @@ def check_adam(model, opt, g, rtol=2e-6):
             np.testing.assert_allclose(opt.max_exp_avg_sq[k].cpu().numpy(), g["final_max_exp_avg_sq_" + k], rtol=rtol,
                                        atol=1e-20, err_msg=k)
     assert float(opt.global_steps) == float(g["final_global_steps"])
+
+
+# ---- random cases: tests/test_train_ops_cpu.py::test_random_views_and_steps_against_reference_classes ----------------
+# The reference's Counter / SparseOptimizer ran on exactly these inputs in tests/golden/make_golden_train_random.py; what
+# they computed is stored in tests/golden/train_random_<seed>.npz.
+RANDOM_LR = {"xyz": 0.00016, "xyz_final": 0.0000016, "colors": 0.0025, "shs": 0.000125, "scaling": 0.005, "opacity": 0.05,
+             "rotation": 0.001, "max_steps": 30000}
+
+
+def random_case(seed):
+    """Random sizes, views with random visible sets / radii / id lists, random subsets of keys without gradient, amsgrad
+    on odd seeds, one to three Adam steps.  -> dict(P, views, shapes, amsgrad, start_steps, steps, init_model)."""
+    rng = np.random.default_rng(100 + seed)
+    g = torch.Generator().manual_seed(seed)
+    P = int(rng.integers(50, 3000))
+    views = []
+    for _ in range(int(rng.integers(1, 4))):
+        nv = int(rng.integers(1, P + 1))
+        vis = rng.permutation(P)[:nv]
+        n_leaf = int(rng.integers(0, nv + 1))
+        radii = rng.integers(0, 40000, nv).astype(np.int32) * (rng.random(nv) < 0.8)       # > int16 range too (.short() wraps)
+        k = int(rng.integers(0, nv + 1))
+        pid = np.sort(rng.permutation(nv)[:k]).astype(np.int32)
+        views.append(dict(index=vis[:n_leaf], index_node=vis[n_leaf:], grad=rng.standard_normal((nv, 3)).astype(np.float32),
+                          radii=radii.astype(np.int32), pw=rng.random(nv).astype(np.float32), pid=pid,
+                          pc=rng.integers(1, 5000, k).astype(np.int64)))
+    amsgrad = bool(seed % 2)
+    shapes = {"xyz": (3,), "colors": (3,), "scaling": (3,), "opacity": (1,), "rotation": (4,), "shs": (int(rng.integers(1, 16)), 3)}
+
+    def init_model():
+        gg = torch.Generator().manual_seed(seed)
+        return types.SimpleNamespace(**{k: torch.randn(P, *s, generator=gg) for k, s in shapes.items()})
+
+    steps = []
+    for _ in range(int(rng.integers(1, 4))):
+        m = int(rng.integers(1, P + 1))
+        index = torch.randperm(P, generator=g)[:m]
+        flag_vis = torch.rand(m, generator=g) < 0.7
+        no_grad = {k for k in shapes if rng.random() < 0.25}
+        grads = {k: torch.randn(m, *s, generator=g) * 10.0 ** float(rng.integers(-6, 1)) for k, s in shapes.items()}
+        steps.append(dict(index=index, flag_vis=flag_vis, no_grad=no_grad, grads=grads))
+    return dict(P=P, views=views, shapes=shapes, amsgrad=amsgrad, start_steps=int(seed * 7), steps=steps,
+                init_model=init_model)
+
+
+def random_counter_output(views):
+    """The `output` dict Counter.update_by_output receives, for random_case()'s views."""
+    t = torch.from_numpy
+    return {"render": [None] * len(views),
+            "visibility_flag": [{"index": t(v["index"]), "index_node": t(v["index_node"])} for v in views],
+            "viewspace_points": [types.SimpleNamespace(grad=t(v["grad"])) for v in views],
+            "radii": [t(v["radii"]) for v in views], "point_weight": [t(v["pw"]) for v in views],
+            "point_id": [t(v["pid"]) for v in views], "point_count": [t(v["pc"]) for v in views]}
+
+
+def random_step_params(model, step, shapes):
+    """The `params` of one SparseOptimizer.step call: the selected rows as fresh leaves, gradients on all but `no_grad`."""
+    out = {}
+    for k in shapes:
+        p = torch.nn.Parameter(getattr(model, k)[step["index"]].clone())
+        if k not in step["no_grad"]:
+            p.grad = step["grads"][k].clone()
+        out[k] = p
+    return out
