@@ -4,7 +4,7 @@ import ctypes
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("LOGRAST_LIB") or os.path.join(_HERE, "lib", "liblograst.so")  # env: experiment builds only
+LIB_PATH = os.environ.get("LOGRAST_LIB") or os.path.join(_HERE, "lib", "liblograst.so")  # env: another build (variant, parent)
 
 FILTER_NONE, FILTER_DILATE, FILTER_CLAMP = 0, 1, 2
 FORM_AUTO, FORM_ROWS, FORM_QUADRANT = 0, 1, 2

@@ -32,8 +32,8 @@ def _newer(target, deps):
 
 
 def build(force=False, verbose=True, variant=None, extra_flags=()):
-    """variant: name of an experimental build (liblograst_<variant>.so with extra_flags), used only by
-    tools/experiments; the product library is the default build."""
+    """variant: name of another build of the same sources (liblograst_<variant>.so, compiled with extra_flags added),
+    loaded through LOGRAST_LIB to compare compiler switches; the product library is the default build."""
     global LIB, OBJDIR
     lib, objdir = LIB, OBJDIR
     if variant:

@@ -41,8 +41,8 @@ void lr_launch_fill(int N, int gx, const void* geom, uint32_t* state, uint32_t t
 void lr_launch_tile_rows(const LrView& v, int N, const float* means, const float* scales, const float* rots,
                          uint32_t* rows, hipStream_t s);
 void lr_launch_stream_copy(const void* src, void* dst, size_t bytes, int blocks, hipStream_t s);
-int lr_launch_sort(uint32_t* state, uint32_t tiles, uint64_t* keys, uint32_t* plist, uint32_t capacity,
-                   uint32_t max_len, int lazy, hipStream_t s);
+void lr_launch_sort(uint32_t* state, uint32_t tiles, uint64_t* keys, uint32_t* plist, uint32_t capacity,
+                    uint32_t max_len, int lazy, hipStream_t s);
 void lr_launch_sort_rest(uint32_t* state, uint32_t tiles, uint64_t* keys, uint32_t* plist, uint32_t capacity,
                          uint32_t max_len, int mode, hipStream_t s);
 void lr_launch_ordered_lengths(const uint32_t* state, uint32_t tiles, uint32_t* out, hipStream_t s);
@@ -152,21 +152,16 @@ static std::atomic<int> g_tile_cull{-1};
 // puts several instances into a tile (that is what it saves in memory-side atomics) and at most 32768 Gaussians (16-bit
 // ranks); a workgroup takes as many batches as its LDS holds (up to 4), which makes the runs it reserves in a tile
 // adjacent (longer contiguous key writes in the fill) and leaves one workgroup per CU per round.
-// LOGRAST_BATCH overrides the batch size (0 disables batching), LOGRAST_BATCH_PLANES caps the planes.
+// LOGRAST_BATCH_PLANES caps the planes.
 struct LrBatching { uint32_t batch, planes; };
 static LrBatching lr_pick_batch(int32_t n, uint32_t tiles, uint32_t gx, uint32_t gy) {
-  static const int forced = LR_EXPERIMENT_INT("LOGRAST_BATCH", -1);   // experiment builds: Gaussians per batch, 0 = unbatched kernel
   LR_KNOB(max_planes_k, "LOGRAST_BATCH_PLANES", 4);
   const uint32_t max_planes = (uint32_t)max_planes_k;
-  if (n <= 0 || tiles > LR_BATCH_MAX_TILES || gx > 8191u || gy > 8191u || forced == 0) return {0u, 1u};  // 13-bit tile coordinates in the fill record
+  if (n <= 0 || tiles > LR_BATCH_MAX_TILES || gx > 8191u || gy > 8191u) return {0u, 1u};  // 13-bit tile coordinates in the fill record
   uint32_t smax = (uint32_t)(LR_BATCH_LDS_BYTES / (sizeof(uint32_t) * (size_t)tiles));
   if (smax > max_planes) smax = max_planes;
   if (smax > 4u) smax = 4u;
   if (smax < 1u) smax = 1u;
-  if (forced > 0) {
-    const uint32_t b = (uint32_t)((forced > 32768 ? 32768 : forced) + 1023) / 1024u * 1024u;  // 16-bit LDS counts
-    return {b, smax};
-  }
   // One workgroup of 1024 threads per CU (82 VGPRs): 256 run at a time.  Size the work so that the workgroups fill
   // whole rounds of 256 (10 M Gaussians: 306 batches of 32768 = 1.2 rounds ran as long as 2).
   LR_KNOB(slots_k, "LOGRAST_BATCH_SLOTS", 256);
@@ -428,8 +423,6 @@ static int lr_stage2(const LrView& v, int32_t n, const void* geom, uint32_t* st,
                      int32_t* point_id_pixel, float* point_weight_pixel, float* point_weight, float* bwd_scratch,
                      int32_t bwd_scratch_floats, uint32_t* status, hipStream_t s, int speculative = 0) {
   const uint32_t tiles = (uint32_t)(v.gx * v.gy);
-  static const int stop_after_project = LR_EXPERIMENT_INT("LOGRAST_STOP_AFTER_PROJECT", 0);   // experiment builds (tools/kernel_probe.py)
-  if (stop_after_project) return LOGRAST_OK;
   if (n == 0 && status)   // no fill kernel runs: this forward's entries of the status block
     LR_HIP(hipMemsetAsync(status + LOGRAST_STATUS_LAST_INSTANCES, 0, 4 * sizeof(uint32_t), s));
   // point_weight (atomicMax target) and the optional backward scratch (one 64-byte accumulator row per Gaussian) are
@@ -453,15 +446,13 @@ static int lr_stage2(const LrView& v, int32_t n, const void* geom, uint32_t* st,
   lr_launch_fill(n, v.gx, geom, st, tiles, keys, capacity, max_tile_len, status,
                  zero_n, zero_floats > 0 ? zero_block : nullptr, zero_floats,
                  (lr_big_input(n) && staged_k == 0) ? 1 : 0, speculative, lr_band_sparse(v, (int)fill_batch) ? 1 : 0, staged_k, s);
-  static const int stop_after_fill = LR_EXPERIMENT_INT("LOGRAST_STOP_AFTER_FILL", 0);   // experiment builds (tools/fill_probe.py)
-  if (stop_after_fill) return LOGRAST_OK;
   // LOGRAST_LAZY_SORT (default 1): lists of more than 4096 keys are ordered over their first window only (7680 positions;
   // the walk of a view ends far in front of that: common.hpp, sorted[]); the compositing kernels mark the tiles that needed
   // more, and the second pair of launches -- idle in every benched view -- finishes exactly those.  0: every list to its
   // end before the first compositing pass (what lograst_finish_lists produces afterwards).
   LR_KNOB(lazy_knob, "LOGRAST_LAZY_SORT", 1);
-  const int lazy_asked = (lazy_knob && max_tile_len_allows_streaming(max_tile_len, capacity)) ? 1 : 0;
-  const int lazy = lr_launch_sort(st, tiles, keys, point_list, capacity, max_tile_len, lazy_asked, s);
+  const int lazy = (lazy_knob && max_tile_len_allows_streaming(max_tile_len, capacity)) ? 1 : 0;
+  lr_launch_sort(st, tiles, keys, point_list, capacity, max_tile_len, lazy, s);
   float* const zrows = touched_only ? bwd_scratch : nullptr;
   lr_launch_blend_fwd(v, geom, st, tiles, point_list, capacity, image, final_t, n_contrib, point_id_pixel,
                       point_weight_pixel, point_weight, zrows, lr_big_input(n) ? 1 : 0, lazy, v.masks, s);

@@ -23,29 +23,6 @@
 #define LR_LANDED(q0, q1, c, i)                                                                                  \
   asm volatile("" : "+v"((q0).x), "+v"((q0).y), "+v"((q0).z), "+v"((q0).w), "+v"((q1).x), "+v"((q1).y), "+v"((q1).z), \
                "+v"((q1).w), "+v"(c), "+v"(i))
-// Occupancy hints (waves per SIMD the register allocator aims for), per kernel: compile-time so that A/B builds
-// (`python -m log_amd.build <variant> -DLR_OCC_BWD_ROWS_WAVES=5`) can measure them; empty = the allocator's own choice.
-#define LR_OCC_ATTR(n) __attribute__((amdgpu_waves_per_eu(n)))
-#ifdef LR_OCC_BWD_ROWS_WAVES
-#define LR_OCC_BWD_ROWS LR_OCC_ATTR(LR_OCC_BWD_ROWS_WAVES)
-#else
-#define LR_OCC_BWD_ROWS
-#endif
-#ifndef LR_OCC_FWD_ROWS_WAVES
-#define LR_OCC_FWD_ROWS_WAVES 5   // round 6: with the unconditional prefetch loads the allocator's own choice is 102 VGPRs (4 waves); 96 fit without a spill
-#endif
-#define LR_OCC_FWD_ROWS LR_OCC_ATTR(LR_OCC_FWD_ROWS_WAVES)
-#ifdef LR_OCC_BWD_WAVES
-#define LR_OCC_BWD LR_OCC_ATTR(LR_OCC_BWD_WAVES)
-#else
-#define LR_OCC_BWD
-#endif
-#ifdef LR_OCC_FWD_WAVES
-#define LR_OCC_FWD LR_OCC_ATTR(LR_OCC_FWD_WAVES)
-#else
-#define LR_OCC_FWD
-#endif
-
 
 // blockIdx -> tile.  Workgroup b is observed to run on XCD b % 8 (speed only, never correctness).
 //   mode 0: identity -- consecutive tiles round-robin over the XCDs: best balance, no L2 sharing;
@@ -228,7 +205,7 @@ LR_DEV void lr_fwd_commit_chunk(uint32_t* wmx, int lane, uint32_t id_prev, float
 }
 
 template <bool EXTRAS>
-__global__ void __launch_bounds__(256) LR_OCC_FWD
+__global__ void __launch_bounds__(256)
 lr_blend_fwd_kernel(LrView v, const float4* __restrict__ geom, const uint32_t* __restrict__ state,
                     uint32_t tiles, const uint32_t* __restrict__ plist, uint32_t capacity,
                     float* __restrict__ image, float* __restrict__ final_T, int* __restrict__ n_contrib,
@@ -288,7 +265,7 @@ lr_blend_fwd_kernel(LrView v, const float4* __restrict__ geom, const uint32_t* _
     id_n = id_nn;
     id_nn = load_id(ch + 2);
     if (id_n != 0xffffffffu) { g0_n = geom[LR_REC_QUADS * (size_t)id_n]; g1_n = *reinterpret_cast<const float2*>(geom + LR_REC_QUADS * (size_t)id_n + 1); }
-    const bool rel = (id != 0xffffffffu) && (cull ? lr_support_hits(g0, g1, bx0, bx1, by0, by1) : true);
+    const bool rel = (id != 0xffffffffu) && (cull ? lr_support_hits(g0, g1, bx0, bx1, by0, by1) : true);   // (cull: always 1, see the launch)
     uint64_t todo = __ballot(rel);
     const int pos0 = (int)(first + ch * 64u);
     if (mrow_out && lane == 0) mrow_out[4 * (size_t)(pos0 >> 6)] = todo;   // for the reverse walk (hit masks, above)
@@ -420,12 +397,12 @@ LR_DEV void lr_reduce9(const float v[9], float& r0, float& r1, float& r2) {
 }
 
 template <bool MASKS>
-__global__ void __launch_bounds__(256) LR_OCC_BWD
+__global__ void __launch_bounds__(256)
 lr_blend_bwd_kernel(LrView v, const float4* __restrict__ geom, const uint32_t* __restrict__ state,
                     uint32_t tiles, const uint32_t* __restrict__ plist, uint32_t capacity,
                     const float* __restrict__ final_T, const int* __restrict__ n_contrib,
                     const float* __restrict__ dL_dimage, float* __restrict__ acc_rows,
-                    int xcd_mode, int cull, const uint64_t* __restrict__ masks) {
+                    int xcd_mode, const uint64_t* __restrict__ masks) {
   if (lr_bail(state, capacity)) return;
   const uint32_t tile = lr_tile_of_block(blockIdx.x, tiles, v.gx, v.gy, xcd_mode, state);
   if (tile >= tiles) return;
@@ -500,7 +477,7 @@ lr_blend_bwd_kernel(LrView v, const float4* __restrict__ geom, const uint32_t* _
       todo = lr_mask_before(__builtin_bitreverse64(mk), hi, maxc);
     } else {
       if (id_n != 0xffffffffu) { g0_n = geom[LR_REC_QUADS * (size_t)id_n]; g1_n = *reinterpret_cast<const float2*>(geom + LR_REC_QUADS * (size_t)id_n + 1); }
-      const bool rel = (id != 0xffffffffu) && (cull ? lr_support_hits(g0, g1, bx0, bx1, by0, by1) : true);
+      const bool rel = (id != 0xffffffffu) && lr_support_hits(g0, g1, bx0, bx1, by0, by1);
       todo = __ballot(rel);
     }
     // Two entries per iteration: both alpha evaluations are issued together (independent chains), the
@@ -653,12 +630,12 @@ LR_DEV uint64_t lr_row_mask(int row, uint64_t m0, uint64_t m1, uint64_t m2, uint
 }
 
 template <bool MASKS>
-__global__ void __launch_bounds__(256) LR_OCC_BWD_ROWS
+__global__ void __launch_bounds__(256)
 lr_blend_bwd_rows_kernel(LrView v, const float4* __restrict__ geom, const uint32_t* __restrict__ state,
                          uint32_t tiles, const uint32_t* __restrict__ plist, uint32_t capacity,
                          const float* __restrict__ final_T, const int* __restrict__ n_contrib,
                          const float* __restrict__ dL_dimage, float* __restrict__ acc_rows,
-                         int xcd_mode, int cull, int block_test, const uint64_t* __restrict__ masks LR_ABLATE_PARAM) {
+                         int xcd_mode, int block_test, const uint64_t* __restrict__ masks) {
   __shared__ float4 lr_stage[4][65 * LR_RB_SLOT];
   if (lr_bail(state, capacity)) return;
   const uint32_t tile = lr_tile_of_block(blockIdx.x, tiles, v.gx, v.gy, xcd_mode, state);
@@ -790,7 +767,7 @@ lr_blend_bwd_rows_kernel(LrView v, const float4* __restrict__ geom, const uint32
     const bool valid = id != 0xffffffffu;
     const int pos = hi - 1 - lane;
     bool r0 = valid & (pos < rm0), r1 = valid & (pos < rm1), r2 = valid & (pos < rm2), r3 = valid & (pos < rm3);
-    if (cull && !use_masks) {
+    if (!use_masks) {
       const LrSupport sp = lr_support_prepare(g0.x, g0.y, g0.z, g0.w, g1.x, g1.y);
       if (block_test) {   // the exact ellipse-vs-box test for each of the four blocks (~75 VALU each)
         bool k0, k1, k2, k3;   // (two blocks at a time: lr_support_box2, the decisions of four lr_support_box calls)
@@ -813,7 +790,6 @@ lr_blend_bwd_rows_kernel(LrView v, const float4* __restrict__ geom, const uint32
     if (use_masks) mrow = lr_mask_before(lr_row_mask(row, __builtin_bitreverse64(mk.m0), __builtin_bitreverse64(mk.m1),
                                                      __builtin_bitreverse64(mk.m2), __builtin_bitreverse64(mk.m3)), hi, rmax);   // (rmax: this lane's row's deepest contributor)
     else mrow = lr_row_mask(row, __ballot(r0), __ballot(r1), __ballot(r2), __ballot(r3));
-    if (LR_ABLATED(4)) mrow = 0ull;   // experiment builds: the chunk prologue alone
     while (__builtin_amdgcn_ballot_w64(mrow != 0ull) != 0) {
       // every row's next two entries (64 = none: the all-zero slot)
       const uint32_t ja = lr_take_bit(mrow), jb = lr_take_bit(mrow);
@@ -890,10 +866,8 @@ lr_blend_bwd_rows_kernel(LrView v, const float4* __restrict__ geom, const uint32
       // one instruction per entry: nine lanes of every row, one 64-byte line per row
       const float xa = sel == 0 ? s1a : (sel == 1 ? s2a : s3);
       const float xb = sel == 0 ? s1b : (sel == 1 ? s2b : s3);
-      if (!LR_ABLATED(1)) {
-        if (on_a && gida != 0xffffffffu) lr_atomic_add_noret(dst + (size_t)gida * LOGRAST_BWD_ROW_FLOATS, xa);
-        if (on_b && gidb != 0xffffffffu) lr_atomic_add_noret(dst + (size_t)gidb * LOGRAST_BWD_ROW_FLOATS, xb);
-      }
+      if (on_a && gida != 0xffffffffu) lr_atomic_add_noret(dst + (size_t)gida * LOGRAST_BWD_ROW_FLOATS, xa);
+      if (on_b && gidb != 0xffffffffu) lr_atomic_add_noret(dst + (size_t)gidb * LOGRAST_BWD_ROW_FLOATS, xb);
     }
   }
 }
@@ -906,13 +880,15 @@ lr_blend_bwd_rows_kernel(LrView v, const float4* __restrict__ geom, const uint32
 // (row, Gaussian) visit (row maximum by four DPP steps), and the Gaussian's accumulator row is cleared by the row's
 // first four lanes.
 template <bool EXTRAS>
-__global__ void __launch_bounds__(256) LR_OCC_FWD_ROWS
+// 5 waves per SIMD: with the unconditional prefetch loads the allocator's own choice is 102 VGPRs (4 waves); 96 fit
+// without a spill (round 6)
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5)))
 lr_blend_fwd_rows_kernel(LrView v, const float4* __restrict__ geom, const uint32_t* __restrict__ state,
                          uint32_t tiles, const uint32_t* __restrict__ plist, uint32_t capacity,
                          float* __restrict__ image, float* __restrict__ final_T, int* __restrict__ n_contrib,
                          int* __restrict__ pid, float* __restrict__ pwp, float* __restrict__ pw,
                          float4* __restrict__ zero_rows, int xcd_mode, int cull, uint32_t* __restrict__ lazy_state,
-                         int lazy, uint64_t* __restrict__ masks, uint32_t* __restrict__ hdr_w, int block_test LR_ABLATE_PARAM) {
+                         int lazy, uint64_t* __restrict__ masks, uint32_t* __restrict__ hdr_w, int block_test) {
   __shared__ float4 lr_stage[4][65 * LR_RB_SLOT];
   if (lr_bail(state, capacity)) return;
   if (lazy == 2 && !lazy_state[LR_HDR_OPEN]) return;         // nobody parked (lazy_state: the tile state again, through the pointer these kernels WRITE sorted[] / open[] / the flag with)
@@ -941,7 +917,6 @@ lr_blend_fwd_rows_kernel(LrView v, const float4* __restrict__ geom, const uint32
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    if (!LR_ABLATED(8))
     for (uint32_t i = (uint32_t)lane; i < mcount * 4u; i += 64u)   // lane -> (chunk i / 4, block i % 4): 32 adjacent bytes per chunk
       mslot[16 * (size_t)(mfirst + (i >> 2)) + (i & 3u)] = lr_mbuf[wq][i];
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -1019,7 +994,7 @@ lr_blend_fwd_rows_kernel(LrView v, const float4* __restrict__ geom, const uint32
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     const bool valid = id != 0xffffffffu;
     bool r0 = valid, r1 = valid, r2 = valid, r3 = valid;
-    if (cull) {
+    if (cull) {   // (always 1: see the launch)
       const LrSupport sp = lr_support_prepare(g0.x, g0.y, g0.z, g0.w, g1.x, g1.y);
       if (block_test) {
         // the four 4x4 blocks two at a time (lr_support_box2: the decisions of four lr_support_box calls, packed arithmetic)
@@ -1043,10 +1018,9 @@ lr_blend_fwd_rows_kernel(LrView v, const float4* __restrict__ geom, const uint32
     const int pos0 = (int)(first + ch * 64u);
     if (mslot) {                                              // for the reverse walk (hit masks, above)
       if (mcount == 0) mfirst = (uint32_t)pos0 >> 6;
-      if (li == 0 && !LR_ABLATED(16)) lr_mbuf[wq][mcount * 4u + (uint32_t)row] = mrow;
+      if (li == 0) lr_mbuf[wq][mcount * 4u + (uint32_t)row] = mrow;
       if (++mcount == LR_MBUF_CHUNKS) flush_masks();
     }
-    if (LR_ABLATED(4)) mrow = 0ull;   // experiment builds: the chunk prologue alone (gathers, staging, support tests), every list to its end
     while (true) {
       // a row whose 16 pixels are all saturated takes no more entries
       const uint64_t dm = __ballot(done);
@@ -1098,8 +1072,8 @@ lr_blend_fwd_rows_kernel(LrView v, const float4* __restrict__ geom, const uint32
         LR_RMAX(ma, 0x4E); LR_RMAX(mb, 0x4E);
 #undef LR_RMAX
         // (LDS, one lane per row and entry; point_weight and the row clears leave once per chunk: lr_fwd_commit_chunk)
-        if (li == 0 && ma != 0u && !LR_ABLATED(1)) atomicMax(&wmx[ja], ma);
-        if (li == 0 && mb != 0u && !LR_ABLATED(1)) atomicMax(&wmx[jb], mb);
+        if (li == 0 && ma != 0u) atomicMax(&wmx[ja], ma);
+        if (li == 0 && mb != 0u) atomicMax(&wmx[jb], mb);
       }
     }
   }
@@ -1138,17 +1112,14 @@ void lr_launch_blend_fwd(const LrView& v, const void* geom, const uint32_t* stat
   uint32_t* const lazy_state = lazy ? const_cast<uint32_t*>(state) : nullptr;   // (the tile state once more, writable: open[] and header word LR_HDR_OPEN are all a compositing kernel writes there)
   LR_KNOB(xcd_knob, "LOGRAST_XCD_MODE", 3);
   int xcd_mode = xcd_knob;
-  static const int cull = LR_EXPERIMENT_INT("LOGRAST_CULL", 1);   // experiment builds: 0 = no per-quadrant support test
-  static const size_t lds_fwd = (size_t)LR_EXPERIMENT_INT("LOGRAST_BLEND_FWD_LDS_KB", 0) * 1024;   // experiment builds: occupancy cap
   // LOGRAST_FWD_ROWS: 1 = row-split form (lr_blend_fwd_rows_kernel), 0 = one quadrant per wave, 2 (default) = the caller's
   // hint (lograst_view.walk_form), quadrant without one.  Measured, MI355X: 30 M tiny splats 706 -> 658 us (random
   // opacities 1267 -> 1188); C2's 1 M 174 -> 193; a tree-ordered heavy-tailed view 278 -> 347.
-#ifdef LR_EXPERIMENTS
-  static const int fwd_ablate = lr_env_int("LOGRAST_FWD_ABLATE", 0);   // timing experiments (row-split form): 1 no point_weight atomics, 2 no row clears
-#endif
   const int rows = lr_blend_fwd_form(v) == (int)LR_MASK_FORM_ROWS;
   LR_KNOB(fwd_block_test, "LOGRAST_FWD_BLOCK_TEST", 1);
-  if (!cull) masks = nullptr;                                // (experiment builds without support tests: nothing to hand over)
+  // Both forward kernels still take `cull` (always 1: the support tests run) as a run-time argument.  With the tests
+  // unconditional the register allocation of the row-split kernel changed (one more value in scratch) and the forward
+  // measured 1-3 % slower on the 30 M view (quadrant form: 0.6 %).
   uint32_t grid = lr_blend_grid(tiles, v.gx, v.gy, xcd_mode);
   if (lazy == 2) {   // only streamed lists can be open: in the scan's longest-first order they sit in front of every shorter one
     xcd_mode = 3;
@@ -1159,18 +1130,18 @@ void lr_launch_blend_fwd(const LrView& v, const void* geom, const uint32_t* stat
   if (lazy != 2) lr_prof_begin(LRK_BLEND_FWD, s);           // (the second pass is timed by its caller, with the sort of the tails)
   if (rows) {
     if (v.extras)
-      hipLaunchKernelGGL(lr_blend_fwd_rows_kernel<true>, dim3(grid), dim3(256), lds_fwd, s, v, g4, state, tiles, plist, capacity,
-                         image, final_T, n_contrib, pid, pwp, pw, z4, xcd_mode, cull, lazy_state, lazy, masks, hdr_w, fwd_block_test LR_ABLATE_PASS(fwd_ablate));
+      hipLaunchKernelGGL(lr_blend_fwd_rows_kernel<true>, dim3(grid), dim3(256), 0, s, v, g4, state, tiles, plist, capacity,
+                         image, final_T, n_contrib, pid, pwp, pw, z4, xcd_mode, 1, lazy_state, lazy, masks, hdr_w, fwd_block_test);
     else
-      hipLaunchKernelGGL(lr_blend_fwd_rows_kernel<false>, dim3(grid), dim3(256), lds_fwd, s, v, g4, state, tiles, plist, capacity,
-                         image, final_T, n_contrib, pid, pwp, pw, z4, xcd_mode, cull, lazy_state, lazy, masks, hdr_w, fwd_block_test LR_ABLATE_PASS(fwd_ablate));
+      hipLaunchKernelGGL(lr_blend_fwd_rows_kernel<false>, dim3(grid), dim3(256), 0, s, v, g4, state, tiles, plist, capacity,
+                         image, final_T, n_contrib, pid, pwp, pw, z4, xcd_mode, 1, lazy_state, lazy, masks, hdr_w, fwd_block_test);
   } else {
     if (v.extras)
-      hipLaunchKernelGGL(lr_blend_fwd_kernel<true>, dim3(grid), dim3(256), lds_fwd, s, v, g4, state, tiles, plist, capacity,
-                         image, final_T, n_contrib, pid, pwp, pw, z4, xcd_mode, cull, lazy_state, lazy, masks, hdr_w);
+      hipLaunchKernelGGL(lr_blend_fwd_kernel<true>, dim3(grid), dim3(256), 0, s, v, g4, state, tiles, plist, capacity,
+                         image, final_T, n_contrib, pid, pwp, pw, z4, xcd_mode, 1, lazy_state, lazy, masks, hdr_w);
     else
-      hipLaunchKernelGGL(lr_blend_fwd_kernel<false>, dim3(grid), dim3(256), lds_fwd, s, v, g4, state, tiles, plist, capacity,
-                         image, final_T, n_contrib, pid, pwp, pw, z4, xcd_mode, cull, lazy_state, lazy, masks, hdr_w);
+      hipLaunchKernelGGL(lr_blend_fwd_kernel<false>, dim3(grid), dim3(256), 0, s, v, g4, state, tiles, plist, capacity,
+                         image, final_T, n_contrib, pid, pwp, pw, z4, xcd_mode, 1, lazy_state, lazy, masks, hdr_w);
   }
   if (lazy != 2) lr_prof_end(LRK_BLEND_FWD, s);
 }
@@ -1179,35 +1150,30 @@ void lr_launch_blend_bwd(const LrView& v, const void* geom, const uint32_t* stat
                          const uint32_t* plist, uint32_t capacity, const float* final_T, const int* n_contrib,
                          const float* dL_dimage, float* acc_rows, int big_input, const uint64_t* masks, hipStream_t s) {
   LR_KNOB(xcd_mode, "LOGRAST_XCD_MODE", 3);
-  static const int cull = LR_EXPERIMENT_INT("LOGRAST_CULL", 1);   // experiment builds: 0 = no per-quadrant support test
-  static const size_t lds_bwd = (size_t)LR_EXPERIMENT_INT("LOGRAST_BLEND_BWD_LDS_KB", 0) * 1024;   // experiment builds: occupancy cap
   uint32_t grid = lr_blend_grid(tiles, v.gx, v.gy, xcd_mode);
   // LOGRAST_BWD_ROWS=1: the row-split form (the four 16-lane rows of a wave walk their own 4x4 blocks); 0: one
   // (Gaussian, quadrant) pair per visit; 2 (default): the caller's hint (lograst_view.walk_form: row-split for views of
   // tiny splats, few tile instances per Gaussian), else row-split on large inputs.  Measured, MI355X: 30 M tiny splats
-  // 949 -> 700 us, with random opacities 1768 -> 1259; C2's 1 M 292 -> 307; a tree-ordered heavy-tailed view 448 -> 579.  LOGRAST_BWD_ABLATE (timing experiments): 1 = no atomics in the row-split form.
+  // 949 -> 700 us, with random opacities 1768 -> 1259; C2's 1 M 292 -> 307; a tree-ordered heavy-tailed view 448 -> 579.
   LR_KNOB(rows_knob, "LOGRAST_BWD_ROWS", 2);
   const int rows = rows_knob != 2 ? rows_knob
                    : (v.walk_form == LOGRAST_FORM_ROWS ? 1 : (v.walk_form == LOGRAST_FORM_QUADRANT ? 0 : (big_input ? 1 : 0)));
-#ifdef LR_EXPERIMENTS
-  static const int ablate = lr_env_int("LOGRAST_BWD_ABLATE", 0);   // timing experiments: 1 = no atomics in the row-split form
-#endif
   LR_KNOB(block_test, "LOGRAST_BWD_BLOCK_TEST", 1);
   lr_prof_begin(LRK_BLEND_BWD, s);
   // the forward's hit masks serve a reverse walk of the SAME form only (v.mask_form: what the caller says its forward launched)
-  const bool use_masks = masks != nullptr && cull && v.mask_form == (rows ? (int)LR_MASK_FORM_ROWS : (int)LR_MASK_FORM_QUAD);
+  const bool use_masks = masks != nullptr && v.mask_form == (rows ? (int)LR_MASK_FORM_ROWS : (int)LR_MASK_FORM_QUAD);
   const float4* g4 = reinterpret_cast<const float4*>(geom);
   if (rows && use_masks)
-    hipLaunchKernelGGL(lr_blend_bwd_rows_kernel<true>, dim3(grid), dim3(256), lds_bwd, s, v, g4, state, tiles, plist, capacity,
-                       final_T, n_contrib, dL_dimage, acc_rows, xcd_mode, cull, block_test, masks LR_ABLATE_PASS(ablate));
+    hipLaunchKernelGGL(lr_blend_bwd_rows_kernel<true>, dim3(grid), dim3(256), 0, s, v, g4, state, tiles, plist, capacity,
+                       final_T, n_contrib, dL_dimage, acc_rows, xcd_mode, block_test, masks);
   else if (rows)
-    hipLaunchKernelGGL(lr_blend_bwd_rows_kernel<false>, dim3(grid), dim3(256), lds_bwd, s, v, g4, state, tiles, plist, capacity,
-                       final_T, n_contrib, dL_dimage, acc_rows, xcd_mode, cull, block_test, masks LR_ABLATE_PASS(ablate));
+    hipLaunchKernelGGL(lr_blend_bwd_rows_kernel<false>, dim3(grid), dim3(256), 0, s, v, g4, state, tiles, plist, capacity,
+                       final_T, n_contrib, dL_dimage, acc_rows, xcd_mode, block_test, masks);
   else if (use_masks)
-    hipLaunchKernelGGL(lr_blend_bwd_kernel<true>, dim3(grid), dim3(256), lds_bwd, s, v, g4, state, tiles, plist, capacity,
-                       final_T, n_contrib, dL_dimage, acc_rows, xcd_mode, cull, masks);
+    hipLaunchKernelGGL(lr_blend_bwd_kernel<true>, dim3(grid), dim3(256), 0, s, v, g4, state, tiles, plist, capacity,
+                       final_T, n_contrib, dL_dimage, acc_rows, xcd_mode, masks);
   else
-    hipLaunchKernelGGL(lr_blend_bwd_kernel<false>, dim3(grid), dim3(256), lds_bwd, s, v, g4, state, tiles, plist, capacity,
-                       final_T, n_contrib, dL_dimage, acc_rows, xcd_mode, cull, masks);
+    hipLaunchKernelGGL(lr_blend_bwd_kernel<false>, dim3(grid), dim3(256), 0, s, v, g4, state, tiles, plist, capacity,
+                       final_T, n_contrib, dL_dimage, acc_rows, xcd_mode, masks);
   lr_prof_end(LRK_BLEND_BWD, s);
 }

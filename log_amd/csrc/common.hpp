@@ -30,9 +30,7 @@
 // then offsets[Tp]: exclusive offsets (T+1 entries)                                   -- read by sort/blend
 //   cursor[T*S]   fill cursor for the big instances, initialised to offset + ranked
 // then order[T]: tile ids by descending list length (longest-first dispatch order for the blend kernels)
-#ifndef LR_CTR_STRIDE
 #define LR_CTR_STRIDE 16
-#endif
 #define LR_RANKED_TILES 4
 #define LR_HDR_WORDS 16
 #define LR_HDR_NUM 0
@@ -94,9 +92,7 @@ __host__ __device__ inline size_t lr_state_words(uint32_t tiles, uint32_t batche
 // lr_fill_staged_kernel (project.hip; the host's choice of its template parameter: api.hip): threads per workgroup = Gaussians
 // per thread-slot (measured at 30 M, two Gaussians per thread: 1024 threads 327 us, 512: 361-370, 256: 445), and the largest
 // tile grid whose slot-table row the workgroup stages in LDS
-#ifndef LR_FILL_STAGED_ROWS
 #define LR_FILL_STAGED_ROWS 1024
-#endif
 #define LR_FILL_STAGED_MAX_TILES 12288      // 48 KB of LDS
 #define LR_BATCH_MAX_TILES 40000  // 4 B x tiles of LDS counters must fit one workgroup (160 KB): up to 3840x2160
 #define LR_BATCH_LDS_BYTES (160 * 1024 - 512)  // dynamic LDS a projection workgroup may use (counter planes)
@@ -539,27 +535,17 @@ struct ActBwdArgs {
 };
 
 // ---- host-side launch bookkeeping (api.hip) ------------------------------------------------------
+// LRK_SORT_LARGE ("sort_large") keeps its number in the ABI's slot list (include/lograst.h) but no launch records it:
+// long lists are sorted under LRK_SORT_HUGE.  LRK_RESERVED times lr_count_huge_kernel ("count_huge").
 enum LrKernelSlot {
   LRK_RADIUS = 0, LRK_PROJECT, LRK_SCAN, LRK_FILL, LRK_SORT_SMALL, LRK_SORT_LARGE, LRK_SORT_HUGE,
   LRK_BLEND_FWD, LRK_BLEND_BWD, LRK_PROJECT_BWD, LRK_MISC, LRK_LOD, LRK_COUNTER, LRK_ADAM, LRK_HIST, LRK_GATHER, LRK_GATHER_BWD, LRK_RESERVED,
   LRK_REBASE, LRK_LAZY_TAIL   // LRK_LAZY_TAIL: the second sort + compositing pair of lazily ordered lists (normally idle)
 };
-// ---- experiment switches ---------------------------------------------------------------------------------------
-// Timing ablations (kernels that SKIP part of their work) and alternative algorithms kept for A/B measurements exist only
-// in builds made with -DLR_EXPERIMENTS (`python -m log_amd.build <variant> -DLR_EXPERIMENTS`, loaded through LOGRAST_LIB by
-// the scripts under tools/); the product library contains none of them: LR_EXPERIMENT_INT is its default, no kernel
-// takes an `ablate` argument, LR_ABLATED() is `false`.
-#ifdef LR_EXPERIMENTS
-#define LR_EXPERIMENT_INT(name, dflt) lr_env_int(name, dflt)
-#define LR_ABLATE_PARAM , int ablate
-#define LR_ABLATE_PASS(x) , x
-#define LR_ABLATED(bits) ((ablate & (bits)) != 0)
-#else
-#define LR_EXPERIMENT_INT(name, dflt) (dflt)
-#define LR_ABLATE_PARAM
-#define LR_ABLATE_PASS(x)
-#define LR_ABLATED(bits) false
-#endif
+// ---- profiling and environment (api.hip) -------------------------------------------------------------------------
+// Every kernel computes its full result: there are no timing ablations or compile-time algorithm switches.  Compiler
+// switches and alternative builds are compared as build variants (`python -m log_amd.build <variant> <flag>...`, loaded
+// through LOGRAST_LIB); paths that are chosen at run time are the knobs below.
 void lr_prof_begin(int slot, hipStream_t s);
 void lr_prof_end(int slot, hipStream_t s);
 int lr_env_int(const char* name, int dflt);

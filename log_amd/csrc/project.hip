@@ -353,31 +353,6 @@ LR_DEV void lr_reserve_batches(const uint32_t* lds_ctr, int stride, int t_lo, in
 //     v_permlane16_swap / v_permlane32_swap exchange two registers' halves in one instruction (16 instructions for the
 //     16 dwords; the DPP quad-permute form took ~100).  Afterwards lane (row r, column l) holds quad r of the records of
 //     Gaussians l, 16 + l, 32 + l, 48 + l of the wave: every store instruction writes 16 complete lines.
-// Stores of the projection's outputs (records: read next by the compositing kernels, a sort later; fill records: by the
-// fill kernel, after the scan).  LR_PROJECT_NT_STORES: as non-temporal (streaming) stores.
-typedef float lr_f4v __attribute__((ext_vector_type(4)));
-typedef uint32_t lr_u4w __attribute__((ext_vector_type(4)));
-LR_DEV void lr_out_store(float4* p, const float4& v) {
-#ifdef LR_PROJECT_NT_STORES
-  __builtin_nontemporal_store(lr_f4v{v.x, v.y, v.z, v.w}, reinterpret_cast<lr_f4v*>(p));
-#else
-  *p = v;
-#endif
-}
-LR_DEV void lr_out_store(uint4* p, const uint4& v) {
-#ifdef LR_PROJECT_NT_STORES
-  __builtin_nontemporal_store(lr_u4w{v.x, v.y, v.z, v.w}, reinterpret_cast<lr_u4w*>(p));
-#else
-  *p = v;
-#endif
-}
-LR_DEV void lr_out_store(int* p, int v) {
-#ifdef LR_PROJECT_NT_STORES
-  __builtin_nontemporal_store(v, p);
-#else
-  *p = v;
-#endif
-}
 // s_waitcnt immediate (gfx9 encoding): vmcnt in bits [3:0] + [15:14], expcnt [6:4] and lgkmcnt [11:8] left at "no wait"
 #define LR_WAIT_VMCNT(n) ((((n) & 15) | (((n) >> 4) << 14)) | (7 << 4) | (15 << 8))
 LR_DEV void lr_swap16(float& a, float& b) {
@@ -399,21 +374,12 @@ LR_DEV void lr_row_transpose(float4& a, float4& b, float4& c, float4& d) {
 
 // The four quads of the wave's 64 records, from one lane = one Gaussian to full 64-byte lines per store instruction.
 LR_DEV void lr_store_records(float4* __restrict__ rec, int lane, float4& g0, float4& g1, float4& g2, float4& g3) {
-#ifdef LR_PROJECT_QUAD_STORES
-  const int m = lane & 3, b = lane - m;
-  lr_quad_transpose(g0, g1, g2, g3, m);                    // g<k> = quad m of the record of lane (lane - m + k)
-  lr_out_store(&rec[LR_REC_QUADS * (b + 0) + m], g0);
-  lr_out_store(&rec[LR_REC_QUADS * (b + 1) + m], g1);
-  lr_out_store(&rec[LR_REC_QUADS * (b + 2) + m], g2);
-  lr_out_store(&rec[LR_REC_QUADS * (b + 3) + m], g3);
-#else
   lr_row_transpose(g0, g1, g2, g3);                        // g<k> = quad (lane >> 4) of the record of Gaussian 16 k + (lane & 15)
   const int l16 = lane & 15, r = lane >> 4;
-  lr_out_store(&rec[LR_REC_QUADS * l16 + r], g0);
-  lr_out_store(&rec[LR_REC_QUADS * (l16 + 16) + r], g1);
-  lr_out_store(&rec[LR_REC_QUADS * (l16 + 32) + r], g2);
-  lr_out_store(&rec[LR_REC_QUADS * (l16 + 48) + r], g3);
-#endif
+  rec[LR_REC_QUADS * l16 + r] = g0;
+  rec[LR_REC_QUADS * (l16 + 16) + r] = g1;
+  rec[LR_REC_QUADS * (l16 + 32) + r] = g2;
+  rec[LR_REC_QUADS * (l16 + 48) + r] = g3;
 }
 // means3D / scales / rotations (or the six covariance floats) of one Gaussian: what the first part of the loop consumes
 struct LrGeo { float p[3], s[3]; float4 q; };
@@ -430,31 +396,22 @@ LR_DEV uint32_t lr_after(uint32_t off, const float a[3], float b0, float b1, flo
   return off;
 }
 // wm / ws / wr / wc6: the arrays at the wave's first Gaussian (wave-uniform: scalar registers) + the lane's offset
-// (LR_PROJECT_NT_LOADS: the inputs -- read once per view -- as non-temporal loads; measured, no gain: profiles/r04_isa_project.md)
-LR_DEV float lr_in(const float* p) {
-#ifdef LR_PROJECT_NT_LOADS
-  return __builtin_nontemporal_load(p);
-#else
-  return *p;
-#endif
-}
+// (non-temporal loads of these inputs -- read once per view -- gave no gain: profiles/r04_isa_project.md)
+// The fill record is stored through a reference: the same store written as a struct assignment in the loop compiles to a
+// differently scheduled projection loop.
+LR_DEV void lr_store_fill_record(uint4* p, const uint4& fr) { *p = fr; }
 template <bool COV3D>
 LR_DEV LrGeo lr_load_geo(const float* __restrict__ wm, const float* __restrict__ ws, const float* __restrict__ wr,
                          const float* __restrict__ wc6, uint32_t ulane) {
   LrGeo g;
   const size_t lane = ulane;
-  g.p[0] = lr_in(wm + 3 * lane); g.p[1] = lr_in(wm + 3 * lane + 1); g.p[2] = lr_in(wm + 3 * lane + 2);
+  g.p[0] = wm[3 * lane]; g.p[1] = wm[3 * lane + 1]; g.p[2] = wm[3 * lane + 2];
   if (COV3D) {
     g.s[0] = wc6[6 * lane]; g.s[1] = wc6[6 * lane + 1]; g.s[2] = wc6[6 * lane + 2];
     g.q = float4{wc6[6 * lane + 3], wc6[6 * lane + 4], wc6[6 * lane + 5], 0.f};
   } else {
-    g.s[0] = lr_in(ws + 3 * lane); g.s[1] = lr_in(ws + 3 * lane + 1); g.s[2] = lr_in(ws + 3 * lane + 2);
-#ifdef LR_PROJECT_NT_LOADS
-    const lr_f4v q = __builtin_nontemporal_load(reinterpret_cast<const lr_f4v*>(wr) + lane);
-    g.q = float4{q.x, q.y, q.z, q.w};
-#else
+    g.s[0] = ws[3 * lane]; g.s[1] = ws[3 * lane + 1]; g.s[2] = ws[3 * lane + 2];
     g.q = reinterpret_cast<const float4*>(wr)[lane];
-#endif
   }
   return g;
 }
@@ -466,9 +423,7 @@ lr_project_batched_kernel(LrView v, int N, const float* __restrict__ means, cons
                           const float* __restrict__ colors, int* __restrict__ radii, float4* __restrict__ geom,
                           uint32_t* __restrict__ ranked, uint32_t* __restrict__ big, uint32_t* __restrict__ hdr,
                           uint32_t* __restrict__ basetab, uint32_t* __restrict__ hugemask, int tile_cull, int B,
-                          int S, int defer_tiles, int mid_coop, int mid_rank LR_ABLATE_PARAM) {
-  // (experiment builds, LOGRAST_PROJECT_ABLATE: 1 no record stores, 2 no fill-record / radii stores, 4 no ranking atomics,
-  //  8 no arithmetic -- the loop's loads and stores alone --, 16 no reservations at the end; results are garbage)
+                          int S, int defer_tiles, int mid_coop, int mid_rank) {
   extern __shared__ uint32_t lr_lds_ctr[];  // [S][tiles] packed (ranked | big << 16) counts, one plane per batch
   __shared__ uint32_t lr_huge_mask[LR_MAX_PLANES * LR_HUGE_WORDS];   // per batch: bit c = its 256-Gaussian chunk c deferred a rect
   __shared__ uint32_t lr_rank_dummy[64];    // where the ranking atomics of tiles that are not ranked go (see the loop)
@@ -495,10 +450,6 @@ lr_project_batched_kernel(LrView v, int N, const float* __restrict__ means, cons
   const uint32_t ulane = (uint32_t)min(lane, N - 1);
   const int last_first = max(N - 64, 0);
   int iw = i_begin + wave * 64;                              // the wave's first Gaussian of this iteration (scalar)
-  int istep = LR_BATCH_THREADS, iend = i_end;
-  if (LR_ABLATED(32)) {   // experiment builds: workgroups interleaved 1024 Gaussians at a time (wrong lists: timing only)
-    iw = (int)blockIdx.x * LR_BATCH_THREADS + wave * 64; istep = (int)gridDim.x * LR_BATCH_THREADS; iend = N;
-  }
   // plane of the iteration = (iw - i_begin) / B (B is a multiple of the workgroup size): counted, not divided
   int plane = 0, left_in_plane = B / LR_BATCH_THREADS;
   const float* const cov6 = v.cov3d;
@@ -519,24 +470,7 @@ lr_project_batched_kernel(LrView v, int N, const float* __restrict__ means, cons
   // (the first inputs are "used" here, i.e. waited for in front of the loop: see the wait at the loop's end)
   asm volatile("" : "+v"(geo.p[0]), "+v"(geo.p[1]), "+v"(geo.p[2]), "+v"(geo.s[0]), "+v"(geo.s[1]), "+v"(geo.s[2]),
                "+v"(geo.q.x), "+v"(geo.q.y), "+v"(geo.q.z), "+v"(geo.q.w), "+v"(nx_op), "+v"(nx_c0), "+v"(nx_c1), "+v"(nx_c2));
-#ifdef LR_EXPERIMENTS
-  // bits 8 + 64: memory accesses only, and every wave streams TWO blocks per iteration (its own and one half a workgroup
-  // range further on), each prefetched an iteration ahead: twice the bytes in flight per wave -- is the loop bound by
-  // memory-level parallelism?
-  LrGeo geo2 = geo;
-  float sx_op = 0.f, sx_c0 = 0.f, sx_c1 = 0.f, sx_c2 = 0.f;
-  int half = 0;
-  if (LR_ABLATED(64)) {
-    half = ((i_end - i_begin) / 2) / LR_BATCH_THREADS * LR_BATCH_THREADS;
-    iend = i_begin + half;
-    const size_t j0 = (size_t)lr_sgpr((uint32_t)min(iw + half, last_first));
-    geo2 = lr_load_geo<COV3D>(means + 3 * j0, scales + 3 * j0, rots + 4 * j0, COV3D ? cov6 + 6 * j0 : nullptr, ulane);
-    sx_op = (opac + j0)[ulane];
-    sx_c0 = (colors + 3 * j0)[3 * (size_t)ulane]; sx_c1 = (colors + 3 * j0)[3 * (size_t)ulane + 1];
-    sx_c2 = (colors + 3 * j0)[3 * (size_t)ulane + 2];
-  }
-#endif
-  for (; iw + 64 <= iend; iw += istep) {
+  for (; iw + 64 <= i_end; iw += LR_BATCH_THREADS) {
     const size_t iws = (size_t)lr_sgpr((uint32_t)iw);        // (scalar) the Gaussian of lane 0
     if (left_in_plane == 0) { plane++; left_in_plane = B / LR_BATCH_THREADS; }
     left_in_plane--;
@@ -564,40 +498,13 @@ lr_project_batched_kernel(LrView v, int N, const float* __restrict__ means, cons
     const uint32_t olane = lr_after(ulane, e.t, hx, hy, hw, Sg);
     const float in_op = nx_op, in_c0 = nx_c0, in_c1 = nx_c1, in_c2 = nx_c2;
     {
-      const size_t in = (size_t)lr_sgpr((uint32_t)min(iw + istep, last_first));   // (past the workgroup's end: loaded, never used)
-      nx_op = lr_in(opac + in + olane);
+      const size_t in = (size_t)lr_sgpr((uint32_t)min(iw + LR_BATCH_THREADS, last_first));   // (past the workgroup's end: loaded, never used)
+      nx_op = (opac + in)[olane];
       const float* __restrict__ wc = colors + 3 * in;
-      nx_c0 = lr_in(wc + 3 * (size_t)olane); nx_c1 = lr_in(wc + 3 * (size_t)olane + 1); nx_c2 = lr_in(wc + 3 * (size_t)olane + 2);
+      nx_c0 = wc[3 * (size_t)olane]; nx_c1 = wc[3 * (size_t)olane + 1]; nx_c2 = wc[3 * (size_t)olane + 2];
       geo = lr_load_geo<COV3D>(means + 3 * in, scales + 3 * in, rots + 4 * in, COV3D ? cov6 + 6 * in : nullptr, olane);
     }
     // ---- part 2: EWA, conic, radius, rect ----
-    if (LR_ABLATED(8)) {   // experiment builds: the loop's memory accesses with next to no arithmetic behind them
-      float4 a0 = {e.t[0], e.t[1], hx, hy}, a1 = {hw, Sg[0], in_op, in_c0}, a2 = {in_c1, in_c2, Sg[1], Sg[2]},
-             a3 = {Sg[3], Sg[4], Sg[5], tz};
-      if (!LR_ABLATED(2)) {
-        lr_out_store(&(radii + iws)[lane], (int)__float_as_uint(hx) & 1);
-        lr_out_store(&(fillrec + iws)[lane], uint4{__float_as_uint(tz), 0xffffffffu, 0u, 0u});
-      }
-      if (!LR_ABLATED(1)) lr_store_records(geom + LR_REC_QUADS * iws, lane, a0, a1, a2, a3);
-#ifdef LR_EXPERIMENTS
-      if (LR_ABLATED(64)) {
-        const size_t js = (size_t)lr_sgpr((uint32_t)min(iw + half, last_first));
-        float4 b0 = {geo2.p[0], geo2.p[1], geo2.p[2], geo2.s[0]}, b1 = {geo2.s[1], geo2.s[2], geo2.q.x, geo2.q.y},
-               b2 = {geo2.q.z, geo2.q.w, sx_op, sx_c0}, b3 = {sx_c1, sx_c2, 0.f, 0.f};
-        const size_t jn = (size_t)lr_sgpr((uint32_t)min(iw + istep + half, last_first));
-        sx_op = (opac + jn)[ulane];
-        sx_c0 = (colors + 3 * jn)[3 * (size_t)ulane]; sx_c1 = (colors + 3 * jn)[3 * (size_t)ulane + 1];
-        sx_c2 = (colors + 3 * jn)[3 * (size_t)ulane + 2];
-        geo2 = lr_load_geo<COV3D>(means + 3 * jn, scales + 3 * jn, rots + 4 * jn, COV3D ? cov6 + 6 * jn : nullptr, ulane);
-        if (!LR_ABLATED(2)) {
-          lr_out_store(&(radii + js)[lane], (int)__float_as_uint(b0.x) & 1);
-          lr_out_store(&(fillrec + js)[lane], uint4{__float_as_uint(b0.y), 0xffffffffu, 0u, 0u});
-        }
-        if (!LR_ABLATED(1)) lr_store_records(geom + LR_REC_QUADS * js, lane, b0, b1, b2, b3);
-      }
-#endif
-      continue;
-    }
     bool valid = tz > 0.2f;
     const float pw = 1.0f / (hw + 0.0000001f);
     const float nx = hx * pw, ny = hy * pw;
@@ -647,13 +554,10 @@ lr_project_batched_kernel(LrView v, int N, const float* __restrict__ means, cons
       // was followed by its own `s_waitcnt lgkmcnt(0)`: four dependent LDS round trips): a tile that is not ranked sends
       // its lane to the lane's own dummy word instead (64 words, shared by the workgroup's waves: never read)
       uint32_t* const dummy = lr_rank_dummy + lane;
-      uint32_t a0 = 0u, a1 = 0u, a2 = 0u, a3 = 0u;
-      if (!LR_ABLATED(4)) {
-        a0 = atomicAdd(r0 ? &ctr[t0] : dummy, 1u) & 0xffffu;
-        a1 = atomicAdd(r1 ? &ctr[t0 + ty1 * v.gx + tx1] : dummy, 1u) & 0xffffu;
-        a2 = atomicAdd(r2 ? &ctr[t0 + ty2 * v.gx + tx2] : dummy, 1u) & 0xffffu;
-        a3 = atomicAdd(r3 ? &ctr[t0 + ty3 * v.gx + tx3] : dummy, 1u) & 0xffffu;
-      }
+      const uint32_t a0 = atomicAdd(r0 ? &ctr[t0] : dummy, 1u) & 0xffffu;
+      const uint32_t a1 = atomicAdd(r1 ? &ctr[t0 + ty1 * v.gx + tx1] : dummy, 1u) & 0xffffu;
+      const uint32_t a2 = atomicAdd(r2 ? &ctr[t0 + ty2 * v.gx + tx2] : dummy, 1u) & 0xffffu;
+      const uint32_t a3 = atomicAdd(r3 ? &ctr[t0 + ty3 * v.gx + tx3] : dummy, 1u) & 0xffffu;
       if (small) {
         slot0 = r0 ? a0 : 0xffffffffu;
         slot1 = nt > 1 ? (r1 ? a1 : 0xffffffffu) : 0u;
@@ -713,20 +617,18 @@ lr_project_batched_kernel(LrView v, int N, const float* __restrict__ means, cons
     float4 g1 = float4{cC, in_op, in_c0, in_c1};
     float4 g2 = float4{in_c2, tz, __uint_as_float(valid ? r0w : 0u), __uint_as_float(valid ? r1w : 0u)};
     float4 g3 = float4{__uint_as_float(slot0), __uint_as_float(slot1), __uint_as_float(slot2), __uint_as_float(slot3)};
-    if (!LR_ABLATED(2)) {
-      lr_out_store(&(radii + iws)[lane], rad);
-      // fill record (see lr_fill_record): ranks as 16-bit halves, 0xffff = dropped by the support cull
-      const uint32_t h = (uint32_t)(y1 - y0);
-      uint4 fr;
-      fr.x = __float_as_uint(tz);
-      fr.y = !valid ? 0xffffffffu
-                    : (small ? ((uint32_t)x0 | ((uint32_t)y0 << 13) | ((uint32_t)(w - 1) << 26) | ((h - 1u) << 28))
-                             : ((uint32_t)x0 | ((uint32_t)y0 << 13) | (1u << 30) | (mrow >= 0 ? (1u << 31) : 0u)));
-      fr.z = !valid ? 0u : (small ? ((slot0 & 0xffffu) | (slot1 << 16)) : r1w);
-      fr.w = (valid && small) ? ((slot2 & 0xffffu) | (slot3 << 16)) : (mrow >= 0 ? (uint32_t)mrow : 0u);   // bit 31 of y: w = rank row
-      lr_out_store(&(fillrec + iws)[lane], fr);
-    }
-    if (!LR_ABLATED(1)) lr_store_records(geom + LR_REC_QUADS * iws, lane, g0, g1, g2, g3);   // (scalar base + lane offset)
+    (radii + iws)[lane] = rad;
+    // fill record (see lr_fill_record): ranks as 16-bit halves, 0xffff = dropped by the support cull
+    const uint32_t h = (uint32_t)(y1 - y0);
+    uint4 fr;
+    fr.x = __float_as_uint(tz);
+    fr.y = !valid ? 0xffffffffu
+                  : (small ? ((uint32_t)x0 | ((uint32_t)y0 << 13) | ((uint32_t)(w - 1) << 26) | ((h - 1u) << 28))
+                           : ((uint32_t)x0 | ((uint32_t)y0 << 13) | (1u << 30) | (mrow >= 0 ? (1u << 31) : 0u)));
+    fr.z = !valid ? 0u : (small ? ((slot0 & 0xffffu) | (slot1 << 16)) : r1w);
+    fr.w = (valid && small) ? ((slot2 & 0xffffu) | (slot3 << 16)) : (mrow >= 0 ? (uint32_t)mrow : 0u);   // bit 31 of y: w = rank row
+    lr_store_fill_record(&(fillrec + iws)[lane], fr);
+    lr_store_records(geom + LR_REC_QUADS * iws, lane, g0, g1, g2, g3);   // (scalar base + lane offset)
     // The next iteration's inputs were requested BEFORE this iteration's six stores: "at most six memory instructions
     // outstanding" says they have arrived and leaves the stores in flight.  Said here, because at the loop's top the
     // wait-count pass merges this path with the preheader's (where the same loads are the LAST instructions issued) into
@@ -736,7 +638,7 @@ lr_project_batched_kernel(LrView v, int N, const float* __restrict__ means, cons
     __builtin_amdgcn_s_waitcnt(LR_WAIT_VMCNT(6));
     __builtin_amdgcn_sched_barrier(0);
   }
-  if (iw < i_end && !LR_ABLATED(32)) {
+  if (iw < i_end) {
     // the partial wave (at most one in the whole grid: the end of the array) -- lr_project_one, the code of the other
     // projection kernels: the same op sequences, so the same records bit for bit
     const int i = iw + lane;
@@ -760,8 +662,7 @@ lr_project_batched_kernel(LrView v, int N, const float* __restrict__ means, cons
   }
   __syncthreads();
   const int nplanes = min(S, (i_end - i_begin + B - 1) / B);   // batches this workgroup really holds
-  if (!LR_ABLATED(16))
-    lr_reserve_batches(lr_lds_ctr, tiles, 0, tiles, nplanes, tiles, ranked, big, basetab + (size_t)blockIdx.x * S * tiles);
+  lr_reserve_batches(lr_lds_ctr, tiles, 0, tiles, nplanes, tiles, ranked, big, basetab + (size_t)blockIdx.x * S * tiles);
   if ((int)threadIdx.x < nplanes * LR_HUGE_WORDS) {   // complete: the barrier after the Gaussian loop
     const uint32_t mw = lr_huge_mask[threadIdx.x];
     hugemask[(size_t)blockIdx.x * S * LR_HUGE_WORDS + threadIdx.x] = mw;   // (every word of every batch is written: nothing to clear)
@@ -806,7 +707,7 @@ lr_project_band_kernel(LrView v, int N, const float* __restrict__ means, const f
                        const float* __restrict__ colors, int* __restrict__ radii, float4* __restrict__ geom,
                        uint32_t* __restrict__ ranked, uint32_t* __restrict__ big, uint32_t* __restrict__ hdr,
                        uint32_t* __restrict__ basetab, uint32_t* __restrict__ hugemask,
-                       uint32_t* __restrict__ survcount, int tile_cull, int B, int S, int defer_tiles LR_ABLATE_PARAM) {
+                       uint32_t* __restrict__ survcount, int tile_cull, int B, int S, int defer_tiles) {
   extern __shared__ uint32_t lr_lds_ctr[];  // [S][band tiles] packed (ranked | big << 16) counts, one plane per batch
   // which 256-SLOT chunks of the workgroup's fill-record range hold a deferred rect (lr_count_huge_kernel walks slots):
   // the words of "batch" p = slots [p B, (p + 1) B) of the range
@@ -849,9 +750,7 @@ lr_project_band_kernel(LrView v, int N, const float* __restrict__ means, const f
       int rad = 0;
       if (mine) {
         LrRect rc;
-        if (LR_ABLATED(2)) rad = (in.p[0] + in.s[1] + in.q.z == 1.2345e30f) ? 1 : 0;   // experiment builds: loads only
-        else if (lr_project_rect(v, in, rc)) rad = rc.rad;
-        if (LR_ABLATED(1)) rad = 0;                                                      // experiment builds: no phase B
+        if (lr_project_rect(v, in, rc)) rad = rc.rad;
         radii[i] = rad;
       }
       const uint64_t rect_mask = __ballot(rad > 0);
@@ -1093,9 +992,6 @@ void lr_launch_project(const LrView& v, int N, const float* means, const float* 
     uint32_t* hugecount = basetab + (size_t)batches * tiles;   // (hugemask[batches][LR_HUGE_WORDS]: common.hpp)
     LR_KNOB(mid_coop, "LOGRAST_MID_COOP", 16);
     LR_KNOB(mid_rank, "LOGRAST_MID_RANK", 1);
-#ifdef LR_EXPERIMENTS
-    static const int ablate = lr_env_int("LOGRAST_PROJECT_ABLATE", 0);   // timing experiments (tools/): see the band kernel
-#endif
     if (lr_band_sparse(v, batch)) {
       // planes over the band's tiles only: as many batches per workgroup as fit beside the rings (at most 4)
       const int band_tiles = (v.ty1 - v.ty0) * v.gx;
@@ -1105,16 +1001,16 @@ void lr_launch_project(const LrView& v, int N, const float* means, const float* 
       hipLaunchKernelGGL(lr_project_band_kernel, dim3(bgroups), dim3(LR_BATCH_THREADS),
                          sizeof(uint32_t) * (size_t)band_tiles * bp, s, v, N, means, scales, rots, opac, colors, radii,
                          reinterpret_cast<float4*>(geom), ranked, big, hdr, basetab, hugecount,
-                         hugecount + lr_hugemask_words((uint32_t)batches), tile_cull, batch, bp, defer_tiles LR_ABLATE_PASS(ablate));
+                         hugecount + lr_hugemask_words((uint32_t)batches), tile_cull, batch, bp, defer_tiles);
     } else {
       if (v.cov3d)
         hipLaunchKernelGGL(lr_project_batched_kernel<true>, dim3(groups), dim3(LR_BATCH_THREADS), lds * planes, s, v, N,
                            means, scales, rots, opac, colors, radii, reinterpret_cast<float4*>(geom), ranked, big, hdr,
-                           basetab, hugecount, tile_cull, batch, planes, defer_tiles, mid_coop, mid_rank LR_ABLATE_PASS(ablate));
+                           basetab, hugecount, tile_cull, batch, planes, defer_tiles, mid_coop, mid_rank);
       else
         hipLaunchKernelGGL(lr_project_batched_kernel<false>, dim3(groups), dim3(LR_BATCH_THREADS), lds * planes, s, v, N,
                            means, scales, rots, opac, colors, radii, reinterpret_cast<float4*>(geom), ranked, big, hdr,
-                           basetab, hugecount, tile_cull, batch, planes, defer_tiles, mid_coop, mid_rank LR_ABLATE_PASS(ablate));
+                           basetab, hugecount, tile_cull, batch, planes, defer_tiles, mid_coop, mid_rank);
     }
     lr_prof_end(LRK_PROJECT, s);
     lr_prof_begin(LRK_RESERVED, s);
@@ -1349,7 +1245,7 @@ template <typename SlotOf>
 LR_DEV void lr_fill_big_rect(const float4* __restrict__ geom, int i, int x0, int y0, int w, int h, int nt, uint64_t key,
                              int gx, bool tile_cull, uint32_t* __restrict__ cursor, uint64_t* __restrict__ keys, int lane,
                              int mid_coop, bool rmid, int mrow, const uint16_t* __restrict__ midrank, uint32_t batch,
-                             SlotOf&& slot_of LR_ABLATE_PARAM) {
+                             SlotOf&& slot_of) {
   const int y1 = y0 + h, x1 = x0 + w;
   LrSupport sup = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 1};  // mode 1: every tile of the rect
   if (nt > LR_RANKED_TILES && tile_cull && !rmid) {
@@ -1365,7 +1261,7 @@ LR_DEV void lr_fill_big_rect(const float4* __restrict__ geom, int i, int x0, int
       if (r != 0xffffu) keys[slot_of(ty * gx + tx, (uint32_t)lo) + r] = ((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo;
     });
   }
-  const bool mid = !rmid && nt > LR_RANKED_TILES && nt <= LR_COOP_TILES && !LR_ABLATED(4);
+  const bool mid = !rmid && (nt > LR_RANKED_TILES && nt <= LR_COOP_TILES);
   if (mid_coop) {   // the wave expands its 5..16-tile rects together, four per pass (lr_mid_rects)
     if (__builtin_amdgcn_ballot_w64(mid) != 0) {
       lr_mid_rects<true>(mid, x0, y0, w, nt, sup, 0, klo, khi, [&](int, int ty, int tx, bool keep, int, int lo, int hi) {
@@ -1383,7 +1279,7 @@ LR_DEV void lr_fill_big_rect(const float4* __restrict__ geom, int i, int x0, int
           keys[pos] = key;
         }
   }
-  uint64_t bigm = __ballot(nt > LR_COOP_TILES && !LR_ABLATED(8));
+  uint64_t bigm = __ballot(nt > LR_COOP_TILES);
   while (bigm) {
     int src = __builtin_ctzll(bigm);
     bigm &= bigm - 1;
@@ -1413,7 +1309,7 @@ __global__ void __launch_bounds__(256)
 lr_fill_kernel(int N, int gx, const float4* __restrict__ geom, uint32_t* __restrict__ state, uint32_t tiles,
                uint64_t* __restrict__ keys, uint32_t capacity, uint32_t max_len_hint, uint32_t* __restrict__ status,
                float* __restrict__ zero_n, float* __restrict__ zero_block, int zero_block_floats, int xcd_order, int stream_nt,
-               int rebased, int speculative, int mid_coop LR_ABLATE_PARAM) {
+               int rebased, int speculative, int mid_coop) {
   // Per-Gaussian buffers that later kernels accumulate into with atomics (point_weight; the backward scratch)
   // are cleared here, in a kernel that already has one thread per Gaussian, instead of by separate memsets.
   // XCD-contiguous block order (speed only): blocks are dispatched round-robin over the 8 XCDs (block b -> XCD b % 8,
@@ -1437,7 +1333,7 @@ lr_fill_kernel(int N, int gx, const float4* __restrict__ geom, uint32_t* __restr
 #pragma unroll
     for (int u = 0; u < K; u++) {
       const int zi = (int)(vblock_k[u] * 256u + threadIdx.x);
-      if (zi < N && !LR_ABLATED(1)) {
+      if (zi < N) {
         if (stream_nt) {
           if (zero_n) __builtin_nontemporal_store(0.f, &zero_n[zi]);
           for (int k = 0; k < zero_block_floats; k++) __builtin_nontemporal_store(0.f, &zero_block[(size_t)k * N + zi]);
@@ -1539,7 +1435,7 @@ lr_fill_kernel(int N, int gx, const float4* __restrict__ geom, uint32_t* __restr
         const int t = (y0 + ty) * gx + (x0 + tx);
         // batched: slot relative to the batch's run in the tile; lr_rebase_kernel (large inputs) made the table absolute
         const uint32_t pos = (batch ? (rebased ? bbase[t] : offsets[t] + bbase[t]) : offsets[t]) + slot[k];
-        if (!LR_ABLATED(2) || pos == 0xffffffffu) keys[pos] = key;
+        keys[pos] = key;
       }
     }
   }
@@ -1547,7 +1443,7 @@ lr_fill_kernel(int N, int gx, const float4* __restrict__ geom, uint32_t* __restr
                    [&](int t, uint32_t owner) -> uint32_t {
                      const uint32_t* __restrict__ bb = state + lr_basetab_off(tiles) + (size_t)(owner / batch) * tiles;
                      return rebased ? bb[t] : offsets[t] + bb[t];
-                   } LR_ABLATE_PASS(ablate));
+                   });
   }
 }
 
@@ -1564,7 +1460,7 @@ __global__ void __launch_bounds__(LR_FILL_STAGED_ROWS, 8)   // 64 VGPRs: 2048 th
 lr_fill_staged_kernel(int N, int gx, const float4* __restrict__ geom, uint32_t* __restrict__ state, uint32_t tiles,
                       uint64_t* __restrict__ keys, uint32_t capacity, uint32_t max_len_hint, uint32_t* __restrict__ status,
                       float* __restrict__ zero_n, float* __restrict__ zero_block, int zero_block_floats, int xcd_order,
-                      int rebased, int speculative, int mid_coop LR_ABLATE_PARAM) {
+                      int rebased, int speculative, int mid_coop) {
   extern __shared__ uint32_t lr_slot_row[];                       // [tiles]: absolute first slot of this batch's run in every tile
   const uint32_t per_xcd = gridDim.x >> 3;                        // grid is a multiple of 8 (XCD-contiguous order: lr_fill_kernel)
   const uint32_t vblock = xcd_order ? (blockIdx.x & 7u) * per_xcd + (blockIdx.x >> 3) : blockIdx.x;
@@ -1579,10 +1475,8 @@ lr_fill_staged_kernel(int N, int gx, const float4* __restrict__ geom, uint32_t* 
     const uint32_t e = first + u * LR_FILL_STAGED_ROWS + threadIdx.x;
     fr_k[u] = uint4{0u, 0xffffffffu, 0u, 0u};
     if (e < (uint32_t)N) {
-      if (!LR_ABLATED(1)) {                                       // (small inputs: the zero-fills live here, see lr_fill_kernel)
-        if (zero_n) zero_n[e] = 0.f;
-        for (int k = 0; k < zero_block_floats; k++) zero_block[(size_t)k * N + e] = 0.f;
-      }
+      if (zero_n) zero_n[e] = 0.f;                                // (small inputs: the zero-fills live here, see lr_fill_kernel)
+      for (int k = 0; k < zero_block_floats; k++) zero_block[(size_t)k * N + e] = 0.f;
       if (!over) {
         typedef uint32_t lr_u4v __attribute__((ext_vector_type(4)));
         const lr_u4v t4 = __builtin_nontemporal_load(reinterpret_cast<const lr_u4v*>(fillrec + e));
@@ -1652,18 +1546,16 @@ lr_fill_staged_kernel(int N, int gx, const float4* __restrict__ geom, uint32_t* 
       const uint32_t p1 = (nt > 1 && h1 != 0xffffu) ? lr_slot_row[t0 + d1] + h1 : 0xffffffffu;
       const uint32_t p2 = (nt > 2 && h2 != 0xffffu) ? lr_slot_row[t0 + d2] + h2 : 0xffffffffu;
       const uint32_t p3 = (nt > 3 && h3 != 0xffffu) ? lr_slot_row[t0 + d3] + h3 : 0xffffffffu;
-      if (!LR_ABLATED(2)) {
-        if (p0 != 0xffffffffu) keys[p0] = key;
-        if (p1 != 0xffffffffu) keys[p1] = key;
-        if (p2 != 0xffffffffu) keys[p2] = key;
-        if (p3 != 0xffffffffu) keys[p3] = key;
-      }
+      if (p0 != 0xffffffffu) keys[p0] = key;
+      if (p1 != 0xffffffffu) keys[p1] = key;
+      if (p2 != 0xffffffffu) keys[p2] = key;
+      if (p3 != 0xffffffffu) keys[p3] = key;
     }
     // (Rects of more than four tiles, measured and removed: counting the workgroup's instances per tile in LDS first, ONE
     // cursor atomic per touched tile, a second walk placing the keys -- the C3 view's fill 426 -> 545 us: 2048 consecutive
     // rows of a level-of-detail selection do not share enough tiles to pay for two walks of support tests.)
     lr_fill_big_rect(geom, i, x0, y0, w, h_k[u], nt, key, gx, tile_cull, cursor, keys, lane, mid_coop, rmid_k[u], (int)hB_k[u],
-                     midrank, batch, [&](int t, uint32_t) -> uint32_t { return lr_slot_row[t]; } LR_ABLATE_PASS(ablate));
+                     midrank, batch, [&](int t, uint32_t) -> uint32_t { return lr_slot_row[t]; });
   }
 }
 
@@ -1675,9 +1567,6 @@ void lr_launch_fill(int N, int gx, const void* geom, uint32_t* state, uint32_t t
   LR_KNOB(xcd_order, "LOGRAST_FILL_XCD_ORDER", 1);
   LR_KNOB(fill_nt, "LOGRAST_FILL_NT", 1);
   LR_KNOB(mid_coop, "LOGRAST_MID_COOP", 16);
-#ifdef LR_EXPERIMENTS
-  static const int ablate = lr_env_int("LOGRAST_FILL_ABLATE", 0);   // timing experiments (tools/): 1 no zero-fill, 2 no key stores, 4 no 5-16-tile rects, 8 no larger rects
-#endif
   if (staged_k > 0) {   // (decided by the caller -- api.hip: lr_fill_staged_k -- because stage 1 has to know it too: no lr_rebase_kernel then)
     static bool attr_set = false;
     if (!attr_set) {
@@ -1695,7 +1584,7 @@ void lr_launch_fill(int N, int gx, const void* geom, uint32_t* state, uint32_t t
 #define LR_FILL_ST(KK) hipLaunchKernelGGL(lr_fill_staged_kernel<KK>, dim3(blocks), dim3(LR_FILL_STAGED_ROWS),                 \
                        sizeof(uint32_t) * ((tiles + 3u) & ~3u), s, N, gx, reinterpret_cast<const float4*>(geom), state, tiles,  \
                        keys, capacity, max_len_hint, status, zero_n, zero_block, zero_block_floats, xcd_order, rebased,         \
-                       speculative, mid_coop LR_ABLATE_PASS(ablate))
+                       speculative, mid_coop)
     if (K >= 3) LR_FILL_ST(3); else if (K == 2) LR_FILL_ST(2); else LR_FILL_ST(1);   // (four per thread: 40 bytes of scratch at the kernel's 64 VGPRs)
 #undef LR_FILL_ST
     lr_prof_end(LRK_FILL, s);
@@ -1706,7 +1595,7 @@ void lr_launch_fill(int N, int gx, const void* geom, uint32_t* state, uint32_t t
 #define LR_FILL(K) do { const int blocks = (((N + 255) / 256 + K - 1) / K + 7) & ~7;                                     \
     hipLaunchKernelGGL(lr_fill_kernel<K>, dim3(blocks), dim3(256), 0, s, N, gx, reinterpret_cast<const float4*>(geom),  \
                        state, tiles, keys, capacity, max_len_hint, status, zero_n, zero_block, zero_block_floats,       \
-                       xcd_order, fill_nt, rebased, speculative, mid_coop LR_ABLATE_PASS(ablate)); } while (0)
+                       xcd_order, fill_nt, rebased, speculative, mid_coop); } while (0)
   // measured, K = 1 / 2 / 4: the 30 M view 388 / 413 / 424 us; a band view (100 M, a fifth of the slots used: most
   // workgroups only pass through the chain once) 618 / 551 / 510 us
   if (band) per_thread = 4;

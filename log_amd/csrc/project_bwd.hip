@@ -197,9 +197,7 @@ LR_DEV void lr_pbwd_live_row(const LrView& v, int i, const float* means, const f
 // COMPACTED into an LDS list and the chain rule (~600 VALU instructions per row) then runs on full waves: with 15 % of
 // the rows live (30 M Gaussians, opacity 0.999) every wave of a one-thread-per-Gaussian kernel still met a live lane and
 // ran all of it at 15 % lane occupancy (VALU busy 71 % of the launch).
-#ifndef LR_PBWD_ROWS
 #define LR_PBWD_ROWS 1024
-#endif
 // AOS (lograst_backward): the reverse walk's nine sums of a Gaussian sit in ONE 64-byte row of `rows` (slots: 0-1 mean
 // x y, 2-4 conic A B C, 5 opacity, 6-8 colour r g b: include/lograst.h LOGRAST_BWD_ROW_FLOATS) -- a memory-side atomic
 // costs one operation per 64-byte LINE whatever the number of lanes in it (tools/micro/atomic_lines.hip: 17-21 G lines/s

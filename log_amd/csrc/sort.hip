@@ -2,7 +2,7 @@
 // (tile|depth) keys + identifyTileRanges: tiles are already separated by the bucket fill, so each tile's
 // (depth,id) keys are sorted independently, one workgroup per tile: a depth-bucket distribution sort (O(L)), with a
 // register-blocked bitonic network (ascending-only comparators, lists padded with +inf to a power of two) as the
-// fallback for depths no bucket map can spread and as the LOGRAST_BUCKET_SORT=0 reference of the same total order.
+// fallback for depths no bucket map can spread.
 // Keys are unique (the Gaussian index is the low word), hence the order is total and equals the
 // stable (tile, depth) order of index-ordered input.  Output: point_list[I] = Gaussian ids.
 #include "common.hpp"
@@ -113,7 +113,7 @@ LR_DEV void lr_lds_sort(uint64_t* s, uint32_t P2, uint32_t tid) {
 // the image plane: identical depths), so it only has to be correct and not absurd: it runs inside the workgroup that
 // found the list unsortable by buckets -- no extra launches (a separate multi-workgroup version of the same passes cost
 // every view eight launches of idle workgroups, 54 us at 30 M Gaussians, to be there for the rare tile that needs it).
-// s: LDS, lr_sort_lds_bytes(LR_SORT_BLOCK) bytes.  All NT threads call; workgroup-scope visibility of the global
+// s: LDS for one block in network layout, (LR_SORT_BLOCK + LR_SORT_BLOCK / 8) keys.  All NT threads call; workgroup-scope visibility of the global
 // stores between passes comes from the barriers (one workgroup = one CU = one vector L1).
 template <int NT>
 LR_DEV void lr_wg_hybrid_sort(uint64_t* __restrict__ a, uint32_t L, uint64_t* s, uint32_t tid) {
@@ -158,26 +158,6 @@ LR_DEV void lr_wg_hybrid_sort(uint64_t* __restrict__ a, uint32_t L, uint64_t* s,
 }
 static_assert(LR_SORT_BLOCK == 8192, "lr_wg_hybrid_sort hard-codes the top stride exponent of a block");
 
-// Tiles with lo < L <= hi: the whole list in one workgroup's LDS.
-template <int NT>
-__global__ void __launch_bounds__(NT)
-lr_sort_rb_kernel(const uint32_t* __restrict__ state, uint32_t tiles, const uint64_t* __restrict__ keys,
-                  uint32_t* __restrict__ plist, uint32_t lo, uint32_t hi, uint32_t capacity) {
-  extern __shared__ __attribute__((aligned(16))) uint64_t s[];
-  if (lr_bail(state, capacity)) return;
-  const uint32_t* offsets = state + lr_offsets_off(tiles);
-  const uint32_t tile = blockIdx.x;
-  const uint32_t beg = offsets[tile], L = offsets[tile + 1] - beg;
-  if (L <= lo || L > hi) return;
-  const uint32_t tid = threadIdx.x;
-  uint32_t P2 = 8;
-  while (P2 < L) P2 <<= 1;
-  for (uint32_t i = tid; i < P2; i += NT) s[lr_phys(i)] = i < L ? keys[beg + i] : ~0ull;
-  __syncthreads();
-  lr_lds_sort<NT>(s, P2, tid);
-  for (uint32_t i = tid; i < L; i += NT) plist[beg + i] = (uint32_t)s[lr_phys(i)];
-}
-
 // ---- depth-bucket path -----------------------------------------------------------------------------------------
 // The keys of a tile are (depth, id) with depths spread over the tile's depth range, so a distribution sort does in
 // O(L) what the network does in O(L log^2 L): one workgroup per tile,
@@ -219,13 +199,14 @@ LR_DEV uint32_t lr_depth_bucket(const LrDepthMap& m, uint32_t dbits) {
 }
 // Built by the whole workgroup: cellcnt[LR_CELLS] must be zero and hold the sample histogram on entry (filled with
 // lr_depth_cell on a map whose table is not used yet); `sampled` = keys histogrammed; nb = buckets to hand out
-// (nb >= 2 * ncells).  Needs a barrier before and after.
+// (nb >= 2 * ncells); eq: equalised over the histogram, else nb / ncells buckets per cell (the plain linear map).  Needs a
+// barrier before and after.
 LR_DEV void lr_depth_map_build(uint32_t* table, const uint32_t* cellcnt, uint32_t ncells, uint32_t sampled, uint32_t nb,
-                                   bool equalize = true) {
+                               bool eq) {
   if (threadIdx.x < 64u) {                                  // one wave: LR_CELLS <= 64
     const uint32_t t = threadIdx.x;
     const uint32_t c = t < ncells ? cellcnt[t] : 0u;
-    const uint32_t n = t >= ncells ? 0u : (equalize ? 1u + (uint32_t)(((uint64_t)c * (nb - ncells)) / max(sampled, 1u)) : nb / ncells);
+    const uint32_t n = t >= ncells ? 0u : (eq ? 1u + (uint32_t)(((uint64_t)c * (nb - ncells)) / max(sampled, 1u)) : nb / ncells);
     uint32_t inc = n;
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
@@ -291,7 +272,7 @@ LR_DEV void lr_emit_bucket(KeyAt key_at, uint32_t st, uint32_t en, bool valid, u
 // to the network on them.
 template <int NT, int KPT>
 LR_DEV void lr_bucket_tile(const uint64_t* __restrict__ keys, uint32_t* __restrict__ plist, uint32_t beg, uint32_t L,
-                           int equalize, uint64_t* s) {
+                           uint64_t* s) {
   constexpr uint32_t CAP = NT * KPT;                       // longest list of this class (a power of two)
   // s: [A[CAP + CAP/8] (network layout)] | B[CAP] | cnt[CAP/4]
   uint64_t* const A = s;
@@ -334,6 +315,7 @@ LR_DEV void lr_bucket_tile(const uint64_t* __restrict__ keys, uint32_t* __restri
   dmap.table = celltab;
   uint32_t bkt[KPT], rnk[KPT];
   uint32_t run = 0;
+#pragma nounroll   // (two attempts at most; a second copy of the body costs registers)
   for (int attempt = 0;; attempt++) {
     const bool eq = attempt == 1;
     if (eq) {
@@ -377,7 +359,7 @@ LR_DEV void lr_bucket_tile(const uint64_t* __restrict__ keys, uint32_t* __restri
     run = inc - local;
     for (uint32_t w = 0; w < (tid >> 6); w++) run += wave_tot[w];
     if (sh_maxcnt <= LR_BUCKET_MAX) break;
-    if (eq || !equalize) {                                   // clustered beyond the map's reach: the network
+    if (eq) {                                                // clustered beyond the map's reach: the network
       __syncthreads();
       lr_lds_sort<NT>(A, P2, tid);
       for (uint32_t i = tid; i < L; i += NT) plist[beg + i] = (uint32_t)A[lr_phys(i)];
@@ -416,13 +398,13 @@ LR_DEV void lr_bucket_tile(const uint64_t* __restrict__ keys, uint32_t* __restri
 // Lists of up to 1024 keys: one 256-thread workgroup per tile (most tiles of a small scene).
 __global__ void __launch_bounds__(256)
 lr_sort_small_kernel(const uint32_t* __restrict__ state, uint32_t tiles, const uint64_t* __restrict__ keys,
-                     uint32_t* __restrict__ plist, uint32_t capacity, int equalize) {
+                     uint32_t* __restrict__ plist, uint32_t capacity) {
   extern __shared__ __attribute__((aligned(16))) uint64_t lr_sort_lds[];
   if (lr_bail(state, capacity)) return;
   const uint32_t* offsets = state + lr_offsets_off(tiles);
   const uint32_t beg = offsets[blockIdx.x], L = offsets[blockIdx.x + 1] - beg;
   if (L == 0 || L > 1024u) return;
-  lr_bucket_tile<256, 4>(keys, plist, beg, L, equalize, lr_sort_lds);
+  lr_bucket_tile<256, 4>(keys, plist, beg, L, lr_sort_lds);
 }
 static inline size_t lr_bucket_lds_bytes(uint32_t cap) {
   return sizeof(uint64_t) * (size_t)(cap + (cap >> 3)) + sizeof(uint64_t) * cap + sizeof(uint32_t) * (cap >> 2);
@@ -457,8 +439,7 @@ static inline size_t lr_bucket_lds_bytes(uint32_t cap) {
 #define LR_LONG_UNR 8       // independent loads in flight per thread in the streaming passes (64 VGPRs: two workgroups per CU, no spills)
 // One list, by the whole workgroup (lr_sort_long_kernel below); blk = its position in the longest-first order.
 LR_DEV void lr_sort_long_list(uint32_t* __restrict__ state, uint32_t tiles, uint64_t* __restrict__ keys,
-                              uint32_t* __restrict__ ranks, uint32_t* __restrict__ plist, int equalize,
-                              int network_only, int lazy, uint32_t blk) {
+                              uint32_t* __restrict__ ranks, uint32_t* __restrict__ plist, int lazy, uint32_t blk) {
   constexpr uint32_t LR_LONG_WIN = LR_LONG_WIN_BYTES / sizeof(uint64_t);
   extern __shared__ uint32_t lcnt[];  // LR_LONG_NB bucket counters (then their starts) | LR_LONG_WIN + LR_BUCKET_MAX staged keys
   uint64_t* const win = reinterpret_cast<uint64_t*>(lcnt + LR_LONG_NB);
@@ -485,7 +466,7 @@ LR_DEV void lr_sort_long_list(uint32_t* __restrict__ state, uint32_t tiles, uint
   const uint64_t* k = keys + beg;
   uint16_t* rk = reinterpret_cast<uint16_t*>(ranks) + beg;   // one 16-bit bucket id per key (nb <= 4096)
   uint32_t* pl = plist + beg;
-  // Clustered depths (a bucket above LR_BUCKET_MAX keys after both maps) or LOGRAST_BUCKET_SORT=0: the network, by this
+  // Clustered depths (a bucket above LR_BUCKET_MAX keys after both maps): the network, by this
   // workgroup, in place on the tile's keys (the whole dynamic LDS block as its staging area), then the ids.
   auto network = [&]() {
     __syncthreads();
@@ -493,20 +474,9 @@ LR_DEV void lr_sort_long_list(uint32_t* __restrict__ state, uint32_t tiles, uint
     for (uint32_t i = tid; i < L; i += 1024u) pl[i] = (uint32_t)k[i];
     if (lazy && lazy != 2 && tid == 0 && L > LR_LONG_LIST) { *sorted = L; if (lazy == 1) *open = 0u; }
   };
-  if (network_only) {                                       // (lists up to one block were sorted by lr_sort_rb_kernel)
-    if (L > LR_SORT_BLOCK) network();
-    return;
-  }
   // up to 4096 keys: the whole list in LDS, same code as the small lists.  (Up to 8192 the keys could sit in registers --
   // that was a kernel of its own, 145 VGPRs -- but not at the 64 this kernel is held to: they stream like the longer ones.)
-  if (L <= LR_LONG_LIST) { lr_bucket_tile<1024, 4>(keys, plist, beg, L, equalize, reinterpret_cast<uint64_t*>(lcnt)); return; }
-#if defined(LR_EXPERIMENTS) && defined(LR_LONG_TICKS)   // phase timing experiment (-DLR_EXPERIMENTS -DLR_LONG_TICKS): wall_clock64 per phase, printed by three workgroups
-  uint64_t tk[16]; int tn = 0;
-#define LR_TICK() do { if (tn < 16) tk[tn++] = wall_clock64(); } while (0)
-#else
-#define LR_TICK() do { } while (0)
-#endif
-  LR_TICK();
+  if (L <= LR_LONG_LIST) { lr_bucket_tile<1024, 4>(keys, plist, beg, L, reinterpret_cast<uint64_t*>(lcnt)); return; }
   if (lazy == 1 && tid == 0) state[LR_HDR_LAZY] = 1u;       // (every streamed list's workgroup stores the same word)
   uint32_t P2 = 8;
   while (P2 < L) P2 <<= 1;
@@ -543,7 +513,6 @@ LR_DEV void lr_sort_long_list(uint32_t* __restrict__ state, uint32_t tiles, uint
   __syncthreads();
   if ((tid & 63u) == 0u) { atomicMin(&sh_min, dmin); atomicMax(&sh_max, dmax); }
   __syncthreads();
-  LR_TICK();
   // (the sampled range widened by 1 % on either side: the few keys beyond the sample's extremes lie just outside it and
   // get buckets of their own there; clamped into the first / last bucket they overflow it -- measured: every eighth
   // tile of the 30 M-Gaussian workload then took the network fallback)
@@ -559,6 +528,7 @@ LR_DEV void lr_sort_long_list(uint32_t* __restrict__ state, uint32_t tiles, uint
   const uint32_t per = (nb + 1023u) / 1024u;               // <= LR_LONG_NB / 1024
   uint32_t cown[LR_LONG_NB / 1024];
   uint32_t local = 0, inc = 0;
+#pragma nounroll   // (two attempts at most; a second copy of the body costs registers)
   for (int attempt = 0;; attempt++) {
     const bool eq = attempt == 1;
     const uint32_t Lh = min(Ls, 8192u);
@@ -582,7 +552,6 @@ LR_DEV void lr_sort_long_list(uint32_t* __restrict__ state, uint32_t tiles, uint
         if (i + u * 1024u < L) rk[i + u * 1024u] = (uint16_t)cd[u];
     }
     __syncthreads();
-    LR_TICK();
     // exclusive scan of the nb counts: thread t owns counters [t * per, (t + 1) * per); every wave scans the 16 wave totals
     uint32_t lmax = 0;
     local = 0;
@@ -602,7 +571,7 @@ LR_DEV void lr_sort_long_list(uint32_t* __restrict__ state, uint32_t tiles, uint
     for (int d = 32; d > 0; d >>= 1) lmax = max(lmax, (uint32_t)__shfl_xor((int)lmax, d));
     if ((tid & 63u) == 63u) { wave_tot[tid >> 6] = inc; atomicMax(&sh_maxcnt, lmax); }
     __syncthreads();
-    if (sh_maxcnt <= LR_BUCKET_MAX || eq || !equalize) break;
+    if (sh_maxcnt <= LR_BUCKET_MAX || eq) break;
     __syncthreads();                                          // every thread has read sh_maxcnt and its counts
     if (tid == 0) sh_maxcnt = 0u;
     for (uint32_t b = tid; b < nb; b += 1024) lcnt[b] = 0u;
@@ -624,7 +593,6 @@ LR_DEV void lr_sort_long_list(uint32_t* __restrict__ state, uint32_t tiles, uint
     }
   }
   __syncthreads();
-  LR_TICK();
   // windows of whole buckets: [b0, b1) with start(b1) - start(b0) <= LR_LONG_WIN (a bucket holds <= LR_BUCKET_MAX keys)
   uint32_t b0 = 0;
   while (b0 < nb) {
@@ -666,7 +634,6 @@ LR_DEV void lr_sort_long_list(uint32_t* __restrict__ state, uint32_t tiles, uint
       }
     }
     __syncthreads();
-    LR_TICK();
     for (uint32_t bb = b0; bb < b1; bb += 1024u) {           // (uniform trip count: the emit needs whole waves)
       const uint32_t b = bb + tid;
       const bool valid = b < b1;
@@ -683,7 +650,6 @@ LR_DEV void lr_sort_long_list(uint32_t* __restrict__ state, uint32_t tiles, uint
       for (uint32_t p = w0 + tid; p < w1; p += 1024u) pl[p] = ids[2u * (p - w0)];
     }
     __syncthreads();
-    LR_TICK();
     if (lazy == 1 && b1 < nb) {                              // the first window is what a view walks; the rest on demand
       if (tid == 0) { *sorted = lcnt[b1]; *open = 0u; }      // (bucket b1 is untouched: lcnt[b1] is still its first position)
       return;
@@ -691,15 +657,6 @@ LR_DEV void lr_sort_long_list(uint32_t* __restrict__ state, uint32_t tiles, uint
     b0 = b1;
   }
   if (lazy && lazy != 2 && tid == 0) { *sorted = L; if (lazy == 1) *open = 0u; }   // (2: sorted[] stays where the parked waves resume)
-
-#if defined(LR_EXPERIMENTS) && defined(LR_LONG_TICKS)
-  if (tid == 0 && (blk == 0 || blk == 700 || blk == 2000)) {
-    printf("longsort blk %u L %u nb %u ticks(10ns):", blk, L, nb);
-    for (int q = 1; q < tn; q++) printf(" %llu", (unsigned long long)(tk[q] - tk[q - 1]));
-    printf("\n");
-  }
-#endif
-#undef LR_TICK
 }
 // First pass (lazy 0 / 1): one workgroup per list, handed out longest first by the dispatcher.  The passes over the tails
 // (lazy 2 / 3) run a small resident grid that loops over the lists: the per-view launch of mode 2 finds nothing to do in
@@ -709,45 +666,33 @@ LR_DEV void lr_sort_long_list(uint32_t* __restrict__ state, uint32_t tiles, uint
 template <bool REST>
 __global__ void __launch_bounds__(1024, 8)   // two workgroups per CU: 64 VGPRs (at 77 the kernel ran one per CU: 0.62 -> 0.86 ms at 30 M)
 lr_sort_long_kernel(uint32_t* __restrict__ state, uint32_t tiles, uint64_t* __restrict__ keys,
-                    uint32_t* __restrict__ ranks, uint32_t* __restrict__ plist, uint32_t capacity, int equalize,
-                    int network_only, int lazy, uint32_t nblk) {
+                    uint32_t* __restrict__ ranks, uint32_t* __restrict__ plist, uint32_t capacity, int lazy,
+                    uint32_t nblk) {
   if (lr_bail(state, capacity)) return;
   if (!REST) {
-    lr_sort_long_list(state, tiles, keys, ranks, plist, equalize, network_only, lazy, blockIdx.x);
+    lr_sort_long_list(state, tiles, keys, ranks, plist, lazy, blockIdx.x);
     return;
   }
   if (lazy == 2 && !state[LR_HDR_OPEN]) return;
   for (uint32_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
-    lr_sort_long_list(state, tiles, keys, ranks, plist, equalize, network_only, lazy, blk);
+    lr_sort_long_list(state, tiles, keys, ranks, plist, lazy, blk);
     __syncthreads();                                        // (the next list reuses the LDS)
   }
 }
 
-static inline size_t lr_sort_lds_bytes(uint32_t cap) { return sizeof(uint64_t) * (size_t)(cap + (cap >> 3)); }
 static inline size_t lr_long_lds_bytes() {   // (also >= lr_bucket_lds_bytes(4096) = 73728)
   return sizeof(uint32_t) * LR_LONG_NB + LR_LONG_WIN_BYTES + sizeof(uint64_t) * LR_BUCKET_MAX;
 }
 static_assert(sizeof(uint32_t) * LR_LONG_NB + LR_LONG_WIN_BYTES + sizeof(uint64_t) * LR_BUCKET_MAX >=
               sizeof(uint64_t) * (LR_SORT_BLOCK + (LR_SORT_BLOCK >> 3)), "the fallback network stages one block in the same LDS");
 
-// Size classes: the LDS footprint (9 B/key with padding) sets how many workgroups a CU can hold, so small
-// lists must not pay for the largest class.
-#define LR_SORT_CAP0 512             // 64 threads (one wave), 4.5 KB
-#define LR_SORT_CAP1 2048            // 256 threads, 18 KB
-#define LR_SORT_CAP2 LR_SORT_BLOCK   // 256 threads, 72 KB (dynamic LDS beyond the 64 KB static limit)
-
 // max_len: upper bound on the longest tile list known to the HOST (exact count from stage 1, a hint in sync-free
-// operation, or 0 = unknown -> assume `capacity`).  It only decides how many multi-block levels are launched.
-// -> the lazy mode that is really in effect (experiment builds with LOGRAST_BUCKET_SORT=0 order every list to its end: the
-// compositing passes must then not read sorted[] / open[], which still hold dead fill cursors -- round-5 advisory).
-int lr_launch_sort(uint32_t* state, uint32_t tiles, uint64_t* keys, uint32_t* plist, uint32_t capacity,
-                   uint32_t max_len, int lazy, hipStream_t s) {
-  if (tiles == 0) return 0;
+// operation, or 0 = unknown -> assume `capacity`).  It only decides whether the long-list launch is needed.
+void lr_launch_sort(uint32_t* state, uint32_t tiles, uint64_t* keys, uint32_t* plist, uint32_t capacity,
+                    uint32_t max_len, int lazy, hipStream_t s) {
+  if (tiles == 0) return;
   static bool attr_set = false;
   if (!attr_set) {
-    const int big = (int)lr_sort_lds_bytes(LR_SORT_BLOCK);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&lr_sort_rb_kernel<256>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, big);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&lr_sort_long_kernel<false>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lr_long_lds_bytes());
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&lr_sort_long_kernel<true>),
@@ -755,42 +700,21 @@ int lr_launch_sort(uint32_t* state, uint32_t tiles, uint64_t* keys, uint32_t* pl
     attr_set = true;
   }
   if (max_len == 0 || max_len > capacity) max_len = capacity;
-  // LOGRAST_BUCKET_SORT=0: bitonic network only (the reference implementation of the same total order)
-  static const int bucket = LR_EXPERIMENT_INT("LOGRAST_BUCKET_SORT", 1);   // experiment builds: 0 = bitonic network only
-  static const int equalize = LR_EXPERIMENT_INT("LOGRAST_EQUALIZE", 1);   // 0: plain linear depth -> bucket map (experiments)
   // Two launches: one 256-thread workgroup per tile for the lists of up to 1024 keys, and one 1024-thread workgroup
   // (78 KB of LDS, two per CU) per list above that, walking the longest-first order -- LDS-resident up to 4096 keys,
   // keys in registers up to 8192, streamed from memory beyond.  (They used to be four launches by size class: at 30 M
   // Gaussians, where every list is long, the three that found nothing to do cost 100 us of idle workgroups per view.)
-  if (bucket) {
-    lr_prof_begin(LRK_SORT_SMALL, s);
-    hipLaunchKernelGGL(lr_sort_small_kernel, dim3(tiles), dim3(256), lr_bucket_lds_bytes(1024), s, state, tiles, keys,
-                       plist, capacity, equalize);
-    lr_prof_end(LRK_SORT_SMALL, s);
-  } else {
-    lr_prof_begin(LRK_SORT_SMALL, s);
-    hipLaunchKernelGGL(lr_sort_rb_kernel<64>, dim3(tiles), dim3(64), lr_sort_lds_bytes(LR_SORT_CAP0), s, state, tiles,
-                       keys, plist, 0u, (uint32_t)LR_SORT_CAP0, capacity);
-    lr_prof_end(LRK_SORT_SMALL, s);
-    if (max_len > LR_SORT_CAP0) {
-      lr_prof_begin(LRK_SORT_LARGE, s);
-      hipLaunchKernelGGL(lr_sort_rb_kernel<256>, dim3(tiles), dim3(256), lr_sort_lds_bytes(LR_SORT_CAP1), s, state, tiles,
-                         keys, plist, (uint32_t)LR_SORT_CAP0, (uint32_t)LR_SORT_CAP1, capacity);
-      if (max_len > LR_SORT_CAP1)
-        hipLaunchKernelGGL(lr_sort_rb_kernel<256>, dim3(tiles), dim3(256), lr_sort_lds_bytes(LR_SORT_CAP2), s, state,
-                           tiles, keys, plist, (uint32_t)LR_SORT_CAP1, (uint32_t)LR_SORT_CAP2, capacity);
-      lr_prof_end(LRK_SORT_LARGE, s);
-    }
-  }
-  if (bucket ? max_len > 1024u : max_len > LR_SORT_BLOCK) {
+  lr_prof_begin(LRK_SORT_SMALL, s);
+  hipLaunchKernelGGL(lr_sort_small_kernel, dim3(tiles), dim3(256), lr_bucket_lds_bytes(1024), s, state, tiles, keys,
+                     plist, capacity);
+  lr_prof_end(LRK_SORT_SMALL, s);
+  if (max_len > 1024u) {
     lr_prof_begin(LRK_SORT_HUGE, s);
     const uint32_t nblk = min(tiles, capacity / 1024u + 1u);
     hipLaunchKernelGGL(lr_sort_long_kernel<false>, dim3(nblk), dim3(1024), lr_long_lds_bytes(), s,
-                       state, tiles, keys, reinterpret_cast<uint32_t*>(keys + capacity), plist, capacity, equalize,
-                       bucket ? 0 : 1, (bucket && lazy) ? 1 : 0, nblk);
+                       state, tiles, keys, reinterpret_cast<uint32_t*>(keys + capacity), plist, capacity, lazy ? 1 : 0, nblk);
     lr_prof_end(LRK_SORT_HUGE, s);
   }
-  return (bucket && lazy) ? 1 : 0;
 }
 
 // out[t] = leading positions of tile t's list that are in final order (lograst_ordered_lengths)
@@ -817,7 +741,6 @@ void lr_launch_sort_rest(uint32_t* state, uint32_t tiles, uint64_t* keys, uint32
   if (tiles == 0) return;
   if (max_len == 0 || max_len > capacity) max_len = capacity;
   if (max_len <= LR_LONG_LIST) return;
-  static const int equalize = LR_EXPERIMENT_INT("LOGRAST_EQUALIZE", 1);
   // (every tile in front of a streamed list in order[] holds at least LR_LONG_LIST keys itself: lr_scan_kernel's buckets)
   static bool attr_set = false;   // (lograst_finish_lists may be the first caller in a process that only inspects buffers)
   if (!attr_set) {
@@ -827,5 +750,5 @@ void lr_launch_sort_rest(uint32_t* state, uint32_t tiles, uint64_t* keys, uint32
   }
   const uint32_t nblk = min(tiles, capacity / (uint32_t)LR_LONG_LIST + 1u);
   hipLaunchKernelGGL(lr_sort_long_kernel<true>, dim3(min(nblk, 512u)), dim3(1024), lr_long_lds_bytes(), s, state, tiles, keys,
-                     reinterpret_cast<uint32_t*>(keys + capacity), plist, capacity, equalize, 0, mode, nblk);
+                     reinterpret_cast<uint32_t*>(keys + capacity), plist, capacity, mode, nblk);
 }

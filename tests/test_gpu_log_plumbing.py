@@ -5,9 +5,8 @@ training steps on cuda:0 after ``log_amd.install_all()`` -- every kernel below t
 is compared with the same three steps on the CPU, where the classes are left as they are and the rasterizer backend is the
 oracle test double (tests/oracle_backend.py; what tests/test_log_plumbing_cpu.py pins).
 
-Needs the reference tree: `LOG_REFERENCE` (default /root/reference).  It does not exist on the driver's GPU box, where this
-file is skipped; `tools/run_reference_on_gpu.sh` stages a git-ignored copy for ONE gpurun call and removes it afterwards
-(log kept under profiles/)."""
+Needs the reference tree: `LOG_REFERENCE` (default /root/reference).  Where it does not exist this file is skipped
+(logs of the runs that had it are kept under profiles/)."""
 import math
 import os
 import sys

@@ -1,5 +1,5 @@
 """Projection kernel on an LoD-shaped selection (big splats first, BFS level order) vs the same Gaussians shuffled.
-python tools/micro/proj_lod.py   (env: LOGRAST_TILE_CULL, LOGRAST_BATCH)"""
+python tools/micro/proj_lod.py   (env: LOGRAST_TILE_CULL)"""
 import ctypes, math, os, sys, types
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

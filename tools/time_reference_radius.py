@@ -2,8 +2,8 @@
 "alongside the reference's pure-PyTorch/CPU render path timed on the same box's host cores (core count stated)"; SURVEY 8d:
 "additionally time the reference's own geometry.compute_radius (geometry.py:132-151) at P = 1 M").  The reference has no CPU
 renderer; LoG.model.geometry.compute_radius -- the Python twin of LoG/cuda/compute_radius_kernel.cu, A0 of the scope table
--- is its only CPU-runnable arithmetic on this path.  IMPORTS the reference (LOG_REFERENCE or /root/reference: staged on
-the GPU box by tools/run_reference_on_gpu.sh), copies nothing; also runs this framework's A0 kernel on the same inputs when
+-- is its only CPU-runnable arithmetic on this path.  IMPORTS the reference (LOG_REFERENCE or /root/reference), copies
+nothing; also runs this framework's A0 kernel on the same inputs when
 a GPU is there and reports the agreement.
     python tools/time_reference_radius.py [--points 1000000] [--out gpurun_out/reference_python_radius.json]"""
 import argparse
