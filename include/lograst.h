@@ -509,11 +509,37 @@ int lograst_activate_backward(int32_t n, const float* raw_xyz, const float* raw_
                               const float* dl_dact_rotation, const float* dl_dact_colors, float* dl_dscaling,
                               float* dl_dopacity, float* dl_drotation, float* dl_dcolors, float* dl_dshs, void* stream);
 
+/* ---- the photometric training loss (LoG/render/renderer.py:253-266 calculate_loss, LoG/render/loss.py:6-44 SSIM) ----
+ * For render, render_l1, gt of shape [batch, channels, height, width], fp32, each addressed through FOUR ELEMENT STRIDES
+ * (b, c, y, x; host arrays of 4 int64 -- a channels-last view is read in place):
+ *   ssim = 1 - mean(ssim_map(render, gt))   11x11 Gaussian window (sigma 1.5, taps normalised in double and rounded to
+ *                                           fp32 once, applied separably), no padding: (height-10) x (width-10) outputs,
+ *                                           C1 = 0.01^2, C2 = 0.03^2
+ *   l1   = mean |render_l1 - gt|            render_l1 == NULL: render itself (LoG passes its colour-corrected render here)
+ *   loss = ssim_weight * ssim + l1_weight * l1
+ * lograst_loss_forward writes out3 = (loss, l1, ssim) on the device and, for the backward, maps: 3 * batch * channels *
+ * (height-10) * (width-10) floats (the derivatives of the loss's SSIM term with respect to the window mean of render and
+ * the two window second moments that contain render; NULL: forward only).  The two sums are reduced from per-workgroup
+ * partials (scratch: lograst_loss_scratch_bytes) in a fixed order: the same input gives the same bits.
+ * lograst_loss_backward reads the upstream gradient of loss from DEVICE memory (grad_loss, one float) and writes
+ * grad_render [batch, channels, height, width] (contiguous); the L1 term goes to grad_render_l1 (contiguous, same shape)
+ * when render_l1 != NULL and into grad_render otherwise; sign(0) = 0.  gt gets no gradient.
+ * height < 11 or width < 11 is an error; batch * channels == 0 writes zeros to out3 and launches nothing. */
+size_t lograst_loss_scratch_bytes(int32_t batch, int32_t channels, int32_t height, int32_t width);
+int lograst_loss_forward(int32_t batch, int32_t channels, int32_t height, int32_t width, const float* render,
+                         const int64_t* render_strides, const float* render_l1, const int64_t* render_l1_strides,
+                         const float* gt, const int64_t* gt_strides, float ssim_weight, float l1_weight, float* out3,
+                         float* maps, void* scratch, size_t scratch_bytes, void* stream);
+int lograst_loss_backward(int32_t batch, int32_t channels, int32_t height, int32_t width, const float* render,
+                          const int64_t* render_strides, const float* render_l1, const int64_t* render_l1_strides,
+                          const float* gt, const int64_t* gt_strides, float l1_weight, const float* grad_loss,
+                          const float* maps, float* grad_render, float* grad_render_l1, void* stream);
+
 /* ---- per-kernel timing with HIP events on the launch stream (used by bench.py) -----------------
  * When enabled every kernel launch is bracketed by hipEventRecord on its stream.  read() synchronises
  * the recorded events and returns, for kernel slot i < LOGRAST_NUM_KERNELS, accumulated milliseconds
  * and launch counts since the last reset. */
-#define LOGRAST_NUM_KERNELS 20
+#define LOGRAST_NUM_KERNELS 22
 void lograst_profile_enable(int on);
 void lograst_profile_reset(void);
 int lograst_profile_read(double* ms_out, int64_t* count_out);

@@ -11,7 +11,7 @@ FORM_AUTO, FORM_ROWS, FORM_QUADRANT = 0, 1, 2
 GRAD_ROW_FLOATS = 16   # LOGRAST_GRAD_ROW_FLOATS
 REC_FLOATS = 16
 BWD_ROW_FLOATS = 16   # LOGRAST_BWD_ROW_FLOATS: the reverse walk's accumulator row (64 B per Gaussian)
-NUM_KERNELS = 20
+NUM_KERNELS = 22
 
 c_void_p, c_int32, c_uint32, c_float, c_size_t = (ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint32,
                                                   ctypes.c_float, ctypes.c_size_t)
@@ -107,6 +107,10 @@ _SIGNATURES = {
     "lograst_id_histogram_read": (ctypes.c_int, [c_void_p, ctypes.POINTER(c_uint32), c_void_p]),
     "lograst_counter_update": (ctypes.c_int, [c_int32] + [c_void_p] * 4 + [c_int32, c_void_p, c_void_p, c_int32]
                                + [c_void_p] * 10),
+    "lograst_loss_scratch_bytes": (c_size_t, [c_int32] * 4),
+    "lograst_loss_forward": (ctypes.c_int, [c_int32] * 4 + [c_void_p] * 6 + [c_float, c_float, c_void_p, c_void_p, c_void_p,
+                                            c_size_t, c_void_p]),
+    "lograst_loss_backward": (ctypes.c_int, [c_int32] * 4 + [c_void_p] * 6 + [c_float] + [c_void_p] * 5),
     "lograst_sparse_adam": (ctypes.c_int, [c_int32, c_int32, c_void_p, c_void_p, c_int32,
                                            ctypes.POINTER(LograstAdamKey), ctypes.c_double, ctypes.c_double,
                                            ctypes.c_double, ctypes.c_double, c_void_p]),

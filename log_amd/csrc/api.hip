@@ -3,6 +3,7 @@
 // the header says so.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -88,6 +89,10 @@ hipError_t lr_launch_gather_activate(const GatherArgs& a, hipStream_t s);
 hipError_t lr_launch_activate_bwd(const ActBwdArgs& a, hipStream_t s);
 hipError_t lr_launch_activate_bwd_adam(const ActBwdArgs& a, const AdamArgs& f, const float* g_a_xyz, const int32_t* radii,
                                        hipStream_t s);
+
+size_t lr_loss_scratch_bytes(int B, int C, int H, int W);
+hipError_t lr_launch_loss_fwd(const LossArgs& a, float wa, float wb, float* out3, hipStream_t s);
+hipError_t lr_launch_loss_bwd(const LossArgs& a, const float* grad_loss, float* g_render, float* g_render_l1, hipStream_t s);
 
 static thread_local std::string g_err;
 static int lr_fail(int code, const std::string& msg) {
@@ -213,7 +218,8 @@ static int lr_tile_cull() {
 static const char* kKernelNames[LOGRAST_NUM_KERNELS] = {
     "compute_radius", "project", "scan_tiles", "fill_keys", "sort_small", "sort_large", "sort_huge",
     "blend_fwd", "blend_bwd", "project_bwd", "knn3", "lod_traverse", "counter_update", "sparse_adam",
-    "id_histogram", "gather_activate", "activate_bwd", "count_huge", "rebase_slots", "lazy_tail"};
+    "id_histogram", "gather_activate", "activate_bwd", "count_huge", "rebase_slots", "lazy_tail",
+    "loss_fwd", "loss_bwd"};
 struct ProfRec { int slot; hipEvent_t a, b; bool own_a; };
 // Consecutive launches inside one entry point share an event: the end of kernel k is the begin of kernel k+1 (N+1
 // events for a chain of N kernels instead of 2N; every recorded event costs ~1.4 us of stream time).
@@ -966,6 +972,85 @@ int lograst_counter_update(int32_t nv, const int64_t* visible_index, const float
   a.nv = nv; a.k = k; a.num_points = num_points;
   g_prof_call++;
   LR_HIP(lr_launch_counter(a, (hipStream_t)stream));
+  return LOGRAST_OK;
+}
+
+// ---- fused L1 + SSIM loss (loss.hip) ----------------------------------------------------------------------
+size_t lograst_loss_scratch_bytes(int32_t batch, int32_t channels, int32_t height, int32_t width) {
+  return lr_loss_scratch_bytes(batch, channels, height, width);
+}
+
+// Geometry and input checks shared by the two entry points; fills everything of LossArgs but the tile grid.
+static int lr_loss_args(LossArgs& a, int32_t batch, int32_t channels, int32_t height, int32_t width, const float* render,
+                        const int64_t* rs, const float* render_l1, const int64_t* ls, const float* gt, const int64_t* gs) {
+  if (batch < 0 || channels < 0) return lr_fail(LOGRAST_ERR_ARG, "negative batch or channel count");
+  if (height < LS_WIN_TAPS || width < LS_WIN_TAPS)
+    return lr_fail(LOGRAST_ERR_ARG, "image smaller than the 11-pixel window of the SSIM (height and width must be >= 11)");
+  if ((int64_t)batch * channels * (int64_t)height * width > 0x7fffffffLL) return lr_fail(LOGRAST_ERR_ARG, "more than 2^31 - 1 image elements");
+  if ((int64_t)batch * channels == 0) return 1;
+  if (!render || !gt || !rs || !gs || (render_l1 && !ls)) return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
+  // inside a (b, c) plane the kernels address with 32-bit offsets y * stride_y + x * stride_x
+  for (const int64_t* st : {rs, gs, render_l1 ? ls : rs}) {
+    const int64_t sy = st[2] < 0 ? -st[2] : st[2], sx = st[3] < 0 ? -st[3] : st[3];
+    if (sy > 0x7fffffffLL || sx > 0x7fffffffLL || (int64_t)(height - 1) * sy + (int64_t)(width - 1) * sx > 0x7fffffffLL)
+      return lr_fail(LOGRAST_ERR_ARG, "y / x strides reach beyond 2^31 - 1 elements inside one image plane");
+  }
+  bool same = render_l1 == render;
+  for (int i = 0; i < 4; i++) {
+    a.rs[i] = rs[i]; a.gs[i] = gs[i];
+    a.ls[i] = render_l1 ? ls[i] : 0;
+    same = same && (!render_l1 || ls[i] == rs[i]);
+  }
+  a.render = render; a.gt = gt;
+  a.render_l1 = (render_l1 && !same) ? render_l1 : nullptr;
+  a.B = batch; a.C = channels; a.H = height; a.W = width;
+  // the window: exp(-(x-5)^2 / (2 * 1.5^2)) in double, normalised, rounded to fp32 once
+  double g[LS_WIN_TAPS], sum = 0.0;
+  for (int k = 0; k < LS_WIN_TAPS; k++) { g[k] = std::exp(-(double)((k - 5) * (k - 5)) / (2.0 * 1.5 * 1.5)); sum += g[k]; }
+  for (int k = 0; k < LS_WIN_TAPS; k++) a.w[k] = (float)(g[k] / sum);
+  a.scale = 0.f; a.l1_scale = 0.f; a.maps = nullptr; a.partial = nullptr; a.ntx = a.nty = 0;
+  return 0;
+}
+
+int lograst_loss_forward(int32_t batch, int32_t channels, int32_t height, int32_t width, const float* render,
+                         const int64_t* render_strides, const float* render_l1, const int64_t* render_l1_strides,
+                         const float* gt, const int64_t* gt_strides, float ssim_weight, float l1_weight, float* out3,
+                         float* maps, void* scratch, size_t scratch_bytes, void* stream) {
+  LossArgs a;
+  const int rc = lr_loss_args(a, batch, channels, height, width, render, render_strides, render_l1, render_l1_strides, gt, gt_strides);
+  if (rc < 0) return rc;
+  if (!out3) return lr_fail(LOGRAST_ERR_ARG, "out3 is NULL");
+  if (rc == 1) {
+    LR_HIP(hipMemsetAsync(out3, 0, 3 * sizeof(float), (hipStream_t)stream));
+    return LOGRAST_OK;
+  }
+  if (!scratch || scratch_bytes < lr_loss_scratch_bytes(batch, channels, height, width) || (reinterpret_cast<uintptr_t>(scratch) & 7u))
+    return lr_fail(LOGRAST_ERR_ARG, "loss scratch too small (lograst_loss_scratch_bytes) or not 8-byte aligned");
+  a.ntx = (width - 10 + 31) / 32; a.nty = (height - 10 + 31) / 32;
+  const double count = (double)batch * channels * (double)(height - 10) * (double)(width - 10);
+  a.scale = (float)(-(double)ssim_weight / count);
+  a.maps = maps;
+  a.partial = reinterpret_cast<float*>(scratch);
+  g_prof_call++;
+  LR_HIP(lr_launch_loss_fwd(a, ssim_weight, l1_weight, out3, (hipStream_t)stream));
+  return LOGRAST_OK;
+}
+
+int lograst_loss_backward(int32_t batch, int32_t channels, int32_t height, int32_t width, const float* render,
+                          const int64_t* render_strides, const float* render_l1, const int64_t* render_l1_strides,
+                          const float* gt, const int64_t* gt_strides, float l1_weight, const float* grad_loss,
+                          const float* maps, float* grad_render, float* grad_render_l1, void* stream) {
+  LossArgs a;
+  const int rc = lr_loss_args(a, batch, channels, height, width, render, render_strides, render_l1, render_l1_strides, gt, gt_strides);
+  if (rc < 0) return rc;
+  if (rc == 1) return LOGRAST_OK;
+  if (!grad_loss || !maps || !grad_render) return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
+  if (a.render_l1 && !grad_render_l1) return lr_fail(LOGRAST_ERR_ARG, "render_l1 is a tensor of its own but grad_render_l1 is NULL");
+  a.ntx = (width + 31) / 32; a.nty = (height + 31) / 32;
+  a.l1_scale = (float)((double)l1_weight / ((double)batch * channels * (double)height * (double)width));
+  a.maps = const_cast<float*>(maps);
+  g_prof_call++;
+  LR_HIP(lr_launch_loss_bwd(a, grad_loss, grad_render, a.render_l1 ? grad_render_l1 : nullptr, (hipStream_t)stream));
   return LOGRAST_OK;
 }
 

@@ -534,13 +534,27 @@ struct ActBwdArgs {
   int n, K, deg;
 };
 
+// ---- fused L1 + SSIM loss (loss.hip; filled in by api.hip) ----------------------------------------------
+#define LS_WIN_TAPS 11
+struct LossArgs {
+  const float* render; const float* render_l1; const float* gt;   // render_l1 == NULL: the L1 term reads render
+  int64_t rs[4], ls[4], gs[4];                                     // element strides (b, c, y, x)
+  float w[LS_WIN_TAPS];                                            // the normalised window, fp32
+  float scale;                                                     // forward: -ssim_weight / count
+  float l1_scale;                                                  // backward: l1_weight / (B*C*H*W)
+  float* maps;                                                     // 3 x [B*C, H-10, W-10]
+  float* partial;                                                  // forward: 2 floats per workgroup
+  int32_t B, C, H, W, ntx, nty;                                    // ntx * nty tiles per plane (of outputs forward, of the image backward)
+};
+
 // ---- host-side launch bookkeeping (api.hip) ------------------------------------------------------
 // LRK_SORT_LARGE ("sort_large") keeps its number in the ABI's slot list (include/lograst.h) but no launch records it:
 // long lists are sorted under LRK_SORT_HUGE.  LRK_RESERVED times lr_count_huge_kernel ("count_huge").
 enum LrKernelSlot {
   LRK_RADIUS = 0, LRK_PROJECT, LRK_SCAN, LRK_FILL, LRK_SORT_SMALL, LRK_SORT_LARGE, LRK_SORT_HUGE,
   LRK_BLEND_FWD, LRK_BLEND_BWD, LRK_PROJECT_BWD, LRK_MISC, LRK_LOD, LRK_COUNTER, LRK_ADAM, LRK_HIST, LRK_GATHER, LRK_GATHER_BWD, LRK_RESERVED,
-  LRK_REBASE, LRK_LAZY_TAIL   // LRK_LAZY_TAIL: the second sort + compositing pair of lazily ordered lists (normally idle)
+  LRK_REBASE, LRK_LAZY_TAIL,  // LRK_LAZY_TAIL: the second sort + compositing pair of lazily ordered lists (normally idle)
+  LRK_LOSS_FWD, LRK_LOSS_BWD
 };
 // ---- profiling and environment (api.hip) -------------------------------------------------------------------------
 // Every kernel computes its full result: there are no timing ablations or compile-time algorithm switches.  Compiler

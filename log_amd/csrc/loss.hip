@@ -1,0 +1,354 @@
+// loss.hip -- the photometric training loss of LoG (LoG/render/renderer.py:253-266, LoG/render/loss.py:6-44):
+//   loss = a * (1 - mean(ssim_map(render, gt))) + b * mean|render_l1 - gt|,  11x11 Gaussian window (sigma 1.5), no padding.
+// The reference runs five grouped conv2d, ~10 element-wise kernels, two reductions and the autograd backward of all of
+// them; here: one forward kernel + a one-block fixed-order reduction, and one backward kernel.
+//
+// Tiling.  A workgroup of 256 threads (4 waves) owns a LS_T x LS_T = 32 x 32 tile of one (b, c) plane.
+//   forward : stages the (32+10)^2 input tile of render and gt in LDS, runs the horizontal 11-tap pass for the five
+//             moments (42 rows x 32 columns) into LDS, then the vertical pass with four consecutive output rows per
+//             thread (14 LDS reads feed 4 x 11 taps), evaluates the SSIM map and leaves three derivative maps.
+//   backward: the transposed problem -- a 32 x 32 tile of IMAGE pixels needs the (32+10)^2 tile of the three maps
+//             that ends at it; same two passes, then the per-pixel combination with render and gt.
+// LDS banking: in every pass the 32 lanes of a half-wave read 32 consecutive elements of one LDS row -- 4-byte elements
+// (ds_read_b32: bank (addr/4) % 32 per 32-lane half) or 8-byte pairs (ds_read_b64: bank (addr/4) % 64, 32 lanes x 2
+// banks) -- so no pass is strided across rows and no row padding is needed; forward 35.6 KiB (e12 of the horizontal pass
+// goes over the consumed input tile), backward 36.4 KiB per workgroup: 4 workgroups per CU of 160 KiB.
+//
+// Centring.  All moments are taken of (x - 0.5): mu' = w*(x-0.5), s11 = w*(x-0.5)^2 - mu'^2 -- the same real numbers as
+// w*x^2 - mu^2 (the window sums to 1) with the cancellation moved from |x|^2 to |x-0.5|^2 (colours live around [0,1]).
+// The maps the forward leaves are, per output pixel q and scaled by -a/count (d(loss)/d(ssim_map(q))):
+//   maps[0] = d ssim / d mu1' at fixed centred second moments, maps[1] = d ssim / d s11, maps[2] = d ssim / d s12,
+// and the backward is  dL/drender(p) = g * sum_q w(p-q) * (maps0(q) + 2 (render(p)-0.5) maps1(q) + (gt(p)-0.5) maps2(q)).
+//
+// Determinism: fixed tap order (ascending tap index, horizontal then vertical), explicit fmaf only, per-workgroup
+// partial sums reduced in a fixed order by one workgroup in double -- no floating-point atomics anywhere.
+#include "common.hpp"
+
+#define LS_T 32
+#define LS_HALO 10
+#define LS_IN (LS_T + LS_HALO)
+#define LS_THREADS 256
+#define LS_ROWS 4                  // consecutive rows per thread in the vertical pass: LS_T * LS_T / LS_ROWS threads
+#define LS_CENTER 0.5f
+#define LS_STAGE ((LS_IN * LS_IN + LS_THREADS - 1) / LS_THREADS)    // tile elements per thread (7)
+#define LS_HITEMS ((LS_IN * LS_T + LS_THREADS - 1) / LS_THREADS)    // horizontal-pass items per thread (6)
+
+size_t lr_loss_scratch_bytes(int B, int C, int H, int W) {
+  if (B <= 0 || C <= 0 || H < LS_WIN_TAPS || W < LS_WIN_TAPS) return 256;
+  const size_t ntx = (size_t)(W - LS_HALO + LS_T - 1) / LS_T, nty = (size_t)(H - LS_HALO + LS_T - 1) / LS_T;
+  const size_t bytes = 8 * ntx * nty * (size_t)B * (size_t)C;       // (sum ssim_map, sum |render_l1 - gt|) per workgroup
+  return (bytes + 255) & ~(size_t)255;
+}
+
+// A (b, c) plane starts at a 64-bit offset (uniform per workgroup); inside it y * stride_y + x * stride_x fits 32 bits
+// (checked by the entry points).
+LR_DEV const float* ls_plane(const float* p, const int64_t* s, int b, int c) { return p + ((int64_t)b * s[0] + (int64_t)c * s[1]); }
+
+// sum over the workgroup in a fixed order: lanes by shuffle, then the four waves in order; result valid in thread 0
+LR_DEV float ls_block_sum(float v, float* ws) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d);
+  if ((threadIdx.x & 63u) == 0) ws[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((ws[0] + ws[1]) + ws[2]) + ws[3];
+}
+
+// The moments travel in pairs -- (render, gt), (mu1, mu2), (e11, e22) -- one 8-byte LDS access and one packed fp32
+// instruction (v_pk_fma_f32 / v_pk_mul_f32) per pair; element for element the same IEEE operations as scalar code.
+__global__ void __launch_bounds__(LS_THREADS)
+loss_fwd_kernel(LossArgs a) {
+  __shared__ lr_f2 srg[LS_IN * LS_IN];                      // (render - 0.5, gt - 0.5)
+  __shared__ lr_f2 hmu[LS_IN * LS_T], hee[LS_IN * LS_T];    // horizontal pass: (mu1, mu2), (e11, e22)
+  float* he12 = reinterpret_cast<float*>(srg);              // ... and e12, over the input tile once it has been consumed
+  float* ws = he12 + LS_IN * LS_T;                          // 8 floats for the two workgroup sums (35.6 KiB in all: 4 per CU)
+  const int tid = (int)threadIdx.x;
+  int t = (int)blockIdx.x;
+  const int c = t % a.C; t /= a.C;
+  const int tx = t % a.ntx; t /= a.ntx;
+  const int ty = t % a.nty;
+  const int b = t / a.nty;
+  const int x0 = tx * LS_T, y0 = ty * LS_T;
+  const bool last_x = tx == a.ntx - 1, last_y = ty == a.nty - 1;
+  const int OW = a.W - LS_HALO, OH = a.H - LS_HALO;
+  const float* rp = ls_plane(a.render, a.rs, b, c);
+  const float* gp = ls_plane(a.gt, a.gs, b, c);
+  const float* lp = a.render_l1 ? ls_plane(a.render_l1, a.ls, b, c) : nullptr;
+  const int rsy = (int)a.rs[2], rsx = (int)a.rs[3], gsy = (int)a.gs[2], gsx = (int)a.gs[3], lsy = (int)a.ls[2], lsx = (int)a.ls[3];
+
+  // stage the input tile: all of a thread's loads are requested before the first is used.  Every image pixel belongs to
+  // exactly one tile's L1 sum (the last tile of a row / column also owns its halo).
+  float rv[LS_STAGE], gv[LS_STAGE], lv[LS_STAGE];
+  bool own[LS_STAGE];
+#pragma unroll
+  for (int u = 0; u < LS_STAGE; u++) {
+    const int i = tid + u * LS_THREADS;
+    const int ly = i / LS_IN, lx = i - ly * LS_IN;
+    const int y = y0 + ly, x = x0 + lx;
+    const bool in = i < LS_IN * LS_IN && y < a.H && x < a.W;
+    own[u] = in && (lx < LS_T || last_x) && (ly < LS_T || last_y);
+    rv[u] = in ? rp[y * rsy + x * rsx] : LS_CENTER;
+    gv[u] = in ? gp[y * gsy + x * gsx] : LS_CENTER;
+    lv[u] = (lp && own[u]) ? lp[y * lsy + x * lsx] : 0.f;
+  }
+  float l1 = 0.f;
+#pragma unroll
+  for (int u = 0; u < LS_STAGE; u++) {
+    const int i = tid + u * LS_THREADS;
+    if (own[u]) l1 += fabsf((lp ? lv[u] : rv[u]) - gv[u]);
+    if (i < LS_IN * LS_IN) srg[i] = lr_f2{rv[u] - LS_CENTER, gv[u] - LS_CENTER};
+  }
+  __syncthreads();
+
+  // horizontal pass: 42 rows x 32 columns, five moments
+  float e12v[LS_HITEMS];
+#pragma unroll
+  for (int u = 0; u < LS_HITEMS; u++) {
+    const int i = tid + u * LS_THREADS;
+    e12v[u] = 0.f;
+    if (i < LS_IN * LS_T) {
+      const int row = i / LS_T, hx = i - row * LS_T;
+      const lr_f2* p = srg + row * LS_IN + hx;
+      lr_f2 mu = {0.f, 0.f}, ee = {0.f, 0.f};
+      float e12 = 0.f;
+#pragma unroll
+      for (int k = 0; k < LS_WIN_TAPS; k++) {
+        const float w = a.w[k];
+        const lr_f2 v = p[k], w2 = {w, w};
+        mu = lr_fma2(w2, v, mu);
+        ee = lr_fma2(w2, v * v, ee);
+        e12 = lr_fma(w, v.x * v.y, e12);
+      }
+      hmu[i] = mu; hee[i] = ee; e12v[u] = e12;
+    }
+  }
+  __syncthreads();                                          // every read of the input tile is done: e12 goes over it
+#pragma unroll
+  for (int u = 0; u < LS_HITEMS; u++) {
+    const int i = tid + u * LS_THREADS;
+    if (i < LS_IN * LS_T) he12[i] = e12v[u];
+  }
+  __syncthreads();
+
+  // vertical pass: column xo, output rows yq .. yq+3 out of LDS rows yq .. yq+13
+  const int xo = tid & (LS_T - 1), yq = (tid / LS_T) * LS_ROWS;
+  lr_f2 amu[LS_ROWS], aee[LS_ROWS];
+  float a12[LS_ROWS];
+#pragma unroll
+  for (int j = 0; j < LS_ROWS; j++) { amu[j] = lr_f2{0.f, 0.f}; aee[j] = lr_f2{0.f, 0.f}; a12[j] = 0.f; }
+#pragma unroll
+  for (int rr = 0; rr < LS_ROWS + LS_HALO; rr++) {
+    const int o = (yq + rr) * LS_T + xo;
+    const lr_f2 vmu = hmu[o], vee = hee[o];
+    const float v12 = he12[o];
+#pragma unroll
+    for (int j = 0; j < LS_ROWS; j++) {
+      const int k = rr - j;
+      if (k >= 0 && k < LS_WIN_TAPS) {
+        const lr_f2 w2 = {a.w[k], a.w[k]};
+        amu[j] = lr_fma2(w2, vmu, amu[j]);
+        aee[j] = lr_fma2(w2, vee, aee[j]);
+        a12[j] = lr_fma(a.w[k], v12, a12[j]);
+      }
+    }
+  }
+
+  const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
+  float ssum = 0.f;
+  const int ox = x0 + xo;
+  const int64_t plane = (int64_t)OH * OW, bc = (int64_t)b * a.C + c, nbc = (int64_t)a.B * a.C;
+  float* map0 = a.maps + bc * plane;                       // uniform per workgroup
+  float* map1 = map0 + nbc * plane;
+  float* map2 = map1 + nbc * plane;
+#pragma unroll
+  for (int j = 0; j < LS_ROWS; j++) {
+    const int oy = y0 + yq + j;
+    if (ox >= OW || oy >= OH) continue;
+    const float m1c = amu[j].x, m2c = amu[j].y;
+    const float s11 = aee[j].x - m1c * m1c, s22 = aee[j].y - m2c * m2c, s12 = a12[j] - m1c * m2c;
+    const float mu1 = m1c + LS_CENTER, mu2 = m2c + LS_CENTER;
+    const float n1 = lr_fma(2.f * mu1, mu2, C1), n2 = lr_fma(2.f, s12, C2);
+    const float d1 = lr_fma(mu1, mu1, lr_fma(mu2, mu2, C1)), d2 = (s11 + s22) + C2;
+    const float inv = 1.f / (d1 * d2);                      // the one division; 1/d1 = inv * d2, 1/d2 = inv * d1
+    const float ssim = (n1 * n2) * inv;
+    ssum += ssim;
+    if (a.maps) {
+      const float id1 = inv * d2, id2 = inv * d1;
+      const float ds11 = -(ssim * id2);
+      const float ds12 = (2.f * n1) * inv;
+      const float t1 = (2.f * mu2) * (n2 * inv) - (2.f * mu1) * (ssim * id1);    // through n1 and d1 only
+      const float dm1 = (t1 - (2.f * m1c) * ds11) - m2c * ds12;
+      const int o = oy * OW + ox;
+      map0[o] = a.scale * dm1;
+      map1[o] = a.scale * ds11;
+      map2[o] = a.scale * ds12;
+    }
+  }
+  const float bs = ls_block_sum(ssum, ws);
+  const float bl = ls_block_sum(l1, ws + 4);
+  if (tid == 0) reinterpret_cast<float2*>(a.partial)[blockIdx.x] = make_float2(bs, bl);
+}
+
+// one workgroup of 1024: thread t adds partials t, t+1024, ... (four independent chains, combined in order) in double,
+// then a fixed tree over the threads
+#define LS_RED_THREADS 1024
+__global__ void __launch_bounds__(LS_RED_THREADS)
+loss_reduce_kernel(const float2* __restrict__ partial, uint32_t n, double inv_count, double inv_count_l1, float wa, float wb,
+                   float* __restrict__ out3) {
+  __shared__ double s0[LS_RED_THREADS], s1[LS_RED_THREADS];
+  double c0[4] = {0.0, 0.0, 0.0, 0.0}, c1[4] = {0.0, 0.0, 0.0, 0.0};
+  for (uint32_t base = 0; base < n; base += 4u * LS_RED_THREADS) {
+#pragma unroll
+    for (uint32_t u = 0; u < 4u; u++) {
+      const uint32_t i = base + u * LS_RED_THREADS + threadIdx.x;
+      if (i < n) {
+        const float2 v = partial[i];
+        c0[u] += (double)v.x;
+        c1[u] += (double)v.y;
+      }
+    }
+  }
+  s0[threadIdx.x] = (c0[0] + c0[1]) + (c0[2] + c0[3]);
+  s1[threadIdx.x] = (c1[0] + c1[1]) + (c1[2] + c1[3]);
+  __syncthreads();
+  for (uint32_t d = LS_RED_THREADS / 2; d >= 1; d >>= 1) {
+    if (threadIdx.x < d) { s0[threadIdx.x] += s0[threadIdx.x + d]; s1[threadIdx.x] += s1[threadIdx.x + d]; }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const double ssim = 1.0 - s0[0] * inv_count, l1 = s1[0] * inv_count_l1;
+    out3[0] = (float)((double)wa * ssim + (double)wb * l1);
+    out3[1] = (float)l1;
+    out3[2] = (float)ssim;
+  }
+}
+
+__global__ void __launch_bounds__(LS_THREADS)
+loss_bwd_kernel(LossArgs a, const float* __restrict__ grad_loss, float* __restrict__ g_render, float* __restrict__ g_render_l1) {
+  __shared__ lr_f2 sm01[LS_IN * LS_IN];                     // (maps0, maps1)
+  __shared__ float sm2[LS_IN * LS_IN];
+  __shared__ lr_f2 hm01[LS_IN * LS_T];
+  __shared__ float hm2[LS_IN * LS_T];
+  const int tid = (int)threadIdx.x;
+  int t = (int)blockIdx.x;
+  const int c = t % a.C; t /= a.C;
+  const int tx = t % a.ntx; t /= a.ntx;
+  const int ty = t % a.nty;
+  const int b = t / a.nty;
+  const int x0 = tx * LS_T, y0 = ty * LS_T;
+  const int OW = a.W - LS_HALO, OH = a.H - LS_HALO;
+  const int64_t plane = (int64_t)OH * OW, bc = (int64_t)b * a.C + c, nbc = (int64_t)a.B * a.C;
+  const float* map0 = a.maps + bc * plane;                 // uniform per workgroup
+  const float* map1 = map0 + nbc * plane;
+  const float* map2 = map1 + nbc * plane;
+
+  // the image values of this thread's four pixels are requested first (used last)
+  const int xo = tid & (LS_T - 1), yq = (tid / LS_T) * LS_ROWS;
+  const int x = x0 + xo;
+  const float* rp = ls_plane(a.render, a.rs, b, c);
+  const float* gp = ls_plane(a.gt, a.gs, b, c);
+  const float* lp = a.render_l1 ? ls_plane(a.render_l1, a.ls, b, c) : nullptr;
+  const int rsy = (int)a.rs[2], rsx = (int)a.rs[3], gsy = (int)a.gs[2], gsx = (int)a.gs[3], lsy = (int)a.ls[2], lsx = (int)a.ls[3];
+  float pr[LS_ROWS], pg[LS_ROWS], pl[LS_ROWS];
+#pragma unroll
+  for (int j = 0; j < LS_ROWS; j++) {
+    const int y = y0 + yq + j;
+    const bool in = x < a.W && y < a.H;
+    pr[j] = in ? rp[y * rsy + x * rsx] : 0.f;
+    pg[j] = in ? gp[y * gsy + x * gsx] : 0.f;
+    pl[j] = (in && lp) ? lp[y * lsy + x * lsx] : 0.f;
+  }
+
+  // maps at q = p - 10 .. p (zero outside the valid region); all loads requested before the first is used
+  float v0[LS_STAGE], v1[LS_STAGE], v2[LS_STAGE];
+#pragma unroll
+  for (int u = 0; u < LS_STAGE; u++) {
+    const int i = tid + u * LS_THREADS;
+    const int ly = i / LS_IN, lx = i - ly * LS_IN;
+    const int qy = y0 - LS_HALO + ly, qx = x0 - LS_HALO + lx;
+    const bool in = i < LS_IN * LS_IN && qy >= 0 && qy < OH && qx >= 0 && qx < OW;
+    const int o = qy * OW + qx;
+    v0[u] = in ? map0[o] : 0.f;
+    v1[u] = in ? map1[o] : 0.f;
+    v2[u] = in ? map2[o] : 0.f;
+  }
+#pragma unroll
+  for (int u = 0; u < LS_STAGE; u++) {
+    const int i = tid + u * LS_THREADS;
+    if (i < LS_IN * LS_IN) { sm01[i] = lr_f2{v0[u], v1[u]}; sm2[i] = v2[u]; }
+  }
+  __syncthreads();
+
+  // horizontal: image column xo gets tap k from map column xo - k (local xo + 10 - k)
+  for (int i = tid; i < LS_IN * LS_T; i += LS_THREADS) {
+    const int row = i / LS_T, hx = i - row * LS_T;
+    const int base = row * LS_IN + hx + LS_HALO;
+    lr_f2 h01 = {0.f, 0.f};
+    float h2 = 0.f;
+#pragma unroll
+    for (int k = 0; k < LS_WIN_TAPS; k++) {
+      const float w = a.w[k];
+      h01 = lr_fma2(lr_f2{w, w}, sm01[base - k], h01);
+      h2 = lr_fma(w, sm2[base - k], h2);
+    }
+    hm01[i] = h01; hm2[i] = h2;
+  }
+  __syncthreads();
+
+  // vertical: image row yq + j gets tap k from LDS row yq + j + 10 - k; rows walked downwards so that k ascends
+  lr_f2 a01[LS_ROWS];
+  float a2[LS_ROWS];
+#pragma unroll
+  for (int j = 0; j < LS_ROWS; j++) { a01[j] = lr_f2{0.f, 0.f}; a2[j] = 0.f; }
+#pragma unroll
+  for (int rr = LS_ROWS + LS_HALO - 1; rr >= 0; rr--) {
+    const int o = (yq + rr) * LS_T + xo;
+    const lr_f2 v01 = hm01[o];
+    const float v2 = hm2[o];
+#pragma unroll
+    for (int j = 0; j < LS_ROWS; j++) {
+      const int k = j + LS_HALO - rr;
+      if (k >= 0 && k < LS_WIN_TAPS) {
+        a01[j] = lr_fma2(lr_f2{a.w[k], a.w[k]}, v01, a01[j]);
+        a2[j] = lr_fma(a.w[k], v2, a2[j]);
+      }
+    }
+  }
+
+  const float gl = grad_loss[0];
+  if (x >= a.W) return;
+  const int64_t out_plane = bc * ((int64_t)a.H * a.W);
+#pragma unroll
+  for (int j = 0; j < LS_ROWS; j++) {
+    const int y = y0 + yq + j;
+    if (y >= a.H) continue;
+    const float r = pr[j], g = pg[j];
+    float G = gl * lr_fma(g - LS_CENTER, a2[j], lr_fma(2.f * (r - LS_CENTER), a01[j].y, a01[j].x));
+    const float d = (lp ? pl[j] : r) - g;
+    const float sgn = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);       // sign(0) = 0, as torch.nn.L1Loss
+    const float l1g = gl * (a.l1_scale * sgn);
+    const int o = y * a.W + x;
+    if (lp) g_render_l1[out_plane + o] = l1g;
+    else G += l1g;
+    g_render[out_plane + o] = G;
+  }
+}
+
+hipError_t lr_launch_loss_fwd(const LossArgs& a, float wa, float wb, float* out3, hipStream_t s) {
+  const uint32_t blocks = (uint32_t)a.ntx * (uint32_t)a.nty * (uint32_t)a.B * (uint32_t)a.C;
+  lr_prof_begin(LRK_LOSS_FWD, s);
+  hipLaunchKernelGGL(loss_fwd_kernel, dim3(blocks), dim3(LS_THREADS), 0, s, a);
+  const double count = (double)a.B * a.C * (double)(a.H - LS_HALO) * (double)(a.W - LS_HALO);
+  const double count_l1 = (double)a.B * a.C * (double)a.H * (double)a.W;
+  hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(LS_RED_THREADS), 0, s, reinterpret_cast<const float2*>(a.partial), blocks, 1.0 / count,
+                     1.0 / count_l1, wa, wb, out3);
+  lr_prof_end(LRK_LOSS_FWD, s);
+  return hipGetLastError();
+}
+
+hipError_t lr_launch_loss_bwd(const LossArgs& a, const float* grad_loss, float* g_render, float* g_render_l1, hipStream_t s) {
+  const uint32_t blocks = (uint32_t)a.ntx * (uint32_t)a.nty * (uint32_t)a.B * (uint32_t)a.C;
+  lr_prof_begin(LRK_LOSS_BWD, s);
+  hipLaunchKernelGGL(loss_bwd_kernel, dim3(blocks), dim3(LS_THREADS), 0, s, a, grad_loss, g_render, g_render_l1);
+  lr_prof_end(LRK_LOSS_BWD, s);
+  return hipGetLastError();
+}

@@ -1,0 +1,188 @@
+"""The photometric training loss of LoG on the device: ``0.2 * (1 - SSIM) + 0.8 * L1`` as
+LoG/render/renderer.py:253-266 (``calculate_loss``) and LoG/render/loss.py:6-44 (``SSIM``) compute it, in one forward
+kernel + a fixed-order reduction and one backward kernel (log_amd/csrc/loss.hip, C ABI ``lograst_loss_*``) instead of
+five grouped ``conv2d``, a dozen element-wise kernels and their autograd backward.
+
+* ``l1_ssim_loss(render, gt, render_l1=None, ssim_weight=0.2, l1_weight=0.8) -> (loss, l1, ssim)``
+* ``ssim(img1, img2)`` = what ``SSIM(11, C).forward(img1, img2)`` returns (``1 - mean(ssim_map)``)
+* ``install()`` assigns drop-ins onto the reference's classes (``SSIM.forward``, ``NaiveRendererAndLoss.calculate_loss``);
+  ``log_amd.install_all(fused_loss=True)`` calls it.
+
+Tensors are read through their strides (the channels-last ``batch['image'].permute(0, 3, 1, 2)`` LoG passes as ``gt`` is
+not copied); results and gradients are bit-identical from run to run; nothing is read back to the host, so forward and
+backward can be captured in a HIP graph."""
+import ctypes
+import math
+
+import torch
+
+from . import _lib
+from .rasterizer import _ptr, _stream_ptr
+
+WINDOW = 11          # taps of the SSIM window (sigma 1.5), the only size the kernel has
+TILE = 32            # output pixels per workgroup tile side (loss.hip: LS_T)
+
+
+def window_taps():
+    """The 11 fp32 window weights exactly as the library computes them: exp(-(x-5)^2 / (2 * 1.5^2)) in double,
+    normalised in double, rounded to fp32 once.  -> float32 tensor [11] (CPU)."""
+    g = [math.exp(-float((k - 5) * (k - 5)) / (2.0 * 1.5 * 1.5)) for k in range(WINDOW)]
+    s = 0.0
+    for v in g:
+        s += v
+    return torch.tensor([v / s for v in g], dtype=torch.float64).to(torch.float32)
+
+
+def _strides(t):
+    return (ctypes.c_int64 * 4)(*t.stride())
+
+
+def _require(render, gt, render_l1):
+    for name, t in (("render", render), ("gt", gt), ("render_l1", render_l1)):
+        if t is None:
+            continue
+        if t.device.type != "cuda":
+            raise _lib.LograstError(
+                f"log_amd.loss needs tensors on the MI355X ({name} is on '{t.device}'); the HIP kernels are the only "
+                "implementation -- there is no CPU fallback")
+        if t.dtype != torch.float32 or t.dim() != 4:
+            raise ValueError(f"{name}: expected a float32 tensor [B, C, H, W], got {t.dtype} {tuple(t.shape)}")
+        if t.shape != render.shape or t.device != render.device:
+            raise ValueError(f"{name}: shape {tuple(t.shape)} on {t.device} does not match render {tuple(render.shape)} on {render.device}")
+    return _lib.lib()
+
+
+class _L1SSIM(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, render, gt, render_l1, ssim_weight, l1_weight):
+        L = _require(render, gt, render_l1)
+        if ctx.needs_input_grad[1]:
+            raise _lib.LograstError("log_amd.loss: gt gets no gradient (detach it)")
+        device = render.device
+        B, C, H, W = (int(s) for s in render.shape)
+        r, g = render.detach(), gt.detach()
+        rl = None
+        if render_l1 is not None:
+            rl = render_l1.detach()
+            if rl.data_ptr() == r.data_ptr() and rl.stride() == r.stride():
+                rl = None
+        need_grad = any(ctx.needs_input_grad[i] for i in (0, 2))
+        out = torch.empty(3, dtype=torch.float32, device=device)
+        nmaps = 3 * B * C * max(H - WINDOW + 1, 0) * max(W - WINDOW + 1, 0)
+        maps = torch.empty(nmaps, dtype=torch.float32, device=device) if need_grad else None
+        nbytes = L.lograst_loss_scratch_bytes(B, C, H, W)
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        with torch.cuda.device(device):
+            _lib.check(L.lograst_loss_forward(
+                B, C, H, W, _ptr(r), _strides(r), _ptr(rl), _strides(rl) if rl is not None else None, _ptr(g), _strides(g),
+                float(ssim_weight), float(l1_weight), _ptr(out), _ptr(maps), _ptr(scratch), nbytes, _stream_ptr(device)))
+        ctx.geom = (B, C, H, W, float(l1_weight))
+        ctx.tensors = (r, g, rl, maps)
+        ctx.l1_is_input = render_l1 is not None
+        loss, stats = out[0], out[1:3]
+        ctx.mark_non_differentiable(stats)
+        return loss, stats
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_loss, _grad_stats):
+        B, C, H, W, l1_weight = ctx.geom
+        r, g, rl, maps = ctx.tensors
+        device = r.device
+        L = _lib.lib()
+        gl = grad_loss.detach().to(device=device, dtype=torch.float32).reshape(1).contiguous()
+        g_render = torch.empty((B, C, H, W), dtype=torch.float32, device=device)
+        g_l1 = torch.empty((B, C, H, W), dtype=torch.float32, device=device) if rl is not None else None
+        with torch.cuda.device(device):
+            _lib.check(L.lograst_loss_backward(
+                B, C, H, W, _ptr(r), _strides(r), _ptr(rl), _strides(rl) if rl is not None else None, _ptr(g), _strides(g),
+                l1_weight, _ptr(gl), _ptr(maps), _ptr(g_render), _ptr(g_l1), _stream_ptr(device)))
+        if rl is None and ctx.l1_is_input:
+            g_l1 = None          # render_l1 was render itself: its L1 term is already in g_render
+        return (g_render if ctx.needs_input_grad[0] else None, None,
+                g_l1 if ctx.l1_is_input and ctx.needs_input_grad[2] else None, None, None)
+
+
+def _fused(render, gt, render_l1, ssim_weight, l1_weight):
+    if render_l1 is render:
+        render_l1 = None
+    return _L1SSIM.apply(render, gt, render_l1, ssim_weight, l1_weight)
+
+
+def l1_ssim_loss(render, gt, render_l1=None, ssim_weight=0.2, l1_weight=0.8):
+    """-> (loss, l1, ssim): ``loss = ssim_weight * ssim + l1_weight * l1`` carries the graph (gradients for ``render`` and,
+    when it is a tensor of its own, ``render_l1``); ``l1 = mean|render_l1 - gt|`` and ``ssim = 1 - mean(ssim_map(render,
+    gt))`` are detached 0-dim views of the same device buffer.  All tensors [B, C, H, W] float32 on the device, any
+    strides; H, W >= 11."""
+    loss, stats = _fused(render, gt, render_l1, ssim_weight, l1_weight)
+    return loss, stats[0], stats[1]
+
+
+def ssim(img1, img2):
+    """``SSIM(11, C).forward(img1, img2, reduce=True)``: 1 - mean(ssim_map)."""
+    return _fused(img1, img2, None, 1.0, 0.0)[0]
+
+
+# ---- drop-ins for an unmodified LoG checkout ------------------------------------------------------------------------
+
+def _fusable(*tensors):
+    return all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 for t in tensors)
+
+
+def _make_ssim_forward(original):
+    def forward(self, img1, img2, reduce=True):
+        if (reduce and self.window_size == WINDOW and getattr(self, "padding", 0) == 0 and _fusable(img1, img2)
+                and img1.shape == img2.shape and not img2.requires_grad):
+            return ssim(img1, img2)
+        return original(self, img1, img2, reduce)
+    forward._lograst_original = original
+    return forward
+
+
+def _make_calculate_loss(original):
+    def calculate_loss(self, gt_image, render, output, mask_ignore=None):
+        """renderer.py:253-266 with the two losses in one kernel and ONE read-back for loss_dict."""
+        ssim_mod = getattr(self, "ssim_loss", None)
+        if not (_fusable(gt_image, render) and gt_image.shape == render.shape and not gt_image.requires_grad
+                and getattr(ssim_mod, "window_size", None) == WINDOW and getattr(ssim_mod, "padding", 0) == 0
+                and isinstance(getattr(self, "l1_loss", None), torch.nn.L1Loss) and self.l1_loss.reduction == "mean"):
+            return original(self, gt_image, render, output, mask_ignore)
+        if mask_ignore is not None:
+            render = gt_image * mask_ignore[:, None] + render * (1 - mask_ignore[:, None])
+        render_l1 = output["render_correct"][:, :3] if "render_correct" in output.keys() else render
+        if not (_fusable(render_l1) and render_l1.shape == render.shape):
+            return original(self, gt_image, render, output, None)     # (the blend is already applied)
+        loss, stats = _fused(render, gt_image, render_l1, 0.2, 0.8)
+        l1_value, ssim_value = stats.tolist()
+        output["loss_dict"] = {"l1": l1_value, "ssim": ssim_value}
+        output["loss"] = loss
+    calculate_loss._lograst_original = original
+    return calculate_loss
+
+
+def install(renderer=True):
+    """Patch the reference in place (needs LoG importable): SSIM.forward, and -- when LoG.render.renderer can be
+    imported (it needs cv2) -- NaiveRendererAndLoss.calculate_loss (MaskForeground inherits it).  Calls the kernels do not
+    cover (reduce=False, another window, CPU tensors) go to the methods that were replaced."""
+    from LoG.render.loss import SSIM
+    if not hasattr(SSIM.forward, "_lograst_original"):
+        SSIM.forward = _make_ssim_forward(SSIM.forward)
+    if renderer:
+        try:
+            import LoG.render.renderer as rr
+        except ImportError:
+            rr = None
+        if rr is not None and not hasattr(rr.NaiveRendererAndLoss.calculate_loss, "_lograst_original"):
+            rr.NaiveRendererAndLoss.calculate_loss = _make_calculate_loss(rr.NaiveRendererAndLoss.calculate_loss)
+    return SSIM
+
+
+def uninstall():
+    """Put back what install() replaced."""
+    import sys
+    mod = sys.modules.get("LoG.render.loss")
+    if mod is not None and hasattr(mod.SSIM.forward, "_lograst_original"):
+        mod.SSIM.forward = mod.SSIM.forward._lograst_original
+    rr = sys.modules.get("LoG.render.renderer")
+    if rr is not None and hasattr(rr.NaiveRendererAndLoss.calculate_loss, "_lograst_original"):
+        rr.NaiveRendererAndLoss.calculate_loss = rr.NaiveRendererAndLoss.calculate_loss._lograst_original

@@ -213,7 +213,11 @@ def view(wl, st, cam_pack, fused, clock):
     image, radii, pid, pwp, pw = rast(means3D=act["xyz"], means2D=means2D, shs=None, colors_precomp=act["colors"],
                                       opacities=act["opacity"], scales=act["scaling"], rotations=act["rotation"],
                                       cov3D_precomp=None)
-    image.backward(gradient=wl.wloss)
+    if LOSS_MODE is None:
+        image.backward(gradient=wl.wloss)
+    else:
+        clock("loss")
+        photometric_loss(wl, image).backward()
     clock("id_histogram")
     n = int(act["xyz"].shape[0])
     ids, counts = counter.unique_ids(pid, n) if fused else torch_unique(pid)
@@ -234,6 +238,53 @@ def view(wl, st, cam_pack, fused, clock):
         torch_adam(wl, st, index, params, flag_leaf)
     clock(None)
     return n, int(ids.numel())
+
+
+# ---- the photometric loss in place of the fixed dL/dimage (--with-loss) ---------------------------------------------
+LOSS_MODE = None          # None: image.backward(gradient=wl.wloss); "fused": log_amd.loss.l1_ssim_loss; "torch": the reference's ops
+
+
+def photometric_loss(wl, image):
+    """0.2 * (1 - SSIM) + 0.8 * L1 against a fixed channels-last ground-truth image, as renderer.py:253-266 computes it
+    (without its two .item() read-backs): through the fused kernels or through five grouped conv2d + element-wise ops."""
+    import torch.nn.functional as F
+    if not hasattr(wl, "gt_image"):
+        g = torch.Generator(device=wl.dev).manual_seed(7)
+        wl.gt_image = torch.rand(1, H, W, 3, device=wl.dev, generator=g).permute(0, 3, 1, 2)
+        from log_amd.loss import window_taps
+        t = window_taps().to(wl.dev)
+        wl.ssim_window = (t[:, None] * t[None, :]).expand(3, 1, 11, 11).contiguous()
+    render, gt = image[None], wl.gt_image
+    if LOSS_MODE == "fused":
+        from log_amd.loss import l1_ssim_loss
+        return l1_ssim_loss(render, gt)[0]
+    w = wl.ssim_window
+    mu1, mu2 = F.conv2d(render, w, groups=3), F.conv2d(gt, w, groups=3)
+    s11 = F.conv2d(render * render, w, groups=3) - mu1 * mu1
+    s22 = F.conv2d(gt * gt, w, groups=3) - mu2 * mu2
+    s12 = F.conv2d(render * gt, w, groups=3) - mu1 * mu2
+    ssim_map = ((2 * mu1 * mu2 + 1e-4) * (2 * s12 + 9e-4)) / ((mu1 * mu1 + mu2 * mu2 + 1e-4) * (s11 + s22 + 9e-4))
+    return 0.2 * (1.0 - ssim_map.mean()) + 0.8 * F.l1_loss(render, gt)
+
+
+def with_loss_leg(roots=40000, levels=7, sh_degree=3, views=8, root_scale=0.03, dev=None):
+    """The C3 training view (drop-ins everywhere) three times: backward seeded with a fixed dL/dimage (what every other leg
+    times), with the fused loss, with the torch loss.  -> ms per view each, and the loss stage's own clock."""
+    global LOSS_MODE
+    wl = Workload(roots, levels, sh_degree, views, root_scale, dev)
+    out = {}
+    try:
+        for mode in (None, "fused", "torch"):
+            LOSS_MODE = mode
+            tot, _, _, _ = run(wl, True, False)
+            _, stages, _, _ = run(wl, True, True)
+            key = mode or "fixed_gradient"
+            out["ms_per_view_" + key] = tot
+            if mode:
+                out["loss_stage_ms_" + key] = stages.get("loss")
+    finally:
+        LOSS_MODE = None
+    return out
 
 
 def run(wl, fused, staged):
@@ -375,6 +426,13 @@ def c3_pipeline(roots=40000, levels=7, sh_degree=3, views=8, root_scale=0.03, wi
 
 if __name__ == "__main__":
     a = sys.argv[1:]
+    if "--with-loss" in a:
+        a = [v for v in a if not v.startswith("--")]
+        res = with_loss_leg(int(a[0]) if len(a) > 0 else 40000, int(a[1]) if len(a) > 1 else 7, int(a[2]) if len(a) > 2 else 3,
+                            int(a[3]) if len(a) > 3 else 8, float(a[4]) if len(a) > 4 else 0.03)
+        res["bench"] = "log_step_with_loss"
+        print(json.dumps(res))
+        sys.exit(0)
     res = c3_pipeline(int(a[0]) if len(a) > 0 else 40000, int(a[1]) if len(a) > 1 else 7, int(a[2]) if len(a) > 2 else 3,
                       int(a[3]) if len(a) > 3 else 8, float(a[4]) if len(a) > 4 else 0.03, with_torch="--torch" in a)
     res["bench"] = "log_step"
