@@ -14,85 +14,7 @@
 #include <vector>
 
 #include "common.hpp"
-
-// launchers (defined next to their kernels)
-void lr_launch_radius(int P, const float* means, const float* scales, const float* rots, const float* proj,
-                      const float* view, float fx, float fy, float tanfovx, float tanfovy, float* radii,
-                      hipStream_t s);
-void lr_launch_project(const LrView& v, int N, const float* means, const float* scales, const float* rots,
-                       const float* opac, const float* colors, int* radii, void* geom, uint32_t* ranked,
-                       uint32_t* big, uint32_t* hdr, uint32_t* basetab, int batch, int planes, int tile_cull,
-                       hipStream_t s);
-void lr_launch_scan(uint32_t* state, uint32_t tiles, uint32_t cs, uint32_t big_off, hipStream_t s);
-void lr_launch_rebase(uint32_t* state, uint32_t tiles, uint32_t batches, uint32_t t_lo, uint32_t t_hi, hipStream_t s);
-bool lr_band_sparse(const LrView& v, int batch);
-void lr_launch_zero_words(uint32_t* p, size_t words, hipStream_t s);
-void lr_launch_zero_floats(float* p, size_t n, hipStream_t s);
-// exchange.hip
-void lx_launch_pack_rows(float* rows, int groups, long long rows_per_group, int kmax, float* packed,
-                         size_t seg_floats, uint32_t* overflow, int clear, const uint32_t* hint, long long hint_rows,
-                         hipStream_t s);
-void lx_launch_add_visible(float* seen, const int32_t* radii, long long n, hipStream_t s);
-void lx_launch_add_visible_n(float* seen, const int32_t* const* radii, int k, long long n, hipStream_t s);
-void lx_launch_unpack_rows(float* dest, const float* packed, int segments, int kmax, size_t seg_floats,
-                           long long rows_per_group, long long dest_group_rows, int add, int zero, hipStream_t s);
-void lr_launch_fill(int N, int gx, const void* geom, uint32_t* state, uint32_t tiles, uint64_t* keys,
-                    uint32_t capacity, uint32_t max_len_hint, uint32_t* status, float* zero_n, float* zero_block,
-                    int zero_block_floats, int rebased, int speculative, int band, int staged_k, hipStream_t s);
-void lr_launch_tile_rows(const LrView& v, int N, const float* means, const float* scales, const float* rots,
-                         uint32_t* rows, hipStream_t s);
-void lr_launch_stream_copy(const void* src, void* dst, size_t bytes, int blocks, hipStream_t s);
-void lr_launch_sort(uint32_t* state, uint32_t tiles, uint64_t* keys, uint32_t* plist, uint32_t capacity,
-                    uint32_t max_len, int lazy, hipStream_t s);
-void lr_launch_sort_rest(uint32_t* state, uint32_t tiles, uint64_t* keys, uint32_t* plist, uint32_t capacity,
-                         uint32_t max_len, int mode, hipStream_t s);
-void lr_launch_ordered_lengths(const uint32_t* state, uint32_t tiles, uint32_t* out, hipStream_t s);
-void lr_launch_blend_fwd(const LrView& v, const void* geom, const uint32_t* state, uint32_t tiles,
-                         const uint32_t* plist, uint32_t capacity, float* image, float* final_T, int* n_contrib,
-                         int* pid, float* pwp, float* pw, float* zero_conic, int big_input, int lazy, uint64_t* masks,
-                         hipStream_t s);
-int lr_blend_fwd_form(const LrView& v);
-void lr_launch_blend_bwd(const LrView& v, const void* geom, const uint32_t* state, uint32_t tiles,
-                         const uint32_t* plist, uint32_t capacity, const float* final_T, const int* n_contrib,
-                         const float* dL_dimage, float* acc_rows, int big_input, const uint64_t* masks, hipStream_t s);
-void lr_launch_project_bwd(const LrView& v, int N, const float* means, const float* scales, const float* rots,
-                           const int* radii, const float* g_mean2d, const float* g_conic, const float* rows,
-                           float* o_mean2d, float* o_opac, float* o_col, const float* pw,
-                           float* g_means3d, float* g_scales, float* g_rots, bool accumulate, bool sink_rows,
-                           hipStream_t s);
-
-size_t lr_knn_scratch_bytes(int P);
-hipError_t lr_launch_knn(int P, const float* pts, float* out, void* scratch, size_t scratch_bytes, hipStream_t s);
-
-void lr_launch_sh_fwd(int N, int deg, int M, const float* means, const float* campos, const float* shs, float* colors,
-                      uint8_t* clamped, hipStream_t s);
-void lr_launch_sh_bwd(int N, int deg, int M, const float* means, const float* campos, const float* shs,
-                      const uint8_t* clamped, const float* g_colors, float* g_shs, float* g_means, bool accumulate,
-                      hipStream_t s);
-
-size_t lr_lod_scratch_bytes(int num_roots, int num_nodes, int max_child);
-hipError_t lr_launch_lod(int num_points, int num_nodes, int max_child, const int32_t* node_index, const int32_t* tree,
-                         const float* xyz, const float* scaling, const float* rotation, const int64_t* root_index,
-                         int num_roots, const float* proj, const float* view, float fx, float fy, float tanfovx,
-                         float tanfovy, float min_px, int levels, int64_t* out, uint32_t out_capacity, void* scratch,
-                         hipStream_t s);
-int lr_lod_max_levels();
-uint32_t lr_lod_total_word();   // header words TOTAL, OVERFLOW, LEFT are consecutive
-
-size_t lr_hist_scratch_bytes(int n);
-hipError_t lr_launch_id_histogram(int n, const int32_t* pid, int npix, int32_t* ids, int64_t* counts, void* scratch,
-                                  hipStream_t s);
-hipError_t lr_launch_counter(const CounterArgs& a, hipStream_t s);
-hipError_t lr_launch_sparse_adam(const AdamArgs& a, int num_keys, hipStream_t s);
-
-hipError_t lr_launch_gather_activate(const GatherArgs& a, hipStream_t s);
-hipError_t lr_launch_activate_bwd(const ActBwdArgs& a, hipStream_t s);
-hipError_t lr_launch_activate_bwd_adam(const ActBwdArgs& a, const AdamArgs& f, const float* g_a_xyz, const int32_t* radii,
-                                       hipStream_t s);
-
-size_t lr_loss_scratch_bytes(int B, int C, int H, int W);
-hipError_t lr_launch_loss_fwd(const LossArgs& a, float wa, float wb, float* out3, hipStream_t s);
-hipError_t lr_launch_loss_bwd(const LossArgs& a, const float* grad_loss, float* g_render, float* g_render_l1, hipStream_t s);
+#include "launch.hpp"
 
 static thread_local std::string g_err;
 static int lr_fail(int code, const std::string& msg) {
@@ -106,71 +28,90 @@ static int lr_fail(int code, const std::string& msg) {
       return lr_fail(LOGRAST_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));              \
   } while (0)
 
-int lr_env_int(const char* name, int dflt) {
+static int lr_env_int(const char* name, int dflt) {
   const char* e = std::getenv(name);
   return (e && *e) ? std::atoi(e) : dflt;
 }
 // ---- performance knobs ------------------------------------------------------------------------------------
-// The tunable ones (lograst_knob_info enumerates them for log_amd.tune): name = the environment variable, default, range.
-struct LrKnobInfo { const char* name; int dflt, lo, hi; const char* what; };
-static const LrKnobInfo kKnobs[] = {
-    {"LOGRAST_HELPER_MIN_N", 4000000, 0, 2000000000, "Gaussians from which the helper passes (absolute slot table, touched-only dL/dconic clearing, separate zero-fill kernels) pay for their launches"},
-    {"LOGRAST_HIT_MASKS", 1, 0, 1, "the compositing kernels leave their per-chunk support ballots in lograst_view.hit_masks (when the caller provides it) and the reverse walk reads them instead of running the tests again; 0 = ignore the buffer"},
-    {"LOGRAST_LAZY_SORT", 1, 0, 1, "lists of more than 4096 keys are ordered over their first window (7680 positions) only; tiles whose walk needs more are marked by the compositing kernels and finished by a second, normally idle sort + compositing pair; 0 = every list to its end up front"},
-    {"LOGRAST_PBWD_LIST", 1, 0, 2, "large inputs with running-sum gradients: the chain rule runs over a compact list of the rows with point_weight > 0 (a streaming compaction pass + a list pass) instead of one kernel that tests every row: 0 never, 1 on band views, 2 always"},
-    {"LOGRAST_MID_RANK", 1, 0, 1, "rects of 5..16 tiles are RANKED by the batched projection (LDS atomics; 32-byte rank rows in geom), so the fill places them without cursor atomics or support tests; 0 = counted only, placed through the per-tile cursors"},
-    {"LOGRAST_MID_COOP", 16, 0, 64, "rects of 5..16 tiles are counted (projection: in waves that hold at most this many of them) and placed (fill: any non-zero value) by the whole wave, four rects per pass, instead of by their lane; 0 = per lane"},
-    {"LOGRAST_DEFER_TILES", LR_COOP_TILES, 4, 4096, "rects above this many tiles are counted by lr_count_huge_kernel (one wave per rect) instead of by their lane"},
-    {"LOGRAST_HUGE_CHUNK", LR_HUGE_CHUNK, 256, 8192, "Gaussians per workgroup of lr_count_huge_kernel (multiple of 256)"},
-    {"LOGRAST_BATCH_PLANES", 4, 1, 4, "consecutive projection batches one workgroup owns"},
-    {"LOGRAST_BATCH_SLOTS", 256, 64, 1024, "workgroups per round the batched projection sizes its batches for"},
-    {"LOGRAST_SEPARATE_ZERO", 1, 0, 1, "large inputs: zero-fills streamed by kernels of their own instead of inside the fill kernel"},
-    {"LOGRAST_FILL_XCD_ORDER", 1, 0, 1, "fill kernel walks the Gaussians XCD-contiguously"},
-    {"LOGRAST_FILL_NT", 1, 0, 1, "fill kernel: non-temporal streams for the fill records and zero-fills"},
-    {"LOGRAST_XCD_MODE", 3, 0, 3, "blockIdx -> tile mapping of the compositing kernels (3 = longest list first)"},
-    {"LOGRAST_PROJECT_BLOCKS", 512, 64, 65536, "grid cap of the unbatched projection kernel"},
-    {"LOGRAST_BWD_ROWS", 2, 0, 2, "reverse walk: 1 = row-split form (four 4x4 blocks per wave), 0 = one quadrant per wave, 2 = the view's walk_form hint (none: row-split from LOGRAST_HELPER_MIN_N Gaussians)"},
-    {"LOGRAST_FWD_ROWS", 2, 0, 2, "compositing: 1 = row-split form (four 4x4 blocks per wave), 0 = one quadrant per wave, 2 = the view's walk_form hint"},
-    {"LOGRAST_FILL_STAGED", 2, 0, 3, "bucket fill of batched full views: K = the batch's slot-table row staged in LDS by workgroups of up to K x 1024 consecutive Gaussians (K per thread), 0 = one table look-up per tile instance"},
-    {"LOGRAST_FILL_PER_THREAD", 1, 1, 4, "bucket fill: Gaussians per thread (their fill records are requested together): 1, 2 or 4"},
-    {"LOGRAST_BAND_SPARSE", 1, 0, 1, "band views (tile_row_begin/end a proper part of the grid): 1 = the band projection (Gaussians without a rect cost 44 bytes, survivors compacted into full waves), 0 = the full-view kernel"},
-    {"LOGRAST_FWD_BLOCK_TEST", 1, 0, 1, "row-split compositing: 1 = exact support test per 4x4 block, 0 = exact for the quadrant + bounding box per block (the reverse walk on the forward's hit masks visits what the forward's test kept)"},
-    {"LOGRAST_BWD_BLOCK_TEST", 1, 0, 1, "row-split reverse walk: 1 = exact support test per 4x4 block, 0 = exact for the quadrant + bounding box per block"},
+// The one table (common.hpp: LrKnob): name = the environment variable, default, range, what lograst_knob_info tells log_amd.tune.
+struct LrKnobInfo { LrKnob id; const char* name; int dflt, lo, hi; const char* what; };
+static constexpr LrKnobInfo kKnobs[] = {
+    {LRKNOB_HELPER_MIN_N, "LOGRAST_HELPER_MIN_N", 4000000, 0, 2000000000, "Gaussians from which the helper passes (absolute slot table, touched-only dL/dconic clearing, separate zero-fill kernels) pay for their launches"},
+    {LRKNOB_HIT_MASKS, "LOGRAST_HIT_MASKS", 1, 0, 1, "the compositing kernels leave their per-chunk support ballots in lograst_view.hit_masks (when the caller provides it) and the reverse walk reads them instead of running the tests again; 0 = ignore the buffer"},
+    {LRKNOB_LAZY_SORT, "LOGRAST_LAZY_SORT", 1, 0, 1, "lists of more than 4096 keys are ordered over their first window (7680 positions) only; tiles whose walk needs more are marked by the compositing kernels and finished by a second, normally idle sort + compositing pair; 0 = every list to its end up front"},
+    {LRKNOB_PBWD_LIST, "LOGRAST_PBWD_LIST", 1, 0, 2, "large inputs with running-sum gradients: the chain rule runs over a compact list of the rows with point_weight > 0 (a streaming compaction pass + a list pass) instead of one kernel that tests every row: 0 never, 1 on band views, 2 always"},
+    {LRKNOB_MID_RANK, "LOGRAST_MID_RANK", 1, 0, 1, "rects of 5..16 tiles are RANKED by the batched projection (LDS atomics; 32-byte rank rows in geom), so the fill places them without cursor atomics or support tests; 0 = counted only, placed through the per-tile cursors"},
+    {LRKNOB_MID_COOP, "LOGRAST_MID_COOP", 16, 0, 64, "rects of 5..16 tiles are counted (projection: in waves that hold at most this many of them) and placed (fill: any non-zero value) by the whole wave, four rects per pass, instead of by their lane; 0 = per lane"},
+    {LRKNOB_DEFER_TILES, "LOGRAST_DEFER_TILES", LR_COOP_TILES, 4, 4096, "rects above this many tiles are counted by lr_count_huge_kernel (one wave per rect) instead of by their lane"},
+    {LRKNOB_HUGE_CHUNK, "LOGRAST_HUGE_CHUNK", LR_HUGE_CHUNK, 256, 8192, "Gaussians per workgroup of lr_count_huge_kernel (multiple of 256)"},
+    {LRKNOB_BATCH_PLANES, "LOGRAST_BATCH_PLANES", 4, 1, 4, "consecutive projection batches one workgroup owns"},
+    {LRKNOB_BATCH_SLOTS, "LOGRAST_BATCH_SLOTS", 256, 64, 1024, "workgroups per round the batched projection sizes its batches for"},
+    {LRKNOB_SEPARATE_ZERO, "LOGRAST_SEPARATE_ZERO", 1, 0, 1, "large inputs: zero-fills streamed by kernels of their own instead of inside the fill kernel"},
+    {LRKNOB_FILL_XCD_ORDER, "LOGRAST_FILL_XCD_ORDER", 1, 0, 1, "fill kernel walks the Gaussians XCD-contiguously"},
+    {LRKNOB_FILL_NT, "LOGRAST_FILL_NT", 1, 0, 1, "fill kernel: non-temporal streams for the fill records and zero-fills"},
+    {LRKNOB_XCD_MODE, "LOGRAST_XCD_MODE", 3, 0, 3, "blockIdx -> tile mapping of the compositing kernels (3 = longest list first)"},
+    {LRKNOB_PROJECT_BLOCKS, "LOGRAST_PROJECT_BLOCKS", 512, 64, 65536, "grid cap of the unbatched projection kernel"},
+    {LRKNOB_BWD_ROWS, "LOGRAST_BWD_ROWS", 2, 0, 2, "reverse walk: 1 = row-split form (four 4x4 blocks per wave), 0 = one quadrant per wave, 2 = the view's walk_form hint (none: row-split from LOGRAST_HELPER_MIN_N Gaussians)"},
+    {LRKNOB_FWD_ROWS, "LOGRAST_FWD_ROWS", 2, 0, 2, "compositing: 1 = row-split form (four 4x4 blocks per wave), 0 = one quadrant per wave, 2 = the view's walk_form hint"},
+    {LRKNOB_FILL_STAGED, "LOGRAST_FILL_STAGED", 2, 0, 3, "bucket fill of batched full views: K = the batch's slot-table row staged in LDS by workgroups of up to K x 1024 consecutive Gaussians (K per thread), 0 = one table look-up per tile instance"},
+    {LRKNOB_FILL_PER_THREAD, "LOGRAST_FILL_PER_THREAD", 1, 1, 4, "bucket fill: Gaussians per thread (their fill records are requested together): 1, 2 or 4"},
+    {LRKNOB_BAND_SPARSE, "LOGRAST_BAND_SPARSE", 1, 0, 1, "band views (tile_row_begin/end a proper part of the grid): 1 = the band projection (Gaussians without a rect cost 44 bytes, survivors compacted into full waves), 0 = the full-view kernel"},
+    {LRKNOB_FWD_BLOCK_TEST, "LOGRAST_FWD_BLOCK_TEST", 1, 0, 1, "row-split compositing: 1 = exact support test per 4x4 block, 0 = exact for the quadrant + bounding box per block (the reverse walk on the forward's hit masks visits what the forward's test kept)"},
+    {LRKNOB_BWD_BLOCK_TEST, "LOGRAST_BWD_BLOCK_TEST", 1, 0, 1, "row-split reverse walk: 1 = exact support test per 4x4 block, 0 = exact for the quadrant + bounding box per block"},
 };
-static const int kNumKnobs = (int)(sizeof(kKnobs) / sizeof(kKnobs[0]));
-static std::mutex g_knob_mu;
-static std::vector<std::pair<std::string, int>> g_knob_over;   // overrides set through lograst_set_knob
-static std::atomic<unsigned> g_knob_gen{1};
-unsigned lr_knob_generation() { return g_knob_gen.load(std::memory_order_acquire); }
-int lr_knob_lookup(const char* name, int dflt) {
-  {
-    std::lock_guard<std::mutex> lk(g_knob_mu);
-    for (auto& kv : g_knob_over)
-      if (kv.first == name) return kv.second;
-  }
-  return lr_env_int(name, dflt);
+static constexpr bool lr_knobs_in_enum_order() {
+  for (int i = 0; i < LRKNOB_COUNT; i++)
+    if (kKnobs[i].id != i) return false;
+  return true;
 }
-// Support cull in the binning kernels (project.hip): on unless LOGRAST_TILE_CULL=0 or lograst_set_tile_cull(0).
-static std::atomic<int> g_tile_cull{-1};
+static_assert(sizeof(kKnobs) / sizeof(kKnobs[0]) == LRKNOB_COUNT && lr_knobs_in_enum_order(), "kKnobs[]: one row per LrKnob, in the enum's order");
+static std::mutex g_knob_mu;
+static bool g_knob_set[LRKNOB_COUNT];            // lograst_set_knob overrides (under g_knob_mu)
+static int32_t g_knob_over[LRKNOB_COUNT];
+static std::atomic<int32_t> g_knob_val[LRKNOB_COUNT];   // what the next launch reads
+static std::atomic<bool> g_knobs_resolved{false};
+static void lr_resolve_knobs_locked() {
+  for (int i = 0; i < LRKNOB_COUNT; i++)
+    g_knob_val[i].store(g_knob_set[i] ? g_knob_over[i] : lr_env_int(kKnobs[i].name, kKnobs[i].dflt), std::memory_order_relaxed);
+  g_knobs_resolved.store(true, std::memory_order_release);
+}
+int lr_knob(LrKnob k) {
+  if (!g_knobs_resolved.load(std::memory_order_acquire)) {   // first use in this process
+    std::lock_guard<std::mutex> lk(g_knob_mu);
+    if (!g_knobs_resolved.load(std::memory_order_relaxed)) lr_resolve_knobs_locked();
+  }
+  return g_knob_val[k].load(std::memory_order_relaxed);
+}
+
+// ---- the plan of a forward ----------------------------------------------------------------------------------
+// Every launch decision of a forward that depends on (view, n) only, made once per entry point (lr_plan) and handed to both
+// stages: stage 1 skips lr_rebase_kernel exactly when stage 2's fill stages the slot-table row, because both read `staged_k`.
+struct LrPlan {
+  uint32_t tiles;
+  uint32_t batch, planes;   // Gaussians per projection batch (0 = unbatched kernel), consecutive batches per workgroup
+  uint32_t batches;
+  bool band;                // the batched projection runs in its band form (project.hip: lr_band_sparse)
+  int staged_k;             // the fill stages the batch's slot-table row in LDS, K Gaussians per thread (0 = look-up form)
+  bool big_input;           // n >= LOGRAST_HELPER_MIN_N: the helper passes pay for their launches
+};
 // Gaussians per projection batch (project.hip: lr_project_batched_kernel), 0 = unbatched kernel, and the number of
 // consecutive batches one workgroup owns (`planes`: one plane of LDS tile counters each).  A batch is big enough that it
 // puts several instances into a tile (that is what it saves in memory-side atomics) and at most 32768 Gaussians (16-bit
 // ranks); a workgroup takes as many batches as its LDS holds (up to 4), which makes the runs it reserves in a tile
 // adjacent (longer contiguous key writes in the fill) and leaves one workgroup per CU per round.
 // LOGRAST_BATCH_PLANES caps the planes.
-struct LrBatching { uint32_t batch, planes; };
-static LrBatching lr_pick_batch(int32_t n, uint32_t tiles, uint32_t gx, uint32_t gy) {
-  LR_KNOB(max_planes_k, "LOGRAST_BATCH_PLANES", 4);
-  const uint32_t max_planes = (uint32_t)max_planes_k;
-  if (n <= 0 || tiles > LR_BATCH_MAX_TILES || gx > 8191u || gy > 8191u) return {0u, 1u};  // 13-bit tile coordinates in the fill record
+static void lr_pick_batch(LrPlan& p, int32_t n, uint32_t gx, uint32_t gy) {
+  const uint32_t tiles = p.tiles, max_planes = (uint32_t)lr_knob(LRKNOB_BATCH_PLANES);
+  p.batch = 0u; p.planes = 1u;
+  if (n <= 0 || tiles > LR_BATCH_MAX_TILES || gx > 8191u || gy > 8191u) return;  // 13-bit tile coordinates in the fill record
   uint32_t smax = (uint32_t)(LR_BATCH_LDS_BYTES / (sizeof(uint32_t) * (size_t)tiles));
   if (smax > max_planes) smax = max_planes;
   if (smax > 4u) smax = 4u;
   if (smax < 1u) smax = 1u;
   // One workgroup of 1024 threads per CU (82 VGPRs): 256 run at a time.  Size the work so that the workgroups fill
   // whole rounds of 256 (10 M Gaussians: 306 batches of 32768 = 1.2 rounds ran as long as 2).
-  LR_KNOB(slots_k, "LOGRAST_BATCH_SLOTS", 256);
-  const uint32_t slots = (uint32_t)(slots_k > 0 ? slots_k : 256);
+  const int slots_k = lr_knob(LRKNOB_BATCH_SLOTS);
+  const uint32_t slots = (uint32_t)(slots_k > 0 ? slots_k : kKnobs[LRKNOB_BATCH_SLOTS].dflt);
   const uint64_t per_round = (uint64_t)slots * 32768u * smax;
   const uint32_t rounds = (uint32_t)(((uint64_t)n + per_round - 1u) / per_round);
   const uint32_t groups = slots * rounds;                                  // workgroups
@@ -181,30 +122,38 @@ static LrBatching lr_pick_batch(int32_t n, uint32_t tiles, uint32_t gx, uint32_t
   uint32_t b = ((g + planes - 1u) / planes + 2047u) / 2048u * 2048u;   // (multiples of 2048: a fill workgroup of 1024 threads x 2 stays inside one batch)
   if (b < 4096u) b = 4096u;
   if (b > 32768u) b = 32768u;
-  return {b, planes};
+  p.batch = b; p.planes = planes;
 }
-static uint32_t lr_batches(int32_t n, uint32_t batch) { return batch ? ((uint32_t)n + batch - 1u) / batch : 0u; }
 // Does the fill of this view stage the batch's slot-table row in LDS (project.hip: lr_fill_staged_kernel), and with how
 // many Gaussians per thread?  0 = no (unbatched, band form, tile grids whose row does not fit: the look-up form).  K x 1024
-// consecutive Gaussians of a workgroup share one table row: the largest K <= the knob that divides the batch.  Both stages
-// of a forward ask with the same arguments: stage 1 skips lr_rebase_kernel when the fill adds `offsets[]` while staging.
-static int lr_fill_staged_k(const LrView& v, uint32_t tiles, uint32_t batch) {
-  LR_KNOB(staged_knob, "LOGRAST_FILL_STAGED", 2);
-  if (staged_knob <= 0 || batch == 0u || tiles > LR_FILL_STAGED_MAX_TILES || lr_band_sparse(v, (int)batch)) return 0;
-  if (batch % LR_FILL_STAGED_ROWS != 0u) return 0;
-  const int per_batch = (int)(batch / LR_FILL_STAGED_ROWS);
+// consecutive Gaussians of a workgroup share one table row: the largest K <= the knob that divides the batch.
+static int lr_fill_staged_k(const LrPlan& p) {
+  const int staged_knob = lr_knob(LRKNOB_FILL_STAGED);
+  if (staged_knob <= 0 || p.batch == 0u || p.tiles > LR_FILL_STAGED_MAX_TILES || p.band) return 0;
+  if (p.batch % LR_FILL_STAGED_ROWS != 0u) return 0;
+  const int per_batch = (int)(p.batch / LR_FILL_STAGED_ROWS);
   int K = staged_knob > 3 ? 3 : staged_knob;
   while (K > 1 && per_batch % K != 0) K--;
   return K;
 }
-// Two helper passes pay for their launch only on large inputs (each is ~10 us at 1 M Gaussians, where the work they
-// save is smaller than that): lr_rebase_kernel (absolute slot table for the fill) and the touched-only clearing of
-// dL/dconic.  Both stages of a forward evaluate this with the same n.
-static bool lr_big_input(int32_t n) {
-  LR_KNOB(min_n, "LOGRAST_HELPER_MIN_N", 4000000);
-  return n >= min_n;
+// The helper passes pay for their launch only on large inputs (each is ~10 us at 1 M Gaussians, where the work they
+// save is smaller than that): lr_rebase_kernel (absolute slot table for the fill), the touched-only clearing of
+// dL/dconic, the separate zero-fill kernels, and in the backward the row-split reverse walk and the chain rule's
+// streamed dL/dmeans2D zeros.
+static bool lr_big_input(int32_t n) { return n >= lr_knob(LRKNOB_HELPER_MIN_N); }
+static LrPlan lr_plan(const LrView& v, int32_t n) {
+  LrPlan p;
+  p.tiles = (uint32_t)v.gx * (uint32_t)v.gy;
+  lr_pick_batch(p, n, (uint32_t)v.gx, (uint32_t)v.gy);
+  p.batches = p.batch ? ((uint32_t)n + p.batch - 1u) / p.batch : 0u;
+  p.band = lr_band_sparse(v, (int)p.batch);
+  p.staged_k = lr_fill_staged_k(p);
+  p.big_input = lr_big_input(n);
+  return p;
 }
 
+// Support cull in the binning kernels (project.hip): on unless LOGRAST_TILE_CULL=0 or lograst_set_tile_cull(0).
+static std::atomic<int> g_tile_cull{-1};
 static int lr_tile_cull() {
   int c = g_tile_cull.load(std::memory_order_relaxed);
   if (c < 0) {
@@ -306,9 +255,8 @@ static int lr_make_view(const lograst_view* in, LrView* out) {
   out->cov3d = in->cov3d_precomp; out->g_cov3d = in->dl_dcov3d;
   if (in->walk_form < LOGRAST_FORM_AUTO || in->walk_form > LOGRAST_FORM_QUADRANT) return lr_fail(LOGRAST_ERR_ARG, "bad walk_form");
   out->walk_form = in->walk_form;
-  LR_KNOB(hit_masks, "LOGRAST_HIT_MASKS", 1);
   if (in->hit_masks && (reinterpret_cast<uintptr_t>(in->hit_masks) & 31u)) return lr_fail(LOGRAST_ERR_ARG, "hit_masks must be 32-byte aligned");
-  out->masks = hit_masks ? in->hit_masks : nullptr;
+  out->masks = lr_knob(LRKNOB_HIT_MASKS) ? in->hit_masks : nullptr;
   out->mask_words = in->hit_mask_words;
   if (in->hit_mask_form < 0 || in->hit_mask_form > 2) return lr_fail(LOGRAST_ERR_ARG, "bad hit_mask_form");
   out->mask_form = in->hit_mask_form;
@@ -321,8 +269,12 @@ int lograst_version(void) { return LOGRAST_VERSION; }
 const char* lograst_last_error(void) { return g_err.c_str(); }
 
 size_t lograst_tile_state_bytes(int32_t width, int32_t height, int32_t n) {
-  uint32_t gx = (uint32_t)(width + LOGRAST_TILE - 1) / LOGRAST_TILE, gy = (uint32_t)(height + LOGRAST_TILE - 1) / LOGRAST_TILE;
-  return sizeof(uint32_t) * lr_state_words(gx * gy, lr_batches(n, lr_pick_batch(n, gx * gy, gx, gy).batch));
+  LrView v = {};   // the whole image: the tile grid is all of a view that the batching looks at
+  v.W = width; v.H = height;
+  v.gx = (int)((uint32_t)(width + LOGRAST_TILE - 1) / LOGRAST_TILE); v.gy = (int)((uint32_t)(height + LOGRAST_TILE - 1) / LOGRAST_TILE);
+  v.ty1 = v.gy;
+  const LrPlan p = lr_plan(v, n);
+  return sizeof(uint32_t) * lr_state_words(p.tiles, p.batches);
 }
 size_t lograst_geom_bytes(int32_t n) {  // 64-byte records + the 16-byte fill records of the batched projection + a 4-byte index each (band views) + the rank rows of the 5..16-tile rects (common.hpp)
   const size_t nn = (size_t)(n > 0 ? n : 0);
@@ -394,26 +346,32 @@ int lograst_compute_radius(int32_t p, const float* means3d, const float* scales,
   return LOGRAST_OK;
 }
 
+// What the four forward entry points share: the parameters of lograst_forward (include/lograst.h), in its order, so that an
+// entry point fills it with one braced list, and the two hooks that are lograst_forward_speculative's alone.
+struct LrForwardArgs {
+  const lograst_view* view; int32_t n;
+  const float *means3d, *scales, *rotations, *opacities, *colors; int32_t* radii; void* geom; void* tile_state;   // stage 1
+  uint64_t* keys; uint32_t* point_list; uint32_t capacity, max_tile_len;                                           // stage 2
+  float *image, *final_t; int32_t* n_contrib; int32_t* point_id_pixel; float *point_weight_pixel, *point_weight;
+  float* bwd_scratch; int32_t bwd_scratch_floats; uint32_t* status;
+  void* stream;
+  int speculative;              // stage 2 is enqueued before the host knows whether `capacity` suffices
+  hipEvent_t after_stage1;      // recorded between the stages (or nullptr)
+};
+
 // stage 1 launches: memset of header + counters, projection (+ counting / ranking), tile scan
-static int lr_stage1(const LrView& v, int32_t n, const float* means3d, const float* scales, const float* rotations,
-                     const float* opacities, const float* colors, int32_t* radii, void* geom, uint32_t* st,
-                     hipStream_t s) {
-  const uint32_t tiles = (uint32_t)(v.gx * v.gy);
-  const LrBatching bt = lr_pick_batch(n, tiles, (uint32_t)v.gx, (uint32_t)v.gy);
+static void lr_stage1(const LrView& v, const LrPlan& p, const LrForwardArgs& a, uint32_t* st, hipStream_t s) {
+  const uint32_t tiles = p.tiles;
   // Counters: batched projection -> dense (ranked[tiles] | big[tiles] right behind the header), unbatched -> one
   // counter per 64 B.  Header and counters are zeroed by ONE memset (offsets/cursors are fully rewritten by the scan).
-  const uint32_t cs = bt.batch ? 1u : (uint32_t)LR_CTR_STRIDE;
-  const uint32_t big_off = bt.batch ? lr_ranked_off(tiles) + tiles : lr_big_off(tiles);
+  const uint32_t cs = p.batch ? 1u : (uint32_t)LR_CTR_STRIDE;
+  const uint32_t big_off = p.batch ? lr_ranked_off(tiles) + tiles : lr_big_off(tiles);
   lr_launch_zero_words(st, ((size_t)(big_off + tiles * cs) + 3) & ~(size_t)3, s);   // the words behind the counters (offsets[]) are rewritten by the scan
-  lr_launch_project(v, n, means3d, scales, rotations, opacities, colors, radii, geom, st + lr_ranked_off(tiles),
-                    st + big_off, st, st + lr_basetab_off(tiles), (int)bt.batch, (int)bt.planes, lr_tile_cull(), s);
+  lr_launch_project(v, a.n, a.means3d, a.scales, a.rotations, a.opacities, a.colors, a.radii, a.geom, st + lr_ranked_off(tiles),
+                    st + big_off, st, st + lr_basetab_off(tiles), (int)p.batch, (int)p.planes, p.band, lr_tile_cull(), s);
   lr_launch_scan(st, tiles, cs, big_off, s);
-  if (lr_big_input(n) && lr_fill_staged_k(v, tiles, bt.batch) == 0) {   // (the staged fill adds offsets[] itself)
-    const bool band = lr_band_sparse(v, (int)bt.batch);   // only the band's tiles have slot-table entries
-    lr_launch_rebase(st, tiles, lr_batches(n, bt.batch), band ? (uint32_t)(v.ty0 * v.gx) : 0u,
-                     band ? (uint32_t)(v.ty1 * v.gx) : tiles, s);
-  }
-  return LOGRAST_OK;
+  if (p.big_input && p.staged_k == 0)   // (the staged fill adds offsets[] itself); only the band's tiles have slot-table entries
+    lr_launch_rebase(st, tiles, p.batches, p.band ? (uint32_t)(v.ty0 * v.gx) : 0u, p.band ? (uint32_t)(v.ty1 * v.gx) : tiles, s);
 }
 
 // (a list is streamed -- and may be left at its first window -- only above LR_LONG_LIST keys: with a smaller bound on the
@@ -424,64 +382,55 @@ static inline bool max_tile_len_allows_streaming(uint32_t max_tile_len, uint32_t
 }
 
 // stage 2 launches: bucket fill (+ zero-fills), per-tile sort, compositing
-static int lr_stage2(const LrView& v, int32_t n, const void* geom, uint32_t* st, uint64_t* keys, uint32_t* point_list,
-                     uint32_t capacity, uint32_t max_tile_len, float* image, float* final_t, int32_t* n_contrib,
-                     int32_t* point_id_pixel, float* point_weight_pixel, float* point_weight, float* bwd_scratch,
-                     int32_t bwd_scratch_floats, uint32_t* status, hipStream_t s, int speculative = 0) {
-  const uint32_t tiles = (uint32_t)(v.gx * v.gy);
-  if (n == 0 && status)   // no fill kernel runs: this forward's entries of the status block
-    LR_HIP(hipMemsetAsync(status + LOGRAST_STATUS_LAST_INSTANCES, 0, 4 * sizeof(uint32_t), s));
+static int lr_stage2(const LrView& v, const LrPlan& p, const LrForwardArgs& a, uint32_t* st, hipStream_t s) {
+  const int32_t n = a.n;
+  if (n == 0 && a.status)   // no fill kernel runs: this forward's entries of the status block
+    LR_HIP(hipMemsetAsync(a.status + LOGRAST_STATUS_LAST_INSTANCES, 0, 4 * sizeof(uint32_t), s));
   // point_weight (atomicMax target) and the optional backward scratch (one 64-byte accumulator row per Gaussian) are
   // cleared by the fill kernel -- except, in the 5-tuple flavour on large inputs, the scratch: only the rows of
   // Gaussians that contribute to a pixel will ever be read, and the compositing kernel clears exactly those when it
   // meets them (a separate pass over point_weight afterwards cost 70 us per 30 M-Gaussian view, the stores inside the
   // kernel 30)
-  const bool touched_only = v.extras && bwd_scratch_floats > 0 && lr_big_input(n);
-  float* zero_block = bwd_scratch_floats > 0 ? bwd_scratch : nullptr;
-  int zero_floats = bwd_scratch_floats;
+  const bool touched_only = v.extras && a.bwd_scratch_floats > 0 && p.big_input;
+  float* zero_block = a.bwd_scratch_floats > 0 ? a.bwd_scratch : nullptr;
+  int zero_floats = a.bwd_scratch_floats;
   if (touched_only) { zero_block = nullptr; zero_floats = 0; }
-  float* zero_n = v.extras ? point_weight : nullptr;
-  LR_KNOB(separate_zero, "LOGRAST_SEPARATE_ZERO", 1);   // 0: always inside the fill kernel
-  if (separate_zero && lr_big_input(n)) {   // large inputs: streamed by kernels of their own (see lr_zero_floats_kernel)
+  float* zero_n = v.extras ? a.point_weight : nullptr;
+  if (lr_knob(LRKNOB_SEPARATE_ZERO) && p.big_input) {   // large inputs: streamed by kernels of their own (see lr_zero_floats_kernel); knob 0: always inside the fill kernel
     lr_launch_zero_floats(zero_n, (size_t)n, s);
     if (zero_floats > 0) lr_launch_zero_floats(zero_block, (size_t)zero_floats * (size_t)n, s);
     zero_n = nullptr; zero_floats = 0;
   }
-  const uint32_t fill_batch = lr_pick_batch(n, tiles, (uint32_t)v.gx, (uint32_t)v.gy).batch;
-  const int staged_k = lr_fill_staged_k(v, tiles, fill_batch);
-  lr_launch_fill(n, v.gx, geom, st, tiles, keys, capacity, max_tile_len, status,
+  lr_launch_fill(n, v.gx, a.geom, st, p.tiles, a.keys, a.capacity, a.max_tile_len, a.status,
                  zero_n, zero_floats > 0 ? zero_block : nullptr, zero_floats,
-                 (lr_big_input(n) && staged_k == 0) ? 1 : 0, speculative, lr_band_sparse(v, (int)fill_batch) ? 1 : 0, staged_k, s);
+                 (p.big_input && p.staged_k == 0) ? 1 : 0, a.speculative, p.band ? 1 : 0, p.staged_k, s);
   // LOGRAST_LAZY_SORT (default 1): lists of more than 4096 keys are ordered over their first window only (7680 positions;
   // the walk of a view ends far in front of that: common.hpp, sorted[]); the compositing kernels mark the tiles that needed
   // more, and the second pair of launches -- idle in every benched view -- finishes exactly those.  0: every list to its
   // end before the first compositing pass (what lograst_finish_lists produces afterwards).
-  LR_KNOB(lazy_knob, "LOGRAST_LAZY_SORT", 1);
-  const int lazy = (lazy_knob && max_tile_len_allows_streaming(max_tile_len, capacity)) ? 1 : 0;
-  lr_launch_sort(st, tiles, keys, point_list, capacity, max_tile_len, lazy, s);
-  float* const zrows = touched_only ? bwd_scratch : nullptr;
-  lr_launch_blend_fwd(v, geom, st, tiles, point_list, capacity, image, final_t, n_contrib, point_id_pixel,
-                      point_weight_pixel, point_weight, zrows, lr_big_input(n) ? 1 : 0, lazy, v.masks, s);
+  const int lazy = (lr_knob(LRKNOB_LAZY_SORT) && max_tile_len_allows_streaming(a.max_tile_len, a.capacity)) ? 1 : 0;
+  lr_launch_sort(st, p.tiles, a.keys, a.point_list, a.capacity, a.max_tile_len, lazy, s);
+  float* const zrows = touched_only ? a.bwd_scratch : nullptr;
+  lr_launch_blend_fwd(v, a.geom, st, p.tiles, a.point_list, a.capacity, a.image, a.final_t, a.n_contrib, a.point_id_pixel,
+                      a.point_weight_pixel, a.point_weight, zrows, p.big_input ? 1 : 0, lazy, v.masks, s);
   if (lazy) {
     lr_prof_begin(LRK_LAZY_TAIL, s);
-    lr_launch_sort_rest(st, tiles, keys, point_list, capacity, max_tile_len, 2, s);
-    lr_launch_blend_fwd(v, geom, st, tiles, point_list, capacity, image, final_t, n_contrib, point_id_pixel,
-                        point_weight_pixel, point_weight, zrows, lr_big_input(n) ? 1 : 0, 2, v.masks, s);
+    lr_launch_sort_rest(st, p.tiles, a.keys, a.point_list, a.capacity, a.max_tile_len, 2, s);
+    lr_launch_blend_fwd(v, a.geom, st, p.tiles, a.point_list, a.capacity, a.image, a.final_t, a.n_contrib, a.point_id_pixel,
+                        a.point_weight_pixel, a.point_weight, zrows, p.big_input ? 1 : 0, 2, v.masks, s);
     lr_prof_end(LRK_LAZY_TAIL, s);
   }
   return LOGRAST_OK;
 }
 
-static int lr_check_stage1_args(const LrView& v, int32_t n, const float* means3d, const float* scales,
-                                const float* rotations, const float* opacities, const float* colors,
-                                const int32_t* radii, const void* geom, const void* tile_state) {
-  if (n < 0) return lr_fail(LOGRAST_ERR_ARG, "negative Gaussian count");
-  if (!tile_state) return lr_fail(LOGRAST_ERR_ARG, "tile_state is NULL");
-  if (n > 0 && (!means3d || !opacities || !colors || !radii || !geom))
+static int lr_check_stage1_args(const LrView& v, const LrForwardArgs& a) {
+  if (a.n < 0) return lr_fail(LOGRAST_ERR_ARG, "negative Gaussian count");
+  if (!a.tile_state) return lr_fail(LOGRAST_ERR_ARG, "tile_state is NULL");
+  if (a.n > 0 && (!a.means3d || !a.opacities || !a.colors || !a.radii || !a.geom))
     return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
-  if (n > 0 && !v.cov3d && (!scales || !rotations))
+  if (a.n > 0 && !v.cov3d && (!a.scales || !a.rotations))
     return lr_fail(LOGRAST_ERR_ARG, "scales / rotations are NULL and the view carries no cov3d_precomp");
-  if ((reinterpret_cast<uintptr_t>(rotations) | reinterpret_cast<uintptr_t>(geom) | reinterpret_cast<uintptr_t>(tile_state)) & 15u)
+  if ((reinterpret_cast<uintptr_t>(a.rotations) | reinterpret_cast<uintptr_t>(a.geom) | reinterpret_cast<uintptr_t>(a.tile_state)) & 15u)
     return lr_fail(LOGRAST_ERR_ARG, "rotations / geom / tile_state must be 16-byte aligned");
   return LOGRAST_OK;
 }
@@ -497,43 +446,61 @@ static int lr_check_cov_args(const LrView& v, const float* scales, const float* 
   return LOGRAST_OK;
 }
 
-static int lr_check_stage2_args(const LrView& v, int32_t n, const void* tile_state, const uint64_t* keys,
-                                const uint32_t* point_list, uint32_t capacity, const float* image, const float* final_t,
-                                const int32_t* n_contrib, const int32_t* point_id_pixel, const float* point_weight_pixel,
-                                const float* point_weight, const float* bwd_scratch, int32_t bwd_scratch_floats) {
-  if (n < 0) return lr_fail(LOGRAST_ERR_ARG, "negative Gaussian count");
-  if (!tile_state || !image || !final_t || !n_contrib) return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
-  if (capacity > 0 && (!keys || !point_list)) return lr_fail(LOGRAST_ERR_ARG, "keys/point_list NULL with capacity > 0");
-  if (v.extras && (!point_id_pixel || !point_weight_pixel || (n > 0 && !point_weight)))
+static int lr_check_stage2_args(const LrView& v, const LrForwardArgs& a) {
+  if (a.n < 0) return lr_fail(LOGRAST_ERR_ARG, "negative Gaussian count");
+  if (!a.tile_state || !a.image || !a.final_t || !a.n_contrib) return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
+  if (a.capacity > 0 && (!a.keys || !a.point_list)) return lr_fail(LOGRAST_ERR_ARG, "keys/point_list NULL with capacity > 0");
+  if (v.extras && (!a.point_id_pixel || !a.point_weight_pixel || (a.n > 0 && !a.point_weight)))
     return lr_fail(LOGRAST_ERR_ARG, "extras requested but output pointers are NULL");
-  if ((bwd_scratch_floats != 0 && bwd_scratch_floats != LOGRAST_BWD_ROW_FLOATS) ||
-      (bwd_scratch_floats > 0 && n > 0 && !bwd_scratch))
+  if ((a.bwd_scratch_floats != 0 && a.bwd_scratch_floats != LOGRAST_BWD_ROW_FLOATS) ||
+      (a.bwd_scratch_floats > 0 && a.n > 0 && !a.bwd_scratch))
     return lr_fail(LOGRAST_ERR_ARG, "bwd_scratch: 0 or LOGRAST_BWD_ROW_FLOATS (16) floats per Gaussian and a non-NULL block");
-  if (bwd_scratch_floats > 0 && (reinterpret_cast<uintptr_t>(bwd_scratch) & 63u))
+  if (a.bwd_scratch_floats > 0 && (reinterpret_cast<uintptr_t>(a.bwd_scratch) & 63u))
     return lr_fail(LOGRAST_ERR_ARG, "bwd_scratch must be 64-byte aligned (one accumulator row per line)");
-  if (v.masks && (size_t)v.mask_words * sizeof(uint64_t) < lograst_hit_mask_bytes(capacity, v.W, v.H))
+  if (v.masks && (size_t)v.mask_words * sizeof(uint64_t) < lograst_hit_mask_bytes(a.capacity, v.W, v.H))
     return lr_fail(LOGRAST_ERR_ARG, "hit_mask_words is smaller than lograst_hit_mask_bytes(capacity, width, height) / 8");
   return LOGRAST_OK;
+}
+
+// The one forward body behind the four entry points, in two halves (lograst_forward_speculative has checks of its own
+// between them): the view and the argument checks of the stages asked for, stage 1's first; then plan and launches.
+static int lr_forward_check(const LrForwardArgs& a, bool stage1, bool stage2, LrView* v) {
+  g_prof_call++;
+  int rc = lr_make_view(a.view, v);
+  if (rc) return rc;
+  if (stage1 && (rc = lr_check_stage1_args(*v, a))) return rc;
+  if (stage2 && (rc = lr_check_stage2_args(*v, a))) return rc;
+  return LOGRAST_OK;
+}
+static int lr_forward_launch(const LrView& v, const LrForwardArgs& a, bool stage1, bool stage2) {
+  int rc;
+  const LrPlan p = lr_plan(v, a.n);
+  hipStream_t s = (hipStream_t)a.stream;
+  uint32_t* st = reinterpret_cast<uint32_t*>(a.tile_state);
+  if (stage1) lr_stage1(v, p, a, st, s);
+  if (a.after_stage1) LR_HIP(hipEventRecord(a.after_stage1, s));
+  if (stage2 && (rc = lr_stage2(v, p, a, st, s))) return rc;
+  LR_HIP(hipGetLastError());
+  return LOGRAST_OK;
+}
+static int lr_forward(const LrForwardArgs& a, bool stage1, bool stage2) {
+  LrView v;
+  const int rc = lr_forward_check(a, stage1, stage2, &v);
+  return rc ? rc : lr_forward_launch(v, a, stage1, stage2);
 }
 
 int lograst_forward_project(const lograst_view* view, int32_t n, const float* means3d, const float* scales,
                             const float* rotations, const float* opacities, const float* colors,
                             int32_t* radii, void* geom, void* tile_state, uint32_t* num_instances_host,
                             uint32_t* max_tile_len_host, void* stream) {
-  g_prof_call++;
-  LrView v;
-  int rc = lr_make_view(view, &v);
+  LrForwardArgs a = {view, n, means3d, scales, rotations, opacities, colors, radii, geom, tile_state};
+  a.stream = stream;
+  int rc = lr_forward(a, true, false);
   if (rc) return rc;
-  rc = lr_check_stage1_args(v, n, means3d, scales, rotations, opacities, colors, radii, geom, tile_state);
-  if (rc) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  uint32_t* st = reinterpret_cast<uint32_t*>(tile_state);
-  rc = lr_stage1(v, n, means3d, scales, rotations, opacities, colors, radii, geom, st, s);
-  if (rc) return rc;
-  LR_HIP(hipGetLastError());
   if (num_instances_host || max_tile_len_host) {
+    hipStream_t s = (hipStream_t)stream;
     uint32_t hdr[LR_HDR_WORDS] = {0};
-    LR_HIP(hipMemcpyAsync(hdr, st, sizeof(uint32_t) * 4, hipMemcpyDeviceToHost, s));
+    LR_HIP(hipMemcpyAsync(hdr, tile_state, sizeof(uint32_t) * 4, hipMemcpyDeviceToHost, s));
     LR_HIP(hipStreamSynchronize(s));
     if (num_instances_host) *num_instances_host = hdr[LR_HDR_NUM];
     if (max_tile_len_host) *max_tile_len_host = hdr[LR_HDR_MAXLEN];
@@ -546,19 +513,10 @@ int lograst_forward_render(const lograst_view* view, int32_t n, const void* geom
                            float* image, float* final_t, int32_t* n_contrib, int32_t* point_id_pixel,
                            float* point_weight_pixel, float* point_weight, float* bwd_scratch,
                            int32_t bwd_scratch_floats, uint32_t* status, void* stream) {
-  g_prof_call++;
-  LrView v;
-  int rc = lr_make_view(view, &v);
-  if (rc) return rc;
-  rc = lr_check_stage2_args(v, n, tile_state, keys, point_list, capacity, image, final_t, n_contrib, point_id_pixel,
-                            point_weight_pixel, point_weight, bwd_scratch, bwd_scratch_floats);
-  if (rc) return rc;
-  rc = lr_stage2(v, n, geom, reinterpret_cast<uint32_t*>(tile_state), keys, point_list, capacity, max_tile_len, image,
-                 final_t, n_contrib, point_id_pixel, point_weight_pixel, point_weight, bwd_scratch, bwd_scratch_floats,
-                 status, (hipStream_t)stream);
-  if (rc) return rc;
-  LR_HIP(hipGetLastError());
-  return LOGRAST_OK;
+  const LrForwardArgs a = {view, n, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, const_cast<void*>(geom), tile_state,
+                           keys, point_list, capacity, max_tile_len, image, final_t, n_contrib, point_id_pixel,
+                           point_weight_pixel, point_weight, bwd_scratch, bwd_scratch_floats, status, stream};
+  return lr_forward(a, false, true);
 }
 
 int lograst_forward(const lograst_view* view, int32_t n, const float* means3d, const float* scales,
@@ -567,24 +525,10 @@ int lograst_forward(const lograst_view* view, int32_t n, const float* means3d, c
                     float* image, float* final_t, int32_t* n_contrib, int32_t* point_id_pixel,
                     float* point_weight_pixel, float* point_weight, float* bwd_scratch, int32_t bwd_scratch_floats,
                     uint32_t* status, void* stream) {
-  g_prof_call++;
-  LrView v;
-  int rc = lr_make_view(view, &v);
-  if (rc) return rc;
-  rc = lr_check_stage1_args(v, n, means3d, scales, rotations, opacities, colors, radii, geom, tile_state);
-  if (rc) return rc;
-  rc = lr_check_stage2_args(v, n, tile_state, keys, point_list, capacity, image, final_t, n_contrib, point_id_pixel,
-                            point_weight_pixel, point_weight, bwd_scratch, bwd_scratch_floats);
-  if (rc) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  uint32_t* st = reinterpret_cast<uint32_t*>(tile_state);
-  rc = lr_stage1(v, n, means3d, scales, rotations, opacities, colors, radii, geom, st, s);
-  if (rc) return rc;
-  rc = lr_stage2(v, n, geom, st, keys, point_list, capacity, max_tile_len, image, final_t, n_contrib, point_id_pixel,
-                 point_weight_pixel, point_weight, bwd_scratch, bwd_scratch_floats, status, s);
-  if (rc) return rc;
-  LR_HIP(hipGetLastError());
-  return LOGRAST_OK;
+  const LrForwardArgs a = {view, n, means3d, scales, rotations, opacities, colors, radii, geom, tile_state,
+                           keys, point_list, capacity, max_tile_len, image, final_t, n_contrib, point_id_pixel,
+                           point_weight_pixel, point_weight, bwd_scratch, bwd_scratch_floats, status, stream};
+  return lr_forward(a, true, true);
 }
 
 // Side stream + event + pinned words for the read-back of lograst_forward_speculative, one set per host thread and
@@ -612,33 +556,25 @@ int lograst_forward_speculative(const lograst_view* view, int32_t n, const float
                                 int32_t* point_id_pixel, float* point_weight_pixel, float* point_weight,
                                 float* bwd_scratch, int32_t bwd_scratch_floats, uint32_t* status,
                                 uint32_t* num_instances_host, uint32_t* max_tile_len_host, void* stream) {
-  g_prof_call++;
+  LrForwardArgs a = {view, n, means3d, scales, rotations, opacities, colors, radii, geom, tile_state,
+                     keys, point_list, capacity, max_tile_len, image, final_t, n_contrib, point_id_pixel,
+                     point_weight_pixel, point_weight, bwd_scratch, bwd_scratch_floats, status, stream};
   LrView v;
-  int rc = lr_make_view(view, &v);
-  if (rc) return rc;
-  rc = lr_check_stage1_args(v, n, means3d, scales, rotations, opacities, colors, radii, geom, tile_state);
-  if (rc) return rc;
-  rc = lr_check_stage2_args(v, n, tile_state, keys, point_list, capacity, image, final_t, n_contrib, point_id_pixel,
-                            point_weight_pixel, point_weight, bwd_scratch, bwd_scratch_floats);
+  int rc = lr_forward_check(a, true, true, &v);
   if (rc) return rc;
   if (!num_instances_host || !max_tile_len_host) return lr_fail(LOGRAST_ERR_ARG, "NULL host pointer");
-  hipStream_t s = (hipStream_t)stream;
-  uint32_t* st = reinterpret_cast<uint32_t*>(tile_state);
   LrSpec* sp = nullptr;
   rc = lr_spec_get(&sp);
   if (rc) return rc;
-  rc = lr_stage1(v, n, means3d, scales, rotations, opacities, colors, radii, geom, st, s);
+  // stage 2 is enqueued before the host knows whether `capacity` suffices: the stream never waits for the host ...
+  a.speculative = 1;
+  a.after_stage1 = sp->ev;   // the scan has written the header: instance count and longest list
+  rc = lr_forward_launch(v, a, true, true);
   if (rc) return rc;
-  LR_HIP(hipEventRecord(sp->ev, s));   // the scan has written the header: instance count and longest list
-  // stage 2 is enqueued before the host knows whether `capacity` suffices: the stream never waits for the host
-  rc = lr_stage2(v, n, geom, st, keys, point_list, capacity, max_tile_len, image, final_t, n_contrib, point_id_pixel,
-                 point_weight_pixel, point_weight, bwd_scratch, bwd_scratch_floats, status, s, 1);
-  if (rc) return rc;
-  LR_HIP(hipGetLastError());
   // ... and the header is read on a side stream that waits for stage 1 only (the fill kernel rewrites only the overflow
   // word, which is not read here)
   LR_HIP(hipStreamWaitEvent(sp->side, sp->ev, 0));
-  LR_HIP(hipMemcpyAsync(sp->pinned, st, sizeof(uint32_t) * 4, hipMemcpyDeviceToHost, sp->side));
+  LR_HIP(hipMemcpyAsync(sp->pinned, tile_state, sizeof(uint32_t) * 4, hipMemcpyDeviceToHost, sp->side));
   LR_HIP(hipStreamSynchronize(sp->side));
   *num_instances_host = sp->pinned[LR_HDR_NUM];
   *max_tile_len_host = sp->pinned[LR_HDR_MAXLEN];
@@ -736,9 +672,9 @@ int lograst_stream_copy(void* dst, const void* src, size_t bytes, int32_t blocks
   return LOGRAST_OK;
 }
 
-int lograst_knob_count(void) { return kNumKnobs; }
+int lograst_knob_count(void) { return LRKNOB_COUNT; }
 int lograst_knob_info(int32_t index, const char** name, int32_t* dflt, int32_t* lo, int32_t* hi, const char** what) {
-  if (index < 0 || index >= kNumKnobs) return lr_fail(LOGRAST_ERR_ARG, "knob index out of range");
+  if (index < 0 || index >= LRKNOB_COUNT) return lr_fail(LOGRAST_ERR_ARG, "knob index out of range");
   if (name) *name = kKnobs[index].name;
   if (dflt) *dflt = kKnobs[index].dflt;
   if (lo) *lo = kKnobs[index].lo;
@@ -748,36 +684,30 @@ int lograst_knob_info(int32_t index, const char** name, int32_t* dflt, int32_t* 
 }
 static const LrKnobInfo* lr_find_knob(const char* name) {
   if (!name) return nullptr;
-  for (int i = 0; i < kNumKnobs; i++)
-    if (std::strcmp(kKnobs[i].name, name) == 0) return &kKnobs[i];
+  for (const LrKnobInfo& k : kKnobs)
+    if (std::strcmp(k.name, name) == 0) return &k;
   return nullptr;
 }
 int lograst_set_knob(const char* name, int32_t value) {
   const LrKnobInfo* k = lr_find_knob(name);
   if (!k) return lr_fail(LOGRAST_ERR_ARG, std::string("unknown knob: ") + (name ? name : "(null)"));
   if (value < k->lo || value > k->hi) return lr_fail(LOGRAST_ERR_ARG, std::string(name) + ": value out of range");
-  {
-    std::lock_guard<std::mutex> lk(g_knob_mu);
-    bool found = false;
-    for (auto& kv : g_knob_over)
-      if (kv.first == name) { kv.second = value; found = true; }
-    if (!found) g_knob_over.emplace_back(name, value);
-  }
-  g_knob_gen.fetch_add(1, std::memory_order_acq_rel);
+  std::lock_guard<std::mutex> lk(g_knob_mu);
+  g_knob_set[k->id] = true;
+  g_knob_over[k->id] = value;
+  lr_resolve_knobs_locked();
   return LOGRAST_OK;
 }
 int lograst_get_knob(const char* name, int32_t* value) {
   const LrKnobInfo* k = lr_find_knob(name);
   if (!k || !value) return lr_fail(LOGRAST_ERR_ARG, "unknown knob or NULL pointer");
-  *value = lr_knob_lookup(k->name, k->dflt);
+  *value = lr_knob(k->id);
   return LOGRAST_OK;
 }
 int lograst_reset_knobs(void) {
-  {
-    std::lock_guard<std::mutex> lk(g_knob_mu);
-    g_knob_over.clear();
-  }
-  g_knob_gen.fetch_add(1, std::memory_order_acq_rel);
+  std::lock_guard<std::mutex> lk(g_knob_mu);
+  for (bool& set : g_knob_set) set = false;
+  lr_resolve_knobs_locked();
   return LOGRAST_OK;
 }
 
@@ -840,7 +770,8 @@ int lograst_backward(const lograst_view* view, int32_t n, const float* means3d, 
     return lr_fail(LOGRAST_ERR_ARG, "LOGRAST_BWD_CONIC_TOUCHED_ONLY needs point_weight");
   // A forward with extras on a large input clears the dL/dconic rows of contributing Gaussians only (lr_stage2:
   // touched_only); the chain rule must then skip the others, which it does exactly when it is handed point_weight.
-  if ((flags & LOGRAST_BWD_SCRATCH_ZEROED) && v.extras && lr_big_input(n) && !point_weight)
+  const bool big_input = lr_big_input(n);
+  if ((flags & LOGRAST_BWD_SCRATCH_ZEROED) && v.extras && big_input && !point_weight)
     return lr_fail(LOGRAST_ERR_ARG, "LOGRAST_BWD_SCRATCH_ZEROED after a forward with view.extras and n >= "
                                     "LOGRAST_HELPER_MIN_N: dL/dconic is cleared for contributing Gaussians only, pass "
                                     "point_weight (+ LOGRAST_BWD_CONIC_TOUCHED_ONLY)");
@@ -848,11 +779,11 @@ int lograst_backward(const lograst_view* view, int32_t n, const float* means3d, 
     LR_HIP(hipMemsetAsync(dl_dconic, 0, sizeof(float) * LOGRAST_BWD_ROW_FLOATS * (size_t)n, s));
   // capacity check is a forward concern: a list that rendered is by construction within capacity
   lr_launch_blend_bwd(v, geom, st, tiles, point_list, 0xffffffffu, final_t, n_contrib, dl_dimage, dl_dconic,
-                      lr_big_input(n) ? 1 : 0, v.masks, s);
+                      big_input ? 1 : 0, v.masks, s);
   // the chain rule reads every live Gaussian's accumulator row and hands out the separate outputs: dL/dmeans2D (written
   // for all rows), dL/dopacities and dL/dcolors (written, or added to the caller's running sums)
   lr_launch_project_bwd(v, n, means3d, scales, rotations, radii, nullptr, nullptr, dl_dconic, dl_dmeans2d, dl_dopacities,
-                        dl_dcolors, point_weight, dl_dmeans3d, dl_dscales, dl_drotations, accumulate, sink_rows, s);
+                        dl_dcolors, point_weight, dl_dmeans3d, dl_dscales, dl_drotations, accumulate, sink_rows, big_input, s);
   LR_HIP(hipGetLastError());
   return LOGRAST_OK;
 }
@@ -875,7 +806,7 @@ int lograst_project_backward(const lograst_view* view, int32_t n, const float* m
        reinterpret_cast<uintptr_t>(dl_drotations)) & 15u)
     return lr_fail(LOGRAST_ERR_ARG, "rotations / dl_dconic / dl_drotations must be 16-byte aligned");
   lr_launch_project_bwd(v, n, means3d, scales, rotations, radii, dl_dmeans2d, dl_dconic, nullptr, nullptr, nullptr,
-                        nullptr, nullptr, dl_dmeans3d, dl_dscales, dl_drotations, false, false, (hipStream_t)stream);
+                        nullptr, nullptr, dl_dmeans3d, dl_dscales, dl_drotations, false, false, false, (hipStream_t)stream);
   LR_HIP(hipGetLastError());
   return LOGRAST_OK;
 }

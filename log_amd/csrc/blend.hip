@@ -18,6 +18,7 @@
 // v_permlane32_swap / v_permlane16_swap + DPP row-rotate tree (28 VALU ops for 9 sums) and committed with
 // 3 atomic instructions -- not 9 atomics per (pixel, Gaussian) as in the third-party kernel.
 #include "common.hpp"
+#include "launch.hpp"
 // "These prefetched values have landed": an empty asm that reads and writes them -- the compiler has to wait for their loads
 // right here.  (A bare __builtin_amdgcn_s_waitcnt in front of a loop is hoisted above the loads it was meant for.)
 #define LR_LANDED(q0, q1, c, i)                                                                                  \
@@ -1099,7 +1100,7 @@ lr_blend_fwd_rows_kernel(LrView v, const float4* __restrict__ geom, const uint32
 // Which form the forward's compositing launches for this view (1 = row-split, 2 = quadrant): lr_launch_blend_fwd's rule,
 // also behind lograst_forward_form (the caller of lograst_backward passes it back as lograst_view.hit_mask_form).
 int lr_blend_fwd_form(const LrView& v) {
-  LR_KNOB(rows_knob, "LOGRAST_FWD_ROWS", 2);
+  const int rows_knob = lr_knob(LRKNOB_FWD_ROWS);
   const int rows = rows_knob != 2 ? rows_knob : (v.walk_form == LOGRAST_FORM_ROWS ? 1 : 0);   // no hint: quadrant
   return rows ? (int)LR_MASK_FORM_ROWS : (int)LR_MASK_FORM_QUAD;
 }
@@ -1110,13 +1111,12 @@ void lr_launch_blend_fwd(const LrView& v, const void* geom, const uint32_t* stat
                          hipStream_t s) {
   uint32_t* const hdr_w = const_cast<uint32_t*>(state);     // (header word LR_HDR_MASKS: which form left hit masks)
   uint32_t* const lazy_state = lazy ? const_cast<uint32_t*>(state) : nullptr;   // (the tile state once more, writable: open[] and header word LR_HDR_OPEN are all a compositing kernel writes there)
-  LR_KNOB(xcd_knob, "LOGRAST_XCD_MODE", 3);
-  int xcd_mode = xcd_knob;
+  int xcd_mode = lr_knob(LRKNOB_XCD_MODE);
   // LOGRAST_FWD_ROWS: 1 = row-split form (lr_blend_fwd_rows_kernel), 0 = one quadrant per wave, 2 (default) = the caller's
   // hint (lograst_view.walk_form), quadrant without one.  Measured, MI355X: 30 M tiny splats 706 -> 658 us (random
   // opacities 1267 -> 1188); C2's 1 M 174 -> 193; a tree-ordered heavy-tailed view 278 -> 347.
   const int rows = lr_blend_fwd_form(v) == (int)LR_MASK_FORM_ROWS;
-  LR_KNOB(fwd_block_test, "LOGRAST_FWD_BLOCK_TEST", 1);
+  const int fwd_block_test = lr_knob(LRKNOB_FWD_BLOCK_TEST);
   // Both forward kernels still take `cull` (always 1: the support tests run) as a run-time argument.  With the tests
   // unconditional the register allocation of the row-split kernel changed (one more value in scratch) and the forward
   // measured 1-3 % slower on the 30 M view (quadrant form: 0.6 %).
@@ -1149,16 +1149,16 @@ void lr_launch_blend_fwd(const LrView& v, const void* geom, const uint32_t* stat
 void lr_launch_blend_bwd(const LrView& v, const void* geom, const uint32_t* state, uint32_t tiles,
                          const uint32_t* plist, uint32_t capacity, const float* final_T, const int* n_contrib,
                          const float* dL_dimage, float* acc_rows, int big_input, const uint64_t* masks, hipStream_t s) {
-  LR_KNOB(xcd_mode, "LOGRAST_XCD_MODE", 3);
+  const int xcd_mode = lr_knob(LRKNOB_XCD_MODE);
   uint32_t grid = lr_blend_grid(tiles, v.gx, v.gy, xcd_mode);
   // LOGRAST_BWD_ROWS=1: the row-split form (the four 16-lane rows of a wave walk their own 4x4 blocks); 0: one
   // (Gaussian, quadrant) pair per visit; 2 (default): the caller's hint (lograst_view.walk_form: row-split for views of
   // tiny splats, few tile instances per Gaussian), else row-split on large inputs.  Measured, MI355X: 30 M tiny splats
   // 949 -> 700 us, with random opacities 1768 -> 1259; C2's 1 M 292 -> 307; a tree-ordered heavy-tailed view 448 -> 579.
-  LR_KNOB(rows_knob, "LOGRAST_BWD_ROWS", 2);
+  const int rows_knob = lr_knob(LRKNOB_BWD_ROWS);
   const int rows = rows_knob != 2 ? rows_knob
                    : (v.walk_form == LOGRAST_FORM_ROWS ? 1 : (v.walk_form == LOGRAST_FORM_QUADRANT ? 0 : (big_input ? 1 : 0)));
-  LR_KNOB(block_test, "LOGRAST_BWD_BLOCK_TEST", 1);
+  const int block_test = lr_knob(LRKNOB_BWD_BLOCK_TEST);
   lr_prof_begin(LRK_BLEND_BWD, s);
   // the forward's hit masks serve a reverse walk of the SAME form only (v.mask_form: what the caller says its forward launched)
   const bool use_masks = masks != nullptr && v.mask_form == (rows ? (int)LR_MASK_FORM_ROWS : (int)LR_MASK_FORM_QUAD);

@@ -562,27 +562,16 @@ enum LrKernelSlot {
 // through LOGRAST_LIB); paths that are chosen at run time are the knobs below.
 void lr_prof_begin(int slot, hipStream_t s);
 void lr_prof_end(int slot, hipStream_t s);
-int lr_env_int(const char* name, int dflt);
-// Performance knobs (api.hip): value = lograst_set_knob override, else the environment variable of that name, else the
-// default.  Read at every launch through a per-call-site cache that is refreshed when any knob changes, so that
-// log_amd.tune() can move them at run time.  None of them changes a result (tests/test_gpu_knobs.py sweeps them and
-// compares bit for bit).
-// The cache is one 64-bit atomic (generation << 32 | value): a reader sees a generation together with the value that
-// was looked up FOR it -- the generation is read once, before the look-up, so a lograst_set_knob on another thread in
-// between only makes the next launch look again (round-3 advisory: two plain fields, generation re-read after the look-up).
-extern unsigned lr_knob_generation();
-int lr_knob_lookup(const char* name, int dflt);
-#define LR_KNOB(var, name, dflt)                                                                       \
-  static std::atomic<uint64_t> var##_cache{~0ull};                                                     \
-  int var##_value;                                                                                     \
-  {                                                                                                    \
-    const unsigned var##_gen = lr_knob_generation();                                                   \
-    const uint64_t var##_c = var##_cache.load(std::memory_order_acquire);                              \
-    if ((unsigned)(var##_c >> 32) == var##_gen) {                                                      \
-      var##_value = (int)(uint32_t)var##_c;                                                            \
-    } else {                                                                                           \
-      var##_value = lr_knob_lookup(name, dflt);                                                        \
-      var##_cache.store(((uint64_t)var##_gen << 32) | (uint32_t)var##_value, std::memory_order_release); \
-    }                                                                                                  \
-  }                                                                                                    \
-  const int var = var##_value
+// Performance knobs: one row per knob in kKnobs[] (api.hip), in the order of this enum -- the only place a name, a default
+// or a range is written; lograst_knob_info enumerates that table for log_amd.tune.  Value = lograst_set_knob override, else
+// the environment variable of the knob's name, else the default; resolved into one array on first use and again whenever
+// lograst_set_knob / lograst_reset_knobs change an override, so log_amd.tune() can move them at run time and a launch
+// reads one relaxed atomic.  None of them changes a result (tests/test_gpu_knobs.py sweeps them and compares bit for bit).
+enum LrKnob {
+  LRKNOB_HELPER_MIN_N, LRKNOB_HIT_MASKS, LRKNOB_LAZY_SORT, LRKNOB_PBWD_LIST, LRKNOB_MID_RANK, LRKNOB_MID_COOP,
+  LRKNOB_DEFER_TILES, LRKNOB_HUGE_CHUNK, LRKNOB_BATCH_PLANES, LRKNOB_BATCH_SLOTS, LRKNOB_SEPARATE_ZERO,
+  LRKNOB_FILL_XCD_ORDER, LRKNOB_FILL_NT, LRKNOB_XCD_MODE, LRKNOB_PROJECT_BLOCKS, LRKNOB_BWD_ROWS, LRKNOB_FWD_ROWS,
+  LRKNOB_FILL_STAGED, LRKNOB_FILL_PER_THREAD, LRKNOB_BAND_SPARSE, LRKNOB_FWD_BLOCK_TEST, LRKNOB_BWD_BLOCK_TEST,
+  LRKNOB_COUNT
+};
+int lr_knob(LrKnob k);

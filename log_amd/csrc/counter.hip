@@ -9,6 +9,7 @@
 //                              index.cpu(), no state gather/scatter round trip).
 // All of it is streaming / scattered-row work: HBM-bound, no LDS tiling needed beyond the block scans.
 #include "common.hpp"
+#include "launch.hpp"
 
 #define CNT_CHUNK 1024u
 #define CNT_HDR_WORDS 4u   // [0] number of distinct ids

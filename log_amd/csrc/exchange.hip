@@ -11,6 +11,7 @@
 // With torch ops the same work took 6 ms (pack), 30 ms (index_add_ of 8 M rows) and 180 ms (gathered rows back into the
 // bucket) at 30 M Gaussians -- many times the link time the sparse exchange saves; these kernels stream.
 #include "common.hpp"
+#include "launch.hpp"
 
 #define LX_ROWS_PER_BLOCK 1024
 

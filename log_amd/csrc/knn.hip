@@ -18,6 +18,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "common.hpp"
+#include "launch.hpp"
 
 #define LR_KNN_BOX 1024
 

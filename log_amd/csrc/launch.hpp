@@ -1,0 +1,97 @@
+// launch.hpp -- the host-side launchers and sizing helpers that the kernel files define and api.hip calls, declared once:
+// api.hip and every defining .hip file include this header, so a definition that drifts from its prototype does not compile.
+#pragma once
+#include "common.hpp"
+
+// project.hip
+void lr_launch_radius(int P, const float* means, const float* scales, const float* rots, const float* proj,
+                      const float* view, float fx, float fy, float tanfovx, float tanfovy, float* radii,
+                      hipStream_t s);
+bool lr_band_sparse(const LrView& v, int batch);
+// band: lr_band_sparse(v, batch), as the caller's plan holds it
+void lr_launch_project(const LrView& v, int N, const float* means, const float* scales, const float* rots,
+                       const float* opac, const float* colors, int* radii, void* geom, uint32_t* ranked,
+                       uint32_t* big, uint32_t* hdr, uint32_t* basetab, int batch, int planes, bool band, int tile_cull,
+                       hipStream_t s);
+void lr_launch_scan(uint32_t* state, uint32_t tiles, uint32_t cs, uint32_t big_off, hipStream_t s);
+void lr_launch_rebase(uint32_t* state, uint32_t tiles, uint32_t batches, uint32_t t_lo, uint32_t t_hi, hipStream_t s);
+void lr_launch_zero_words(uint32_t* p, size_t words, hipStream_t s);
+void lr_launch_zero_floats(float* p, size_t n, hipStream_t s);
+void lr_launch_fill(int N, int gx, const void* geom, uint32_t* state, uint32_t tiles, uint64_t* keys,
+                    uint32_t capacity, uint32_t max_len_hint, uint32_t* status, float* zero_n, float* zero_block,
+                    int zero_block_floats, int rebased, int speculative, int band, int staged_k, hipStream_t s);
+void lr_launch_tile_rows(const LrView& v, int N, const float* means, const float* scales, const float* rots,
+                         uint32_t* rows, hipStream_t s);
+void lr_launch_stream_copy(const void* src, void* dst, size_t bytes, int blocks, hipStream_t s);
+
+// sort.hip
+void lr_launch_sort(uint32_t* state, uint32_t tiles, uint64_t* keys, uint32_t* plist, uint32_t capacity,
+                    uint32_t max_len, int lazy, hipStream_t s);
+void lr_launch_sort_rest(uint32_t* state, uint32_t tiles, uint64_t* keys, uint32_t* plist, uint32_t capacity,
+                         uint32_t max_len, int mode, hipStream_t s);
+void lr_launch_ordered_lengths(const uint32_t* state, uint32_t tiles, uint32_t* out, hipStream_t s);
+
+// blend.hip
+void lr_launch_blend_fwd(const LrView& v, const void* geom, const uint32_t* state, uint32_t tiles,
+                         const uint32_t* plist, uint32_t capacity, float* image, float* final_T, int* n_contrib,
+                         int* pid, float* pwp, float* pw, float* zero_conic, int big_input, int lazy, uint64_t* masks,
+                         hipStream_t s);
+int lr_blend_fwd_form(const LrView& v);
+void lr_launch_blend_bwd(const LrView& v, const void* geom, const uint32_t* state, uint32_t tiles,
+                         const uint32_t* plist, uint32_t capacity, const float* final_T, const int* n_contrib,
+                         const float* dL_dimage, float* acc_rows, int big_input, const uint64_t* masks, hipStream_t s);
+
+// project_bwd.hip
+// rows != NULL: the 64-byte accumulator rows of lograst_backward (+ its three separate outputs); NULL: g_mean2d / g_conic.
+// big_input: the caller's large-input predicate (n >= LOGRAST_HELPER_MIN_N); only looked at when rows != NULL.
+void lr_launch_project_bwd(const LrView& v, int N, const float* means, const float* scales, const float* rots,
+                           const int* radii, const float* g_mean2d, const float* g_conic, const float* rows,
+                           float* o_mean2d, float* o_opac, float* o_col, const float* pw,
+                           float* g_means3d, float* g_scales, float* g_rots, bool accumulate, bool sink_rows,
+                           bool big_input, hipStream_t s);
+
+// exchange.hip
+void lx_launch_pack_rows(float* rows, int groups, long long rows_per_group, int kmax, float* packed,
+                         size_t seg_floats, uint32_t* overflow, int clear, const uint32_t* hint, long long hint_rows,
+                         hipStream_t s);
+void lx_launch_add_visible(float* seen, const int32_t* radii, long long n, hipStream_t s);
+void lx_launch_add_visible_n(float* seen, const int32_t* const* radii, int k, long long n, hipStream_t s);
+void lx_launch_unpack_rows(float* dest, const float* packed, int segments, int kmax, size_t seg_floats,
+                           long long rows_per_group, long long dest_group_rows, int add, int zero, hipStream_t s);
+
+// knn.hip
+size_t lr_knn_scratch_bytes(int P);
+hipError_t lr_launch_knn(int P, const float* pts, float* out, void* scratch, size_t scratch_bytes, hipStream_t s);
+
+// sh.hip
+void lr_launch_sh_fwd(int N, int deg, int M, const float* means, const float* campos, const float* shs, float* colors,
+                      uint8_t* clamped, hipStream_t s);
+void lr_launch_sh_bwd(int N, int deg, int M, const float* means, const float* campos, const float* shs,
+                      const uint8_t* clamped, const float* g_colors, float* g_shs, float* g_means, bool accumulate,
+                      hipStream_t s);
+hipError_t lr_launch_gather_activate(const GatherArgs& a, hipStream_t s);
+hipError_t lr_launch_activate_bwd(const ActBwdArgs& a, hipStream_t s);
+hipError_t lr_launch_activate_bwd_adam(const ActBwdArgs& a, const AdamArgs& f, const float* g_a_xyz, const int32_t* radii,
+                                       hipStream_t s);
+
+// lod.hip
+size_t lr_lod_scratch_bytes(int num_roots, int num_nodes, int max_child);
+hipError_t lr_launch_lod(int num_points, int num_nodes, int max_child, const int32_t* node_index, const int32_t* tree,
+                         const float* xyz, const float* scaling, const float* rotation, const int64_t* root_index,
+                         int num_roots, const float* proj, const float* view, float fx, float fy, float tanfovx,
+                         float tanfovy, float min_px, int levels, int64_t* out, uint32_t out_capacity, void* scratch,
+                         hipStream_t s);
+int lr_lod_max_levels();
+uint32_t lr_lod_total_word();   // header words TOTAL, OVERFLOW, LEFT are consecutive
+
+// counter.hip
+size_t lr_hist_scratch_bytes(int n);
+hipError_t lr_launch_id_histogram(int n, const int32_t* pid, int npix, int32_t* ids, int64_t* counts, void* scratch,
+                                  hipStream_t s);
+hipError_t lr_launch_counter(const CounterArgs& a, hipStream_t s);
+hipError_t lr_launch_sparse_adam(const AdamArgs& a, int num_keys, hipStream_t s);
+
+// loss.hip
+size_t lr_loss_scratch_bytes(int B, int C, int H, int W);
+hipError_t lr_launch_loss_fwd(const LossArgs& a, float wa, float wb, float* out3, hipStream_t s);
+hipError_t lr_launch_loss_bwd(const LossArgs& a, const float* grad_loss, float* g_render, float* g_render_l1, hipStream_t s);

@@ -11,6 +11,7 @@
 // activate, project, decide keep/next; per-1024-slot counts) -> scan of the chunk counts (one workgroup) ->
 // scatter (ballot ranks inside the chunk + the chunk's prefix).  A point is visited at most once per call.
 #include "common.hpp"
+#include "launch.hpp"
 
 #define LOD_MAX_LEVELS 128
 #define LOD_HDR_COUNT 0                          // [l] frontier size entering level l (l >= 1)

@@ -23,6 +23,7 @@
 // Determinism: fixed tap order (ascending tap index, horizontal then vertical), explicit fmaf only, per-workgroup
 // partial sums reduced in a fixed order by one workgroup in double -- no floating-point atomics anywhere.
 #include "common.hpp"
+#include "launch.hpp"
 
 #define LS_T 32
 #define LS_HALO 10

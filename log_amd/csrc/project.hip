@@ -2,6 +2,7 @@
 // tile scan, and A3 per-tile bucket fill.  HBM-bound: every Gaussian attribute is read exactly once,
 // coalesced; the 64-byte projected record is written once.
 #include "common.hpp"
+#include "launch.hpp"
 
 // ---- A0 -------------------------------------------------------------------------------------------
 // Stands for compute_radius_cuda (/root/reference/LoG/cuda/compute_radius_kernel.cu:107-156):
@@ -952,20 +953,18 @@ lr_count_huge_kernel(int N, int gx, int tiles, const float4* __restrict__ geom, 
   }
 }
 
-// Does the batched projection of this view run in its band form (lr_project_batched_kernel<true>)?
 // Does the batched projection of this view run in its band form (lr_project_band_kernel)?  A proper band of tile rows
 // whose counter plane fits beside the rings (a band of more than half of a 3840x2160 grid does not: the full-view kernel).
 #define LR_BAND_LDS_BYTES (160 * 1024 - 512)
 bool lr_band_sparse(const LrView& v, int batch) {
-  LR_KNOB(sparse_knob, "LOGRAST_BAND_SPARSE", 1);
   const size_t plane = sizeof(uint32_t) * (size_t)((v.ty1 - v.ty0) * v.gx);
-  return sparse_knob && batch > 0 && (v.ty0 > 0 || v.ty1 < v.gy) && v.ty1 > v.ty0 &&
+  return lr_knob(LRKNOB_BAND_SPARSE) && batch > 0 && (v.ty0 > 0 || v.ty1 < v.gy) && v.ty1 > v.ty0 &&
          plane + LR_BAND_STATIC_LDS <= LR_BAND_LDS_BYTES;
 }
 
 void lr_launch_project(const LrView& v, int N, const float* means, const float* scales, const float* rots,
                        const float* opac, const float* colors, int* radii, void* geom, uint32_t* ranked,
-                       uint32_t* big, uint32_t* hdr, uint32_t* basetab, int batch, int planes, int tile_cull,
+                       uint32_t* big, uint32_t* hdr, uint32_t* basetab, int batch, int planes, bool band, int tile_cull,
                        hipStream_t s) {
   if (N <= 0) return;
   lr_prof_begin(LRK_PROJECT, s);
@@ -984,15 +983,13 @@ void lr_launch_project(const LrView& v, int N, const float* means, const float* 
                                 hipFuncAttributeMaxDynamicSharedMemorySize, LR_BATCH_LDS_BYTES);
       attr_set = true;
     }
-    LR_KNOB(defer_tiles, "LOGRAST_DEFER_TILES", LR_COOP_TILES);
-    LR_KNOB(chunk_k, "LOGRAST_HUGE_CHUNK", LR_HUGE_CHUNK);
+    const int defer_tiles = lr_knob(LRKNOB_DEFER_TILES), chunk_k = lr_knob(LRKNOB_HUGE_CHUNK);
     const int chunk = chunk_k >= 256 ? chunk_k / 256 * 256 : 256;
     const int batches = (N + batch - 1) / batch;
     const int groups = (batches + planes - 1) / planes;     // workgroups: `planes` consecutive batches each
     uint32_t* hugecount = basetab + (size_t)batches * tiles;   // (hugemask[batches][LR_HUGE_WORDS]: common.hpp)
-    LR_KNOB(mid_coop, "LOGRAST_MID_COOP", 16);
-    LR_KNOB(mid_rank, "LOGRAST_MID_RANK", 1);
-    if (lr_band_sparse(v, batch)) {
+    const int mid_coop = lr_knob(LRKNOB_MID_COOP), mid_rank = lr_knob(LRKNOB_MID_RANK);
+    if (band) {
       // planes over the band's tiles only: as many batches per workgroup as fit beside the rings (at most 4)
       const int band_tiles = (v.ty1 - v.ty0) * v.gx;
       int bp = (int)((LR_BAND_LDS_BYTES - LR_BAND_STATIC_LDS) / (sizeof(uint32_t) * (size_t)band_tiles));
@@ -1020,7 +1017,7 @@ void lr_launch_project(const LrView& v, int N, const float* means, const float* 
     lr_prof_end(LRK_RESERVED, s);
     return;
   } else {
-    LR_KNOB(max_blocks, "LOGRAST_PROJECT_BLOCKS", 512);  // 2 workgroups per CU: measured optimum
+    const int max_blocks = lr_knob(LRKNOB_PROJECT_BLOCKS);  // default: 2 workgroups per CU: measured optimum
     int blocks = (N + 255) / 256;
     if (max_blocks > 0 && blocks > max_blocks) blocks = max_blocks;
     hipLaunchKernelGGL(lr_project_kernel, dim3(blocks), dim3(256), 0, s, v, N, means, scales, rots, opac, colors, radii,
@@ -1564,10 +1561,8 @@ void lr_launch_fill(int N, int gx, const void* geom, uint32_t* state, uint32_t t
                     int zero_block_floats, int rebased, int speculative, int band, int staged_k, hipStream_t s) {
   if (N <= 0) return;
   lr_prof_begin(LRK_FILL, s);
-  LR_KNOB(xcd_order, "LOGRAST_FILL_XCD_ORDER", 1);
-  LR_KNOB(fill_nt, "LOGRAST_FILL_NT", 1);
-  LR_KNOB(mid_coop, "LOGRAST_MID_COOP", 16);
-  if (staged_k > 0) {   // (decided by the caller -- api.hip: lr_fill_staged_k -- because stage 1 has to know it too: no lr_rebase_kernel then)
+  const int xcd_order = lr_knob(LRKNOB_FILL_XCD_ORDER), fill_nt = lr_knob(LRKNOB_FILL_NT), mid_coop = lr_knob(LRKNOB_MID_COOP);
+  if (staged_k > 0) {   // (decided by the caller -- api.hip: lr_plan -- because stage 1 has to know it too: no lr_rebase_kernel then)
     static bool attr_set = false;
     if (!attr_set) {
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lr_fill_staged_kernel<1>),
@@ -1590,8 +1585,7 @@ void lr_launch_fill(int N, int gx, const void* geom, uint32_t* state, uint32_t t
     lr_prof_end(LRK_FILL, s);
     return;
   }
-  LR_KNOB(per_thread_knob, "LOGRAST_FILL_PER_THREAD", 1);
-  int per_thread = per_thread_knob;
+  int per_thread = lr_knob(LRKNOB_FILL_PER_THREAD);
 #define LR_FILL(K) do { const int blocks = (((N + 255) / 256 + K - 1) / K + 7) & ~7;                                     \
     hipLaunchKernelGGL(lr_fill_kernel<K>, dim3(blocks), dim3(256), 0, s, N, gx, reinterpret_cast<const float4*>(geom),  \
                        state, tiles, keys, capacity, max_len_hint, status, zero_n, zero_block, zero_block_floats,       \

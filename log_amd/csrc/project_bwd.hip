@@ -4,6 +4,7 @@
 // of HBM traffic each way).  Conventions: SURVEY.md Appendix B; the alpha cap and the 0.1 floor in the
 // radius formula carry no gradient; the fork's max(.,0.3) low-pass has the standard sub-gradient.
 #include "common.hpp"
+#include "launch.hpp"
 
 // TOUCHED (lograst_backward with a point_weight array): a Gaussian whose forward blend weight stayed 0 contributed
 // to no pixel, so the reverse walk added nothing to its dL/dmean2D and dL/dconic -- both are exactly zero and so is
@@ -383,14 +384,11 @@ lr_pbwd_list_kernel(LrView v, int N, const float* __restrict__ means, const floa
   }
 }
 
-void lr_launch_zero_floats(float* p, size_t n, hipStream_t s);   // project.hip
-void lr_launch_zero_words(uint32_t* p, size_t words, hipStream_t s);   // project.hip
-// rows != NULL: the 64-byte accumulator rows of lograst_backward (+ its three separate outputs); NULL: g_mean2d / g_conic
 void lr_launch_project_bwd(const LrView& v, int N, const float* means, const float* scales, const float* rots,
                            const int* radii, const float* g_mean2d, const float* g_conic, const float* rows,
                            float* o_mean2d, float* o_opac, float* o_col, const float* pw,
                            float* g_means3d, float* g_scales, float* g_rots, bool accumulate, bool sink_rows,
-                           hipStream_t s) {
+                           bool big_input, hipStream_t s) {
   if (N <= 0) return;
   lr_prof_begin(LRK_PROJECT_BWD, s);
   const dim3 grid((N + LR_PBWD_ROWS - 1) / LR_PBWD_ROWS), block(256);
@@ -400,8 +398,7 @@ void lr_launch_project_bwd(const LrView& v, int N, const float* means, const flo
   // stores) in front of the chain rule instead of by its workgroups between their flag reads and their barrier: a band
   // view of 100 M rows 1040 -> 730 us (with the radii read gone), the 30 M view unchanged (415 us).  With fresh gradients
   // (every output zeroed for every dead row: 68 bytes per row) the same split LOSES (30 M: 763 -> 858 us): kept inside.
-  LR_KNOB(separate_min_n, "LOGRAST_HELPER_MIN_N", 4000000);
-  const int clear_inside = (rows && (accumulate || sink_rows) && N >= separate_min_n) ? 0 : 1;
+  const int clear_inside = (rows && (accumulate || sink_rows) && big_input) ? 0 : 1;
   if (!clear_inside) lr_launch_zero_floats(o_mean2d, 3 * (size_t)N, s);
   // Large inputs, running sums, the forward's point_weight at hand, no cov3d_precomp: the live rows through a compact list
   // (see lr_pbwd_compact_kernel) -- on BAND views, where a per cent of the rows is live and the one-kernel form is nearly
@@ -409,7 +406,7 @@ void lr_launch_project_bwd(const LrView& v, int N, const float* means, const flo
   // either way (~7 lines per live row at ~50 G lines/s): measured at 30 M rows, list / one kernel: 7 % live 419 / 469 us,
   // 7.5 % (trained-like) 451 / 481, 14 % (opacity = rand) 690 / 610 -- not worth a second form there.
   // LOGRAST_PBWD_LIST: 0 never, 1 band views (default), 2 always.
-  LR_KNOB(list_knob, "LOGRAST_PBWD_LIST", 1);
+  const int list_knob = lr_knob(LRKNOB_PBWD_LIST);
   const bool band_view = v.ty0 > 0 || v.ty1 < v.gy;
   if ((list_knob == 2 || (list_knob == 1 && band_view)) && !clear_inside && pw && !v.cov3d && N >= 8) {
     float4* rows_w = const_cast<float4*>(rows4);   // (the accumulator rows are the caller's scratch: slots 12-15 are this path's)

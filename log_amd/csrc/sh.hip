@@ -5,6 +5,7 @@
 // LoG/model/activation.py:27-34 -- and passes colors_precomp, LoG/render/renderer.py:144-145); the basis is
 // pinned against that file in tests/test_sh.py.  Streaming, one thread per Gaussian, coefficients staged per wave.
 #include "common.hpp"
+#include "launch.hpp"
 
 #define SH_C0 0.28209479177387814f
 #define SH_C1 0.4886025119029199f

@@ -6,6 +6,7 @@
 // Keys are unique (the Gaussian index is the low word), hence the order is total and equals the
 // stable (tile, depth) order of index-ordered input.  Output: point_list[I] = Gaussian ids.
 #include "common.hpp"
+#include "launch.hpp"
 
 // ---- register-blocked LDS path -----------------------------------------------------------------------------
 // Tiles with lo < L <= hi.  Keys live in LDS (padded to a power of two with +inf), but every thread pulls EIGHT

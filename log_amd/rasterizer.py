@@ -17,6 +17,7 @@ and ``diff_gaussian_rasterization_wodilate`` (chingswy fork, branch ``antialias`
 All arithmetic runs in hand-written HIP kernels (log_amd/csrc) through the C ABI of liblograst.so
 (include/lograst.h).  Tensors must live on the MI355X; there is no CPU fallback.
 """
+import contextlib
 import ctypes
 import threading
 from typing import NamedTuple
@@ -373,25 +374,25 @@ class HipBackend:
 
     last_forms = None   # {"fwd": "rows" | "quadrant", "bwd": ...} of the most recent forward / backward (diagnostics)
 
-    def _note_form(self, kind, walk_form, n):
-        """Which compositing kernel the library launches for this call: the rule of lr_launch_blend_fwd / _bwd
-        (log_amd/csrc/blend.hip) restated -- knob LOGRAST_{FWD,BWD}_ROWS, else the view's hint, else (reverse walk only)
-        row-split from LOGRAST_HELPER_MIN_N Gaussians.  bench.py / the parity tests record it next to their numbers."""
-        L = _lib.lib()
-        val = ctypes.c_int32(2)
-        L.lograst_get_knob(("LOGRAST_%s_ROWS" % kind.upper()).encode(), ctypes.byref(val))
-        if val.value != 2:
-            rows = val.value == 1
-        elif walk_form != _lib.FORM_AUTO:
-            rows = walk_form == _lib.FORM_ROWS
-        elif kind == "bwd":
-            L.lograst_get_knob(b"LOGRAST_HELPER_MIN_N", ctypes.byref(val))
-            rows = n >= val.value
-        else:
-            rows = False
+    def _note_form(self, kind, rows):
+        """Which compositing kernel the library launches for this call ("rows" = row-split): bench.py / the parity tests
+        record it next to their numbers."""
         if self.last_forms is None:
             self.last_forms = {}
         self.last_forms[kind] = "rows" if rows else "quadrant"
+
+    def _bwd_rows(self, walk_form, n):
+        """The rule of lr_launch_blend_bwd (log_amd/csrc/blend.hip) restated, the library exports none for the reverse
+        walk: knob LOGRAST_BWD_ROWS, else the view's hint, else row-split from LOGRAST_HELPER_MIN_N Gaussians."""
+        L = _lib.lib()
+        val = ctypes.c_int32(2)
+        L.lograst_get_knob(b"LOGRAST_BWD_ROWS", ctypes.byref(val))
+        if val.value != 2:
+            return val.value == 1
+        if walk_form != _lib.FORM_AUTO:
+            return walk_form == _lib.FORM_ROWS
+        L.lograst_get_knob(b"LOGRAST_HELPER_MIN_N", ctypes.byref(val))
+        return n >= val.value
 
     @staticmethod
     def _carve(device, parts):
@@ -431,11 +432,11 @@ class HipBackend:
                      pw=torch.empty(N, dtype=f32, device=device))
         kept = [("geom", u8, (L.lograst_geom_bytes(N),)), ("state", u8, (L.lograst_tile_state_bytes(W, H, N),)),
                 ("final_T", f32, (H, W)), ("n_contrib", i32, (H, W))]
-        scratch_floats = _lib.BWD_ROW_FLOATS if scratch_floats else 0
-        if scratch_floats and N:
+        scratch_floats = _lib.BWD_ROW_FLOATS if scratch_floats and N else 0
+        if scratch_floats:
             kept.append(("bwd_scratch", f32, (N * scratch_floats,)))
         instances = None
-        want_masks = bool(_hit_masks and scratch_floats and N)
+        want_masks = bool(_hit_masks and scratch_floats)
         if want_masks:   # (knob LOGRAST_HIT_MASKS = 0: the library would ignore the buffer, and a backward under a different
             kv = ctypes.c_int32(1)   # knob value must not find an unwritten one)
             L.lograst_get_knob(b"LOGRAST_HIT_MASKS", ctypes.byref(kv))
@@ -455,65 +456,50 @@ class HipBackend:
         # them (speculative / exact mode), or the caller's capacity (sync-free mode)
         pin = _pinned_form()
         view.walk_form = pin or self.walk_form(_capacity_hint if _capacity_hint is not None else hist_ratio * N, N)
-        self._note_form("fwd", view.walk_form, N)
+        fwd_form = int(L.lograst_forward_form(ctypes.byref(view)))   # 1 = row-split, 2 = quadrant
+        self._note_form("fwd", fwd_form == 1)
+
+        def lists_for(cap, plist=None):
+            """point list, key buffer and hit masks of a stage 2 with room for `cap` tile instances.  The list is an
+            allocation of its own unless the caller carved it from the arena: a guessed one would stay pinned there, at its
+            guessed size and next to the exact one after a retry, until backward -- round-3 advisory."""
+            return (plist if plist is not None else torch.empty(cap, dtype=i32, device=device),
+                    torch.empty(L.lograst_keys_bytes(cap), dtype=u8, device=device), masks_for(cap))
+
+        def stage1_args(k):
+            return (ctypes.byref(view), N, _ptr(means3D), _ptr(scales), _ptr(rotations), _ptr(opacities), _ptr(colors),
+                    _ptr(o["radii"]), _ptr(k["geom"]), _ptr(k["state"]))
+
+        def stage2_args(k, keys, plist, capacity, max_len):
+            return (_ptr(keys), _ptr(plist), capacity, max_len, _ptr(o["image"]), _ptr(k["final_T"]), _ptr(k["n_contrib"]),
+                    _ptr(o.get("pid")), _ptr(o.get("pwp")), _ptr(o.get("pw")), _ptr(k.get("bwd_scratch")), scratch_floats,
+                    _ptr(status), stream)
+        n_host, m_host = ctypes.c_uint32(0), ctypes.c_uint32(0)
         with torch.cuda.device(device):
-            if _capacity_hint is None and _speculative and N > 0:
-                tiles = ((W + 15) // 16) * ((H + 15) // 16)
-                capacity, max_len = _cap_model.guess(ckey, N, tiles)
-                # (the guessed list is an allocation of its own: inside the arena it would stay pinned, at its guessed
-                # size and next to the exact one after a retry, until backward -- round-3 advisory)
-                k = self._carve(device, kept)
-                plist = torch.empty(capacity, dtype=i32, device=device)
-                keys = torch.empty(L.lograst_keys_bytes(capacity), dtype=u8, device=device)
-                masks = masks_for(capacity)
-                n_host, m_host = ctypes.c_uint32(0), ctypes.c_uint32(0)
-                _lib.check(L.lograst_forward_speculative(
-                    ctypes.byref(view), N, _ptr(means3D), _ptr(scales), _ptr(rotations), _ptr(opacities), _ptr(colors),
-                    _ptr(o["radii"]), _ptr(k["geom"]), _ptr(k["state"]), _ptr(keys), _ptr(plist), capacity, max_len,
-                    _ptr(o["image"]), _ptr(k["final_T"]), _ptr(k["n_contrib"]), _ptr(o.get("pid")), _ptr(o.get("pwp")),
-                    _ptr(o.get("pw")), _ptr(k.get("bwd_scratch")), scratch_floats if "bwd_scratch" in k else 0,
-                    _ptr(status), ctypes.byref(n_host), ctypes.byref(m_host), stream))
-                n_inst, n_len = int(n_host.value), int(m_host.value)
-                instances = n_inst
-                retry = n_inst > capacity or (max_len != 0 and n_len > max_len)
-                _cap_model.update(ckey, N, n_inst, n_len, retry)
-                if retry:   # the speculative stage 2 rendered nothing: once more with exact buffers
-                    capacity, max_len = n_inst, max(n_len, 1)
-                    plist = torch.empty(capacity, dtype=i32, device=device)
-                    keys = torch.empty(L.lograst_keys_bytes(capacity), dtype=u8, device=device)
-                    masks = masks_for(capacity)
-                    _lib.check(L.lograst_forward_render(
-                        ctypes.byref(view), N, _ptr(k["geom"]), _ptr(k["state"]), _ptr(keys), _ptr(plist), capacity, max_len,
-                        _ptr(o["image"]), _ptr(k["final_T"]), _ptr(k["n_contrib"]), _ptr(o.get("pid")), _ptr(o.get("pwp")),
-                        _ptr(o.get("pw")), _ptr(k.get("bwd_scratch")), scratch_floats if "bwd_scratch" in k else 0,
-                        _ptr(status), stream))
-            elif _capacity_hint is None:
-                k = self._carve(device, kept)
-                n_host, m_host = ctypes.c_uint32(0), ctypes.c_uint32(0)
-                _lib.check(L.lograst_forward_project(ctypes.byref(view), N, _ptr(means3D), _ptr(scales), _ptr(rotations),
-                                                     _ptr(opacities), _ptr(colors), _ptr(o["radii"]), _ptr(k["geom"]),
-                                                     _ptr(k["state"]), ctypes.byref(n_host), ctypes.byref(m_host), stream))
-                capacity, max_len = int(n_host.value), max(int(m_host.value), 1)
-                plist = torch.empty(capacity, dtype=i32, device=device)
-                keys = torch.empty(L.lograst_keys_bytes(capacity), dtype=u8, device=device)
-                masks = masks_for(capacity)
-                _lib.check(L.lograst_forward_render(
-                    ctypes.byref(view), N, _ptr(k["geom"]), _ptr(k["state"]), _ptr(keys), _ptr(plist), capacity, max_len,
-                    _ptr(o["image"]), _ptr(k["final_T"]), _ptr(k["n_contrib"]), _ptr(o.get("pid")), _ptr(o.get("pwp")),
-                    _ptr(o.get("pw")), _ptr(k.get("bwd_scratch")), scratch_floats if "bwd_scratch" in k else 0,
-                    _ptr(status), stream))
-            else:
+            if _capacity_hint is not None:   # sync-free: the caller's capacity, one call
                 capacity, max_len = _capacity_hint, _max_len_hint
                 k = self._carve(device, kept + [("plist", i32, (capacity,))])
-                plist = k["plist"]
-                keys = torch.empty(L.lograst_keys_bytes(capacity), dtype=u8, device=device)
-                masks = masks_for(capacity)
-                _lib.check(L.lograst_forward(
-                    ctypes.byref(view), N, _ptr(means3D), _ptr(scales), _ptr(rotations), _ptr(opacities), _ptr(colors),
-                    _ptr(o["radii"]), _ptr(k["geom"]), _ptr(k["state"]), _ptr(keys), _ptr(plist), capacity, max_len,
-                    _ptr(o["image"]), _ptr(k["final_T"]), _ptr(k["n_contrib"]), _ptr(o.get("pid")), _ptr(o.get("pwp")),
-                    _ptr(o.get("pw")), _ptr(k.get("bwd_scratch")), scratch_floats if "bwd_scratch" in k else 0,
-                    _ptr(status), stream))
+                plist, keys, masks = lists_for(capacity, plist=k["plist"])
+                _lib.check(L.lograst_forward(*stage1_args(k), *stage2_args(k, keys, plist, capacity, max_len)))
+            else:
+                k = self._carve(device, kept)
+                retry = True
+                if _speculative and N > 0:   # both stages with a guessed capacity; the host reads the real one afterwards
+                    tiles = ((W + 15) // 16) * ((H + 15) // 16)
+                    capacity, max_len = _cap_model.guess(ckey, N, tiles)
+                    plist, keys, masks = lists_for(capacity)
+                    _lib.check(L.lograst_forward_speculative(*stage1_args(k), *stage2_args(k, keys, plist, capacity, max_len)[:-1],
+                                                             ctypes.byref(n_host), ctypes.byref(m_host), stream))
+                    instances = int(n_host.value)
+                    retry = instances > capacity or (max_len != 0 and int(m_host.value) > max_len)
+                    _cap_model.update(ckey, N, instances, int(m_host.value), retry)
+                else:                        # exact: stage 1, read the header, stage 2
+                    _lib.check(L.lograst_forward_project(*stage1_args(k), ctypes.byref(n_host), ctypes.byref(m_host), stream))
+                if retry:   # (a speculative stage 2 that did not fit rendered nothing: once more with exact buffers)
+                    capacity, max_len = int(n_host.value), max(int(m_host.value), 1)
+                    plist, keys, masks = lists_for(capacity)
+                    _lib.check(L.lograst_forward_render(ctypes.byref(view), N, _ptr(k["geom"]), _ptr(k["state"]),
+                                                        *stage2_args(k, keys, plist, capacity, max_len)))
         if instances is None:
             instances = capacity          # exact mode: the real count; sync-free: the caller's (tight) upper bound
         if _DEBUG_ADDR:
@@ -524,7 +510,7 @@ class HipBackend:
                      final_T=k["final_T"], n_contrib=k["n_contrib"], bwd_scratch=k.get("bwd_scratch"),
                      point_weight=o.get("pw"), tile_rows=(view.tile_row_begin, view.tile_row_end), instances=int(instances),
                      walk_form_pin=pin, hit_masks=masks if want_masks else None,
-                     hit_mask_form=int(L.lograst_forward_form(ctypes.byref(view))) if want_masks else 0)
+                     hit_mask_form=fwd_form if want_masks else 0)
         if kept_keys is not None:
             saved["keys"], saved["capacity"] = kept_keys
         return o["image"], o["radii"], o.get("pid"), o.get("pwp"), o.get("pw"), saved
@@ -560,7 +546,7 @@ class HipBackend:
             flags |= 4
         # tiny splats -> the row-split reverse walk; a form pinned for the forward holds for its backward
         view.walk_form = saved.get("walk_form_pin", 0) or self.walk_form(saved.get("instances", 0), N)
-        self._note_form("bwd", view.walk_form, N)
+        self._note_form("bwd", self._bwd_rows(view.walk_form, N))
         hm = saved.get("hit_masks")      # the forward's support ballots (lograst_view.hit_masks): the reverse walk reads them
         if hm is not None:
             view.hit_masks, view.hit_mask_words = hm.data_ptr(), hm.numel()
@@ -988,12 +974,8 @@ class _RasterizeGaussians(torch.autograd.Function):
         wants_grad = any(ctx.needs_input_grad[:7])   # all False under torch.no_grad()
         wants_grad = wants_grad or (cov is not None and ctx.needs_input_grad[10])
         scratch_floats = _lib.BWD_ROW_FLOATS if wants_grad else 0
-        if cov is not None:
-            image, radii, pid, pwp, pw, saved = _backend.forward(rs, flavour, use_filter, m, None, None, o, c,
-                                                                 scratch_floats=scratch_floats, cov3D=cov)
-        else:
-            image, radii, pid, pwp, pw, saved = _backend.forward(rs, flavour, use_filter, m, s, r, o, c,
-                                                                 scratch_floats=scratch_floats)
+        image, radii, pid, pwp, pw, saved = _backend.forward(rs, flavour, use_filter, m, *((s, r) if cov is None else (None, None)),
+                                                             o, c, scratch_floats=scratch_floats, cov3D=cov)
         ctx.cov = cov
         ctx.rs, ctx.flavour, ctx.use_filter = rs, flavour, use_filter
         ctx.set_materialize_grads(False)   # no zero-filled gradients for radii / the fork maps (4 fill kernels per view)
@@ -1126,11 +1108,8 @@ class GaussianRasterizer(nn.Module):
             raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
         if shs is not None and not 0 <= int(self.raster_settings.sh_degree) <= 3:
             raise ValueError("sh_degree must be 0..3")
-        if self.walk_form not in (None, "auto"):
-            with walk_form(self.walk_form):
-                ret = _RasterizeGaussians.apply(means3D, means2D, colors_precomp, shs, opacities, scales, rotations,
-                                                self.raster_settings, flavour, use_filter, cov3D_precomp)
-        else:
+        # (a rasterizer without a form of its own leaves an enclosing ``with walk_form(...)`` block in force)
+        with walk_form(self.walk_form) if self.walk_form not in (None, "auto") else contextlib.nullcontext():
             ret = _RasterizeGaussians.apply(means3D, means2D, colors_precomp, shs, opacities, scales, rotations,
                                             self.raster_settings, flavour, use_filter, cov3D_precomp)
         if flavour.extras:

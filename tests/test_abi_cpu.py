@@ -153,14 +153,77 @@ def test_ctypes_signatures_match_the_header_prototypes():
         assert got == want, (name, got, want)
 
 
+def _knob_table(L):
+    """[(name, default, lo, hi)] as lograst_knob_info enumerates it."""
+    rows = []
+    for i in range(L.lograst_knob_count()):
+        name, what = ctypes.c_char_p(), ctypes.c_char_p()
+        d, lo, hi = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+        assert L.lograst_knob_info(i, ctypes.byref(name), ctypes.byref(d), ctypes.byref(lo), ctypes.byref(hi),
+                                   ctypes.byref(what)) == 0
+        rows.append((name.value.decode(), d.value, lo.value, hi.value))
+    return rows
+
+
 def test_every_tunable_knob_is_documented():
     """The knob table of the library (api.hip: kKnobs -- what lograst_knob_info enumerates) against INTEGRATION.md: a knob
     a host can move must be described where a host looks."""
-    import re
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = open(os.path.join(root, "log_amd", "csrc", "api.hip")).read()
-    i = src.index("static const LrKnobInfo kKnobs[]")
-    names = re.findall(r'\{"(LOGRAST_[A-Z_]+)"', src[i:src.index("};", i)])
-    assert len(names) >= 20
-    doc = open(os.path.join(root, "INTEGRATION.md")).read()
+    from log_amd import _lib
+    names = [row[0] for row in _knob_table(_lib.lib())]
+    assert len(names) >= 20 and all(re.fullmatch(r"LOGRAST_[A-Z_]+", n) for n in names)
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
     assert [n for n in names if n not in doc] == []
+
+
+_KNOB_CHILD = r"""
+import ctypes, json, sys
+sys.path.insert(0, sys.argv[1])
+from log_amd import _lib
+L = _lib.lib()
+def get(name):
+    v = ctypes.c_int32(-12345)
+    rc = L.lograst_get_knob(name, ctypes.byref(v))
+    return [rc, v.value]
+out = {"env": get(b"LOGRAST_MID_COOP")}
+out["set_rc"] = L.lograst_set_knob(b"LOGRAST_MID_COOP", 32)
+out["set"] = get(b"LOGRAST_MID_COOP")
+out["range_rc"] = L.lograst_set_knob(b"LOGRAST_MID_COOP", 65)
+out["range_err"] = L.lograst_last_error().decode()
+out["after_range"] = get(b"LOGRAST_MID_COOP")
+out["unknown_rc"] = L.lograst_set_knob(b"LOGRAST_NOPE", 1)
+out["unknown_err"] = L.lograst_last_error().decode()
+out["reset_rc"] = L.lograst_reset_knobs()
+out["reset"] = get(b"LOGRAST_MID_COOP")
+out["all"] = []
+for i in range(L.lograst_knob_count()):
+    name, d = ctypes.c_char_p(), ctypes.c_int32()
+    assert L.lograst_knob_info(i, ctypes.byref(name), ctypes.byref(d), None, None, None) == 0
+    out["all"].append([name.value.decode(), d.value] + get(name.value))
+print(json.dumps(out))
+"""
+
+
+def test_knob_precedence_override_environment_default():
+    """lograst_get_knob answers what the next launch reads: a lograst_set_knob override, else the environment variable of
+    the knob's name (read in a child process that starts with it), else the default that lograst_knob_info reports."""
+    import json
+    import subprocess
+    import sys
+    from log_amd import _lib
+    clean = {k: v for k, v in os.environ.items() if not k.startswith("LOGRAST_") or k == "LOGRAST_LIB"}
+
+    def child(**env):
+        text = subprocess.check_output([sys.executable, "-c", _KNOB_CHILD, ROOT], env=dict(clean, **env), text=True)
+        return json.loads(text.strip().splitlines()[-1])
+    out = child(LOGRAST_MID_COOP="8")
+    assert out["env"] == [0, 8]
+    assert out["set_rc"] == 0 and out["set"] == [0, 32]
+    assert out["range_rc"] == -1 and out["range_err"] == "LOGRAST_MID_COOP: value out of range"
+    assert out["after_range"] == [0, 32]          # a refused value changes nothing
+    assert out["unknown_rc"] == -1 and out["unknown_err"] == "unknown knob: LOGRAST_NOPE"
+    assert out["reset_rc"] == 0 and out["reset"] == [0, 8]
+    # a clean environment: every knob at the default that lograst_knob_info reports
+    out = child()
+    assert len(out["all"]) == 22 and out["env"] == [0, 16] and out["reset"] == [0, 16]
+    for name, dflt, rc, value in out["all"]:
+        assert rc == 0 and value == dflt, (name, value, dflt)
