@@ -124,6 +124,9 @@ typedef const float __attribute__((address_space(4))) lr_cfloat;
 LR_DEV const lr_cfloat* lr_uniform(const float* p) { return (const lr_cfloat*)p; }
 
 LR_DEV float lr_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+// max(a, b) that hands a NaN on, like torch.maximum (fmaxf returns the other operand): the amsgrad maximum of a row whose
+// gradient is NaN becomes NaN with its moments, as in the reference's _single_tensor_adam
+LR_DEV float lr_max_nan(float a, float b) { return (b >= a || b != b) ? b : a; }
 LR_DEV float lr_dot3p(float a0, float a1, float a2, float b0, float b1, float b2, float c) {
   return lr_fma(a0, b0, lr_fma(a1, b1, lr_fma(a2, b2, c)));
 }

@@ -252,7 +252,7 @@ adam_kernel(AdamArgs a) {
       k.exp_avg_sq[o[u]] = v;
       float vd = v;
       if (k.max_exp_avg_sq) {
-        vd = fmaxf(vm[u], v);
+        vd = lr_max_nan(vm[u], v);
         k.max_exp_avg_sq[o[u]] = vd;
       }
       const float denom = sqrtf(vd) / a.bc2_sqrt + a.eps;

@@ -116,7 +116,7 @@ lr_sh_fwd_kernel(int N, int deg, int M, const float* __restrict__ means, const f
 #pragma unroll
   for (int ch = 0; ch < 3; ch++) {
     clamped[3 * (size_t)i + ch] = c[ch] < 0.f;
-    colors[3 * (size_t)i + ch] = fmaxf(c[ch], 0.f);
+    colors[3 * (size_t)i + ch] = c[ch] < 0.f ? 0.f : c[ch];   // (not fmaxf: a NaN colour stays a NaN)
   }
 }
 
@@ -234,13 +234,13 @@ ga_fwd_kernel(GatherArgs a) {
   if (L > 0) {
     float* const wl = lr_sh_lds + wave * 64 * (L + 1);
     lr_sh_wave_sync();                                      // rowid[] written by this wave
-    const uint32_t magic = 0xffffffffu / (uint32_t)a.K + 1u;  // e / K for e < 65536
+    const uint32_t magic = 0xffffffffu / (uint32_t)a.K + 1u;  // e / K for e < 65536 and K >= 2 (K = 1: 2^32 does not fit)
     float* const out = a.r_shs + (size_t)i0 * L;
     // lanes walk the rows' coefficients contiguously, one (r, g, b) triple = 12 bytes per access (a float at a time this
     // loop was 45 dependent 4-byte gathers per lane at degree 3), four in flight
 #pragma unroll 4
     for (int e = lane; e < rows * a.K; e += 64) {
-      const int g = (int)__umulhi((uint32_t)e, magic), j = e - g * a.K;
+      const int g = a.K == 1 ? e : (int)__umulhi((uint32_t)e, magic), j = e - g * a.K;
       const float* __restrict__ src = a.shs + (size_t)rowid[wave][g] * L + 3 * j;
       const float v0 = src[0], v1 = src[1], v2 = src[2];
       float* o = out + 3 * (size_t)e;                         // the raw copy is contiguous in e
@@ -355,7 +355,7 @@ LR_DEV void ga_adam_store(const AdamKey& k, const AdamArgs& f, const GaElem& e) 
   k.exp_avg_sq[e.o] = v;
   float vd = v;
   if (k.max_exp_avg_sq) {
-    vd = fmaxf(e.vm, v);
+    vd = lr_max_nan(e.vm, v);
     k.max_exp_avg_sq[e.o] = vd;
   }
   const float denom = sqrtf(vd) / f.bc2_sqrt + f.eps;

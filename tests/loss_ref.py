@@ -33,7 +33,7 @@ def blur(x, window=None):
     applied as two 1-D passes)."""
     H, W = x.shape[-2:]
     if window is None:
-        t = taps64().to(x.device)
+        t = taps64().to(device=x.device, dtype=x.dtype)
         h = sum(t[k] * x[..., :, k:W - WINDOW + 1 + k] for k in range(WINDOW))
         return sum(t[k] * h[..., k:H - WINDOW + 1 + k, :] for k in range(WINDOW))
     w = window.to(device=x.device, dtype=x.dtype)
@@ -49,12 +49,14 @@ def ssim_map(render, gt, window=None):
     return ((2 * mu1 * mu2 + C1) * (2 * s12 + C2)) / ((mu1 * mu1 + mu2 * mu2 + C1) * (s11 + s22 + C2))
 
 
-def loss_ref(render, gt, render_l1=None, ssim_weight=0.2, l1_weight=0.8, window=None, upstream=1.0):
-    """All inputs any float dtype / device; computed in float64.  -> dict(loss, l1, ssim: python floats; grad_render,
-    grad_render_l1 (None when render_l1 is None): float64 tensors, the gradient of upstream * loss)."""
-    r = render.detach().to(torch.float64).clone().requires_grad_(True)
-    g = gt.detach().to(torch.float64)
-    rl = None if render_l1 is None else render_l1.detach().to(torch.float64).clone().requires_grad_(True)
+def loss_ref(render, gt, render_l1=None, ssim_weight=0.2, l1_weight=0.8, window=None, upstream=1.0, dtype=torch.float64):
+    """All inputs any float dtype / device; computed in `dtype` (float64: the reference value; float32: the same formula at
+    the kernels' precision, whose distance to the float64 run is the yardstick for a second fp32 evaluation).  -> dict(loss,
+    l1, ssim: python floats; grad_render, grad_render_l1 (None when render_l1 is None): tensors of `dtype`, the gradient of
+    upstream * loss)."""
+    r = render.detach().to(dtype).clone().requires_grad_(True)
+    g = gt.detach().to(dtype)
+    rl = None if render_l1 is None else render_l1.detach().to(dtype).clone().requires_grad_(True)
     ssim = 1.0 - ssim_map(r, g, window).mean()
     l1 = ((r if rl is None else rl) - g).abs().mean()
     loss = ssim_weight * ssim + l1_weight * l1

@@ -122,3 +122,11 @@ def test_cached_tree_depth_hint_and_stale_hint(oracle_mod):
                                     480 / (2 * tfy), tfx, tfy, 3.0, 30, 2)
     tree._lograst_depth = None
     np.testing.assert_array_equal(lod.traverse(tree, model, roots, rast, max_depth=2).cpu().numpy(), want2)
+
+
+@pytest.mark.parametrize("seed", range(8))
+def test_traverse_follows_reference_on_random_trees(seed, oracle_mod):
+    """The reference's recorded random trees (tests/golden/lodrand_<seed>.npz: random arity, depth, removal rate, camera and
+    threshold) through the HIP traversal: the body and assertions of the CPU test of those files."""
+    from lod_util import check_random_tree_case
+    check_random_tree_case(seed, "cuda:0", oracle_mod)

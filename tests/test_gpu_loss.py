@@ -7,7 +7,13 @@ Tolerances.  A gradient is within rel-L2 1e-4 of float64 (the project's standing
 gap32 = the distance between the reference's own fp32 and float64 runs, stored in the fixtures by the generator: the HIP
 kernels and the reference's fp32 run are two fp32 evaluations in different summation orders, so their errors add (x2), and
 the largest gap over a handful of cases underestimates the tail (x4).  The three scalars are within 8 * max(gap32 over all
-fixtures).  Inputs that are no fixture take the gap32 of the fixture made by the same recipe (named at each test)."""
+fixtures).  Inputs that are no fixture take the gap32 of the fixture made by the same recipe (named at each test).
+
+The cases at the end of the file (other channel / batch counts, strides, weights, contents) take their yardstick from the
+restatement itself, loss_ref(dtype=float32) on the same inputs: gradients by the same rule with that gap32; scalars within
+8 * max(the fixtures' gap32, this input's own |fp32 - float64|) -- never tighter than the rule above, wider only where the
+input's own fp32 evaluation is coarser than any fixture's (values outside [0, 1]); where the gradient is analytically zero
+(render == gt) the 1e-4 cap, relative to a norm of 1e-17, is left out.  See _check_against_restatement."""
 import glob
 import math
 import os
@@ -44,7 +50,8 @@ def _run(render, gt, render_l1=None, a=0.2, b=0.8, upstream=None):
     """-> (loss, l1, ssim as python floats via ONE transfer; grad_render; grad_render_l1 or None; the raw 0-dim tensors)"""
     from log_amd.loss import l1_ssim_loss
     r = render.detach().clone().requires_grad_(True) if render.is_contiguous() else render.detach().requires_grad_(True)
-    rl = None if render_l1 is None else render_l1.detach().clone().requires_grad_(True)
+    rl = None if render_l1 is None else (render_l1.detach().clone() if render_l1.is_contiguous()
+                                         else render_l1.detach()).requires_grad_(True)
     loss, l1, ssim = l1_ssim_loss(r, gt, rl, a, b)
     assert loss.requires_grad and not l1.requires_grad and not ssim.requires_grad
     assert loss.dim() == 0 and l1.dim() == 0 and ssim.dim() == 0 and loss.is_cuda
@@ -231,3 +238,103 @@ def test_profile_slots_time_the_new_kernels():
     finally:
         _lib.profile_enable(False)
     assert prof["loss_fwd"][1] == 1 and prof["loss_bwd"][1] == 1
+
+
+# ---- shapes, strides and contents no fixture has: each against loss_ref in float64, the yardstick taken from
+# ---- loss_ref(dtype=float32) on the same inputs ----------------------------------------------------------------------
+def _pair(B, C, H, W, seed, lo=0.0, hi=1.0):
+    """_image_pair's recipe for any channel count and value range."""
+    g = torch.Generator(device=DEV).manual_seed(seed)
+    coarse = torch.rand(B, C, max(H // 8, 2), max(W // 8, 2), device=DEV, generator=g, dtype=torch.float64)
+    field = torch.nn.functional.interpolate(coarse, size=(H, W), mode="bilinear", align_corners=True)
+    noisy = lambda s: ((field + s * torch.randn(field.shape, device=DEV, generator=g, dtype=torch.float64)).clamp(0, 1)
+                       * (hi - lo) + lo).float().contiguous()
+    return noisy(0.05), noisy(0.08)
+
+
+def _check_against_restatement(tag, render, gt, render_l1=None, a=0.2, b=0.8, zero_gradient=False):
+    """Scalars: within 8 * the larger of the fixtures' gap32 and this input's own |fp32 - float64| (values beyond [0, 1]
+    round coarser than any fixture's).  Gradients: the file's rule, rel-L2 <= min(1e-4, 8 * gap32), with gap32 = rel-L2 of
+    loss_ref(dtype=float32) to loss_ref(float64) on these inputs -- written without the division, so that it also holds
+    where the gradient is analytically zero (zero_gradient: render == gt, a maximum of SSIM and the kink of L1; the 1e-4 cap
+    is relative to a norm that is rounding noise there and is left out)."""
+    ref = loss_ref.loss_ref(render, gt, render_l1, a, b)
+    ref32 = loss_ref.loss_ref(render, gt, render_l1, a, b, dtype=torch.float32)
+    scalars, g, gl, _ = _run(render, gt, render_l1, a, b)
+    gaps = _gaps()
+    for k, got in zip(("loss", "l1", "ssim"), scalars):
+        err, bound = abs(got - ref[k]), FACTOR * max(gaps[k], abs(ref32[k] - ref[k]))
+        print(f"{tag} {k}: |{got:.9f} - {ref[k]:.9f}| = {err:.3e} <= {bound:.3e}")
+        assert err <= bound, (tag, k, err, bound)
+    norm = lambda t: float(torch.linalg.norm(t.double()))
+    for name, got, want, want32 in (("grad_render", g, ref["grad_render"], ref32["grad_render"]),
+                                    ("grad_render_l1", gl, ref["grad_render_l1"], ref32["grad_render_l1"])):
+        if want is None:
+            assert got is None
+            continue
+        assert torch.isfinite(got).all()
+        err, gap, n64 = norm(got.double() - want), norm(want32.double() - want), norm(want)
+        bound = FACTOR * gap if zero_gradient else min(GRAD_TOL * n64, FACTOR * gap)
+        print(f"{tag} {name}: |hip - ref64| {err:.3e} <= {bound:.3e} (|ref32 - ref64| {gap:.3e}, |ref64| {n64:.3e})")
+        assert err <= bound, (tag, name, err, bound)
+    return scalars, g, gl
+
+
+@pytest.mark.parametrize("B,C,H,W", [(3, 1, 64, 80), (5, 4, 50, 70), (5, 1, 43, 44), (3, 4, 33, 75)])
+def test_other_channel_and_batch_counts(B, C, H, W):
+    render, gt = _pair(B, C, H, W, 10 * B + C)
+    _check_against_restatement(f"B={B} C={C}", render, gt)
+    _check_against_restatement(f"B={B} C={C} render_l1", render, gt, (render * 1.03 + 0.01).contiguous())
+
+
+def test_render_l1_as_a_channel_slice_of_a_four_channel_tensor():
+    """calculate_loss passes output["render_correct"][:, :3]: rows of 3 channels out of 4, at 270x480."""
+    render, gt = _pair(2, 3, 270, 480, 21)
+    g = torch.Generator(device=DEV).manual_seed(22)
+    four = torch.rand(2, 4, 270, 480, device=DEV, generator=g)
+    four[:, :3] = (render * 0.97 + 0.02)
+    rl = four[:, :3]
+    assert not rl.is_contiguous() and rl.stride()[0] == 4 * 270 * 480
+    s_v, g_v, gl_v = _check_against_restatement("render_l1 = [:, :3]", render, gt, rl)
+    s_c, g_c, gl_c, _ = _run(render, gt, rl.contiguous())
+    assert s_v == s_c and torch.equal(g_v, g_c) and torch.equal(gl_v, gl_c)          # strides change nothing
+
+
+def test_gt_expanded_over_the_batch_and_cropped_views():
+    render, gt = _pair(3, 3, 96, 130, 31)
+    gt_e = gt[:1].expand(3, -1, -1, -1)
+    assert gt_e.stride()[0] == 0
+    s_v, g_v, _ = _check_against_restatement("gt stride 0", render, gt_e)
+    s_c, g_c, _, _ = _run(render, gt_e.contiguous())
+    assert s_v == s_c and torch.equal(g_v, g_c)
+    # W- and H-cropped views of larger tensors (all three inputs)
+    big_r, big_g = _pair(2, 3, 140, 200, 32)
+    crop = (slice(None), slice(None), slice(9, 9 + 75), slice(13, 13 + 131))
+    r_v, g_v_, rl_v = big_r[crop], big_g[crop], (big_r * 1.02)[crop]
+    assert not r_v.is_contiguous() and r_v.stride()[2] == 200
+    s_v, gr_v, gl_v = _check_against_restatement("cropped views", r_v, g_v_, rl_v)
+    s_c, gr_c, gl_c, _ = _run(r_v.contiguous(), g_v_.contiguous(), rl_v.contiguous())
+    assert s_v == s_c and torch.equal(gr_v, gr_c) and torch.equal(gl_v, gl_c)
+
+
+@pytest.mark.parametrize("a,b", [(1.0, 0.0), (0.0, 1.0), (0.5, 0.5)])
+def test_other_weights(a, b):
+    render, gt = _pair(2, 3, 75, 131, 41)
+    _check_against_restatement(f"weights ({a}, {b})", render, gt, None, a, b)
+    _check_against_restatement(f"weights ({a}, {b}) render_l1", render, gt, (render * 1.03).contiguous(), a, b)
+
+
+def test_inputs_outside_the_unit_interval():
+    render, gt = _pair(2, 3, 64, 96, 51, lo=-1.5, hi=3.0)
+    assert float(render.min()) < -0.5 and float(render.max()) > 2.0
+    _check_against_restatement("[-1.5, 3]", render, gt)
+
+
+def test_constant_images_and_equal_images():
+    ones = torch.ones(2, 3, 48, 60, device=DEV)
+    level = lambda vals: (ones * torch.tensor(vals, device=DEV).view(1, 3, 1, 1)).contiguous()
+    _check_against_restatement("constant, different", level([0.3, 0.5, 0.9]), level([0.6, 0.5, 0.1]))
+    _check_against_restatement("constant, black and white", level([0.0, 0.0, 1.0]), level([1.0, 0.0, 1.0]))
+    render, _ = _pair(2, 3, 48, 60, 61)
+    scalars, g, _ = _check_against_restatement("render == gt", render, render.clone(), zero_gradient=True)
+    assert scalars[1] == 0.0                                    # |x - x| sums to exactly 0

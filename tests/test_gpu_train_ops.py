@@ -337,3 +337,10 @@ def test_fused_step_through_the_drop_ins():
         da = (a.bufs[k] - wl.bufs[k]).double()
         assert float((b.bufs[k] - a.bufs[k]).double().norm()) <= 1e-4 * float(da.norm()), k
         assert float(da.norm()) > 0
+
+
+@pytest.mark.parametrize("seed", range(6))
+def test_random_views_and_steps_against_reference_classes_on_device(seed):
+    """The reference's recorded random cases (radii beyond int16, keys without gradient, amsgrad, K from 1 to 15) through the
+    HIP counter and sparse Adam: the body, assertions and tolerances of the CPU test of the same name."""
+    U.check_random_case(seed, DEV)

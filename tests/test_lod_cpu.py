@@ -88,34 +88,11 @@ def test_oracle_and_dropin_follow_reference_on_random_trees(seed, oracle_mod):
     random camera and threshold: the oracle and the drop-in (through the test double) return the list the reference's
     traverse returned (tests/golden/lodrand_<seed>.npz, written by tests/golden/make_golden_lod_random.py: the tree
     buffers, the reference's lists, and the candidate lists from which the parameters are drawn again here)."""
-    import sys
-    sys.path.insert(0, os.path.join(os.path.dirname(__file__), "golden"))
-    import make_golden_lod as G
     import oracle_backend
     from oracle_backend import OracleBackend
-    from log_amd import lod
-    ref = np.load(os.path.join(os.path.dirname(__file__), "golden", "lodrand_%d.npz" % seed))
+    from lod_util import check_random_tree_case
     oracle_backend.install(OracleBackend())
     try:
-        cands = [ref["cand_%d" % i] for i in range(int(ref["n_cands"]))]
-        rng, _, xyz, scaling, rotation, rast = G.random_tree_case(seed, cands=cands)
-        assert xyz.shape[0] == ref["node_index"].shape[0]
-        tree = types.SimpleNamespace(node_index=torch.from_numpy(ref["node_index"]), tree=torch.from_numpy(ref["tree"]),
-                                     depth=torch.from_numpy(ref["depth"]), max_level=int(ref["max_level"]))
-        roots, queries = G.random_tree_queries(rng, torch.from_numpy(ref["root_index"]))
-        np.testing.assert_array_equal(np.array(queries, np.float64), ref["queries"])
-        for q, (min_px, max_depth) in enumerate(queries):
-            want = ref["index_%d" % q]
-            rs = rast.raster_settings
-            fx, fy = rs.image_width / (2 * rs.tanfovx), rs.image_height / (2 * rs.tanfovy)
-            got = oracle_mod.lod_traverse(tree.node_index.numpy(), tree.tree.numpy(), xyz.numpy(), scaling.numpy(),
-                                          rotation.numpy(), roots.numpy(), rs.projmatrix.numpy(), rs.viewmatrix.numpy(),
-                                          fx, fy, rs.tanfovx, rs.tanfovy, min_px, tree.max_level, max_depth)
-            np.testing.assert_array_equal(got, want)
-            g = types.SimpleNamespace(xyz=xyz, scaling=scaling, rotation=rotation,
-                                      activation=types.SimpleNamespace(scaling_activation=torch.exp,
-                                                                       rotation_activation=torch.nn.functional.normalize))
-            tree.min_resolution_pixel = min_px
-            np.testing.assert_array_equal(lod.traverse(tree, g, roots, rast, max_depth=max_depth).numpy(), want)
+        check_random_tree_case(seed, "cpu", oracle_mod)
     finally:
         oracle_backend.install(None)

@@ -146,47 +146,4 @@ def test_random_views_and_steps_against_reference_classes(seed, double):
     see the inputs the reference's Counter and SparseOptimizer (unpatched, torch CPU) saw, and compute what they computed
     (tests/golden/train_random_<seed>.npz: tests/golden/make_golden_train_random.py runs the reference classes on
     train_util.random_case(seed))."""
-    import types
-    from log_amd import counter, sparse_optimizer
-    c = U.random_case(seed)
-    ref = U.load("train_random_%d.npz" % seed)
-    P = c["P"]
-    assert int(ref["P"]) == P and int(ref["n_views"]) == len(c["views"]) and int(ref["n_steps"]) == len(c["steps"])
-    # ---- counter
-    c_new = U.fresh_counter(P, "cpu")
-    o_new = U.random_counter_output(c["views"])
-    counter.update_by_output(c_new, o_new, fix_parent=True)
-    for k in U.COUNTER_DTYPES:
-        a, b = getattr(c_new, k).numpy(), ref["counter_" + k]
-        assert a.dtype == b.dtype, k
-        if a.dtype.kind == "f":
-            np.testing.assert_allclose(a, b, rtol=3e-6, atol=1e-12, err_msg=k)
-        else:
-            np.testing.assert_array_equal(a, b, err_msg=k)
-    for v in range(len(c["views"])):
-        assert torch.equal(o_new["visibility_flag"][v]["flag_vis"], torch.from_numpy(ref[f"v{v}_flag_vis"]))
-        assert torch.equal(o_new["visibility_flag"][v]["index_vis"], torch.from_numpy(ref[f"v{v}_index_vis"]))
-    # ---- sparse Adam: what SparseOptimizer.__init__ sets up that step() reads, with the reference's learning rates
-    amsgrad, shapes = c["amsgrad"], c["shapes"]
-    m_new = c["init_model"]()
-    zeros = lambda: {k: torch.zeros_like(getattr(m_new, k)) for k in shapes}
-    lrs = {int(ref[f"s{i}_step"]): (float(ref[f"s{i}_lr_xyz"]), float(ref[f"s{i}_lr_scaling"])) for i in range(len(c["steps"]))}
-    op_new = types.SimpleNamespace(
-        global_steps=torch.tensor(float(ref["start_global_steps"]), dtype=torch.float32),
-        lr_dict={k: float(ref["lr_" + k]) for k in ("colors", "shs", "opacity", "rotation")}, exp_avg=zeros(),
-        exp_avg_sq=zeros(), use_amsgrad=amsgrad, xyz_lr=None, xyz_scheduler_args=lambda step: lrs[step][0],
-        scaling_scheduler_args=lambda step: lrs[step][1])
-    if amsgrad:
-        op_new.max_exp_avg_sq = zeros()
-    for st in c["steps"]:
-        sparse_optimizer.step(op_new, m_new, st["index"], U.random_step_params(m_new, st, shapes), st["flag_vis"])
-    assert float(op_new.global_steps) == float(ref["final_global_steps"])
-    if not np.isnan(float(ref["final_xyz_lr"])):
-        assert op_new.xyz_lr == float(ref["final_xyz_lr"])
-    for k in shapes:
-        np.testing.assert_allclose(getattr(m_new, k).numpy(), ref["final_" + k], rtol=3e-6, atol=2e-8, err_msg=k)
-        np.testing.assert_allclose(op_new.exp_avg[k].numpy(), ref["final_exp_avg_" + k], rtol=3e-6, atol=1e-12, err_msg=k)
-        np.testing.assert_allclose(op_new.exp_avg_sq[k].numpy(), ref["final_exp_avg_sq_" + k], rtol=3e-6, atol=1e-20, err_msg=k)
-        if amsgrad:
-            np.testing.assert_allclose(op_new.max_exp_avg_sq[k].numpy(), ref["final_max_exp_avg_sq_" + k], rtol=3e-6,
-                                       atol=1e-20, err_msg=k)
+    U.check_random_case(seed, "cpu")

@@ -143,9 +143,9 @@ def random_case(seed):
                 init_model=init_model)
 
 
-def random_counter_output(views):
+def random_counter_output(views, device="cpu"):
     """The `output` dict Counter.update_by_output receives, for random_case()'s views."""
-    t = torch.from_numpy
+    t = lambda a: torch.from_numpy(a).to(device)
     return {"render": [None] * len(views),
             "visibility_flag": [{"index": t(v["index"]), "index_node": t(v["index_node"])} for v in views],
             "viewspace_points": [types.SimpleNamespace(grad=t(v["grad"])) for v in views],
@@ -162,3 +162,56 @@ def random_step_params(model, step, shapes):
             p.grad = step["grads"][k].clone()
         out[k] = p
     return out
+
+
+def check_random_case(seed, device):
+    """random_case(seed) through the drop-ins on `device` (the backend installed there does the arithmetic) against what
+    the reference's unpatched Counter / SparseOptimizer computed on the same inputs (train_random_<seed>.npz).  One body
+    for the CPU test (oracle backend) and the GPU test (HIP kernels): same assertions, same tolerances."""
+    from log_amd import counter, sparse_optimizer
+    c = random_case(seed)
+    ref = load("train_random_%d.npz" % seed)
+    P = c["P"]
+    assert int(ref["P"]) == P and int(ref["n_views"]) == len(c["views"]) and int(ref["n_steps"]) == len(c["steps"])
+    # ---- counter
+    c_new = fresh_counter(P, device)
+    o_new = random_counter_output(c["views"], device)
+    counter.update_by_output(c_new, o_new, fix_parent=True)
+    for k in COUNTER_DTYPES:
+        a, b = getattr(c_new, k).cpu().numpy(), ref["counter_" + k]
+        assert a.dtype == b.dtype, k
+        if a.dtype.kind == "f":
+            np.testing.assert_allclose(a, b, rtol=3e-6, atol=1e-12, err_msg=k)
+        else:
+            np.testing.assert_array_equal(a, b, err_msg=k)
+    for v in range(len(c["views"])):
+        assert torch.equal(o_new["visibility_flag"][v]["flag_vis"].cpu(), torch.from_numpy(ref[f"v{v}_flag_vis"]))
+        assert torch.equal(o_new["visibility_flag"][v]["index_vis"].cpu(), torch.from_numpy(ref[f"v{v}_index_vis"]))
+    # ---- sparse Adam: what SparseOptimizer.__init__ sets up that step() reads, with the reference's learning rates
+    amsgrad, shapes = c["amsgrad"], c["shapes"]
+    m_new = c["init_model"]()
+    for k in shapes:
+        setattr(m_new, k, getattr(m_new, k).to(device))
+    zeros = lambda: {k: torch.zeros_like(getattr(m_new, k)) for k in shapes}
+    lrs = {int(ref[f"s{i}_step"]): (float(ref[f"s{i}_lr_xyz"]), float(ref[f"s{i}_lr_scaling"])) for i in range(len(c["steps"]))}
+    op_new = types.SimpleNamespace(
+        global_steps=torch.tensor(float(ref["start_global_steps"]), dtype=torch.float32, device=device),
+        lr_dict={k: float(ref["lr_" + k]) for k in ("colors", "shs", "opacity", "rotation")}, exp_avg=zeros(),
+        exp_avg_sq=zeros(), use_amsgrad=amsgrad, xyz_lr=None, xyz_scheduler_args=lambda step: lrs[step][0],
+        scaling_scheduler_args=lambda step: lrs[step][1])
+    if amsgrad:
+        op_new.max_exp_avg_sq = zeros()
+    for st in c["steps"]:
+        st = dict(st, index=st["index"].to(device), flag_vis=st["flag_vis"].to(device),
+                  grads={k: v.to(device) for k, v in st["grads"].items()})
+        sparse_optimizer.step(op_new, m_new, st["index"], random_step_params(m_new, st, shapes), st["flag_vis"])
+    assert float(op_new.global_steps) == float(ref["final_global_steps"])
+    if not np.isnan(float(ref["final_xyz_lr"])):
+        assert op_new.xyz_lr == float(ref["final_xyz_lr"])
+    for k in shapes:
+        np.testing.assert_allclose(getattr(m_new, k).cpu().numpy(), ref["final_" + k], rtol=3e-6, atol=2e-8, err_msg=k)
+        np.testing.assert_allclose(op_new.exp_avg[k].cpu().numpy(), ref["final_exp_avg_" + k], rtol=3e-6, atol=1e-12, err_msg=k)
+        np.testing.assert_allclose(op_new.exp_avg_sq[k].cpu().numpy(), ref["final_exp_avg_sq_" + k], rtol=3e-6, atol=1e-20, err_msg=k)
+        if amsgrad:
+            np.testing.assert_allclose(op_new.max_exp_avg_sq[k].cpu().numpy(), ref["final_max_exp_avg_sq_" + k], rtol=3e-6,
+                                       atol=1e-20, err_msg=k)
