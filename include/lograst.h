@@ -36,7 +36,9 @@ extern "C" {
  * per-chunk support ballots for the reverse walk (below); new entry points: lograst_hit_mask_bytes, lograst_forward_form,
  * lograst_pack_rows_clear, lograst_unpack_rows(atomic = 2), lograst_activate_backward_adam.  Added later in round 6 without a
  * version change (new entry points only): lograst_pack_rows_hinted, lograst_add_visible, lograst_add_visible_n.
- * 2: lograst_view gained cov3d_precomp / dl_dcov3d; 3: the backward accumulates into 64-byte rows (bwd_rows); lograst_view gained walk_form.  Added since without a version change (new entry points only): lograst_sparse_segment_floats / lograst_pack_rows / lograst_unpack_rows / lograst_ordered_lengths / lograst_finish_lists */
+ * 2: lograst_view gained cov3d_precomp / dl_dcov3d; 3: the backward accumulates into 64-byte rows (bwd_rows); lograst_view gained walk_form.  Added since without a version change (new entry points only): lograst_sparse_segment_floats / lograst_pack_rows / lograst_unpack_rows / lograst_ordered_lengths / lograst_finish_lists.
+ * lograst_recomposite / lograst_record_bytes and the profiling slot "recolor" (LOGRAST_NUM_KERNELS 22 -> 23, appended) are
+ * additions within version 4: no existing entry point, layout or default changed. */
 #define LOGRAST_TILE 16        /* pixels per tile side (tile rects are part of the integer contract) */
 #define LOGRAST_REC_FLOATS 16  /* floats per projected-Gaussian record (64 B): see log_amd/csrc/project.hip */
 /* The reverse walk's accumulators: ONE 64-byte row per Gaussian -- slots 0-1 dL/d(ndc mean x, y), 2-4 dL/d(conic A, B, C),
@@ -64,6 +66,10 @@ extern "C" {
 #define LOGRAST_STATUS_MAX_INSTANCES 5   /* running maxima over all forwards since the caller cleared the block */
 #define LOGRAST_STATUS_MAX_MAX_LEN 6
 #define LOGRAST_STATUS_FORWARDS 7        /* forwards recorded since then */
+/* A lograst_recomposite records itself as a forward: it repeats the instance count, longest list, rect count and overflow
+ * verdict of the forward whose lists it walks in the LAST_* words, takes part in the running maxima and in FORWARDS, and
+ * never raises the sticky bit of LOGRAST_STATUS_OVERFLOW (it fills nothing, so it cannot overflow anything; a forward
+ * that did overflow raised the bit itself, and a recomposite over its lists renders nothing, like that forward). */
 
 /* error codes */
 #define LOGRAST_OK 0
@@ -129,6 +135,9 @@ size_t lograst_tile_state_bytes(int32_t width, int32_t height, int32_t n);
  * undefined: a view that owns a band of tile rows does not write them (a Gaussian without a rect then costs the 40 bytes
  * its rect is computed from and its radii word). */
 size_t lograst_geom_bytes(int32_t n);
+/* bytes of the N 64-byte records alone -- the only part of `geom` that the compositing kernels and lograst_backward read
+ * (fill records, indices and rank rows are the binning stage's): the size of lograst_recomposite's `records` */
+size_t lograst_record_bytes(int32_t n);
 /* bytes of the (depth,id) key buffer (keys + an equally large scratch half used by the long-list sort) / of the
  * sorted id list, for `capacity` tile instances */
 size_t lograst_keys_bytes(uint32_t capacity);
@@ -205,6 +214,29 @@ int lograst_forward(const lograst_view* view, int32_t n, const float* means3d, c
                     float* image, float* final_t, int32_t* n_contrib, int32_t* point_id_pixel,
                     float* point_weight_pixel, float* point_weight, float* bwd_scratch, int32_t bwd_scratch_floats,
                     uint32_t* status, void* stream);
+
+/* ---- the same Gaussians, other colours: a second compositing pass over a forward's tile lists ---------------------------
+ * LoG's depth pass (render_depth: True, LoG/render/renderer.py:186-201) calls the rasterizer a second time with the same
+ * means3D / opacities / scales / rotations and colors_precomp = [view depth, world z, 1].  Nothing a forward bins, counts,
+ * scans, fills or sorts depends on the colours, so this entry point produces the stage-2 outputs of such a second forward
+ * from the FIRST forward's radii / geom / tile_state / point_list (all four only read -- the compositing kernels store
+ * into tile_state nothing but the open[] bits and header words it already holds --, so that forward's lograst_backward
+ * may still run afterwards): one streaming kernel copies the records into `records` (lograst_record_bytes(n), 16-byte
+ * aligned, not geom itself) with the colour fields replaced from colors[n,3], writes radii_out[n] (= radii: an array of
+ * the second call's own), clears point_weight[n] and bwd_scratch as lograst_forward_render does; then the compositing
+ * launch(es) of a stage 2 run over `records`.  No fill, no sort, no host read-back: capturable like lograst_forward.
+ * capacity / max_tile_len: the values the first forward's stage 2 ran with (they decide, as there, whether long lists
+ * are walked lazily: the second walk parks and resumes exactly where the first did, over tails that the first forward
+ * ordered).  view: the first forward's (same matrices, filter, walk_form, whole image: a band is an error), with a
+ * hit_masks buffer OF ITS OWN when the second call is to be differentiated with masks.  Outputs as lograst_forward_render;
+ * lograst_backward then takes (radii_out, records, tile_state, point_list, final_t, n_contrib, bwd_scratch,
+ * point_weight) of this call.  status: see LOGRAST_STATUS_*.  Results are bit for bit those of a full forward with
+ * `colors`. */
+int lograst_recomposite(const lograst_view* view, int32_t n, const int32_t* radii, const void* geom,
+                        const void* tile_state, const uint32_t* point_list, uint32_t capacity, uint32_t max_tile_len,
+                        const float* colors, void* records, int32_t* radii_out, float* image, float* final_t,
+                        int32_t* n_contrib, int32_t* point_id_pixel, float* point_weight_pixel, float* point_weight,
+                        float* bwd_scratch, int32_t bwd_scratch_floats, uint32_t* status, void* stream);
 
 /* The forward in one call for a caller that has only a GUESS of the capacity (and of max_tile_len): what the drop-in
  * package's default mode runs (log_amd/rasterizer.py).  Stage 1, then stage 2 with the guessed buffers are enqueued back
@@ -539,7 +571,7 @@ int lograst_loss_backward(int32_t batch, int32_t channels, int32_t height, int32
  * When enabled every kernel launch is bracketed by hipEventRecord on its stream.  read() synchronises
  * the recorded events and returns, for kernel slot i < LOGRAST_NUM_KERNELS, accumulated milliseconds
  * and launch counts since the last reset. */
-#define LOGRAST_NUM_KERNELS 22
+#define LOGRAST_NUM_KERNELS 23   /* 22 + "recolor" (lograst_recomposite), appended within version 4 */
 void lograst_profile_enable(int on);
 void lograst_profile_reset(void);
 int lograst_profile_read(double* ms_out, int64_t* count_out);

@@ -16,7 +16,7 @@ def install_compute_radius():
     return shim
 
 
-def install_all(fused_step=False, fused_loss=False):
+def install_all(fused_step=False, fused_loss=False, reuse_geometry=False):
     """Everything a LoG process needs, in one call: the LoG.cuda.compute_radius module, then every
     drop-in method assigned onto LoG's own classes (needs LoG importable): LoG.get_all, TensorTree.traverse,
     Counter.update_by_output, SparseOptimizer.step.
@@ -24,8 +24,13 @@ def install_all(fused_step=False, fused_loss=False):
     computes the raw gradients (log_amd.get_all.set_fused_step: the update then happens at backward time -- the same result
     for LoG's trainer, one backward per step).
     fused_loss (opt-in): SSIM.forward and NaiveRendererAndLoss.calculate_loss go through the fused L1 + SSIM kernels
-    (log_amd.loss.install); without it the loss stays the reference's torch code."""
+    (log_amd.loss.install); without it the loss stays the reference's torch code.
+    reuse_geometry (opt-in): the second rasterizer call of a view (LoG's depth pass, render_depth: True) composites the first
+    call's tile lists again with its own colours instead of binning again (log_amd.rasterizer.set_geometry_reuse: same
+    results; a rasterizer object then keeps one forward's records and lists alive until its next call)."""
     install_compute_radius()
+    from . import rasterizer
+    rasterizer.set_geometry_reuse(bool(reuse_geometry))
     from . import counter, get_all, lod, sparse_optimizer
     get_all.set_fused_step(bool(fused_step))
     installed = [m.install() for m in (get_all, lod, counter, sparse_optimizer)]

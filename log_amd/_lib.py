@@ -11,7 +11,8 @@ FORM_AUTO, FORM_ROWS, FORM_QUADRANT = 0, 1, 2
 GRAD_ROW_FLOATS = 16   # LOGRAST_GRAD_ROW_FLOATS
 REC_FLOATS = 16
 BWD_ROW_FLOATS = 16   # LOGRAST_BWD_ROW_FLOATS: the reverse walk's accumulator row (64 B per Gaussian)
-NUM_KERNELS = 22
+NUM_KERNELS = 22          # the profiling slots version 4 started with (their order and count are pinned by the tests)
+NUM_KERNEL_SLOTS = 23     # LOGRAST_NUM_KERNELS: + "recolor", appended within version 4 -- what lograst_profile_read fills
 
 c_void_p, c_int32, c_uint32, c_float, c_size_t = (ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint32,
                                                   ctypes.c_float, ctypes.c_size_t)
@@ -49,6 +50,7 @@ _SIGNATURES = {
     "lograst_last_error": (ctypes.c_char_p, []),
     "lograst_tile_state_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
     "lograst_geom_bytes": (c_size_t, [c_int32]),
+    "lograst_record_bytes": (c_size_t, [c_int32]),
     "lograst_keys_bytes": (c_size_t, [c_uint32]),
     "lograst_hit_mask_bytes": (c_size_t, [c_uint32, c_int32, c_int32]),
     "lograst_forward_form": (ctypes.c_int, [ctypes.POINTER(LograstView)]),
@@ -66,6 +68,8 @@ _SIGNATURES = {
                                               c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
     "lograst_forward": (ctypes.c_int, [ctypes.POINTER(LograstView), c_int32] + [c_void_p] * 10 + [c_uint32, c_uint32]
                         + [c_void_p] * 7 + [c_int32, c_void_p, c_void_p]),
+    "lograst_recomposite": (ctypes.c_int, [ctypes.POINTER(LograstView), c_int32] + [c_void_p] * 4 + [c_uint32, c_uint32]
+                            + [c_void_p] * 10 + [c_int32, c_void_p, c_void_p]),
     "lograst_forward_speculative": (ctypes.c_int, [ctypes.POINTER(LograstView), c_int32] + [c_void_p] * 10
                                     + [c_uint32, c_uint32] + [c_void_p] * 7 + [c_int32, c_void_p]
                                     + [ctypes.POINTER(c_uint32), ctypes.POINTER(c_uint32), c_void_p]),
@@ -163,7 +167,7 @@ def profile_reset():
 
 def profile_read():
     """-> {kernel_name: (total_ms, launches)} since the last reset (synchronises recorded events)."""
-    ms = (ctypes.c_double * NUM_KERNELS)()
-    cnt = (ctypes.c_int64 * NUM_KERNELS)()
+    ms = (ctypes.c_double * NUM_KERNEL_SLOTS)()
+    cnt = (ctypes.c_int64 * NUM_KERNEL_SLOTS)()
     check(lib().lograst_profile_read(ms, cnt))
-    return {lib().lograst_kernel_name(i).decode(): (ms[i], cnt[i]) for i in range(NUM_KERNELS) if cnt[i]}
+    return {lib().lograst_kernel_name(i).decode(): (ms[i], cnt[i]) for i in range(NUM_KERNEL_SLOTS) if cnt[i]}

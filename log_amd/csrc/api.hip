@@ -168,7 +168,7 @@ static const char* kKernelNames[LOGRAST_NUM_KERNELS] = {
     "compute_radius", "project", "scan_tiles", "fill_keys", "sort_small", "sort_large", "sort_huge",
     "blend_fwd", "blend_bwd", "project_bwd", "knn3", "lod_traverse", "counter_update", "sparse_adam",
     "id_histogram", "gather_activate", "activate_bwd", "count_huge", "rebase_slots", "lazy_tail",
-    "loss_fwd", "loss_bwd"};
+    "loss_fwd", "loss_bwd", "recolor"};
 struct ProfRec { int slot; hipEvent_t a, b; bool own_a; };
 // Consecutive launches inside one entry point share an event: the end of kernel k is the begin of kernel k+1 (N+1
 // events for a chain of N kernels instead of 2N; every recorded event costs ~1.4 us of stream time).
@@ -280,6 +280,7 @@ size_t lograst_geom_bytes(int32_t n) {  // 64-byte records + the 16-byte fill re
   const size_t nn = (size_t)(n > 0 ? n : 0);
   return lr_midrank_off_bytes(nn) + lr_midrank_bytes(nn);
 }
+size_t lograst_record_bytes(int32_t n) { return sizeof(float) * LOGRAST_REC_FLOATS * (size_t)(n > 0 ? n : 0); }   // the records alone: all of geom that the compositing kernels and the reverse walk read
 size_t lograst_keys_bytes(uint32_t capacity) { return 2 * sizeof(uint64_t) * (size_t)capacity; }  // keys + sort scratch
 int lograst_forward_form(const lograst_view* view) {
   LrView v;
@@ -381,45 +382,70 @@ static inline bool max_tile_len_allows_streaming(uint32_t max_tile_len, uint32_t
   return m > LR_LONG_LIST;
 }
 
+// What a stage 2 and a lograst_recomposite decide alike from (view, plan, arguments): who clears what, and whether the lists
+// are walked lazily.
+// point_weight (atomicMax target) and the optional backward scratch (one 64-byte accumulator row per Gaussian) are
+// cleared by a streaming pass over the Gaussians (the fill kernel; lr_recolor_kernel) -- except, in the 5-tuple flavour on
+// large inputs, the scratch: only the rows of Gaussians that contribute to a pixel will ever be read, and the compositing
+// kernel clears exactly those when it meets them (a separate pass over point_weight afterwards cost 70 us per 30 M-Gaussian
+// view, the stores inside the kernel 30)
+// LOGRAST_LAZY_SORT (default 1): lists of more than 4096 keys are ordered over their first window only (7680 positions;
+// the walk of a view ends far in front of that: common.hpp, sorted[]); the compositing kernels mark the tiles that needed
+// more, and the second pair of launches -- idle in every benched view -- finishes exactly those.  0: every list to its
+// end before the first compositing pass (what lograst_finish_lists produces afterwards).
+struct LrCompositePlan {
+  bool touched_only;    // the compositing kernel clears the accumulator rows it meets; nobody clears the others
+  float* zero_n;        // point_weight[n] to clear up front, or nullptr
+  float* zero_block;    // accumulator rows to clear up front, or nullptr
+  int zero_floats;      // ... floats per Gaussian (0 with nullptr)
+  int lazy;
+};
+static LrCompositePlan lr_composite_plan(const LrView& v, const LrPlan& p, const LrForwardArgs& a) {
+  LrCompositePlan c;
+  c.touched_only = v.extras && a.bwd_scratch_floats > 0 && p.big_input;
+  c.zero_block = (a.bwd_scratch_floats > 0 && !c.touched_only) ? a.bwd_scratch : nullptr;
+  c.zero_floats = c.zero_block ? a.bwd_scratch_floats : 0;
+  c.zero_n = v.extras ? a.point_weight : nullptr;
+  c.lazy = (lr_knob(LRKNOB_LAZY_SORT) && max_tile_len_allows_streaming(a.max_tile_len, a.capacity)) ? 1 : 0;
+  return c;
+}
+// The compositing pass over the records `geom` and, after a lazy one, the pass of the waves that parked.  sort_rest: order
+// the tails of the lists they parked in first (a forward: the keys are still there).  Without it (lograst_recomposite) the
+// tails must already be in order: the walk of an earlier forward over the same geometry and opacities parked the same waves
+// at the same places, and its second pair of launches ordered exactly those lists to their end (sort.hip: sorted[] stays at
+// the first window, open[] keeps the bits).
+static void lr_composite(const LrView& v, const LrPlan& p, const LrForwardArgs& a, const void* geom, const LrCompositePlan& c,
+                         uint32_t* st, bool sort_rest, hipStream_t s) {
+  float* const zrows = c.touched_only ? a.bwd_scratch : nullptr;
+  lr_launch_blend_fwd(v, geom, st, p.tiles, a.point_list, a.capacity, a.image, a.final_t, a.n_contrib, a.point_id_pixel,
+                      a.point_weight_pixel, a.point_weight, zrows, p.big_input ? 1 : 0, c.lazy, v.masks, s);
+  if (c.lazy) {
+    lr_prof_begin(LRK_LAZY_TAIL, s);
+    if (sort_rest) lr_launch_sort_rest(st, p.tiles, a.keys, a.point_list, a.capacity, a.max_tile_len, 2, s);
+    lr_launch_blend_fwd(v, geom, st, p.tiles, a.point_list, a.capacity, a.image, a.final_t, a.n_contrib, a.point_id_pixel,
+                        a.point_weight_pixel, a.point_weight, zrows, p.big_input ? 1 : 0, 2, v.masks, s);
+    lr_prof_end(LRK_LAZY_TAIL, s);
+  }
+}
+
 // stage 2 launches: bucket fill (+ zero-fills), per-tile sort, compositing
 static int lr_stage2(const LrView& v, const LrPlan& p, const LrForwardArgs& a, uint32_t* st, hipStream_t s) {
   const int32_t n = a.n;
   if (n == 0 && a.status)   // no fill kernel runs: this forward's entries of the status block
     LR_HIP(hipMemsetAsync(a.status + LOGRAST_STATUS_LAST_INSTANCES, 0, 4 * sizeof(uint32_t), s));
-  // point_weight (atomicMax target) and the optional backward scratch (one 64-byte accumulator row per Gaussian) are
-  // cleared by the fill kernel -- except, in the 5-tuple flavour on large inputs, the scratch: only the rows of
-  // Gaussians that contribute to a pixel will ever be read, and the compositing kernel clears exactly those when it
-  // meets them (a separate pass over point_weight afterwards cost 70 us per 30 M-Gaussian view, the stores inside the
-  // kernel 30)
-  const bool touched_only = v.extras && a.bwd_scratch_floats > 0 && p.big_input;
-  float* zero_block = a.bwd_scratch_floats > 0 ? a.bwd_scratch : nullptr;
-  int zero_floats = a.bwd_scratch_floats;
-  if (touched_only) { zero_block = nullptr; zero_floats = 0; }
-  float* zero_n = v.extras ? a.point_weight : nullptr;
+  const LrCompositePlan c = lr_composite_plan(v, p, a);
+  float* zero_n = c.zero_n;
+  int zero_floats = c.zero_floats;
   if (lr_knob(LRKNOB_SEPARATE_ZERO) && p.big_input) {   // large inputs: streamed by kernels of their own (see lr_zero_floats_kernel); knob 0: always inside the fill kernel
     lr_launch_zero_floats(zero_n, (size_t)n, s);
-    if (zero_floats > 0) lr_launch_zero_floats(zero_block, (size_t)zero_floats * (size_t)n, s);
+    if (zero_floats > 0) lr_launch_zero_floats(c.zero_block, (size_t)zero_floats * (size_t)n, s);
     zero_n = nullptr; zero_floats = 0;
   }
   lr_launch_fill(n, v.gx, a.geom, st, p.tiles, a.keys, a.capacity, a.max_tile_len, a.status,
-                 zero_n, zero_floats > 0 ? zero_block : nullptr, zero_floats,
+                 zero_n, zero_floats > 0 ? c.zero_block : nullptr, zero_floats,
                  (p.big_input && p.staged_k == 0) ? 1 : 0, a.speculative, p.band ? 1 : 0, p.staged_k, s);
-  // LOGRAST_LAZY_SORT (default 1): lists of more than 4096 keys are ordered over their first window only (7680 positions;
-  // the walk of a view ends far in front of that: common.hpp, sorted[]); the compositing kernels mark the tiles that needed
-  // more, and the second pair of launches -- idle in every benched view -- finishes exactly those.  0: every list to its
-  // end before the first compositing pass (what lograst_finish_lists produces afterwards).
-  const int lazy = (lr_knob(LRKNOB_LAZY_SORT) && max_tile_len_allows_streaming(a.max_tile_len, a.capacity)) ? 1 : 0;
-  lr_launch_sort(st, p.tiles, a.keys, a.point_list, a.capacity, a.max_tile_len, lazy, s);
-  float* const zrows = touched_only ? a.bwd_scratch : nullptr;
-  lr_launch_blend_fwd(v, a.geom, st, p.tiles, a.point_list, a.capacity, a.image, a.final_t, a.n_contrib, a.point_id_pixel,
-                      a.point_weight_pixel, a.point_weight, zrows, p.big_input ? 1 : 0, lazy, v.masks, s);
-  if (lazy) {
-    lr_prof_begin(LRK_LAZY_TAIL, s);
-    lr_launch_sort_rest(st, p.tiles, a.keys, a.point_list, a.capacity, a.max_tile_len, 2, s);
-    lr_launch_blend_fwd(v, a.geom, st, p.tiles, a.point_list, a.capacity, a.image, a.final_t, a.n_contrib, a.point_id_pixel,
-                        a.point_weight_pixel, a.point_weight, zrows, p.big_input ? 1 : 0, 2, v.masks, s);
-    lr_prof_end(LRK_LAZY_TAIL, s);
-  }
+  lr_launch_sort(st, p.tiles, a.keys, a.point_list, a.capacity, a.max_tile_len, c.lazy, s);
+  lr_composite(v, p, a, a.geom, c, st, true, s);
   return LOGRAST_OK;
 }
 
@@ -446,10 +472,11 @@ static int lr_check_cov_args(const LrView& v, const float* scales, const float* 
   return LOGRAST_OK;
 }
 
-static int lr_check_stage2_args(const LrView& v, const LrForwardArgs& a) {
+// sorts: the call fills and sorts (stage 2: needs `keys`); false: it walks lists that are there (lograst_recomposite)
+static int lr_check_stage2_args(const LrView& v, const LrForwardArgs& a, bool sorts = true) {
   if (a.n < 0) return lr_fail(LOGRAST_ERR_ARG, "negative Gaussian count");
   if (!a.tile_state || !a.image || !a.final_t || !a.n_contrib) return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
-  if (a.capacity > 0 && (!a.keys || !a.point_list)) return lr_fail(LOGRAST_ERR_ARG, "keys/point_list NULL with capacity > 0");
+  if (a.capacity > 0 && ((sorts && !a.keys) || !a.point_list)) return lr_fail(LOGRAST_ERR_ARG, "keys/point_list NULL with capacity > 0");
   if (v.extras && (!a.point_id_pixel || !a.point_weight_pixel || (a.n > 0 && !a.point_weight)))
     return lr_fail(LOGRAST_ERR_ARG, "extras requested but output pointers are NULL");
   if ((a.bwd_scratch_floats != 0 && a.bwd_scratch_floats != LOGRAST_BWD_ROW_FLOATS) ||
@@ -529,6 +556,38 @@ int lograst_forward(const lograst_view* view, int32_t n, const float* means3d, c
                            keys, point_list, capacity, max_tile_len, image, final_t, n_contrib, point_id_pixel,
                            point_weight_pixel, point_weight, bwd_scratch, bwd_scratch_floats, status, stream};
   return lr_forward(a, true, true);
+}
+
+// The stage-2 outputs of a forward once more, for other colours, from the lists of a forward that ran: no fill, no sort.
+int lograst_recomposite(const lograst_view* view, int32_t n, const int32_t* radii, const void* geom, const void* tile_state,
+                        const uint32_t* point_list, uint32_t capacity, uint32_t max_tile_len, const float* colors,
+                        void* records, int32_t* radii_out, float* image, float* final_t, int32_t* n_contrib,
+                        int32_t* point_id_pixel, float* point_weight_pixel, float* point_weight, float* bwd_scratch,
+                        int32_t bwd_scratch_floats, uint32_t* status, void* stream) {
+  const LrForwardArgs a = {view, n, nullptr, nullptr, nullptr, nullptr, colors, const_cast<int32_t*>(radii), records,
+                           const_cast<void*>(tile_state), nullptr, const_cast<uint32_t*>(point_list), capacity, max_tile_len,
+                           image, final_t, n_contrib, point_id_pixel, point_weight_pixel, point_weight, bwd_scratch,
+                           bwd_scratch_floats, status, stream};
+  g_prof_call++;
+  LrView v;
+  int rc = lr_make_view(view, &v);
+  if (rc) return rc;
+  if ((rc = lr_check_stage2_args(v, a, false))) return rc;
+  if (n > 0 && (!radii || !geom || !colors || !records || !radii_out)) return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
+  if ((reinterpret_cast<uintptr_t>(geom) | reinterpret_cast<uintptr_t>(records) | reinterpret_cast<uintptr_t>(tile_state)) & 15u)
+    return lr_fail(LOGRAST_ERR_ARG, "geom / records / tile_state must be 16-byte aligned");
+  if (n > 0 && records == geom) return lr_fail(LOGRAST_ERR_ARG, "records must not be the first forward's geom (its backward still reads it)");
+  if (v.ty0 != 0 || v.ty1 != v.gy) return lr_fail(LOGRAST_ERR_ARG, "lograst_recomposite renders whole images only (tile_row_begin / tile_row_end)");
+  const LrPlan p = lr_plan(v, n);
+  hipStream_t s = (hipStream_t)stream;
+  uint32_t* st = reinterpret_cast<uint32_t*>(a.tile_state);   // (written by the compositing kernels only with what it holds: open[], LR_HDR_OPEN)
+  if (n == 0 && status)   // no recolour kernel runs: this pass's entries of the status block
+    LR_HIP(hipMemsetAsync(status + LOGRAST_STATUS_LAST_INSTANCES, 0, 4 * sizeof(uint32_t), s));
+  const LrCompositePlan c = lr_composite_plan(v, p, a);
+  lr_launch_recolor(n, radii, geom, colors, records, radii_out, c.zero_n, c.zero_block, st, status, s);
+  lr_composite(v, p, a, records, c, st, false, s);
+  LR_HIP(hipGetLastError());
+  return LOGRAST_OK;
 }
 
 // Side stream + event + pinned words for the read-back of lograst_forward_speculative, one set per host thread and

@@ -557,7 +557,8 @@ enum LrKernelSlot {
   LRK_RADIUS = 0, LRK_PROJECT, LRK_SCAN, LRK_FILL, LRK_SORT_SMALL, LRK_SORT_LARGE, LRK_SORT_HUGE,
   LRK_BLEND_FWD, LRK_BLEND_BWD, LRK_PROJECT_BWD, LRK_MISC, LRK_LOD, LRK_COUNTER, LRK_ADAM, LRK_HIST, LRK_GATHER, LRK_GATHER_BWD, LRK_RESERVED,
   LRK_REBASE, LRK_LAZY_TAIL,  // LRK_LAZY_TAIL: the second sort + compositing pair of lazily ordered lists (normally idle)
-  LRK_LOSS_FWD, LRK_LOSS_BWD
+  LRK_LOSS_FWD, LRK_LOSS_BWD,
+  LRK_RECOLOR   // lr_recolor_kernel (lograst_recomposite)
 };
 // ---- profiling and environment (api.hip) -------------------------------------------------------------------------
 // Every kernel computes its full result: there are no timing ablations or compile-time algorithm switches.  Compiler

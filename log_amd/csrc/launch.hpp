@@ -23,6 +23,10 @@ void lr_launch_fill(int N, int gx, const void* geom, uint32_t* state, uint32_t t
 void lr_launch_tile_rows(const LrView& v, int N, const float* means, const float* scales, const float* rots,
                          uint32_t* rows, hipStream_t s);
 void lr_launch_stream_copy(const void* src, void* dst, size_t bytes, int blocks, hipStream_t s);
+// lograst_recomposite: records = geom's N 64-byte records with the colour fields taken from colors[N, 3] (radii > 0 only),
+// radii_out = radii, zero_n[N] (or NULL) and zero_rows[N][16] (or NULL) cleared, the pass recorded in status (or NULL)
+void lr_launch_recolor(int N, const int* radii, const void* geom, const float* colors, void* records, int* radii_out,
+                       float* zero_n, float* zero_rows, const uint32_t* state, uint32_t* status, hipStream_t s);
 
 // sort.hip
 void lr_launch_sort(uint32_t* state, uint32_t tiles, uint64_t* keys, uint32_t* plist, uint32_t capacity,

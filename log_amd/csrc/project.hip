@@ -1731,3 +1731,56 @@ void lr_launch_tile_rows(const LrView& v, int N, const float* means, const float
   if (N <= 0) return;
   hipLaunchKernelGGL(lr_tile_rows_kernel, dim3((N + 255) / 256), dim3(256), 0, s, v, N, means, scales, rots, rows);
 }
+
+// ---- a second pass over a view's tile lists: the records once more, with other colours (lograst_recomposite) ----------
+// Everything a forward bins and orders depends on geometry and opacity alone; a caller that composites the same Gaussians
+// again with other colours (LoG's depth pass: LoG/render/renderer.py:186-201) needs new records, not new lists.  Streaming
+// pass, FOUR lanes per Gaussian: lane (t & 3) moves quad (t & 3) of record t >> 2, so a record is read and written as one
+// full 64-byte line by four neighbouring lanes and a wave moves sixteen consecutive lines.  The colour fields (q1.z, q1.w,
+// q2.x: the layout at the top of this file) come from colors[N, 3]; everything else is the first forward's, bit for bit.
+// Records of Gaussians with radii == 0 stay undefined, as the projection leaves them.  The same lanes write the second
+// call's own radii, clear its point_weight (zero_n) and -- unless the compositing kernel clears the rows it meets (api.hip:
+// touched_only) -- its accumulator rows (zero_rows: one line per Gaussian, a quad per lane), which is what the fill kernel
+// does for a full forward.  `src` and `state` are only read.  One thread records the pass in the caller's status block as
+// a forward with the first forward's counts (include/lograst.h: LOGRAST_STATUS_*); it never raises the sticky overflow bit.
+__global__ void __launch_bounds__(256)
+lr_recolor_kernel(int N, const int* __restrict__ radii, const float4* __restrict__ src, const float* __restrict__ colors,
+                  float4* __restrict__ dst, int* __restrict__ radii_out, float* __restrict__ zero_n,
+                  float4* __restrict__ zero_rows, const uint32_t* __restrict__ state, uint32_t* __restrict__ status) {
+  if (status && blockIdx.x == 0 && threadIdx.x == 0) {
+    const uint32_t total = state[LR_HDR_NUM], maxlen = state[LR_HDR_MAXLEN];
+    status[LOGRAST_STATUS_LAST_INSTANCES] = total;
+    status[LOGRAST_STATUS_LAST_OVERFLOW] = state[LR_HDR_OVERFLOW];   // (the first forward's verdict: nothing renders after it either)
+    status[LOGRAST_STATUS_LAST_MAX_LEN] = maxlen;
+    status[LOGRAST_STATUS_LAST_RECT] = state[LR_HDR_RECT];
+    atomicMax(&status[LOGRAST_STATUS_MAX_INSTANCES], total);
+    atomicMax(&status[LOGRAST_STATUS_MAX_MAX_LEN], maxlen);
+    atomicAdd(&status[LOGRAST_STATUS_FORWARDS], 1u);
+  }
+  const size_t t = (size_t)blockIdx.x * 256u + threadIdx.x;   // quad index: 4 * N of them
+  const size_t i = t >> 2;
+  if (i >= (size_t)N) return;
+  const int sub = (int)(t & 3u);
+  const int rad = radii[i];
+  if (rad > 0) {
+    float4 q = src[t];
+    if (sub == 1) { q.z = colors[3 * i]; q.w = colors[3 * i + 1]; }
+    if (sub == 2) q.x = colors[3 * i + 2];
+    dst[t] = q;
+  }
+  if (sub == 0) {
+    radii_out[i] = rad;
+    if (zero_n) zero_n[i] = 0.f;
+  }
+  if (zero_rows) __builtin_nontemporal_store(lr_u4v{0u, 0u, 0u, 0u}, reinterpret_cast<lr_u4v*>(zero_rows) + t);
+}
+void lr_launch_recolor(int N, const int* radii, const void* geom, const float* colors, void* records, int* radii_out,
+                       float* zero_n, float* zero_rows, const uint32_t* state, uint32_t* status, hipStream_t s) {
+  if (N <= 0) return;
+  const size_t quads = 4u * (size_t)N;
+  lr_prof_begin(LRK_RECOLOR, s);
+  hipLaunchKernelGGL(lr_recolor_kernel, dim3((uint32_t)((quads + 255u) / 256u)), dim3(256), 0, s, N, radii,
+                     reinterpret_cast<const float4*>(geom), colors, reinterpret_cast<float4*>(records), radii_out, zero_n,
+                     reinterpret_cast<float4*>(zero_rows), state, status);
+  lr_prof_end(LRK_RECOLOR, s);
+}

@@ -105,6 +105,127 @@ def set_hit_masks(enabled):
     return prev
 
 
+# ---- geometry reuse: the second call of a view composites again, it does not bin again (opt-in) -------------------------
+# LoG's documented training configuration (render_depth: True) calls the SAME rasterizer object twice per view with the same
+# means3D / opacities / scales / rotations; only colors_precomp differs (LoG/render/renderer.py:186-201).  Everything a
+# forward projects, culls, counts, scans, fills and sorts is a function of geometry and opacity alone, so with reuse on the
+# second call recolours the first call's records and walks its tile lists again (lograst_recomposite) -- same bits out.
+_geometry_reuse = False
+_reuse_stats = {"reused": 0, "fallback": {}}
+_reuse_lock = threading.Lock()
+
+
+def set_geometry_reuse(enabled):
+    """Opt-in (default False).  True: a ``GaussianRasterizer`` remembers its last full forward, and the next call through
+    the SAME object with the same geometry tensors (means3D, scales, rotations, opacities: same storage, shape, stride and
+    version), raster_settings object, flavour, use_filter, device, stream, pinned walk form, launch plan and capacity
+    policy, on the whole image, only recolours that forward's records and composites its tile lists again -- no
+    projection, binning, scan, fill or sort.  colors_precomp / shs may differ; outputs, saved state and gradients are those
+    of a full forward, bit for bit (gradient sums up to atomic order).  Any other call runs the full forward, silently;
+    ``geometry_reuse_stats()`` says which and why.
+    The geometry check rests on tensor version counters: a write that bypasses them between the two calls
+    (``scales.data.mul_(...)``: ``.data`` has a counter of its own) is not seen, as autograd's own saved-tensor check
+    does not see it.  Inside a graph capture only a forward of the same capture is reused.
+    Memory: while this is on, every rasterizer object keeps one forward's records, tile state and point list (and its
+    detached fp32 inputs) alive until its next full forward or its own death -- LoG builds one rasterizer per view
+    (LoG/render/renderer.py:222), so that is one view's worth.  Returns the previous setting."""
+    global _geometry_reuse
+    prev, _geometry_reuse = _geometry_reuse, bool(enabled)
+    return prev
+
+
+def geometry_reuse_stats(reset=False):
+    """dict(reused=<calls that recomposited>, fallback={reason: <calls that ran the full forward>}) of the rasterizer calls
+    made while ``set_geometry_reuse(True)`` was in force; a fallback is keyed by the FIRST condition that failed, in the
+    order of ``_ReuseSlot.match`` ("first": nothing remembered for that object yet)."""
+    with _reuse_lock:
+        out = dict(reused=_reuse_stats["reused"], fallback=dict(_reuse_stats["fallback"]))
+        if reset:
+            _reuse_stats["reused"] = 0
+            _reuse_stats["fallback"].clear()
+    return out
+
+
+def _count_reuse(reason):
+    with _reuse_lock:
+        if reason is None:
+            _reuse_stats["reused"] += 1
+        else:
+            _reuse_stats["fallback"][reason] = _reuse_stats["fallback"].get(reason, 0) + 1
+
+
+def _sig(t):
+    return (t.data_ptr(), tuple(t.shape), t.stride(), t._version)
+
+
+def _capturing(device):
+    return bool(device.type == "cuda" and torch.cuda.is_current_stream_capturing())
+
+
+class _ReuseSlot:
+    """What one GaussianRasterizer remembers of its last full forward while geometry reuse is on: the forward's `saved`
+    dict (records, tile state, point list: alive as long as this is) and the detached fp32 inputs it ran on -- held, so that
+    their addresses cannot be recycled for other tensors, and compared through data_ptr / shape / stride / _version (a
+    detached view shares the caller's version counter: an in-place change of the caller's tensor shows)."""
+
+    def __init__(self):
+        self.entry = None
+
+    def forget(self):
+        self.entry = None
+
+    def remember(self, backend, rs, flavour, use_filter, device, geometry, saved, radii):
+        self.entry = dict(rs=rs, flavour=flavour, use_filter=use_filter, device=device,
+                          stream=torch.cuda.current_stream(device).cuda_stream if device.type == "cuda" else 0,
+                          view=tuple(t._version for t in (rs.bg, rs.viewmatrix, rs.projmatrix)),
+                          geometry=geometry, sigs=tuple(_sig(t) for t in geometry), saved=saved, radii=radii,
+                          radii_version=radii._version, band=_tile_rows.get(), pin=_pinned_form(),
+                          plan=backend.plan_key(saved) if hasattr(backend, "plan_key") else None, capturing=_capturing(device),
+                          hint=(_capacity_hint, _max_len_hint))
+
+    def match(self, backend, rs, flavour, use_filter, device, geometry, cov3D):
+        """-> (saved dict of the remembered forward, None) when the next call may composite it again, else (None, reason):
+        the name of the first condition that does not hold."""
+        e = self.entry
+        if not hasattr(backend, "recomposite"):
+            return None, "no_recomposite"
+        if cov3D is not None:
+            return None, "cov3D"
+        if geometry[0].shape[0] == 0:
+            return None, "empty"
+        if e is None:
+            return None, "first"
+        if e["flavour"] != flavour:
+            return None, "flavour"
+        if e["use_filter"] != use_filter:
+            return None, "use_filter"
+        if e["rs"] is not rs:
+            return None, "settings"
+        if e["view"] != tuple(t._version for t in (rs.bg, rs.viewmatrix, rs.projmatrix)):
+            return None, "view_modified"
+        if e["device"] != device:
+            return None, "device"
+        if e["stream"] != (torch.cuda.current_stream(device).cuda_stream if device.type == "cuda" else 0):
+            return None, "stream"
+        if e["capturing"] != _capturing(device):   # (a graph must not read buffers of a forward made outside its capture:
+            return None, "graph_capture"           # they are freed when this object forgets that forward)
+        if e["band"] != (0, 0) or _tile_rows.get() != (0, 0):
+            return None, "band"
+        if e["pin"] != _pinned_form():
+            return None, "walk_form"
+        if e["plan"] != (backend.plan_key(e["saved"]) if hasattr(backend, "plan_key") else None):
+            return None, "plan"
+        if e["hint"] != (_capacity_hint, _max_len_hint):
+            return None, "capacity_hint"
+        if e["sigs"] != tuple(_sig(t) for t in geometry):
+            return None, "geometry"
+        if e["radii"]._version != e["radii_version"]:
+            return None, "radii_modified"
+        if isinstance(e["saved"], dict) and e["saved"].get("instances", 1) == 0:
+            return None, "no_instances"
+        return e["saved"], None
+
+
 def set_speculative(enabled):
     """Default-mode forward: True (default) = speculative stage 2 from the running capacity estimate, False = stage 1,
     read-back, exact allocation, stage 2.  Returns the previous setting."""
@@ -395,6 +516,27 @@ class HipBackend:
         return n >= val.value
 
     @staticmethod
+    def _want_masks(L, scratch_floats):
+        """Does a forward that prepares `scratch_floats` accumulator floats per Gaussian get a hit-mask buffer?"""
+        want = bool(_hit_masks and scratch_floats)
+        if want:   # (knob LOGRAST_HIT_MASKS = 0: the library would ignore the buffer, and a backward under a different
+            kv = ctypes.c_int32(1)   # knob value must not find an unwritten one)
+            L.lograst_get_knob(b"LOGRAST_HIT_MASKS", ctypes.byref(kv))
+            want = kv.value != 0
+        return want
+
+    def plan_key(self, saved):
+        """The knob-dependent launch decisions that a recomposite must share with the forward whose lists it walks: whether
+        long lists are ordered lazily, the large-input threshold, and the compositing form for that forward's walk_form."""
+        L = _lib.lib()
+        vals = []
+        for name in (b"LOGRAST_LAZY_SORT", b"LOGRAST_HELPER_MIN_N", b"LOGRAST_FWD_ROWS"):
+            v = ctypes.c_int32(0)
+            L.lograst_get_knob(name, ctypes.byref(v))
+            vals.append(v.value)
+        return tuple(vals)
+
+    @staticmethod
     def _carve(device, parts):
         """One allocation for several buffers: parts = [(name, dtype, shape)], every buffer 256-byte aligned inside it
         (one caching-allocator call instead of one per buffer: the host side of a forward is mostly such calls)."""
@@ -436,11 +578,7 @@ class HipBackend:
         if scratch_floats:
             kept.append(("bwd_scratch", f32, (N * scratch_floats,)))
         instances = None
-        want_masks = bool(_hit_masks and scratch_floats)
-        if want_masks:   # (knob LOGRAST_HIT_MASKS = 0: the library would ignore the buffer, and a backward under a different
-            kv = ctypes.c_int32(1)   # knob value must not find an unwritten one)
-            L.lograst_get_knob(b"LOGRAST_HIT_MASKS", ctypes.byref(kv))
-            want_masks = kv.value != 0
+        want_masks = self._want_masks(L, scratch_floats)
 
         def masks_for(cap):
             """The hit-mask buffer of a training forward with room for `cap` tile instances (uninitialised)."""
@@ -510,10 +648,58 @@ class HipBackend:
                      final_T=k["final_T"], n_contrib=k["n_contrib"], bwd_scratch=k.get("bwd_scratch"),
                      point_weight=o.get("pw"), tile_rows=(view.tile_row_begin, view.tile_row_end), instances=int(instances),
                      walk_form_pin=pin, hit_masks=masks if want_masks else None,
-                     hit_mask_form=fwd_form if want_masks else 0)
+                     hit_mask_form=fwd_form if want_masks else 0,
+                     # what this stage 2 ran with (a recomposite walks the lists under the same decisions)
+                     capacity=int(capacity), max_len=int(max_len), fwd_walk_form=int(view.walk_form))
         if kept_keys is not None:
             saved["keys"], saved["capacity"] = kept_keys
         return o["image"], o["radii"], o.get("pid"), o.get("pwp"), o.get("pw"), saved
+
+    def recomposite(self, rs, flavour, use_filter, saved, colors, scratch_floats=0):
+        """The forward of the same Gaussians with other colours, from the `saved` dict of a forward that ran (full image,
+        scales / rotations form): lograst_recomposite -- one streaming kernel writes new records, then the compositing
+        launches; no projection, fill or sort.  Returns what forward() returns.  The new `saved` shares state / plist /
+        instances / walk_form_pin / tile_rows with the first call's (only read); geom (the new records), radii, final_T,
+        n_contrib, bwd_scratch, point_weight, hit_masks and hit_mask_form are its own, so the unchanged backward() works on
+        either dict in either order."""
+        device = colors.device
+        L = self.require(device)
+        N = colors.shape[0]
+        H, W = int(rs.image_height), int(rs.image_width)
+        view, keep = self.make_view(rs, flavour, use_filter, device)
+        view.walk_form = int(saved["fwd_walk_form"])     # the form the first walk ran in (the history may have moved since)
+        fwd_form = int(L.lograst_forward_form(ctypes.byref(view)))
+        self._note_form("fwd", fwd_form == 1)
+        i32, f32, u8 = torch.int32, torch.float32, torch.uint8
+        o = {"image": torch.empty(3, H, W, dtype=f32, device=device), "radii": torch.empty(N, dtype=i32, device=device)}
+        if flavour.extras:
+            o.update(pid=torch.empty(H, W, dtype=i32, device=device), pwp=torch.empty(H, W, dtype=f32, device=device),
+                     pw=torch.empty(N, dtype=f32, device=device))
+        kept = [("geom", u8, (L.lograst_record_bytes(N),)), ("final_T", f32, (H, W)), ("n_contrib", i32, (H, W))]
+        scratch_floats = _lib.BWD_ROW_FLOATS if scratch_floats and N else 0
+        if scratch_floats:
+            kept.append(("bwd_scratch", f32, (N * scratch_floats,)))
+        capacity, max_len = int(saved["capacity"]), int(saved["max_len"])
+        masks = None
+        want_masks = self._want_masks(L, scratch_floats)
+        if want_masks:   # a buffer of this call's own: the first call's backward has not run yet
+            masks = (torch.zeros if _zero_hit_masks else torch.empty)(L.lograst_hit_mask_bytes(capacity, W, H) // 8,
+                                                                      dtype=torch.int64, device=device)
+            view.hit_masks, view.hit_mask_words = masks.data_ptr(), masks.numel()
+        with torch.cuda.device(device):
+            k = self._carve(device, kept)
+            _lib.check(L.lograst_recomposite(
+                ctypes.byref(view), N, _ptr(saved["radii"]), _ptr(saved["geom"]), _ptr(saved["state"]), _ptr(saved["plist"]),
+                capacity, max_len, _ptr(colors), _ptr(k["geom"]), _ptr(o["radii"]), _ptr(o["image"]), _ptr(k["final_T"]),
+                _ptr(k["n_contrib"]), _ptr(o.get("pid")), _ptr(o.get("pwp")), _ptr(o.get("pw")), _ptr(k.get("bwd_scratch")),
+                scratch_floats, _ptr(_status_block(device)), _stream_ptr(device)))
+        del keep
+        out = dict(radii=o["radii"], geom=k["geom"].view(f32), state=saved["state"], plist=saved["plist"],
+                   final_T=k["final_T"], n_contrib=k["n_contrib"], bwd_scratch=k.get("bwd_scratch"),
+                   point_weight=o.get("pw"), tile_rows=saved["tile_rows"], instances=saved["instances"],
+                   walk_form_pin=saved["walk_form_pin"], hit_masks=masks, hit_mask_form=fwd_form if want_masks else 0,
+                   capacity=capacity, max_len=max_len, fwd_walk_form=int(view.walk_form))
+        return o["image"], o["radii"], o.get("pid"), o.get("pwp"), o.get("pw"), out
 
     def backward(self, rs, flavour, use_filter, means3D, scales, rotations, saved, grad_image, sink=None, cov3D=None):
         """sink: optional dict of running-sum tensors (means3D, scales, rotations, opacities, colors) that this call
@@ -944,7 +1130,9 @@ def _leaf_grad_sink(leaves, device):
 
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, means3D, means2D, colors, shs, opacities, scales, rotations, rs, flavour, use_filter, cov3D=None):
+    def forward(ctx, means3D, means2D, colors, shs, opacities, scales, rotations, rs, flavour, use_filter, cov3D=None,
+                reuse=None):
+        """reuse: the calling rasterizer object's _ReuseSlot while geometry reuse is on (set_geometry_reuse), else None."""
         m = means3D.detach().to(torch.float32).contiguous()
         cov = None
         if cov3D is not None:   # the packages' cov3D_precomp input (not LoG's path): scales / rotations are absent
@@ -974,8 +1162,21 @@ class _RasterizeGaussians(torch.autograd.Function):
         wants_grad = any(ctx.needs_input_grad[:7])   # all False under torch.no_grad()
         wants_grad = wants_grad or (cov is not None and ctx.needs_input_grad[10])
         scratch_floats = _lib.BWD_ROW_FLOATS if wants_grad else 0
-        image, radii, pid, pwp, pw, saved = _backend.forward(rs, flavour, use_filter, m, *((s, r) if cov is None else (None, None)),
-                                                             o, c, scratch_floats=scratch_floats, cov3D=cov)
+        first = None
+        if reuse is not None:   # the same Gaussians as this object's last forward: composite its lists again
+            first, why = reuse.match(_backend, rs, flavour, use_filter, m.device, (m, s, r, o), cov)
+            _count_reuse(why)
+        if first is not None:
+            image, radii, pid, pwp, pw, saved = _backend.recomposite(rs, flavour, use_filter, first, c,
+                                                                     scratch_floats=scratch_floats)
+        else:
+            image, radii, pid, pwp, pw, saved = _backend.forward(rs, flavour, use_filter, m, *((s, r) if cov is None else (None, None)),
+                                                                 o, c, scratch_floats=scratch_floats, cov3D=cov)
+            if reuse is not None:
+                if cov is None and n > 0:
+                    reuse.remember(_backend, rs, flavour, use_filter, m.device, (m, s, r, o), saved, radii)
+                else:
+                    reuse.forget()
         ctx.cov = cov
         ctx.rs, ctx.flavour, ctx.use_filter = rs, flavour, use_filter
         ctx.set_materialize_grads(False)   # no zero-filled gradients for radii / the fork maps (4 fill kernels per view)
@@ -997,7 +1198,7 @@ class _RasterizeGaussians(torch.autograd.Function):
     def backward(ctx, grad_image, *unused):
         m, s, r = ctx.saved_tensors
         if grad_image is None:   # only non-differentiable outputs were used downstream
-            return (None,) * 11
+            return (None,) * 12
         # which view's backward is running: nodes further down the same graph (log_amd.get_all's fused step) read the
         # visibility of THIS render from here (the rasterizer's node runs before the nodes that produced its inputs)
         _backward_view.radii = ctx.saved.get("radii") if isinstance(ctx.saved, dict) else None
@@ -1014,7 +1215,7 @@ class _RasterizeGaussians(torch.autograd.Function):
             if sh is not None:
                 g_sh = _backend.sh_backward(m, ctx.rs.campos, sh, int(ctx.rs.sh_degree), clamped, g_c.contiguous(), g_m3)
                 g_c = None
-            return g_m3, g_m2.reshape(m2_shape), g_c, g_sh, g_o.reshape(o_shape), None, None, None, None, None, g_cov
+            return g_m3, g_m2.reshape(m2_shape), g_c, g_sh, g_o.reshape(o_shape), None, None, None, None, None, g_cov, None
         sink = _grad_sink
         if sink is None and ctx.leaves is not None and (
                 _inplace_leaf_grads or all(getattr(t, _INPLACE_TAG, False) for t in ctx.leaves if t is not None)):
@@ -1027,7 +1228,7 @@ class _RasterizeGaussians(torch.autograd.Function):
                 raise ValueError("gradient sink does not match the rasterizer inputs")
             _, g_m2, _, _, _, _ = _backend.backward(ctx.rs, ctx.flavour, ctx.use_filter, m, s, r, ctx.saved, grad_image,
                                                     sink=sink)
-            return None, g_m2.reshape(m2_shape), None, None, None, None, None, None, None, None, None
+            return None, g_m2.reshape(m2_shape), None, None, None, None, None, None, None, None, None, None
         if sink is not None and (sh is None or "shs" in sink):
             n = m.shape[0]
             if not (sink["means3D"].shape == (n, 3) and sink["scales"].shape == (n, 3) and
@@ -1047,14 +1248,14 @@ class _RasterizeGaussians(torch.autograd.Function):
                                                         grad_image, sink=dict(sink, colors=g_c))
                 _backend.sh_backward(m, ctx.rs.campos, sh, int(ctx.rs.sh_degree), clamped, g_c, sink["means3D"],
                                      into=sink["shs"])
-            return None, g_m2.reshape(m2_shape), None, None, None, None, None, None, None, None, None
+            return None, g_m2.reshape(m2_shape), None, None, None, None, None, None, None, None, None, None
         g_m3, g_m2, g_c, g_o, g_s, g_r = _backend.backward(ctx.rs, ctx.flavour, ctx.use_filter, m, s, r, ctx.saved,
                                                            grad_image)
         g_sh = None
         if sh is not None:
             g_sh = _backend.sh_backward(m, ctx.rs.campos, sh, int(ctx.rs.sh_degree), clamped, g_c.contiguous(), g_m3)
             g_c = None
-        return g_m3, g_m2.reshape(m2_shape), g_c, g_sh, g_o.reshape(o_shape), g_s, g_r, None, None, None, None
+        return g_m3, g_m2.reshape(m2_shape), g_c, g_sh, g_o.reshape(o_shape), g_s, g_r, None, None, None, None, None
 
 
 class GaussianRasterizer(nn.Module):
@@ -1109,9 +1310,16 @@ class GaussianRasterizer(nn.Module):
         if shs is not None and not 0 <= int(self.raster_settings.sh_degree) <= 3:
             raise ValueError("sh_degree must be 0..3")
         # (a rasterizer without a form of its own leaves an enclosing ``with walk_form(...)`` block in force)
+        slot = None
+        if _geometry_reuse:   # (opt-in: set_geometry_reuse) this object remembers its last full forward
+            slot = self.__dict__.get("_reuse_slot")
+            if slot is None:
+                slot = self.__dict__["_reuse_slot"] = _ReuseSlot()
+        elif "_reuse_slot" in self.__dict__:
+            del self.__dict__["_reuse_slot"]    # switched off: nothing stays pinned
         with walk_form(self.walk_form) if self.walk_form not in (None, "auto") else contextlib.nullcontext():
             ret = _RasterizeGaussians.apply(means3D, means2D, colors_precomp, shs, opacities, scales, rotations,
-                                            self.raster_settings, flavour, use_filter, cov3D_precomp)
+                                            self.raster_settings, flavour, use_filter, cov3D_precomp, slot)
         if flavour.extras:
             # how many Gaussians the ids of point_id_pixel index: lets log_amd.counter's stand-in for the
             # torch.unique call at LoG/render/renderer.py:156 recognise the map and take the histogram kernel
