@@ -567,6 +567,32 @@ int lograst_loss_backward(int32_t batch, int32_t channels, int32_t height, int32
                           const float* gt, const int64_t* gt_strides, float l1_weight, const float* grad_loss,
                           const float* maps, float* grad_render, float* grad_render_l1, void* stream);
 
+/* ---- the depth term of depth-supervised training (LoG/render/renderer.py:268-292 append_depth_loss with
+ * LoG/render/loss.py:47-117 ScaleAndShiftInvariantLoss, one gradient scale) --------------------------------------------
+ * pred, gt, acc: [height, width] fp32, each addressed through TWO ELEMENT STRIDES (y, x; host arrays of 2 int64).
+ * rows, cols: n int64 patch origins ON THE DEVICE (never read by the host); patches are 64 x 64, 1 <= n <= 256.
+ * Per pixel m = acc > threshold, p = 1 / (pred + eps); per patch the least-squares (s, h) of s p + h onto gt over m
+ * (s = h = 0 where the determinant is exactly 0), d = m (s p + h - gt);
+ *   loss = (sum_k sum d^2 + alpha * sum_k sum_{horizontal and vertical neighbour pairs inside the patch} m m' |d' - d|) / M,
+ *   M = the number of valid pixels over all patches (M == 0: loss = nan).
+ * All arithmetic is double; sums run in a fixed order, so the same input gives the same bits.
+ * lograst_depth_loss_forward writes out (16 bytes, 8-byte aligned: the loss as a float at byte 0, M as a double at byte 8)
+ * and records (lograst_depth_loss_record_bytes(n) = 128 * (n + 1) bytes, 8-byte aligned: a header and one record of 16
+ * doubles per patch), all the backward needs besides the three images.  A patch that does not lie inside the image is
+ * not read: the loss becomes nan and the patch adds nothing to the gradient.
+ * lograst_depth_loss_backward reads the upstream gradient of loss from DEVICE memory (grad_loss, one float) and writes
+ * every element of grad_pred [height, width] (contiguous) once: scale and shift are not detached; pixels outside every
+ * patch get 0.  gt and acc get no gradient.
+ * height or width below 64, n outside 1..256, NULL pointers and too small a records buffer are errors. */
+size_t lograst_depth_loss_record_bytes(int32_t n);
+int lograst_depth_loss_forward(int32_t height, int32_t width, const float* pred, const int64_t* pred_strides,
+                               const float* gt, const int64_t* gt_strides, const float* acc, const int64_t* acc_strides,
+                               int32_t n, const int64_t* rows, const int64_t* cols, double alpha, double eps,
+                               double threshold, void* out, void* records, size_t record_bytes, void* stream);
+int lograst_depth_loss_backward(int32_t height, int32_t width, const float* pred, const int64_t* pred_strides,
+                                const float* gt, const int64_t* gt_strides, const float* acc, const int64_t* acc_strides,
+                                int32_t n, const void* records, const float* grad_loss, float* grad_pred, void* stream);
+
 /* ---- per-kernel timing with HIP events on the launch stream (used by bench.py) -----------------
  * When enabled every kernel launch is bracketed by hipEventRecord on its stream.  read() synchronises
  * the recorded events and returns, for kernel slot i < LOGRAST_NUM_KERNELS, accumulated milliseconds

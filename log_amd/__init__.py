@@ -16,7 +16,7 @@ def install_compute_radius():
     return shim
 
 
-def install_all(fused_step=False, fused_loss=False, reuse_geometry=False):
+def install_all(fused_step=False, fused_loss=False, reuse_geometry=False, fused_depth_loss=False):
     """Everything a LoG process needs, in one call: the LoG.cuda.compute_radius module, then every
     drop-in method assigned onto LoG's own classes (needs LoG importable): LoG.get_all, TensorTree.traverse,
     Counter.update_by_output, SparseOptimizer.step.
@@ -27,7 +27,10 @@ def install_all(fused_step=False, fused_loss=False, reuse_geometry=False):
     (log_amd.loss.install); without it the loss stays the reference's torch code.
     reuse_geometry (opt-in): the second rasterizer call of a view (LoG's depth pass, render_depth: True) composites the first
     call's tile lists again with its own colours instead of binning again (log_amd.rasterizer.set_geometry_reuse: same
-    results; a rasterizer object then keeps one forward's records and lists alive until its next call)."""
+    results; a rasterizer object then keeps one forward's records and lists alive until its next call).
+    fused_depth_loss (opt-in): NaiveRendererAndLoss.append_depth_loss (the depth term of render_depth: True) goes through the
+    fused patch-loss kernels (log_amd.depth_loss.install: double arithmetic, no read-backs); without it the depth term stays
+    the reference's torch code, whatever fused_loss says."""
     install_compute_radius()
     from . import rasterizer
     rasterizer.set_geometry_reuse(bool(reuse_geometry))
@@ -37,4 +40,7 @@ def install_all(fused_step=False, fused_loss=False, reuse_geometry=False):
     if fused_loss:
         from . import loss
         installed.append(loss.install())
+    if fused_depth_loss:
+        from . import depth_loss
+        installed.append(depth_loss.install())
     return installed

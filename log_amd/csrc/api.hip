@@ -1044,6 +1044,52 @@ int lograst_loss_backward(int32_t batch, int32_t channels, int32_t height, int32
   return LOGRAST_OK;
 }
 
+// ---- fused depth patch loss (depth_loss.hip) --------------------------------------------------------------
+size_t lograst_depth_loss_record_bytes(int32_t n) { return lr_depth_loss_record_bytes(n); }
+
+// Checks shared by the two entry points; everything here runs before any device work.
+static int lr_depth_loss_args(DepthLossArgs& a, int32_t height, int32_t width, const float* pred, const int64_t* ps,
+                              const float* gt, const int64_t* gs, const float* acc, const int64_t* as, int32_t n) {
+  if (height < 0 || width < 0) return lr_fail(LOGRAST_ERR_ARG, "negative image size");
+  if (height < DL_PATCH || width < DL_PATCH)
+    return lr_fail(LOGRAST_ERR_ARG, "image smaller than the 64-pixel patch of the depth loss (height and width must be >= 64)");
+  if (n < 1 || n > DL_MAX_PATCHES) return lr_fail(LOGRAST_ERR_ARG, "patch count must be 1..256");
+  if (!pred || !gt || !acc || !ps || !gs || !as) return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
+  a.pred = pred; a.gt = gt; a.acc = acc;
+  for (int i = 0; i < 2; i++) { a.ps[i] = ps[i]; a.gs[i] = gs[i]; a.as[i] = as[i]; }
+  a.H = height; a.W = width;
+  return 0;
+}
+
+int lograst_depth_loss_forward(int32_t height, int32_t width, const float* pred, const int64_t* pred_strides,
+                               const float* gt, const int64_t* gt_strides, const float* acc, const int64_t* acc_strides,
+                               int32_t n, const int64_t* rows, const int64_t* cols, double alpha, double eps,
+                               double threshold, void* out, void* records, size_t record_bytes, void* stream) {
+  DepthLossArgs a;
+  const int rc = lr_depth_loss_args(a, height, width, pred, pred_strides, gt, gt_strides, acc, acc_strides, n);
+  if (rc < 0) return rc;
+  if (!rows || !cols || !out) return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
+  if (reinterpret_cast<uintptr_t>(out) & 7u) return lr_fail(LOGRAST_ERR_ARG, "out must be 8-byte aligned (float loss at byte 0, double M at byte 8)");
+  if (!records || record_bytes < lr_depth_loss_record_bytes(n) || (reinterpret_cast<uintptr_t>(records) & 7u))
+    return lr_fail(LOGRAST_ERR_ARG, "depth loss records too small (lograst_depth_loss_record_bytes) or not 8-byte aligned");
+  g_prof_call++;
+  LR_HIP(lr_launch_depth_loss_fwd(a, n, rows, cols, alpha, eps, threshold, out, reinterpret_cast<double*>(records), (hipStream_t)stream));
+  return LOGRAST_OK;
+}
+
+int lograst_depth_loss_backward(int32_t height, int32_t width, const float* pred, const int64_t* pred_strides,
+                                const float* gt, const int64_t* gt_strides, const float* acc, const int64_t* acc_strides,
+                                int32_t n, const void* records, const float* grad_loss, float* grad_pred, void* stream) {
+  DepthLossArgs a;
+  const int rc = lr_depth_loss_args(a, height, width, pred, pred_strides, gt, gt_strides, acc, acc_strides, n);
+  if (rc < 0) return rc;
+  if (!records || !grad_loss || !grad_pred) return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
+  if (reinterpret_cast<uintptr_t>(records) & 7u) return lr_fail(LOGRAST_ERR_ARG, "depth loss records must be 8-byte aligned");
+  g_prof_call++;
+  LR_HIP(lr_launch_depth_loss_bwd(a, n, reinterpret_cast<const double*>(records), grad_loss, grad_pred, (hipStream_t)stream));
+  return LOGRAST_OK;
+}
+
 int lograst_sparse_adam(int32_t m, int32_t num_points, const int64_t* index, const uint8_t* flag_vis,
                         int32_t num_keys, const lograst_adam_key* keys, double beta1, double beta2,
                         double bias_correction2_sqrt, double eps, void* stream) {

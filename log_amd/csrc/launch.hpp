@@ -99,3 +99,18 @@ hipError_t lr_launch_sparse_adam(const AdamArgs& a, int num_keys, hipStream_t s)
 size_t lr_loss_scratch_bytes(int B, int C, int H, int W);
 hipError_t lr_launch_loss_fwd(const LossArgs& a, float wa, float wb, float* out3, hipStream_t s);
 hipError_t lr_launch_loss_bwd(const LossArgs& a, const float* grad_loss, float* g_render, float* g_render_l1, hipStream_t s);
+
+// depth_loss.hip
+#define DL_PATCH 64             // the patch side, the only one the kernels have
+#define DL_MAX_PATCHES 256
+#define DL_REC 16               // doubles per record slot: slot 0 the header, slot 1 + k patch k (layout: depth_loss.hip)
+struct DepthLossArgs {
+  const float* pred; const float* gt; const float* acc;   // [H, W] each
+  int64_t ps[2], gs[2], as[2];                            // element strides (y, x)
+  int32_t H, W;
+};
+size_t lr_depth_loss_record_bytes(int n);
+hipError_t lr_launch_depth_loss_fwd(const DepthLossArgs& a, int n, const int64_t* rows, const int64_t* cols, double alpha,
+                                    double eps, double thr, void* out, double* records, hipStream_t s);
+hipError_t lr_launch_depth_loss_bwd(const DepthLossArgs& a, int n, const double* records, const float* grad_loss,
+                                    float* grad_pred, hipStream_t s);
