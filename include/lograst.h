@@ -517,6 +517,66 @@ int lograst_activate_backward_adam(int32_t n, const float* raw_xyz, const float*
                                    const lograst_adam_key* keys, double beta1, double beta2, double bias_correction2_sqrt,
                                    double eps, void* stream);
 
+/* ---- densification: TensorTree.split_and_remove + Splitter.split_and_remove(_other) on the device ----------------
+ * (LoG/model/tensor_tree.py:65-129, LoG/model/splitter.py:5-31, :95-220).  One call of the reference method is:
+ * lograst_densify_plan, lograst_densify_read (the only host synchronisation: the caller allocates the new buffers from
+ * the counts), lograst_densify_src_rows, then lograst_densify_move_rows / _split_uniform / _tree as the method needs.
+ * children = the tree's max_child = Splitter.N, one of 2, 4, 8.  No call allocates; all work on `stream`.
+ *
+ * lograst_densify_plan: flag_split / flag_remove u8[p] (torch bool).  With node_index (i32[p]), index_parent (i32[p]) and
+ * depth (i8[p]) given (all three or none) the tree's masks are applied first: remove &= leaf & ~root, split &= leaf &
+ * depth < max_level.  split_out / remove_out u8[p] receive the masked flags (not the inputs' storage).  A row is kept
+ * unless it is removed, or split while remove_split != 0.  keep_dest i32[p] = the new row of a kept row, -1 otherwise.
+ * The scratch header then holds num_keep, num_split and overlap = rows flagged for both while remove_split == 0 (the
+ * reference leaves that case undefined: callers fall back).  scratch: lograst_densify_scratch_bytes(p), kept until
+ * lograst_densify_src_rows has run. */
+size_t lograst_densify_scratch_bytes(int32_t p);
+int lograst_densify_plan(int32_t p, const uint8_t* flag_split, const uint8_t* flag_remove, int32_t remove_split,
+                         int32_t children, const int32_t* node_index, const int32_t* index_parent, const int8_t* depth,
+                         int32_t max_level, uint8_t* split_out, uint8_t* remove_out, int32_t* keep_dest, void* scratch,
+                         size_t scratch_bytes, void* stream);
+/* Synchronises the stream and returns the three counts. */
+int lograst_densify_read(const void* scratch, uint32_t* num_keep_host, uint32_t* num_split_host, uint32_t* overlap_host,
+                         void* stream);
+/* src_row i32[num_keep + children * num_split]: new row d < num_keep came from old row src_row[d]; new row
+ * num_keep + children * k + j is child j of the k-th split row (ascending old index), src_row = that row.
+ * split / remove: the masked flags of the plan; num_keep / num_split: what lograst_densify_read returned. */
+int lograst_densify_src_rows(int32_t p, int32_t children, int32_t remove_split, const uint8_t* split, const uint8_t* remove,
+                             int32_t num_keep, int32_t num_split, int32_t* src_row, const void* scratch, void* stream);
+
+/* lograst_densify_move_rows: dst[d] = src[src_row[d]] for up to 8 keys in one launch, 16-byte stores throughout and
+ * 16-byte loads where the row size allows.  Rows d >= num_keep follow child_mode.  dst must be 16-byte aligned and src
+ * aligned to elem_size; both contiguous. */
+#define LOGRAST_MOVE_COPY_PARENT 0
+#define LOGRAST_MOVE_ZERO 1
+#define LOGRAST_MOVE_SKIP 2      /* another kernel writes the children (lograst_densify_split_uniform) */
+typedef struct lograst_move_key {
+  const void* src;          /* [src_rows, columns] of elem_size bytes */
+  void* dst;                /* [num_new, columns] */
+  int32_t elem_size;        /* 1, 2 or 4 */
+  int32_t columns;          /* elements per row, elem_size * columns <= 65536 */
+  int32_t child_mode;       /* LOGRAST_MOVE_* */
+} lograst_move_key;
+int lograst_densify_move_rows(int32_t num_keep, int32_t num_new, int32_t src_rows, const int32_t* src_row,
+                              int32_t num_keys, const lograst_move_key* keys, void* stream);
+
+/* split_by_uniform (splitter.py:95-130): rows num_keep.. of xyz_new f32[num_new, 3] and scaling_new f32[num_new, 3] (raw
+ * log-scales) from the old xyz / scaling (raw) / rotation (raw quaternion, normalised inside) rows src_row names:
+ * log2(children) rounds, each halving the longest CURRENT axis (ties: lowest axis) by scaling_factor and moving the two
+ * halves +-0.5 * scale[axis] along that axis.  Child order: parent-major, then (--, -+, +-, ++). */
+int lograst_densify_split_uniform(int32_t num_keep, int32_t num_split, int32_t children, float scaling_factor,
+                                  int32_t src_rows, const int32_t* src_row, const float* xyz, const float* scaling,
+                                  const float* rotation, float* xyz_new, float* scaling_new, void* stream);
+
+/* The tree buffers that TensorTree.split followed by TensorTree.remove leave (tensor_tree.py:65-118): node_index_new,
+ * index_parent_new i32[num_new], local_index_new, depth_new i8[num_new], tree_new i32[num_nodes + num_split, children];
+ * split = the plan's masked split flags (remove_split = 0), keep_dest its output. */
+int lograst_densify_tree(int32_t p, int32_t num_nodes, int32_t children, int32_t num_keep, int32_t num_split,
+                         const int32_t* src_row, const int32_t* keep_dest, const uint8_t* split, const int32_t* node_index,
+                         const int32_t* index_parent, const int8_t* local_index, const int8_t* depth, const int32_t* tree,
+                         int32_t* node_index_new, int32_t* index_parent_new, int8_t* local_index_new, int8_t* depth_new,
+                         int32_t* tree_new, void* stream);
+
 /* ---- rows N2 / N3: LoG.get_all + Activation.activate_root_return, fused ---------------------------------------
  * Replaces the per-key gathers of LoG.get_all (/root/reference/LoG/model/level_of_gaussian.py:262-296) and the
  * activations of Activation.activate_root_return / colors_activation (/root/reference/LoG/model/activation.py:27-44;

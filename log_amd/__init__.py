@@ -16,7 +16,7 @@ def install_compute_radius():
     return shim
 
 
-def install_all(fused_step=False, fused_loss=False, reuse_geometry=False, fused_depth_loss=False):
+def install_all(fused_step=False, fused_loss=False, reuse_geometry=False, fused_depth_loss=False, device_densify=False):
     """Everything a LoG process needs, in one call: the LoG.cuda.compute_radius module, then every
     drop-in method assigned onto LoG's own classes (needs LoG importable): LoG.get_all, TensorTree.traverse,
     Counter.update_by_output, SparseOptimizer.step.
@@ -30,7 +30,10 @@ def install_all(fused_step=False, fused_loss=False, reuse_geometry=False, fused_
     results; a rasterizer object then keeps one forward's records and lists alive until its next call).
     fused_depth_loss (opt-in): NaiveRendererAndLoss.append_depth_loss (the depth term of render_depth: True) goes through the
     fused patch-loss kernels (log_amd.depth_loss.install: double arithmetic, no read-backs); without it the depth term stays
-    the reference's torch code, whatever fused_loss says."""
+    the reference's torch code, whatever fused_loss says.
+    device_densify (opt-in): TensorTree.split_and_remove, Splitter.split_and_remove and Splitter.split_and_remove_other resize
+    the model, the Adam moments and the tree on the device (log_amd.densify.install: one host synchronisation per call, no
+    copy of the model to the CPU); without it densification stays the reference's code."""
     install_compute_radius()
     from . import rasterizer
     rasterizer.set_geometry_reuse(bool(reuse_geometry))
@@ -43,4 +46,7 @@ def install_all(fused_step=False, fused_loss=False, reuse_geometry=False, fused_
     if fused_depth_loss:
         from . import depth_loss
         installed.append(depth_loss.install())
+    if device_densify:
+        from . import densify
+        installed.append(densify.install())
     return installed

@@ -39,6 +39,15 @@ class LograstAdamKey(ctypes.Structure):
                 ("exp_avg_sq", c_void_p), ("max_exp_avg_sq", c_void_p), ("width", c_int32), ("step_size", c_float)]
 
 
+class LograstMoveKey(ctypes.Structure):
+    """struct lograst_move_key (include/lograst.h)."""
+    _fields_ = [("src", c_void_p), ("dst", c_void_p), ("elem_size", c_int32), ("columns", c_int32),
+                ("child_mode", c_int32)]
+
+
+MOVE_COPY_PARENT, MOVE_ZERO, MOVE_SKIP = 0, 1, 2   # LOGRAST_MOVE_*
+
+
 class LograstError(RuntimeError):
     pass
 
@@ -123,6 +132,17 @@ _SIGNATURES = {
     "lograst_sparse_adam": (ctypes.c_int, [c_int32, c_int32, c_void_p, c_void_p, c_int32,
                                            ctypes.POINTER(LograstAdamKey), ctypes.c_double, ctypes.c_double,
                                            ctypes.c_double, ctypes.c_double, c_void_p]),
+    "lograst_densify_scratch_bytes": (c_size_t, [c_int32]),
+    "lograst_densify_plan": (ctypes.c_int, [c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                            c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "lograst_densify_read": (ctypes.c_int, [c_void_p, ctypes.POINTER(c_uint32), ctypes.POINTER(c_uint32),
+                                            ctypes.POINTER(c_uint32), c_void_p]),
+    "lograst_densify_src_rows": (ctypes.c_int, [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p,
+                                                c_void_p, c_void_p]),
+    "lograst_densify_move_rows": (ctypes.c_int, [c_int32, c_int32, c_int32, c_void_p, c_int32,
+                                                 ctypes.POINTER(LograstMoveKey), c_void_p]),
+    "lograst_densify_split_uniform": (ctypes.c_int, [c_int32, c_int32, c_int32, c_float, c_int32] + [c_void_p] * 7),
+    "lograst_densify_tree": (ctypes.c_int, [c_int32] * 5 + [c_void_p] * 14),
     "lograst_activate_backward_adam": (ctypes.c_int, [c_int32] + [c_void_p] * 4 + [c_int32, c_int32] + [c_void_p] * 6 +
                                        [c_int32, c_void_p, c_void_p, ctypes.POINTER(LograstAdamKey), ctypes.c_double,
                                         ctypes.c_double, ctypes.c_double, ctypes.c_double, c_void_p]),

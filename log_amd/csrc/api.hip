@@ -1117,6 +1117,130 @@ int lograst_sparse_adam(int32_t m, int32_t num_points, const int64_t* index, con
   return LOGRAST_OK;
 }
 
+// ---- densification (densify.hip) ---------------------------------------------------------------------------
+static int lr_densify_children(int32_t children) {
+  if (children != 2 && children != 4 && children != 8) return lr_fail(LOGRAST_ERR_ARG, "children must be 2, 4 or 8");
+  return LOGRAST_OK;
+}
+
+size_t lograst_densify_scratch_bytes(int32_t p) { return lr_densify_scratch_bytes(p); }
+
+int lograst_densify_plan(int32_t p, const uint8_t* flag_split, const uint8_t* flag_remove, int32_t remove_split,
+                         int32_t children, const int32_t* node_index, const int32_t* index_parent, const int8_t* depth,
+                         int32_t max_level, uint8_t* split_out, uint8_t* remove_out, int32_t* keep_dest, void* scratch,
+                         size_t scratch_bytes, void* stream) {
+  if (p < 0) return lr_fail(LOGRAST_ERR_ARG, "negative row count");
+  if (lr_densify_children(children)) return LOGRAST_ERR_ARG;
+  if (!scratch || scratch_bytes < lr_densify_scratch_bytes(p)) return lr_fail(LOGRAST_ERR_ARG, "densify scratch too small");
+  if (p > 0 && (!flag_split || !flag_remove || !split_out || !remove_out || !keep_dest)) return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
+  if ((node_index != nullptr) != (index_parent != nullptr) || (node_index != nullptr) != (depth != nullptr))
+    return lr_fail(LOGRAST_ERR_ARG, "node_index, index_parent and depth go together");
+  if (p > 0 && (split_out == flag_split || remove_out == flag_remove)) return lr_fail(LOGRAST_ERR_ARG, "masked flags need their own storage");
+  g_prof_call++;
+  LR_HIP(lr_launch_densify_plan(p, flag_split, flag_remove, remove_split, node_index, index_parent, depth, max_level,
+                                split_out, remove_out, keep_dest, scratch, (hipStream_t)stream));
+  return LOGRAST_OK;
+}
+
+int lograst_densify_read(const void* scratch, uint32_t* num_keep_host, uint32_t* num_split_host, uint32_t* overlap_host,
+                         void* stream) {
+  if (!scratch) return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
+  uint32_t w[3];
+  LR_HIP(hipMemcpyAsync(w, scratch, sizeof(w), hipMemcpyDeviceToHost, (hipStream_t)stream));
+  LR_HIP(hipStreamSynchronize((hipStream_t)stream));
+  if (num_keep_host) *num_keep_host = w[0];
+  if (num_split_host) *num_split_host = w[1];
+  if (overlap_host) *overlap_host = w[2];
+  return LOGRAST_OK;
+}
+
+static int lr_densify_sizes(int32_t num_keep, int32_t num_split, int32_t children) {
+  if (num_keep < 0 || num_split < 0) return lr_fail(LOGRAST_ERR_ARG, "negative row count");
+  if (lr_densify_children(children)) return LOGRAST_ERR_ARG;
+  if ((int64_t)num_keep + (int64_t)num_split * children > (int64_t)0x7fffffff) return lr_fail(LOGRAST_ERR_ARG, "more than 2^31 - 1 new rows");
+  return LOGRAST_OK;
+}
+
+int lograst_densify_src_rows(int32_t p, int32_t children, int32_t remove_split, const uint8_t* split, const uint8_t* remove,
+                             int32_t num_keep, int32_t num_split, int32_t* src_row, const void* scratch, void* stream) {
+  if (p < 0) return lr_fail(LOGRAST_ERR_ARG, "negative row count");
+  if (lr_densify_sizes(num_keep, num_split, children)) return LOGRAST_ERR_ARG;
+  if (num_keep > p || num_split > p) return lr_fail(LOGRAST_ERR_ARG, "more kept or split rows than rows");
+  if (num_keep + num_split == 0) return LOGRAST_OK;
+  if (!split || !remove || !src_row || !scratch) return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
+  g_prof_call++;
+  LR_HIP(lr_launch_densify_src_rows(p, children, remove_split, split, remove, num_keep, num_split, src_row, scratch,
+                                    (hipStream_t)stream));
+  return LOGRAST_OK;
+}
+
+int lograst_densify_move_rows(int32_t num_keep, int32_t num_new, int32_t src_rows, const int32_t* src_row,
+                              int32_t num_keys, const lograst_move_key* keys, void* stream) {
+  if (num_keep < 0 || num_new < 0 || src_rows < 0) return lr_fail(LOGRAST_ERR_ARG, "negative row count");
+  if (num_keep > num_new) return lr_fail(LOGRAST_ERR_ARG, "num_keep exceeds num_new");
+  if (num_keys < 0 || num_keys > LR_MOVE_MAX_KEYS) return lr_fail(LOGRAST_ERR_ARG, "at most 8 keys per call");
+  if (num_keys > 0 && !keys) return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
+  MoveArgs a;
+  memset(&a, 0, sizeof(a));
+  for (int i = 0; i < num_keys; i++) {
+    const lograst_move_key& k = keys[i];
+    if (k.elem_size != 1 && k.elem_size != 2 && k.elem_size != 4) return lr_fail(LOGRAST_ERR_ARG, "element size must be 1, 2 or 4");
+    if (k.columns < 1 || (int64_t)k.columns * k.elem_size > 65536) return lr_fail(LOGRAST_ERR_ARG, "row size must be 1..65536 bytes");
+    if (k.child_mode < LR_MOVE_COPY_PARENT || k.child_mode > LR_MOVE_SKIP) return lr_fail(LOGRAST_ERR_ARG, "unknown child mode");
+    if (num_new > 0 && (!k.src || !k.dst)) return lr_fail(LOGRAST_ERR_ARG, "NULL pointer in key");
+    const uintptr_t sp = (uintptr_t)k.src, dp = (uintptr_t)k.dst;
+    if ((dp & 15u) || (sp & (uintptr_t)(k.elem_size - 1))) return lr_fail(LOGRAST_ERR_ARG, "dst must be 16-byte aligned, src aligned to its element");
+    const uint32_t rb = (uint32_t)k.columns * (uint32_t)k.elem_size;
+    a.key[i].src = k.src; a.key[i].dst = k.dst; a.key[i].row_bytes = rb; a.key[i].child_mode = k.child_mode;
+    a.key[i].unit = (rb % 4u == 0 && (sp & 3u) == 0) ? 4 : ((rb % 2u == 0 && (sp & 1u) == 0) ? 2 : 1);
+    a.key[i].vec16 = (rb % 16u == 0 && (sp & 15u) == 0) ? 1 : 0;
+  }
+  if (num_new == 0 || num_keys == 0) return LOGRAST_OK;
+  if (!src_row) return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
+  a.src_row = src_row; a.num_keep = num_keep; a.num_new = num_new; a.src_rows = src_rows;
+  g_prof_call++;
+  LR_HIP(lr_launch_move_rows(a, num_keys, (hipStream_t)stream));
+  return LOGRAST_OK;
+}
+
+int lograst_densify_split_uniform(int32_t num_keep, int32_t num_split, int32_t children, float scaling_factor,
+                                  int32_t src_rows, const int32_t* src_row, const float* xyz, const float* scaling,
+                                  const float* rotation, float* xyz_new, float* scaling_new, void* stream) {
+  if (src_rows < 0) return lr_fail(LOGRAST_ERR_ARG, "negative row count");
+  if (lr_densify_sizes(num_keep, num_split, children)) return LOGRAST_ERR_ARG;
+  if (num_split == 0) return LOGRAST_OK;
+  if (!src_row || !xyz || !scaling || !rotation || !xyz_new || !scaling_new) return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
+  g_prof_call++;
+  LR_HIP(lr_launch_split_uniform(num_keep, num_split, children, scaling_factor, src_rows, src_row, xyz, scaling, rotation,
+                                 xyz_new, scaling_new, (hipStream_t)stream));
+  return LOGRAST_OK;
+}
+
+int lograst_densify_tree(int32_t p, int32_t num_nodes, int32_t children, int32_t num_keep, int32_t num_split,
+                         const int32_t* src_row, const int32_t* keep_dest, const uint8_t* split, const int32_t* node_index,
+                         const int32_t* index_parent, const int8_t* local_index, const int8_t* depth, const int32_t* tree,
+                         int32_t* node_index_new, int32_t* index_parent_new, int8_t* local_index_new, int8_t* depth_new,
+                         int32_t* tree_new, void* stream) {
+  if (p < 0 || num_nodes < 0) return lr_fail(LOGRAST_ERR_ARG, "negative row count");
+  if (lr_densify_sizes(num_keep, num_split, children)) return LOGRAST_ERR_ARG;
+  if (num_keep > p || num_split > p) return lr_fail(LOGRAST_ERR_ARG, "more kept or split rows than rows");
+  if (((int64_t)num_nodes + num_split) * children > (int64_t)0x7fffffff) return lr_fail(LOGRAST_ERR_ARG, "tree too large");
+  const int64_t num_new = (int64_t)num_keep + (int64_t)num_split * children;
+  if (num_new > 0 && (!src_row || !keep_dest || !split || !node_index || !index_parent || !local_index || !depth ||
+                      !node_index_new || !index_parent_new || !local_index_new || !depth_new))
+    return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
+  if ((num_nodes > 0 && (!tree || !keep_dest)) || (num_nodes + num_split > 0 && !tree_new)) return lr_fail(LOGRAST_ERR_ARG, "NULL tree pointer");
+  TreeArgs a;
+  a.src_row = src_row; a.keep_dest = keep_dest; a.split = split;
+  a.node_index = node_index; a.index_parent = index_parent; a.local_index = local_index; a.depth = depth; a.tree = tree;
+  a.node_index_new = node_index_new; a.index_parent_new = index_parent_new; a.local_index_new = local_index_new;
+  a.depth_new = depth_new; a.tree_new = tree_new;
+  a.p = p; a.num_nodes = num_nodes; a.children = children; a.num_keep = num_keep; a.num_split = num_split;
+  g_prof_call++;
+  LR_HIP(lr_launch_densify_tree(a, (hipStream_t)stream));
+  return LOGRAST_OK;
+}
+
 static int lr_ga_check(int32_t n, int32_t sh_coeffs, int32_t active_degree, const float* camera_center) {
   if (n < 0) return lr_fail(LOGRAST_ERR_ARG, "negative row count");
   if (sh_coeffs < 0 || sh_coeffs > 15) return lr_fail(LOGRAST_ERR_ARG, "sh_coeffs must be 0..15 (degree <= 3)");

@@ -114,3 +114,41 @@ hipError_t lr_launch_depth_loss_fwd(const DepthLossArgs& a, int n, const int64_t
                                     double eps, double thr, void* out, double* records, hipStream_t s);
 hipError_t lr_launch_depth_loss_bwd(const DepthLossArgs& a, int n, const double* records, const float* grad_loss,
                                     float* grad_pred, hipStream_t s);
+
+// densify.hip
+#define LR_MOVE_COPY_PARENT 0   // rows >= num_keep copy src[src_row[d]] like the kept rows
+#define LR_MOVE_ZERO 1          // rows >= num_keep are zero
+#define LR_MOVE_SKIP 2          // rows >= num_keep are left to another kernel
+#define LR_MOVE_MAX_KEYS 8
+struct MoveKey {
+  const void* src; void* dst;   // [src_rows, row_bytes] -> [num_new, row_bytes]; dst 16-byte aligned
+  uint32_t row_bytes;
+  int32_t unit;                 // 4 | 2 | 1: the largest access that every row start of src allows
+  int32_t vec16;                // row_bytes % 16 == 0 and src 16-byte aligned
+  int32_t child_mode;
+};
+struct MoveArgs {
+  MoveKey key[LR_MOVE_MAX_KEYS];
+  const int32_t* src_row;       // [num_new]
+  int32_t num_keep, num_new, src_rows;
+};
+struct TreeArgs {
+  const int32_t* src_row; const int32_t* keep_dest; const uint8_t* split;
+  const int32_t* node_index; const int32_t* index_parent; const int8_t* local_index; const int8_t* depth;
+  const int32_t* tree;          // [num_nodes, children]
+  int32_t* node_index_new; int32_t* index_parent_new; int8_t* local_index_new; int8_t* depth_new;   // [num_new]
+  int32_t* tree_new;            // [num_nodes + num_split, children]
+  int32_t p, num_nodes, children, num_keep, num_split;
+};
+size_t lr_densify_scratch_bytes(int p);
+hipError_t lr_launch_densify_plan(int p, const uint8_t* flag_split, const uint8_t* flag_remove, int remove_split,
+                                  const int32_t* node_index, const int32_t* index_parent, const int8_t* depth,
+                                  int max_level, uint8_t* split_out, uint8_t* remove_out, int32_t* keep_dest,
+                                  void* scratch, hipStream_t s);
+hipError_t lr_launch_densify_src_rows(int p, int children, int remove_split, const uint8_t* split, const uint8_t* remove,
+                                      int num_keep, int num_split, int32_t* src_row, const void* scratch, hipStream_t s);
+hipError_t lr_launch_move_rows(const MoveArgs& a, int num_keys, hipStream_t s);
+hipError_t lr_launch_split_uniform(int num_keep, int num_split, int children, float factor, int src_rows,
+                                   const int32_t* src_row, const float* xyz, const float* scaling, const float* rotation,
+                                   float* xyz_new, float* scaling_new, hipStream_t s);
+hipError_t lr_launch_densify_tree(const TreeArgs& a, hipStream_t s);
