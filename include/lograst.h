@@ -459,6 +459,54 @@ int lograst_lod_traverse(int32_t num_points, int32_t num_nodes, int32_t max_chil
 int lograst_lod_read(const void* scratch, uint32_t* count_host, uint32_t* overflow_host, uint32_t* frontier_left_host,
                      void* stream);
 
+/* ---- view preparation: LoG.prepare, Gaussian.prepare and LoG.clamp_scale on the device ---------------------------
+ * (/root/reference/LoG/model/level_of_gaussian.py:39-53, :90-98, :223-256, :367-398; Python side: log_amd/prepare.py).
+ * No call allocates; all work on `stream`.
+ *
+ * lograst_frustum_select = Gaussian._visible_flag_by_camera + the boolean-mask indexing behind it.  Entry i < n is row
+ * rows[i] (i32, as TensorTree keeps root_index) or row i when rows == NULL; xyz is [num_points, 3]; full_proj the 4x4
+ * full_proj_transform, row-major, applied as [x, y, z, 1] @ M.  flag_out u8[n] = (0 < z' < 1) & (|x'|, |y'| < 1 +
+ * padding), p' = h / (hw + 1e-7), strict comparisons in fp32 (a NaN or an infinity anywhere, or a row outside
+ * [0, num_points), gives 0).  pos_out i64 (capacity n) receives the positions i of the kept entries in ascending order,
+ * row_out (optional, same capacity) their rows.  With the raw scaling[P,3], rotation[P,4] and opacity[P] given (all
+ * three, and the four outputs, or none), xyz_out[.,3], scaling_out[.,3] = exp, rotation_out[.,4] = normalised and
+ * opacity_out[.] = sigmoid hold the kept entries' parameters in the same order (capacity n rows each), bit for bit what
+ * lograst_gather_activate writes for those rows.  The count stays on the device: lograst_frustum_read (one stream
+ * synchronise).  scratch: lograst_frustum_scratch_bytes(n). */
+size_t lograst_frustum_scratch_bytes(int32_t n);
+int lograst_frustum_select(int32_t n, int32_t num_points, const float* xyz, const int32_t* rows, const float* full_proj,
+                           double padding, const float* scaling, const float* rotation, const float* opacity,
+                           uint8_t* flag_out, int64_t* pos_out, int64_t* row_out, float* xyz_out, float* scaling_out,
+                           float* rotation_out, float* opacity_out, void* scratch, size_t scratch_bytes, void* stream);
+int lograst_frustum_read(const void* scratch, uint32_t* count_host, void* stream);
+
+/* lograst_lod_select = the rest of LoG.prepare in one stream of launches and ONE read-back: (1) with root_weight given
+ * (f32[num_roots], the root render's point_weight), root k is dropped unless root_weight[k] > 1e-8, and root_flag[root_pos[k]]
+ * (u8[num_root_flags], the flag of lograst_frustum_select; root_pos = its pos_out) is cleared; (2) lograst_lod_traverse
+ * from the remaining roots (root_rows i64[num_roots], the row_out above), same order and result, into out_index;
+ * (3) a stable partition of out_index into out_leaf / out_node (capacity out_capacity each) by
+ * opt_all_levels ? node_index[i] == -1 && depth[i] > 0 : depth[i] == current_depth (depth: i8[num_points]).
+ * lograst_lod_select_read synchronises and returns the size of out_index, the size of out_leaf, and overflow /
+ * frontier_left as lograst_lod_read does.  scratch: lograst_lod_select_scratch_bytes(...). */
+size_t lograst_lod_select_scratch_bytes(int32_t num_roots, int32_t num_nodes, int32_t max_child, uint32_t out_capacity);
+int lograst_lod_select(int32_t num_points, int32_t num_nodes, int32_t max_child, const int32_t* node_index,
+                       const int32_t* tree, const int8_t* depth, const float* xyz, const float* scaling,
+                       const float* rotation, const int64_t* root_rows, int32_t num_roots, const float* root_weight,
+                       const int64_t* root_pos, uint8_t* root_flag, int32_t num_root_flags, const float* projmatrix,
+                       const float* viewmatrix, float focal_x, float focal_y, float tanfovx, float tanfovy,
+                       float min_resolution_pixel, int32_t levels, int32_t opt_all_levels, int32_t current_depth,
+                       int64_t* out_index, uint32_t out_capacity, int64_t* out_leaf, int64_t* out_node, void* scratch,
+                       size_t scratch_bytes, void* stream);
+int lograst_lod_select_read(const void* scratch, uint32_t* count_all_host, uint32_t* count_leaf_host,
+                            uint32_t* overflow_host, uint32_t* frontier_left_host, void* stream);
+
+/* lograst_clamp_scale = LoG.clamp_scale on the rows index[i] (i64[m], unique, as for lograst_counter_update) with
+ * flag[i] != 0 (u8[m]; NULL: all): scaling[r, :] = clamp(scaling[r, :], logf(radius3d_min[r]), logf(radius3d_max[r])) in
+ * torch.clamp's order -- min > max gives log(max); a NaN in the value, the lower or the upper bound (in that order) is
+ * the result.  Other rows, and rows outside [0, num_points), are not written. */
+int lograst_clamp_scale(int32_t m, const int64_t* index, const uint8_t* flag, int32_t num_points, float* scaling,
+                        const float* radius3d_min, const float* radius3d_max, void* stream);
+
 /* ---- "next" row N4: what LoG does with the rasterizer's outputs after every view ----------------------------
  * (a) lograst_id_histogram replaces `torch.unique(point_id_pixel, sorted=True, return_counts=True)` + dropping the
  *     leading -1 (/root/reference/LoG/render/renderer.py:156-159): ids_out (i32) = the distinct ids >= 0 in

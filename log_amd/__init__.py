@@ -16,7 +16,8 @@ def install_compute_radius():
     return shim
 
 
-def install_all(fused_step=False, fused_loss=False, reuse_geometry=False, fused_depth_loss=False, device_densify=False):
+def install_all(fused_step=False, fused_loss=False, reuse_geometry=False, fused_depth_loss=False, device_densify=False,
+                device_prepare=False):
     """Everything a LoG process needs, in one call: the LoG.cuda.compute_radius module, then every
     drop-in method assigned onto LoG's own classes (needs LoG importable): LoG.get_all, TensorTree.traverse,
     Counter.update_by_output, SparseOptimizer.step.
@@ -33,7 +34,11 @@ def install_all(fused_step=False, fused_loss=False, reuse_geometry=False, fused_
     the reference's torch code, whatever fused_loss says.
     device_densify (opt-in): TensorTree.split_and_remove, Splitter.split_and_remove and Splitter.split_and_remove_other resize
     the model, the Adam moments and the tree on the device (log_amd.densify.install: one host synchronisation per call, no
-    copy of the model to the CPU); without it densification stays the reference's code."""
+    copy of the model to the CPU); without it densification stays the reference's code.
+    device_prepare (opt-in): LoG.prepare, Gaussian.prepare, LoG.clamp_scale and LoG.step run their frustum test, root filter,
+    leaf / node split and scale clamp on the device (log_amd.prepare.install: two host synchronisations per view, none per
+    step, no activation of all points to index out the roots); without it they stay the reference's torch code around the
+    installed TensorTree.traverse."""
     install_compute_radius()
     from . import rasterizer
     rasterizer.set_geometry_reuse(bool(reuse_geometry))
@@ -49,4 +54,7 @@ def install_all(fused_step=False, fused_loss=False, reuse_geometry=False, fused_
     if device_densify:
         from . import densify
         installed.append(densify.install())
+    if device_prepare:
+        from . import prepare
+        installed.append(prepare.install())
     return installed

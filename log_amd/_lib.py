@@ -115,6 +115,16 @@ _SIGNATURES = {
                                             c_void_p, c_size_t, c_void_p]),
     "lograst_lod_read": (ctypes.c_int, [c_void_p, ctypes.POINTER(c_uint32), ctypes.POINTER(c_uint32),
                                         ctypes.POINTER(c_uint32), c_void_p]),
+    "lograst_frustum_scratch_bytes": (c_size_t, [c_int32]),
+    "lograst_frustum_select": (ctypes.c_int, [c_int32, c_int32, c_void_p, c_void_p, c_void_p, ctypes.c_double]
+                               + [c_void_p] * 11 + [c_size_t, c_void_p]),
+    "lograst_frustum_read": (ctypes.c_int, [c_void_p, ctypes.POINTER(c_uint32), c_void_p]),
+    "lograst_lod_select_scratch_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_uint32]),
+    "lograst_lod_select": (ctypes.c_int, [c_int32, c_int32, c_int32] + [c_void_p] * 7 + [c_int32, c_void_p, c_void_p,
+                                          c_void_p, c_int32, c_void_p, c_void_p] + [c_float] * 5 + [c_int32] * 3
+                           + [c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "lograst_lod_select_read": (ctypes.c_int, [c_void_p] + [ctypes.POINTER(c_uint32)] * 4 + [c_void_p]),
+    "lograst_clamp_scale": (ctypes.c_int, [c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "lograst_id_histogram_scratch_bytes": (c_size_t, [c_int32]),
     "lograst_id_histogram": (ctypes.c_int, [c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "lograst_id_histogram_read": (ctypes.c_int, [c_void_p, ctypes.POINTER(c_uint32), c_void_p]),

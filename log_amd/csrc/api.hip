@@ -922,6 +922,106 @@ int lograst_lod_read(const void* scratch, uint32_t* count_host, uint32_t* overfl
   return LOGRAST_OK;
 }
 
+// ---- view preparation (prepare.hip) --------------------------------------------------------------------------
+size_t lograst_frustum_scratch_bytes(int32_t n) { return lr_frustum_scratch_bytes(n); }
+
+int lograst_frustum_select(int32_t n, int32_t num_points, const float* xyz, const int32_t* rows, const float* full_proj,
+                           double padding, const float* scaling, const float* rotation, const float* opacity,
+                           uint8_t* flag_out, int64_t* pos_out, int64_t* row_out, float* xyz_out, float* scaling_out,
+                           float* rotation_out, float* opacity_out, void* scratch, size_t scratch_bytes, void* stream) {
+  if (n < 0 || num_points < 0) return lr_fail(LOGRAST_ERR_ARG, "negative count");
+  if (!rows && n > num_points) return lr_fail(LOGRAST_ERR_ARG, "more entries than points without a row list");
+  if (!scratch || scratch_bytes < lr_frustum_scratch_bytes(n)) return lr_fail(LOGRAST_ERR_ARG, "frustum scratch too small");
+  if (n > 0 && (!xyz || !full_proj || !flag_out || !pos_out)) return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
+  const bool act = scaling || rotation || opacity || xyz_out || scaling_out || rotation_out || opacity_out;
+  if (act && (!scaling || !rotation || !opacity || !xyz_out || !scaling_out || !rotation_out || !opacity_out))
+    return lr_fail(LOGRAST_ERR_ARG, "the raw parameters and the four activated outputs go together");
+  if (!(padding == padding)) return lr_fail(LOGRAST_ERR_ARG, "padding is NaN");
+  g_prof_call++;
+  // torch narrows the Python doubles -1 - padding and 1. + padding to the tensor's fp32 before it compares
+  LR_HIP(lr_launch_frustum(n, num_points, xyz, rows, full_proj, (float)(-1.0 - padding), (float)(1.0 + padding), scaling,
+                           rotation, opacity, flag_out, pos_out, row_out, xyz_out, scaling_out, rotation_out, opacity_out,
+                           scratch, (hipStream_t)stream));
+  return LOGRAST_OK;
+}
+
+int lograst_frustum_read(const void* scratch, uint32_t* count_host, void* stream) {
+  if (!scratch || !count_host) return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
+  uint32_t w = 0;
+  LR_HIP(hipMemcpyAsync(&w, scratch, sizeof(w), hipMemcpyDeviceToHost, (hipStream_t)stream));
+  LR_HIP(hipStreamSynchronize((hipStream_t)stream));
+  *count_host = w;
+  return LOGRAST_OK;
+}
+
+static size_t lr_select_roots_bytes(int32_t num_roots) { return 8 * (((size_t)(num_roots > 0 ? num_roots : 0) + 1) & ~(size_t)1); }
+
+size_t lograst_lod_select_scratch_bytes(int32_t num_roots, int32_t num_nodes, int32_t max_child, uint32_t out_capacity) {
+  return lr_lod_scratch_bytes(num_roots, num_nodes, max_child > 0 ? max_child : 1) + lr_select_roots_bytes(num_roots) +
+         lr_partition_scratch_bytes(out_capacity);
+}
+
+int lograst_lod_select(int32_t num_points, int32_t num_nodes, int32_t max_child, const int32_t* node_index,
+                       const int32_t* tree, const int8_t* depth, const float* xyz, const float* scaling,
+                       const float* rotation, const int64_t* root_rows, int32_t num_roots, const float* root_weight,
+                       const int64_t* root_pos, uint8_t* root_flag, int32_t num_root_flags, const float* projmatrix,
+                       const float* viewmatrix, float focal_x, float focal_y, float tanfovx, float tanfovy,
+                       float min_resolution_pixel, int32_t levels, int32_t opt_all_levels, int32_t current_depth,
+                       int64_t* out_index, uint32_t out_capacity, int64_t* out_leaf, int64_t* out_node, void* scratch,
+                       size_t scratch_bytes, void* stream) {
+  if (num_points < 0 || num_nodes < 0 || num_roots < 0 || num_root_flags < 0) return lr_fail(LOGRAST_ERR_ARG, "negative count");
+  if (max_child < 1) return lr_fail(LOGRAST_ERR_ARG, "max_child must be >= 1");
+  if ((uint64_t)num_nodes * (uint64_t)max_child > 0x7fffffffull) return lr_fail(LOGRAST_ERR_ARG, "tree too large");
+  if (!scratch || scratch_bytes < lograst_lod_select_scratch_bytes(num_roots, num_nodes, max_child, out_capacity))
+    return lr_fail(LOGRAST_ERR_ARG, "lod scratch too small");
+  if (num_roots > 0 && (!root_rows || !node_index || !depth || !xyz || !scaling || !rotation || !projmatrix || !viewmatrix ||
+                        !out_index || !out_leaf || !out_node))
+    return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
+  if (num_nodes > 0 && !tree) return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
+  if (root_weight && num_roots > 0 && (!root_pos || !root_flag)) return lr_fail(LOGRAST_ERR_ARG, "root_weight needs root_pos and root_flag");
+  if (levels < 0) levels = 0;
+  if (levels > lr_lod_max_levels()) levels = lr_lod_max_levels();
+  hipStream_t s = (hipStream_t)stream;
+  char* base = reinterpret_cast<char*>(scratch);
+  const size_t lod_bytes = lr_lod_scratch_bytes(num_roots, num_nodes, max_child);
+  int64_t* roots = reinterpret_cast<int64_t*>(base + lod_bytes);
+  uint32_t* part_chunk = reinterpret_cast<uint32_t*>(base + lod_bytes + lr_select_roots_bytes(num_roots));
+  uint32_t* hdr = reinterpret_cast<uint32_t*>(scratch) + lr_lod_total_word();
+  g_prof_call++;
+  if (root_weight) LR_HIP(lr_launch_root_filter(num_roots, root_rows, root_weight, root_pos, root_flag, num_root_flags, roots, s));
+  LR_HIP(lr_launch_lod(num_points, num_nodes, max_child, node_index, tree, xyz, scaling, rotation,
+                       root_weight ? roots : root_rows, num_roots, projmatrix, viewmatrix, focal_x, focal_y, tanfovx, tanfovy,
+                       min_resolution_pixel, levels, out_index, out_capacity, scratch, s));
+  if (num_roots > 0)
+    LR_HIP(lr_launch_partition(out_index, hdr, out_capacity, node_index, depth, num_points, opt_all_levels != 0,
+                               current_depth, out_leaf, out_node, part_chunk, hdr + 3, s));
+  return LOGRAST_OK;
+}
+
+int lograst_lod_select_read(const void* scratch, uint32_t* count_all_host, uint32_t* count_leaf_host,
+                            uint32_t* overflow_host, uint32_t* frontier_left_host, void* stream) {
+  if (!scratch || !count_all_host || !count_leaf_host) return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
+  uint32_t w[4] = {0, 0, 0, 0};
+  LR_HIP(hipMemcpyAsync(w, reinterpret_cast<const uint32_t*>(scratch) + lr_lod_total_word(), sizeof(w),
+                        hipMemcpyDeviceToHost, (hipStream_t)stream));
+  LR_HIP(hipStreamSynchronize((hipStream_t)stream));
+  *count_all_host = w[0];
+  *count_leaf_host = w[3];
+  if (overflow_host) *overflow_host = w[1];
+  if (frontier_left_host) *frontier_left_host = w[2];
+  return LOGRAST_OK;
+}
+
+int lograst_clamp_scale(int32_t m, const int64_t* index, const uint8_t* flag, int32_t num_points, float* scaling,
+                        const float* radius3d_min, const float* radius3d_max, void* stream) {
+  if (m < 0 || num_points < 0) return lr_fail(LOGRAST_ERR_ARG, "negative count");
+  if (m == 0) return LOGRAST_OK;
+  if (!index || !scaling || !radius3d_min || !radius3d_max) return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
+  g_prof_call++;
+  LR_HIP(lr_launch_clamp_scale(m, index, flag, num_points, scaling, radius3d_min, radius3d_max, (hipStream_t)stream));
+  return LOGRAST_OK;
+}
+
 size_t lograst_id_histogram_scratch_bytes(int32_t n) { return lr_hist_scratch_bytes(n); }
 
 int lograst_id_histogram(int32_t n, const int32_t* point_id_pixel, int32_t num_pixels, int32_t* ids_out,

@@ -318,6 +318,9 @@ LR_DEV void lr_normalize4(float q[4]) {
   q[0] = q[0] / d; q[1] = q[1] / d; q[2] = q[2] / d; q[3] = q[3] / d;
 }
 
+// torch.sigmoid on one opacity, as the gather kernel (sh.hip) and the frustum selection (prepare.hip) activate it
+LR_DEV float ga_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
+
 // ---- alpha-support test against a pixel box, prepared once per Gaussian ------------------------------
 // Can the Gaussian reach alpha >= 1/255 anywhere in the pixel box [x0,x1]x[y0,y1]?  Same conservative rule as
 // blend.hip:lr_support_hits (level set 0.5 d^T Q d <= 1.01 ln(255 opacity) + 0.01, "yes" whenever the fp32

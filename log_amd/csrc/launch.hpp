@@ -86,7 +86,25 @@ hipError_t lr_launch_lod(int num_points, int num_nodes, int max_child, const int
                          float tanfovy, float min_px, int levels, int64_t* out, uint32_t out_capacity, void* scratch,
                          hipStream_t s);
 int lr_lod_max_levels();
-uint32_t lr_lod_total_word();   // header words TOTAL, OVERFLOW, LEFT are consecutive
+uint32_t lr_lod_total_word();   // header words TOTAL, OVERFLOW, LEFT are consecutive; the next one is cleared by every
+                                // traversal and otherwise unused by lod.hip: lograst_lod_select keeps the leaf count there
+
+// prepare.hip
+size_t lr_frustum_scratch_bytes(int n);   // word 0: the kept count
+// rows == NULL: entry i is row i; scaling == NULL: no activated outputs (then rotation, opacity and the four o_* are NULL too)
+hipError_t lr_launch_frustum(int n, int num_points, const float* xyz, const int32_t* rows, const float* proj, float lo,
+                             float hi, const float* scaling, const float* rotation, const float* opacity, uint8_t* flag,
+                             int64_t* pos, int64_t* row_out, float* o_xyz, float* o_scaling, float* o_rotation,
+                             float* o_opacity, void* scratch, hipStream_t s);
+hipError_t lr_launch_root_filter(int k_roots, const int64_t* rows, const float* weight, const int64_t* pos,
+                                 uint8_t* root_flag, int num_flags, int64_t* rows_out, hipStream_t s);
+size_t lr_partition_scratch_bytes(uint32_t capacity);
+// n_dev: the list's length, on the device (capped at capacity); leaf_total: where the number of leaves goes
+hipError_t lr_launch_partition(const int64_t* list, const uint32_t* n_dev, uint32_t capacity, const int32_t* node_index,
+                               const int8_t* depth, int num_points, int all_levels, int current_depth, int64_t* out_leaf,
+                               int64_t* out_node, uint32_t* chunk, uint32_t* leaf_total, hipStream_t s);
+hipError_t lr_launch_clamp_scale(int m, const int64_t* index, const uint8_t* flag, int num_points, float* scaling,
+                                 const float* rmin, const float* rmax, hipStream_t s);
 
 // counter.hip
 size_t lr_hist_scratch_bytes(int n);

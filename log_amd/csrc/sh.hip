@@ -194,8 +194,6 @@ void lr_launch_sh_bwd(int N, int deg, int M, const float* means, const float* ca
 // turns the rasterizer's input gradients into the gradients of the raw copies.
 // LoG's SH layout: colors[P,3] is the DC term, shs[P,K,3] the K = (max_degree+1)^2 - 1 higher coefficients, no clamp.
 
-LR_DEV float ga_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
-
 __global__ void __launch_bounds__(256)
 ga_fwd_kernel(GatherArgs a) {
   extern __shared__ float lr_sh_lds[];  // 4 waves x (64 rows x (L+1) floats)
