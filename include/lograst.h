@@ -701,6 +701,119 @@ int lograst_depth_loss_backward(int32_t height, int32_t width, const float* pred
                                 const float* gt, const int64_t* gt_strides, const float* acc, const int64_t* acc_strides,
                                 int32_t n, const void* records, const float* grad_loss, float* grad_pred, void* stream);
 
+/* ---- densification decisions: LoG.update_depth_stage / update_init_stage up to the flags -------------------------
+ * (LoG/model/level_of_gaussian.py:400-427, :454-508).  One event is: lograst_decide_depth or lograst_decide_init (the
+ * flags, every count and statistic the reference logs and, for the depth stage, the top-k cut, all on `stream`), then
+ * lograst_decide_read -- the only host synchronisation -- and, after the caller has resized the model with the flags,
+ * lograst_decide_child_radius_max.  No call allocates.  p = 0 is legal.
+ *
+ * A statistic is what Counter.str_min_mean_max prints of a population x (fp32): count, min, max (NaN if any x is NaN)
+ * and the sums of x and x * x in double, from which mean = sum / count and the unbiased std =
+ * sqrt((sumsq - sum * sum / count) / (count - 1)).  The sums are formed per workgroup and combined in a fixed order by one
+ * workgroup, without floating-point atomics: the same inputs give the same bits.  count == 0: min = +inf, max = -inf. */
+typedef struct lograst_decide_stat {
+  double sum, sumsq;
+  float min, max;
+  uint32_t count, reserved;
+} lograst_decide_stat;
+
+#define LOGRAST_DECIDE_DEPTH_BINS 256   /* bin = depth + 128 (depth is int8) */
+/* counts[] of the depth stage */
+#define LOGRAST_DECIDE_SPLIT_GRAD 0     /* rows with grad > split_grad_thres */
+#define LOGRAST_DECIDE_SPLIT_RADII 1    /* rows with radii_max_max > radius2d_thres */
+#define LOGRAST_DECIDE_CANDIDATES 2     /* rows of flag_split before the cut */
+#define LOGRAST_DECIDE_REMOVED 3        /* rows of flag_remove */
+#define LOGRAST_DECIDE_DEPTH_LT 4       /* rows with depth < current_depth */
+/* counts[] of the init stage */
+#define LOGRAST_DECIDE_REMOVE_WEIGHT 0  /* weights_max < init_weight_min */
+#define LOGRAST_DECIDE_NONMAX 1         /* weights_max < sigmoid(opacity) * 0.1 */
+#define LOGRAST_DECIDE_REMOVE_SMALL 2   /* radii_max_max < small_thres, before the random half is taken */
+#define LOGRAST_DECIDE_INIT_SPLIT_GRAD 3
+#define LOGRAST_DECIDE_INIT_SPLIT_RADII 4
+typedef struct lograst_decide_record {
+  uint32_t counts[8];
+  /* the cut (depth stage): num_max_split = min(int(fp32(counts[DEPTH_LT]) * 0.05f), max_split_points); need_cut =
+   * counts[CANDIDATES] > num_max_split.  With need_cut and num_max_split > 0, cut_value is the num_max_split-th largest
+   * radii_max_max among the candidates, cut_thres = (float)cut_value, and flag_split keeps the candidates with
+   * (float)radii_max_max >= cut_thres (ties stay).  With need_cut and num_max_split == 0 no cut is applied (the
+   * reference raises there: callers fall back). */
+  uint32_t need_cut, num_max_split;
+  int32_t cut_value;
+  float cut_thres;
+  uint32_t depth_all[LOGRAST_DECIDE_DEPTH_BINS];      /* every row, by depth */
+  uint32_t depth_split[LOGRAST_DECIDE_DEPTH_BINS];    /* rows of the final flag_split with depth < max_level */
+  uint32_t depth_remove[LOGRAST_DECIDE_DEPTH_BINS];   /* rows of flag_remove */
+  /* depth stage: opacity, ratio, grad, radii over the is_parent rows.  init stage: radii_max over the activated rows,
+   * grad over all rows, radii_max over the rows of flag_split, radius3d_min as it will be after the resize (rows that are
+   * neither split nor removed once, split rows `children` times). */
+  lograst_decide_stat stats[4];
+} lograst_decide_record;
+
+/* lograst_decide_depth.  Per row i < p:
+ *   grad      = grad_sum / (float)max(area_sum, 1)                      (one correctly rounded fp32 division)
+ *   is_parent = node_index == -1 && depth < current_depth
+ *   remove    = node_index == -1 && depth > 0 && weights_max < remove_weights_thres && visible_count > 1
+ *   split     = grad > split_grad_thres && (float)radii_max_max > radius2d_thres && is_parent &&
+ *               create_steps > min_steps_split && !remove,   then the cut (lograst_decide_record).
+ * opacity = 1 / (1 + expf(-raw)), ratio = max / (((e0 + e1) + e2) - max - min) of e = expf(scaling): the expressions of
+ * lograst_gather_activate.  flag_split / flag_remove: u8[p] (torch bool), written for every row. */
+typedef struct lograst_decide_depth_args {
+  const float* opacity;            /* f32 [p] raw (column 0 of [p, 1]) */
+  const float* scaling;            /* f32 [p, 3] raw */
+  const int32_t* node_index;       /* i32 [p] */
+  const int8_t* depth;             /* i8  [p] */
+  const int32_t* create_steps;     /* i32 [p] */
+  const float* grad_sum;           /* f32 [p] */
+  const int32_t* area_sum;         /* i32 [p] */
+  const int32_t* radii_max_max;    /* i32 [p] */
+  const float* weights_max;        /* f32 [p] */
+  const int16_t* visible_count;    /* i16 [p] */
+  int32_t current_depth, max_level, min_steps_split, max_split_points;
+  float split_grad_thres, radius2d_thres, remove_weights_thres;
+  uint8_t* flag_split;             /* out u8 [p] */
+  uint8_t* flag_remove;            /* out u8 [p] */
+} lograst_decide_depth_args;
+
+/* lograst_decide_init (init_split_method 'split_by_2d').  Per row:
+ *   remove     = weights_max < init_weight_min || weights_max < sigmoid(opacity) * 0.1f ||
+ *                ((float)radii_max_max < small_thres && rand > 0.5f)
+ *   activation = create_steps > min_steps && radii_max_max > 0
+ *   split      = activation && ((float)radii_max_max > split_thres_sq ||
+ *                (grad > grad_thres && (float)radii_max_max > radius_thres)) && !remove
+ * The caller forms the thresholds from the configuration in double, as Python does, and narrows them once. */
+typedef struct lograst_decide_init_args {
+  const float* opacity;            /* f32 [p] raw */
+  const int32_t* create_steps;     /* i32 [p] */
+  const float* grad_sum;           /* f32 [p] */
+  const int32_t* area_sum;         /* i32 [p] */
+  const int32_t* radii_max_max;    /* i32 [p] */
+  const float* weights_max;        /* f32 [p] */
+  const float* rand;               /* f32 [p]: torch.rand_like(weights_max) */
+  const float* radius3d_min;       /* f32 [p] */
+  int32_t min_steps, children;
+  float init_weight_min;           /* init_weight_min */
+  float small_thres;               /* (init_radius_min * scale) ** 2 */
+  float split_thres_sq;            /* (init_radius_split * scale) ** 2 */
+  float grad_thres;                /* 10 * split_grad_thres */
+  float radius_thres;              /* init_radius_min * scale * 8 */
+  uint8_t* flag_split;             /* out u8 [p] */
+  uint8_t* flag_remove;            /* out u8 [p] */
+} lograst_decide_init_args;
+
+/* scratch: lograst_decide_scratch_bytes(p) bytes, 16-byte aligned, uninitialised, kept until lograst_decide_read. */
+size_t lograst_decide_scratch_bytes(int32_t p);
+int lograst_decide_depth(int32_t p, const lograst_decide_depth_args* args, void* scratch, size_t scratch_bytes, void* stream);
+int lograst_decide_init(int32_t p, const lograst_decide_init_args* args, void* scratch, size_t scratch_bytes, void* stream);
+/* Copies the record of the last lograst_decide_depth / _init on this scratch to the host and synchronises the stream.
+ * record_bytes must be sizeof(lograst_decide_record). */
+int lograst_decide_read(const void* scratch, lograst_decide_record* record_host, size_t record_bytes, void* stream);
+/* After the resize of a depth-stage event (the split rows stay, their children are the last num_children rows):
+ * radius3d_max[j] = scaling_decay * max(expf(scaling[index_parent[j]])) for the rows j >= num_points - num_children
+ * (level_of_gaussian.py:516-519).  index_parent i32[num_points], scaling f32[num_points, 3], radius3d_max
+ * f32[num_points]; a row whose parent is out of range is left alone. */
+int lograst_decide_child_radius_max(int32_t num_points, int32_t num_children, const int32_t* index_parent,
+                                    const float* scaling, float scaling_decay, float* radius3d_max, void* stream);
+
 /* ---- per-kernel timing with HIP events on the launch stream (used by bench.py) -----------------
  * When enabled every kernel launch is bracketed by hipEventRecord on its stream.  read() synchronises
  * the recorded events and returns, for kernel slot i < LOGRAST_NUM_KERNELS, accumulated milliseconds

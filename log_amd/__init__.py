@@ -17,7 +17,7 @@ def install_compute_radius():
 
 
 def install_all(fused_step=False, fused_loss=False, reuse_geometry=False, fused_depth_loss=False, device_densify=False,
-                device_prepare=False):
+                device_prepare=False, device_decide=False):
     """Everything a LoG process needs, in one call: the LoG.cuda.compute_radius module, then every
     drop-in method assigned onto LoG's own classes (needs LoG importable): LoG.get_all, TensorTree.traverse,
     Counter.update_by_output, SparseOptimizer.step.
@@ -38,7 +38,10 @@ def install_all(fused_step=False, fused_loss=False, reuse_geometry=False, fused_
     device_prepare (opt-in): LoG.prepare, Gaussian.prepare, LoG.clamp_scale and LoG.step run their frustum test, root filter,
     leaf / node split and scale clamp on the device (log_amd.prepare.install: two host synchronisations per view, none per
     step, no activation of all points to index out the roots); without it they stay the reference's torch code around the
-    installed TensorTree.traverse."""
+    installed TensorTree.traverse.
+    device_decide (opt-in): LoG.update_depth_stage and LoG.update_init_stage compute their split / remove flags, the top-k cut
+    and every logged statistic on the device (log_amd.decide.install: one read-back of a fixed-size record per event), then
+    call the installed split_and_remove methods; without it the decisions stay the reference's torch code."""
     install_compute_radius()
     from . import rasterizer
     rasterizer.set_geometry_reuse(bool(reuse_geometry))
@@ -57,4 +60,7 @@ def install_all(fused_step=False, fused_loss=False, reuse_geometry=False, fused_
     if device_prepare:
         from . import prepare
         installed.append(prepare.install())
+    if device_decide:
+        from . import decide
+        installed.append(decide.install())
     return installed

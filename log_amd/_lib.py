@@ -48,6 +48,41 @@ class LograstMoveKey(ctypes.Structure):
 MOVE_COPY_PARENT, MOVE_ZERO, MOVE_SKIP = 0, 1, 2   # LOGRAST_MOVE_*
 
 
+class LograstDecideStat(ctypes.Structure):
+    """struct lograst_decide_stat (include/lograst.h)."""
+    _fields_ = [("sum", ctypes.c_double), ("sumsq", ctypes.c_double), ("min", c_float), ("max", c_float),
+                ("count", c_uint32), ("reserved", c_uint32)]
+
+
+DECIDE_DEPTH_BINS = 256   # LOGRAST_DECIDE_DEPTH_BINS
+
+
+class LograstDecideRecord(ctypes.Structure):
+    """struct lograst_decide_record (include/lograst.h)."""
+    _fields_ = [("counts", c_uint32 * 8), ("need_cut", c_uint32), ("num_max_split", c_uint32), ("cut_value", c_int32),
+                ("cut_thres", c_float), ("depth_all", c_uint32 * DECIDE_DEPTH_BINS),
+                ("depth_split", c_uint32 * DECIDE_DEPTH_BINS), ("depth_remove", c_uint32 * DECIDE_DEPTH_BINS),
+                ("stats", LograstDecideStat * 4)]
+
+
+class LograstDecideDepthArgs(ctypes.Structure):
+    """struct lograst_decide_depth_args (include/lograst.h)."""
+    _fields_ = [(k, c_void_p) for k in ("opacity", "scaling", "node_index", "depth", "create_steps", "grad_sum", "area_sum",
+                                        "radii_max_max", "weights_max", "visible_count")] + \
+               [(k, c_int32) for k in ("current_depth", "max_level", "min_steps_split", "max_split_points")] + \
+               [(k, c_float) for k in ("split_grad_thres", "radius2d_thres", "remove_weights_thres")] + \
+               [("flag_split", c_void_p), ("flag_remove", c_void_p)]
+
+
+class LograstDecideInitArgs(ctypes.Structure):
+    """struct lograst_decide_init_args (include/lograst.h)."""
+    _fields_ = [(k, c_void_p) for k in ("opacity", "create_steps", "grad_sum", "area_sum", "radii_max_max", "weights_max",
+                                        "rand", "radius3d_min")] + \
+               [("min_steps", c_int32), ("children", c_int32)] + \
+               [(k, c_float) for k in ("init_weight_min", "small_thres", "split_thres_sq", "grad_thres", "radius_thres")] + \
+               [("flag_split", c_void_p), ("flag_remove", c_void_p)]
+
+
 class LograstError(RuntimeError):
     pass
 
@@ -153,6 +188,11 @@ _SIGNATURES = {
                                                  ctypes.POINTER(LograstMoveKey), c_void_p]),
     "lograst_densify_split_uniform": (ctypes.c_int, [c_int32, c_int32, c_int32, c_float, c_int32] + [c_void_p] * 7),
     "lograst_densify_tree": (ctypes.c_int, [c_int32] * 5 + [c_void_p] * 14),
+    "lograst_decide_scratch_bytes": (c_size_t, [c_int32]),
+    "lograst_decide_depth": (ctypes.c_int, [c_int32, ctypes.POINTER(LograstDecideDepthArgs), c_void_p, c_size_t, c_void_p]),
+    "lograst_decide_init": (ctypes.c_int, [c_int32, ctypes.POINTER(LograstDecideInitArgs), c_void_p, c_size_t, c_void_p]),
+    "lograst_decide_read": (ctypes.c_int, [c_void_p, ctypes.POINTER(LograstDecideRecord), c_size_t, c_void_p]),
+    "lograst_decide_child_radius_max": (ctypes.c_int, [c_int32, c_int32, c_void_p, c_void_p, c_float, c_void_p, c_void_p]),
     "lograst_activate_backward_adam": (ctypes.c_int, [c_int32] + [c_void_p] * 4 + [c_int32, c_int32] + [c_void_p] * 6 +
                                        [c_int32, c_void_p, c_void_p, ctypes.POINTER(LograstAdamKey), ctypes.c_double,
                                         ctypes.c_double, ctypes.c_double, ctypes.c_double, c_void_p]),

@@ -15,6 +15,7 @@
 
 #include "common.hpp"
 #include "launch.hpp"
+#include "decide.hpp"
 
 static thread_local std::string g_err;
 static int lr_fail(int code, const std::string& msg) {
@@ -1338,6 +1339,64 @@ int lograst_densify_tree(int32_t p, int32_t num_nodes, int32_t children, int32_t
   a.p = p; a.num_nodes = num_nodes; a.children = children; a.num_keep = num_keep; a.num_split = num_split;
   g_prof_call++;
   LR_HIP(lr_launch_densify_tree(a, (hipStream_t)stream));
+  return LOGRAST_OK;
+}
+
+// ---- densification decisions (decide.hip) ------------------------------------------------------------------
+size_t lograst_decide_scratch_bytes(int32_t p) { return lr_decide_scratch_bytes(p); }
+
+static int lr_decide_common(int32_t p, const void* args, const void* scratch, size_t scratch_bytes) {
+  if (p < 0) return lr_fail(LOGRAST_ERR_ARG, "negative row count");
+  if (!args) return lr_fail(LOGRAST_ERR_ARG, "args is NULL");
+  if (!scratch || scratch_bytes < lr_decide_scratch_bytes(p)) return lr_fail(LOGRAST_ERR_ARG, "decide scratch too small");
+  if (reinterpret_cast<uintptr_t>(scratch) & 15u) return lr_fail(LOGRAST_ERR_ARG, "decide scratch must be 16-byte aligned");
+  return LOGRAST_OK;
+}
+
+int lograst_decide_depth(int32_t p, const lograst_decide_depth_args* args, void* scratch, size_t scratch_bytes, void* stream) {
+  if (lr_decide_common(p, args, scratch, scratch_bytes)) return LOGRAST_ERR_ARG;
+  const lograst_decide_depth_args& a = *args;
+  if (p > 0 && (!a.opacity || !a.scaling || !a.node_index || !a.depth || !a.create_steps || !a.grad_sum || !a.area_sum ||
+                !a.radii_max_max || !a.weights_max || !a.visible_count || !a.flag_split || !a.flag_remove))
+    return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
+  if (p > 0 && a.flag_split == a.flag_remove) return lr_fail(LOGRAST_ERR_ARG, "flag_split and flag_remove need their own storage");
+  if (a.current_depth < -128 || a.current_depth > 128 || a.max_level < -128 || a.max_level > 128)
+    return lr_fail(LOGRAST_ERR_ARG, "current_depth / max_level outside -128..128 (depth is int8: clip them)");
+  g_prof_call++;
+  LR_HIP(lr_launch_decide_depth(p, a, scratch, (hipStream_t)stream));
+  return LOGRAST_OK;
+}
+
+int lograst_decide_init(int32_t p, const lograst_decide_init_args* args, void* scratch, size_t scratch_bytes, void* stream) {
+  if (lr_decide_common(p, args, scratch, scratch_bytes)) return LOGRAST_ERR_ARG;
+  const lograst_decide_init_args& a = *args;
+  if (p > 0 && (!a.opacity || !a.create_steps || !a.grad_sum || !a.area_sum || !a.radii_max_max || !a.weights_max ||
+                !a.rand || !a.radius3d_min || !a.flag_split || !a.flag_remove))
+    return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
+  if (p > 0 && a.flag_split == a.flag_remove) return lr_fail(LOGRAST_ERR_ARG, "flag_split and flag_remove need their own storage");
+  if (a.children < 1 || a.children > 8) return lr_fail(LOGRAST_ERR_ARG, "children must be 1..8");
+  g_prof_call++;
+  LR_HIP(lr_launch_decide_init(p, a, scratch, (hipStream_t)stream));
+  return LOGRAST_OK;
+}
+
+int lograst_decide_read(const void* scratch, lograst_decide_record* record_host, size_t record_bytes, void* stream) {
+  if (!scratch || !record_host) return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
+  if (record_bytes != sizeof(lograst_decide_record)) return lr_fail(LOGRAST_ERR_ARG, "record_bytes is not sizeof(lograst_decide_record)");
+  LR_HIP(hipMemcpyAsync(record_host, scratch, sizeof(lograst_decide_record), hipMemcpyDeviceToHost, (hipStream_t)stream));
+  LR_HIP(hipStreamSynchronize((hipStream_t)stream));
+  return LOGRAST_OK;
+}
+
+int lograst_decide_child_radius_max(int32_t num_points, int32_t num_children, const int32_t* index_parent,
+                                    const float* scaling, float scaling_decay, float* radius3d_max, void* stream) {
+  if (num_points < 0 || num_children < 0) return lr_fail(LOGRAST_ERR_ARG, "negative row count");
+  if (num_children > num_points) return lr_fail(LOGRAST_ERR_ARG, "more children than rows");
+  if (num_children == 0) return LOGRAST_OK;
+  if (!index_parent || !scaling || !radius3d_max) return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
+  g_prof_call++;
+  LR_HIP(lr_launch_child_radius_max(num_points, num_children, index_parent, scaling, scaling_decay, radius3d_max,
+                                    (hipStream_t)stream));
   return LOGRAST_OK;
 }
 
