@@ -33,7 +33,7 @@ extern "C" {
  * (band views keep the compact live-row list there); (c) point_list tails of streamed lists (> 4096 keys) are unspecified
  * until lograst_finish_lists, which now checks that `keys` is the buffer the forward filled and synchronises the stream;
  * (d) lograst_view gained hit_masks / hit_mask_words / hit_mask_form: an optional buffer in which the forward leaves its
- * per-chunk support ballots for the reverse walk (below); new entry points: lograst_hit_mask_bytes, lograst_forward_form,
+ * per-chunk hit masks for the reverse walk (below); new entry points: lograst_hit_mask_bytes, lograst_forward_form,
  * lograst_pack_rows_clear, lograst_unpack_rows(atomic = 2), lograst_activate_backward_adam.  Added later in round 6 without a
  * version change (new entry points only): lograst_pack_rows_hinted, lograst_add_visible, lograst_add_visible_n.
  * 2: lograst_view gained cov3d_precomp / dl_dcov3d; 3: the backward accumulates into 64-byte rows (bwd_rows); lograst_view gained walk_form.  Added since without a version change (new entry points only): lograst_sparse_segment_floats / lograst_pack_rows / lograst_unpack_rows / lograst_ordered_lengths / lograst_finish_lists.
@@ -110,9 +110,11 @@ typedef struct lograst_view {
    * from earlier forwards (forward) or from this view's forward (backward). */
   int32_t walk_form;
   /* Optional (version 4; NULL = off): a buffer in which the forward's compositing kernels leave, per wave and 64-entry chunk
-   * of a tile list they walked, the ballot of their support tests, and from which the reverse walk of lograst_backward
-   * takes its visits instead of running the tests (and gathering every record of a chunk) again -- same decisions, same
-   * sums.  Device, 32-byte aligned, hit_mask_words 64-bit words >= lograst_hit_mask_bytes(capacity, width, height) / 8,
+   * of a tile list they walked, which entries contributed -- row-split form: per 4x4 block, the entries some pixel of the
+   * block accumulated (LOGRAST_HIT_MASKS=2: the ballot of the support tests, a superset); quadrant form: the ballot of
+   * the support tests -- and from which the reverse walk of lograst_backward takes its visits instead of running the tests
+   * (and gathering every record of a chunk) again.  A visit the masks leave out adds exactly zero to every sum: same
+   * gradients up to the order of the float atomics.  Device, 32-byte aligned, hit_mask_words 64-bit words >= lograst_hit_mask_bytes(capacity, width, height) / 8,
    * uninitialised; the backward must be given the very buffer (contents untouched) of the forward whose tile_state it is
    * handed.  Speed only: 30 M Gaussians, reverse walk 640 -> see DESIGN.md section 4. */
   uint64_t* hit_masks;

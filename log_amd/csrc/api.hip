@@ -38,7 +38,7 @@ static int lr_env_int(const char* name, int dflt) {
 struct LrKnobInfo { LrKnob id; const char* name; int dflt, lo, hi; const char* what; };
 static constexpr LrKnobInfo kKnobs[] = {
     {LRKNOB_HELPER_MIN_N, "LOGRAST_HELPER_MIN_N", 4000000, 0, 2000000000, "Gaussians from which the helper passes (absolute slot table, touched-only dL/dconic clearing, separate zero-fill kernels) pay for their launches"},
-    {LRKNOB_HIT_MASKS, "LOGRAST_HIT_MASKS", 1, 0, 1, "the compositing kernels leave their per-chunk support ballots in lograst_view.hit_masks (when the caller provides it) and the reverse walk reads them instead of running the tests again; 0 = ignore the buffer"},
+    {LRKNOB_HIT_MASKS, "LOGRAST_HIT_MASKS", 1, 0, 2, "the compositing kernels leave their per-chunk hit masks in lograst_view.hit_masks (when the caller provides it) and the reverse walk reads them instead of running the support tests again: 1 = row-split form records the entries some pixel of the 4x4 block accumulated (quadrant form: the support ballots), 2 = the support ballots in both forms (a superset: same gradients, more visits); 0 = ignore the buffer"},
     {LRKNOB_LAZY_SORT, "LOGRAST_LAZY_SORT", 1, 0, 1, "lists of more than 4096 keys are ordered over their first window (7680 positions) only; tiles whose walk needs more are marked by the compositing kernels and finished by a second, normally idle sort + compositing pair; 0 = every list to its end up front"},
     {LRKNOB_PBWD_LIST, "LOGRAST_PBWD_LIST", 1, 0, 2, "large inputs with running-sum gradients: the chain rule runs over a compact list of the rows with point_weight > 0 (a streaming compaction pass + a list pass) instead of one kernel that tests every row: 0 never, 1 on band views, 2 always"},
     {LRKNOB_MID_RANK, "LOGRAST_MID_RANK", 1, 0, 1, "rects of 5..16 tiles are RANKED by the batched projection (LDS atomics; 32-byte rank rows in geom), so the fill places them without cursor atomics or support tests; 0 = counted only, placed through the per-tile cursors"},

@@ -154,6 +154,13 @@ LR_DEV void lr_lazy_resume(const LrView& v, size_t pix, bool& done, float& T, fl
 // form; only the chunks it really walked: a few per cent of a long list) and the reverse walk, now walking the list in the
 // forward's chunks (aligned to multiples of 64 instead of to its deepest contributor), loads them through the scalar cache,
 // gathers only the records whose bit is set and runs no support test.  Same decisions, so the same visits and the same sums.
+// The row-split forward goes one step further (LOGRAST_HIT_MASKS=1, the default; 2 = the support ballots as before): a block's mask holds the entries some pixel of
+// the block ACCUMULATED (w > 0) -- collected during the pass loop, where the row maxima for point_weight already say so --
+// instead of the support ballot.  An entry whose region passes between the block's pixel centres, that meets only saturated
+// pixels, or that lies behind every pixel's last contributor had a support bit, took one of the eight slots of a reverse
+// pass and committed nine zeros (a full memory-side line operation); forward `acc` and backward `hit` are the same predicate
+// on the same op sequence, so leaving those visits out changes no sum beyond the order of the float atomics.  A row whose
+// pixels are all saturated leaves zero masks from there on.  (Quadrant form: support ballots, as before.)
 // Slot of (tile, chunk c): (offsets[tile] >> 6) + tile + c -- disjoint for all tiles (floor(L / 64) + 1 >= ceil(L / 64)),
 // at most capacity / 64 + tiles + 1 slots; a slot holds 16 words (row-split: [wave][block]) or 4 (quadrant: [wave]).
 // Which form wrote them: lograst_view.hit_mask_form of the backward's view (the caller knows what its forward launched:
@@ -889,7 +896,8 @@ lr_blend_fwd_rows_kernel(LrView v, const float4* __restrict__ geom, const uint32
                          float* __restrict__ image, float* __restrict__ final_T, int* __restrict__ n_contrib,
                          int* __restrict__ pid, float* __restrict__ pwp, float* __restrict__ pw,
                          float4* __restrict__ zero_rows, int xcd_mode, int cull, uint32_t* __restrict__ lazy_state,
-                         int lazy, uint64_t* __restrict__ masks, uint32_t* __restrict__ hdr_w, int block_test) {
+                         int lazy, uint64_t* __restrict__ masks, uint32_t* __restrict__ hdr_w, int block_test,
+                         int exact_masks) {
   __shared__ float4 lr_stage[4][65 * LR_RB_SLOT];
   if (lr_bail(state, capacity)) return;
   if (lazy == 2 && !lazy_state[LR_HDR_OPEN]) return;         // nobody parked (lazy_state: the tile state again, through the pointer these kernels WRITE sorted[] / open[] / the flag with)
@@ -1015,12 +1023,15 @@ lr_blend_fwd_rows_kernel(LrView v, const float4* __restrict__ geom, const uint32
         r3 = r3 && q && x_hi && y_hi;
       }
     }
-    uint64_t mrow = lr_row_mask(row, __ballot(r0), __ballot(r1), __ballot(r2), __ballot(r3));   // this lane's row's hit mask
+    uint64_t mrow = lr_row_mask(row, __ballot(r0), __ballot(r1), __ballot(r2), __ballot(r3));   // this lane's row's support mask
     const int pos0 = (int)(first + ch * 64u);
-    if (mslot) {                                              // for the reverse walk (hit masks, above)
+    // For the reverse walk (hit masks, above): the row's word of this chunk starts empty and the pass loop ORs in the entries
+    // some pixel of the row accumulates (LOGRAST_HIT_MASKS=2: it starts as the support ballot, which those are a subset
+    // of).  Without a buffer mcount stays 0 and the ORs land in a word nobody reads.
+    uint64_t* const mword = &lr_mbuf[wq][mcount * 4u + (uint32_t)row];
+    if (mslot) {
       if (mcount == 0) mfirst = (uint32_t)pos0 >> 6;
-      if (li == 0) lr_mbuf[wq][mcount * 4u + (uint32_t)row] = mrow;
-      if (++mcount == LR_MBUF_CHUNKS) flush_masks();
+      if (li == 0) *mword = exact_masks ? 0ull : mrow;
     }
     while (true) {
       // a row whose 16 pixels are all saturated takes no more entries
@@ -1073,10 +1084,16 @@ lr_blend_fwd_rows_kernel(LrView v, const float4* __restrict__ geom, const uint32
         LR_RMAX(ma, 0x4E); LR_RMAX(mb, 0x4E);
 #undef LR_RMAX
         // (LDS, one lane per row and entry; point_weight and the row clears leave once per chunk: lr_fwd_commit_chunk)
-        if (li == 0 && ma != 0u) atomicMax(&wmx[ja], ma);
-        if (li == 0 && mb != 0u) atomicMax(&wmx[jb], mb);
+        if (li == 0 && ma != 0u) { atomicMax(&wmx[ja], ma); atomicOr((unsigned long long*)mword, 1ull << ja); }
+        if (li == 0 && mb != 0u) { atomicMax(&wmx[jb], mb); atomicOr((unsigned long long*)mword, 1ull << jb); }
+      } else if (mslot) {                                     // no row maxima here: the row's share of the two ballots
+        const uint32_t ha = (uint32_t)(__ballot(w0 > 0.f) >> shift16) & (uint32_t)rowbits;
+        const uint32_t hb = (uint32_t)(__ballot(w1 > 0.f) >> shift16) & (uint32_t)rowbits;
+        if (li == 0 && ha != 0u) atomicOr((unsigned long long*)mword, 1ull << ja);
+        if (li == 0 && hb != 0u) atomicOr((unsigned long long*)mword, 1ull << jb);
       }
     }
+    if (mslot && ++mcount == LR_MBUF_CHUNKS) flush_masks();
   }
   if (mslot && mcount) flush_masks();
   lr_fwd_commit_chunk<EXTRAS>(wmx, lane, id_prev, pw, zero_rows);   // the last chunk's
@@ -1117,6 +1134,7 @@ void lr_launch_blend_fwd(const LrView& v, const void* geom, const uint32_t* stat
   // opacities 1267 -> 1188); C2's 1 M 174 -> 193; a tree-ordered heavy-tailed view 278 -> 347.
   const int rows = lr_blend_fwd_form(v) == (int)LR_MASK_FORM_ROWS;
   const int fwd_block_test = lr_knob(LRKNOB_FWD_BLOCK_TEST);
+  const int exact_masks = lr_knob(LRKNOB_HIT_MASKS) != 2;   // row-split form: hit masks = contributions (2: support ballots)
   // Both forward kernels still take `cull` (always 1: the support tests run) as a run-time argument.  With the tests
   // unconditional the register allocation of the row-split kernel changed (one more value in scratch) and the forward
   // measured 1-3 % slower on the 30 M view (quadrant form: 0.6 %).
@@ -1131,10 +1149,10 @@ void lr_launch_blend_fwd(const LrView& v, const void* geom, const uint32_t* stat
   if (rows) {
     if (v.extras)
       hipLaunchKernelGGL(lr_blend_fwd_rows_kernel<true>, dim3(grid), dim3(256), 0, s, v, g4, state, tiles, plist, capacity,
-                         image, final_T, n_contrib, pid, pwp, pw, z4, xcd_mode, 1, lazy_state, lazy, masks, hdr_w, fwd_block_test);
+                         image, final_T, n_contrib, pid, pwp, pw, z4, xcd_mode, 1, lazy_state, lazy, masks, hdr_w, fwd_block_test, exact_masks);
     else
       hipLaunchKernelGGL(lr_blend_fwd_rows_kernel<false>, dim3(grid), dim3(256), 0, s, v, g4, state, tiles, plist, capacity,
-                         image, final_T, n_contrib, pid, pwp, pw, z4, xcd_mode, 1, lazy_state, lazy, masks, hdr_w, fwd_block_test);
+                         image, final_T, n_contrib, pid, pwp, pw, z4, xcd_mode, 1, lazy_state, lazy, masks, hdr_w, fwd_block_test, exact_masks);
   } else {
     if (v.extras)
       hipLaunchKernelGGL(lr_blend_fwd_kernel<true>, dim3(grid), dim3(256), 0, s, v, g4, state, tiles, plist, capacity,

@@ -1,7 +1,8 @@
 """Design study on the device's own data: how many passes the row-split reverse walk needs per chunk, and how many it would
-need if a row's visits were balanced over longer windows.  One training forward (row-split form) of a bench view with a
-ZEROED hit-mask buffer; the masks the compositing kernel left are what the reverse walk visits (cut at each row's deepest
-contributor).  Per wave and 64-entry chunk: h[row] = visits of the row's 4x4 block; passes of today's loop = max_row
+need if a row's visits were balanced over longer windows.  Two training forwards (row-split form) of a bench view with a
+ZEROED hit-mask buffer, one per content of the masks (LOGRAST_HIT_MASKS = 2 / 1): 0 = the support ballots, 1 = the entries a block's pixels
+accumulated; the masks the compositing kernel left are what the reverse walk visits (cut at each row's deepest
+contributor).  One JSON line per knob value, then one with the share of the support visits that contribute nothing.  Per wave and 64-entry chunk: h[row] = visits of the row's 4x4 block; passes of today's loop = max_row
 ceil(h / 2).  Simulated: windows of W chunks (passes = max_row ceil(sum_window h / 2)) and windows filled up to 64 wanted
 entries (the compact-staging design).
     python tools/mask_stats.py [--gaussians N] [--opacity X] [--scene random|trained] [--view V]"""
@@ -36,6 +37,22 @@ def main():
     R._zero_hit_masks = True
     tune.set_knob("LOGRAST_FWD_ROWS", 1)
     b = wl.base
+    lines = {}
+    for knob in (0, 1):
+        tune.set_knob("LOGRAST_HIT_MASKS", 1 if knob else 2)
+        lines[knob] = mask_stats(a, knob, wl, b, R, torch, dev, W, H, gx, gy, tiles)
+        print(json.dumps(lines[knob]), flush=True)
+    s, e = lines[0], lines[1]
+    print(json.dumps({"workload": s["workload"], "support_visits": s["visits_block_pairs"],
+                      "contributing_visits": e["visits_block_pairs"],
+                      "pruned_share": 1.0 - e["visits_block_pairs"] / max(s["visits_block_pairs"], 1),
+                      "passes_per_chunk_support": s["passes_now_per_chunk"],
+                      "passes_per_chunk_contributing": e["passes_now_per_chunk"],
+                      "wanted_entries_per_chunk_support": s["wanted_entries_per_chunk"],
+                      "wanted_entries_per_chunk_contributing": e["wanted_entries_per_chunk"]}), flush=True)
+
+
+def mask_stats(a, knob, wl, b, R, torch, dev, W, H, gx, gy, tiles):
     with torch.no_grad():
         out = R._backend.forward(wl.rasts[a.view].raster_settings, R.WODILATE, True, b["means3D"], b["scales"], b["rotations"],
                                  b["opacities"].reshape(-1), b["colors"], scratch_floats=16)
@@ -75,6 +92,7 @@ def main():
     u = popc(union)
     chunks = int(live.sum())
     res = {"workload": "%d %s Gaussians, opacity %s, view %d" % (a.gaussians, a.scene, a.opacity, a.view),
+           "exact_masks": knob,
            "waves_with_work": int((nch > 0).sum()), "wave_chunks": chunks,
            "visits_block_pairs": int(h.sum()), "wanted_entries": int(u.sum()),
            "wanted_entries_per_chunk": float(u.sum()) / chunks, "visits_per_chunk": float(h.sum()) / chunks}
@@ -120,7 +138,7 @@ def main():
         res["passes_compact_%d" % cap] = int(passes.sum())
         res["passes_compact_%d_per_chunk" % cap] = int(passes.sum()) / chunks
         res["windows_compact_%d" % cap] = int(windows.sum())
-    print(json.dumps(res), flush=True)
+    return res
 
 
 if __name__ == "__main__":
