@@ -22,46 +22,26 @@ reference raises in the last four; they are known from the record, before anythi
 
 Install with ``log_amd.decide.install()`` or ``log_amd.install_all(device_decide=True)``."""
 import ctypes
-import logging
 import math
 
 import torch
 
 from . import _lib
 from . import rasterizer as _r
+from ._dropin import DropIns, Fallback, check_activations, device_and_rows, tensor
 
-_originals = {}
-_logged = set()
-_METHODS = ("update_depth_stage", "update_init_stage")
-_stats = {"calls": {}, "fallbacks": {}, "readbacks": {}}
 C = {"split_grad": 0, "split_radii": 1, "candidates": 2, "removed": 3, "depth_lt": 4}                    # LOGRAST_DECIDE_*
 CI = {"remove_weight": 0, "nonmax": 1, "remove_small": 2, "split_grad": 3, "split_radii": 4}
+_ACTIVATIONS = ({"opacity_activation": torch.sigmoid, "scaling_activation": torch.exp}, "activations other than sigmoid / exp")
 
 
-class _Fallback(Exception):
-    """Raised inside a drop-in for a case the kernels do not cover; the reference's method then runs."""
+def _targets():
+    from LoG.model.level_of_gaussian import LoG
+    return {name: (LoG, name) for name in ("update_depth_stage", "update_init_stage")}
 
 
-def stats():
-    """{'calls': {method: n}, 'fallbacks': {(method, reason): n}, 'readbacks': {method: n}} since the last reset."""
-    return {k: dict(v) for k, v in _stats.items()}
-
-
-def reset_stats():
-    for v in _stats.values():
-        v.clear()
-
-
-def _count(kind, key, n=1):
-    _stats[kind][key] = _stats[kind].get(key, 0) + n
-
-
-def _fell_back(what, why):
-    _count("fallbacks", (what, why))
-    if (what, why) not in _logged:
-        _logged.add((what, why))
-        logging.getLogger("log_amd").warning("log_amd.decide.%s: %s -- the reference's method runs instead (logged once)",
-                                             what, why)
+dropins = DropIns("decide", _targets)
+stats, reset_stats, uninstall = dropins.stats, dropins.reset_stats, dropins.uninstall
 
 
 class Stat:
@@ -117,23 +97,6 @@ class Record:
         return {d: n for d, n in out.items() if n}
 
 
-def _buf(t, device, dtype, shape, what):
-    if not torch.is_tensor(t) or t.device != device:
-        raise _Fallback("tensors are not on the GPU")
-    if t.dtype != dtype or tuple(t.shape) != shape:
-        raise _Fallback(f"{what}: {t.dtype}{tuple(t.shape)} where {dtype}{shape} is needed")
-    return t.detach().contiguous()
-
-
-def _device_and_rows(t):
-    if not torch.is_tensor(t) or t.device.type != "cuda":
-        raise _Fallback("tensors are not on the GPU")
-    p = int(t.shape[0])
-    if p >= 2 ** 31:
-        raise _Fallback("2^31 rows or more")
-    return t.device, p
-
-
 def _clip8(v):
     return max(-128, min(int(v), 128))       # depth is int8: a larger limit never binds
 
@@ -145,14 +108,11 @@ def _threshold_int(v):
 
 def _run(who, device, p, launch, args, keep):
     L = _lib.lib()
-    nbytes = L.lograst_decide_scratch_bytes(p)
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=device)
     raw = _lib.LograstDecideRecord()
-    with torch.cuda.device(device):
-        stream = _r._stream_ptr(device)
-        _lib.check(launch(p, ctypes.byref(args), _r._ptr(scratch), nbytes, stream))
-        _lib.check(L.lograst_decide_read(_r._ptr(scratch), ctypes.byref(raw), ctypes.sizeof(raw), stream))
-    _count("readbacks", who)
+    dropins.launch_and_read(
+        who, device, L.lograst_decide_scratch_bytes(p),
+        lambda scratch, nbytes, stream: launch(p, ctypes.byref(args), scratch, nbytes, stream),
+        lambda scratch, stream: L.lograst_decide_read(scratch, ctypes.byref(raw), ctypes.sizeof(raw), stream))
     del keep
     return Record(raw)
 
@@ -161,17 +121,17 @@ def decide_depth(opacity, scaling, node_index, depth, counter, current_depth, ma
                  radius2d_thres, remove_weights_thres, max_split_points, who="decide_depth"):
     """-> (flag_split, flag_remove, Record): torch.bool[P] on the device, the cut applied (unless the record says
     need_cut with num_max_split == 0).  opacity: raw [P, 1] or [P]; counter: an object with the Counter's buffers."""
-    device, p = _device_and_rows(scaling)
+    device, p = device_and_rows(scaling)
     f32, i32 = torch.float32, torch.int32
     if opacity.dim() == 2:
         opacity = opacity[:, 0]
     a = _lib.LograstDecideDepthArgs()
-    keep = {"opacity": _buf(opacity, device, f32, (p,), "opacity"), "scaling": _buf(scaling, device, f32, (p, 3), "scaling"),
-            "node_index": _buf(node_index, device, i32, (p,), "node_index"),
-            "depth": _buf(depth, device, torch.int8, (p,), "depth")}
+    keep = {"opacity": tensor(opacity, device, f32, (p,), "opacity"), "scaling": tensor(scaling, device, f32, (p, 3), "scaling"),
+            "node_index": tensor(node_index, device, i32, (p,), "node_index"),
+            "depth": tensor(depth, device, torch.int8, (p,), "depth")}
     for name, dt in (("create_steps", i32), ("grad_sum", f32), ("area_sum", i32), ("radii_max_max", i32),
                      ("weights_max", f32), ("visible_count", torch.int16)):
-        keep[name] = _buf(getattr(counter, name), device, dt, (p,), name)
+        keep[name] = tensor(getattr(counter, name), device, dt, (p,), name)
     for name, t in keep.items():
         setattr(a, name, t.data_ptr())
     split = torch.empty(p, dtype=torch.uint8, device=device)
@@ -189,15 +149,15 @@ def decide_depth(opacity, scaling, node_index, depth, counter, current_depth, ma
 def decide_init(opacity, counter, children, init_weight_min, init_radius_min, init_radius_split, split_grad_thres, min_steps,
                 scale, rand, who="decide_init"):
     """-> (flag_split, flag_remove, Record) of update_init_stage's 'split_by_2d' rules; rand: f32[P] on the device."""
-    device, p = _device_and_rows(rand)
+    device, p = device_and_rows(rand)
     f32, i32 = torch.float32, torch.int32
     if opacity.dim() == 2:
         opacity = opacity[:, 0]
     a = _lib.LograstDecideInitArgs()
-    keep = {"opacity": _buf(opacity, device, f32, (p,), "opacity"), "rand": _buf(rand, device, f32, (p,), "rand")}
+    keep = {"opacity": tensor(opacity, device, f32, (p,), "opacity"), "rand": tensor(rand, device, f32, (p,), "rand")}
     for name, dt in (("create_steps", i32), ("grad_sum", f32), ("area_sum", i32), ("radii_max_max", i32),
                      ("weights_max", f32), ("radius3d_min", f32)):
-        keep[name] = _buf(getattr(counter, name), device, dt, (p,), name)
+        keep[name] = tensor(getattr(counter, name), device, dt, (p,), name)
     for name, t in keep.items():
         setattr(a, name, t.data_ptr())
     split = torch.empty(p, dtype=torch.uint8, device=device)
@@ -216,28 +176,24 @@ def decide_init(opacity, counter, children, init_weight_min, init_radius_min, in
 
 def child_radius_max(radius3d_max, index_parent, scaling, num_children, scaling_decay):
     """counter.radius3d_max of the last num_children rows = scaling_decay * max(exp(scaling[index_parent]))."""
-    device, p = _device_and_rows(scaling)
+    device, p = device_and_rows(scaling)
     f32 = torch.float32
-    r = _buf(radius3d_max, device, f32, (p,), "radius3d_max")
+    r = tensor(radius3d_max, device, f32, (p,), "radius3d_max")
     if r.data_ptr() != radius3d_max.data_ptr():
         raise _lib.LograstError("log_amd.decide: radius3d_max must be contiguous")
-    ip = _buf(index_parent, device, torch.int32, (p,), "index_parent")
-    sc = _buf(scaling, device, f32, (p, 3), "scaling")
+    ip = tensor(index_parent, device, torch.int32, (p,), "index_parent")
+    sc = tensor(scaling, device, f32, (p, 3), "scaling")
     with torch.cuda.device(device):
         _lib.check(_lib.lib().lograst_decide_child_radius_max(p, int(num_children), _r._ptr(ip), _r._ptr(sc),
                                                               float(scaling_decay), _r._ptr(r), _r._stream_ptr(device)))
 
 
-def _check_activation(self):
-    act = getattr(self.gaussian, "activation", None)
-    if act is None or act.opacity_activation is not torch.sigmoid or act.scaling_activation is not torch.exp:
-        raise _Fallback("activations other than sigmoid / exp")
-
-
 # ---- LoG.update_depth_stage ----------------------------------------------------------------------------------------
 
-def _depth_device(self, global_iteration):
-    _check_activation(self)
+@dropins.dropin
+def update_depth_stage(self, global_iteration):
+    """LoG.update_depth_stage with its decisions on the device."""
+    check_activations(getattr(self.gaussian, "activation", None), *_ACTIVATIONS)
     cfg = self.densify_and_remove
     name = self.__class__.__name__
     log_prefix = f'[{name}] {global_iteration:06d}'
@@ -249,11 +205,11 @@ def _depth_device(self, global_iteration):
         cfg.remove_weights_thres, cfg.max_split_points, who="update_depth_stage")
     # everything below this point that can fall back does so before a buffer changes
     if rec.stats[0].count == 0:
-        raise _Fallback("no is_parent row")
+        raise Fallback("no is_parent row")
     if rec.need_cut and rec.num_max_split == 0:
-        raise _Fallback("a cut to num_max_split == 0")
+        raise Fallback("a cut to num_max_split == 0")
     if rec.need_cut and cfg.sort_method != 'radii':
-        raise _Fallback(f"a cut with sort_method = {cfg.sort_method!r}")
+        raise Fallback(f"a cut with sort_method = {cfg.sort_method!r}")
     for label, st in zip(("opacity", "ratio", "grad", "radii"), rec.stats):
         print(f'{log_prefix} {st.line(label)}')
     print(f'{log_prefix} split by grad: {rec.counts[C["split_grad"]]:8d} split by radii: {rec.counts[C["split_radii"]]:8d}')
@@ -276,46 +232,35 @@ def _depth_device(self, global_iteration):
         if after.get(depth, 0) == 0:
             continue
         print(f'[{name}] depth = {depth:2d} | {after[depth]:10d} points')
-    return rec
-
-
-def update_depth_stage(self, global_iteration):
-    """LoG.update_depth_stage with its decisions on the device."""
-    _count("calls", "update_depth_stage")
-    try:
-        with torch.no_grad():
-            _depth_device(self, global_iteration)
-            return
-    except _Fallback as why:
-        _fell_back("update_depth_stage", str(why))
-    return _original("update_depth_stage")(self, global_iteration)
 
 
 # ---- LoG.update_init_stage -----------------------------------------------------------------------------------------
 
-def _init_device(self, scale):
-    _check_activation(self)
+@dropins.dropin
+def update_init_stage(self, scale=1):
+    """LoG.update_init_stage ('split_by_2d') with its decisions on the device."""
+    check_activations(getattr(self.gaussian, "activation", None), *_ACTIVATIONS)
     cfg = self.densify_and_remove
     name = self.__class__.__name__
     if cfg.init_split_method != 'split_by_2d':
-        raise _Fallback(f"init_split_method = {cfg.init_split_method!r}")
+        raise Fallback(f"init_split_method = {cfg.init_split_method!r}")
     if cfg.init_radius_split * scale == -1:
-        raise _Fallback("init_radius_split * scale == -1")
+        raise Fallback("init_radius_split * scale == -1")
     wmax = self.counter.weights_max
-    device, p = _device_and_rows(wmax)
+    device, p = device_and_rows(wmax)
     # checked before the draw, so that a fall-back leaves the generator where the reference expects it
     f32, i32 = torch.float32, torch.int32
-    _buf(self.gaussian.opacity, device, f32, (p, 1), "opacity")
+    tensor(self.gaussian.opacity, device, f32, (p, 1), "opacity")
     for key, dt in (("create_steps", i32), ("grad_sum", f32), ("area_sum", i32), ("radii_max_max", i32), ("weights_max", f32),
                     ("radius3d_min", f32)):
-        _buf(getattr(self.counter, key), device, dt, (p,), key)
+        tensor(getattr(self.counter, key), device, dt, (p,), key)
     rand = torch.rand_like(wmax)
     flag_split, flag_remove, rec = decide_init(
         self.gaussian.opacity, self.counter, int(self.splitter.N), cfg.init_weight_min, cfg.init_radius_min,
         cfg.init_radius_split, cfg.split_grad_thres, cfg.min_steps, scale, rand, who="update_init_stage")
     # the reference raises on .min() of an empty selection: known here, before anything is resized
     if rec.stats[0].count == 0 or rec.stats[2].count == 0:
-        raise _Fallback("no activated row" if rec.stats[0].count == 0 else "no row to split")
+        raise Fallback("no activated row" if rec.stats[0].count == 0 else "no row to split")
     print(f'[{name}] {rec.counts[CI["remove_weight"]]:10d} points with weight < {cfg.init_weight_min:.2f}')
     print(f'[{name}] {rec.counts[CI["nonmax"]]:10d} points with weight is non max')
     print(f'[{name}] {rec.counts[CI["remove_small"]]:10d} points with radius < {cfg.init_radius_min:.2f}')
@@ -331,50 +276,10 @@ def _init_device(self, scale):
     self.clamp_scale(index)
     print(f'[{name}] {rec.stats[3].line("radius3d_min")}')
     self.counter.reset(self.num_points)
-    return rec
-
-
-def update_init_stage(self, scale=1):
-    """LoG.update_init_stage ('split_by_2d') with its decisions on the device."""
-    _count("calls", "update_init_stage")
-    try:
-        with torch.no_grad():
-            _init_device(self, scale)
-            return
-    except _Fallback as why:
-        _fell_back("update_init_stage", str(why))
-    return _original("update_init_stage")(self, scale=scale)
 
 
 # ---- installation --------------------------------------------------------------------------------------------------
 
-def _ours(name):
-    return update_depth_stage if name == "update_depth_stage" else update_init_stage
-
-
-def _original(name):
-    if name not in _originals:
-        from LoG.model.level_of_gaussian import LoG
-        fn = getattr(LoG, name)
-        if fn is _ours(name):
-            raise _lib.LograstError(f"log_amd.decide: the reference's {name} was replaced before install() could save it")
-        _originals[name] = fn
-    return _originals[name]
-
-
 def install():
     """Patch LoG in place (needs LoG importable); the original methods are kept for the fall-backs."""
-    from LoG.model.level_of_gaussian import LoG
-    for name in _METHODS:
-        _original(name)
-    for name in _METHODS:
-        setattr(LoG, name, _ours(name))
-    return LoG
-
-
-def uninstall():
-    """Put the reference's methods back."""
-    from LoG.model.level_of_gaussian import LoG
-    for name in _METHODS:
-        if name in _originals:
-            setattr(LoG, name, _originals[name])
+    return dropins.install()["update_depth_stage"][0]

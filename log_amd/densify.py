@@ -28,87 +28,74 @@ never passes it (``split_by_uniform``'s default 0.5 applies unless the caller gi
 What the kernels do not cover goes to the reference's own method, saved by ``install()`` (logged once):
 ``split_method == 'sample'``, ``N`` outside {2, 4, 8}, a 3-D ``xyz`` (frames), activations other than exp / log /
 normalize, tensors that are not on the GPU, moments that live on the CPU, a ``tree_depth`` key, and rows flagged for
-both split and remove while ``remove_split`` is off (undefined in the reference).
+both split and remove while ``remove_split`` is off (undefined in the reference).  ``stats()`` counts calls, fall-backs by
+reason and the library's read-backs (one per call).
 
 Install with ``log_amd.densify.install()`` or ``log_amd.install_all(device_densify=True)``."""
 import ctypes
-import logging
 import math
 
 import torch
 
 from . import _lib
 from . import rasterizer as _r
+from ._dropin import DropIns, Fallback, check_activations, device_and_rows, flag_u8, tree_buffers
 
 _ELEM = {torch.float32: 4, torch.int32: 4, torch.int16: 2, torch.float16: 2, torch.bfloat16: 2, torch.int8: 1,
          torch.uint8: 1, torch.bool: 1}
 _CHILDREN = (2, 4, 8)
-_originals = {}
-_logged = set()
+_ACTIVATIONS = ({"scaling_activation": torch.exp, "scaling_inverse_activation": torch.log,
+                 "rotation_activation": torch.nn.functional.normalize}, "activations other than exp / log / normalize")
 
 
-class _Fallback(Exception):
-    """Raised inside a drop-in for a case the kernels do not cover; the reference's method then runs."""
+def _targets():
+    from LoG.model.splitter import Splitter
+    from LoG.model.tensor_tree import TensorTree
+    return {"tree_split_and_remove": (TensorTree, "split_and_remove"), "split_and_remove": (Splitter, "split_and_remove"),
+            "split_and_remove_other": (Splitter, "split_and_remove_other")}
 
 
-def _log_once(what, why):
-    if (what, why) not in _logged:
-        _logged.add((what, why))
-        logging.getLogger("log_amd").warning("log_amd.densify.%s: %s -- the reference's method runs instead (logged once)",
-                                             what, why)
-
-
-def _u8(flag, device, p):
-    if not torch.is_tensor(flag) or flag.device != device:
-        raise _Fallback("flags are not on the model's device")
-    if flag.dim() != 1 or int(flag.shape[0]) != p:
-        raise ValueError(f"flag of shape {tuple(flag.shape)} for {p} rows")
-    f = flag.detach().contiguous()
-    return f.view(torch.uint8) if f.dtype == torch.bool else (f != 0).view(torch.uint8)
+dropins = DropIns("densify", _targets)
+stats, reset_stats, uninstall = dropins.stats, dropins.reset_stats, dropins.uninstall
 
 
 class Plan:
-    """The row plan of one call: masked flags (bool[P]), keep_dest (i32[P]), src_row (i32[num_new]) and the counts."""
+    """The row plan of one call: masked flags (bool[P]), keep_dest (i32[P]), src_row (i32[num_new]) and the counts.  who:
+    the method whose read-back this is, for stats()."""
 
-    def __init__(self, flag_split, flag_remove, remove_split, children, tree=None):
-        device = flag_split.device
-        if device.type != "cuda":
-            raise _Fallback("tensors are not on the GPU")
+    def __init__(self, flag_split, flag_remove, remove_split, children, tree=None, who="Plan"):
+        device, p = device_and_rows(flag_split)
         L = _lib.lib()
-        p = int(flag_split.shape[0])
-        if p >= 2 ** 31:
-            raise _Fallback("2^31 rows or more")
-        fs, fr = _u8(flag_split, device, p), _u8(flag_remove, device, p)
+        fs, fr = flag_u8(flag_split, device, p), flag_u8(flag_remove, device, p)
         self.p, self.children, self.remove_split, self.device = p, int(children), bool(remove_split), device
         split = torch.empty(p, dtype=torch.uint8, device=device)
         remove = torch.empty(p, dtype=torch.uint8, device=device)
         self.keep_dest = torch.empty(p, dtype=torch.int32, device=device)
-        nbytes = L.lograst_densify_scratch_bytes(p)
-        scratch = torch.empty(nbytes, dtype=torch.uint8, device=device)
         tree_ptrs = [ctypes.c_void_p(0)] * 3
         max_level = 0
         if tree is not None:
-            arrays = _tree_arrays(tree, device, p)
-            tree_ptrs = [ctypes.c_void_p(arrays[k].data_ptr()) for k in ("node_index", "index_parent", "depth")]
+            arrays = tree_buffers(tree, device, p, ("node_index", "index_parent", "depth"))
+            tree_ptrs = [ctypes.c_void_p(t.data_ptr()) for t in arrays.values()]
             max_level = max(-128, min(int(tree.max_level), 127))      # depth is int8: a larger limit never binds
         nk, ns, ov = ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_uint32(0)
+        scratch = dropins.launch_and_read(
+            who, device, L.lograst_densify_scratch_bytes(p),
+            lambda scratch, nbytes, stream: L.lograst_densify_plan(
+                p, _r._ptr(fs), _r._ptr(fr), int(self.remove_split), self.children, *tree_ptrs, max_level, _r._ptr(split),
+                _r._ptr(remove), _r._ptr(self.keep_dest), scratch, nbytes, stream),
+            lambda scratch, stream: L.lograst_densify_read(scratch, ctypes.byref(nk), ctypes.byref(ns), ctypes.byref(ov), stream))
+        self.num_keep, self.num_split, self.overlap = int(nk.value), int(ns.value), int(ov.value)
+        self.num_new = self.num_keep + self.children * self.num_split
+        self.split, self.remove = split.view(torch.bool), remove.view(torch.bool)
+        if self.overlap:
+            raise Fallback("rows flagged for both split and remove with remove_split off")
+        if self.num_new >= 2 ** 31:
+            raise Fallback("2^31 new rows or more")
+        self.src_row = torch.empty(self.num_new, dtype=torch.int32, device=device)
         with torch.cuda.device(device):
-            stream = _r._stream_ptr(device)
-            _lib.check(L.lograst_densify_plan(p, _r._ptr(fs), _r._ptr(fr), int(self.remove_split), self.children, *tree_ptrs,
-                                              max_level, _r._ptr(split), _r._ptr(remove), _r._ptr(self.keep_dest),
-                                              _r._ptr(scratch), nbytes, stream))
-            _lib.check(L.lograst_densify_read(_r._ptr(scratch), ctypes.byref(nk), ctypes.byref(ns), ctypes.byref(ov), stream))
-            self.num_keep, self.num_split, self.overlap = int(nk.value), int(ns.value), int(ov.value)
-            self.num_new = self.num_keep + self.children * self.num_split
-            self.split, self.remove = split.view(torch.bool), remove.view(torch.bool)
-            if self.overlap:
-                raise _Fallback("rows flagged for both split and remove with remove_split off")
-            if self.num_new >= 2 ** 31:
-                raise _Fallback("2^31 new rows or more")
-            self.src_row = torch.empty(self.num_new, dtype=torch.int32, device=device)
             _lib.check(L.lograst_densify_src_rows(p, self.children, int(self.remove_split), _r._ptr(split), _r._ptr(remove),
                                                   self.num_keep, self.num_split, _r._ptr(self.src_row), _r._ptr(scratch),
-                                                  stream))
+                                                  _r._stream_ptr(device)))
 
     def move(self, entries):
         """entries: [(src, child_mode)] or [(src, child_mode, dst)] -> the new tensors, [num_new, ...] each (dst: a
@@ -138,19 +125,6 @@ class Plan:
         return out
 
 
-def _tree_arrays(tree, device, p):
-    want = {"node_index": torch.int32, "index_parent": torch.int32, "local_index": torch.int8, "depth": torch.int8}
-    arrays = {}
-    for name, dt in want.items():
-        t = getattr(tree, name)
-        if t.device != device:
-            raise _Fallback("tree buffers are not on the flags' device")
-        if t.dtype != dt or t.dim() != 1 or int(t.shape[0]) != p:
-            raise ValueError(f"tree buffer {name}: expected {dt}[{p}], got {t.dtype}{tuple(t.shape)}")
-        arrays[name] = t.contiguous()
-    return arrays
-
-
 def _groups(items, size_of):
     """Consecutive groups of at most 8 items whose sizes add up to no more than the largest single item."""
     limit = max([size_of(i) for i in items], default=0)
@@ -171,19 +145,19 @@ def _row_bytes(t):
 
 # ---- TensorTree.split_and_remove -----------------------------------------------------------------------------------
 
-def _tree_device(self, flag_split, flag_remove):
-    device = self.tree.device
-    if device.type != "cuda":
-        raise _Fallback("tensors are not on the GPU")
+@dropins.dropin
+def tree_split_and_remove(self, flag_split, flag_remove):
+    """TensorTree.split_and_remove on the device: returns the masked (flag_split, flag_remove) as the reference does."""
+    device, _ = device_and_rows(self.tree)
     children = int(self.max_child)
     if children not in _CHILDREN:
-        raise _Fallback(f"max_child = {children}")
+        raise Fallback(f"max_child = {children}")
     if self.tree.dtype != torch.int32 or self.tree.dim() != 2 or int(self.tree.shape[1]) != children:
         raise ValueError("tree: expected int32[num_nodes, max_child]")
     p = int(self.node_index.shape[0])
-    plan = Plan(flag_split, flag_remove, False, children, tree=self)
+    plan = Plan(flag_split, flag_remove, False, children, tree=self, who="tree_split_and_remove")
     print(f' -> [{self.__class__.__name__}] split: {plan.num_split} remove: {p - plan.num_keep}')
-    arrays = _tree_arrays(self, device, p)
+    arrays = tree_buffers(self, device, p)
     tree_old = self.tree.contiguous()
     num_nodes = int(tree_old.shape[0])
     new = {k: torch.empty(plan.num_new, dtype=v.dtype, device=device) for k, v in arrays.items()}
@@ -200,65 +174,51 @@ def _tree_device(self, flag_split, flag_remove):
     return plan.split, plan.remove
 
 
-def tree_split_and_remove(self, flag_split, flag_remove):
-    """TensorTree.split_and_remove on the device: returns the masked (flag_split, flag_remove) as the reference does."""
-    try:
-        with torch.no_grad():
-            return _tree_device(self, flag_split, flag_remove)
-    except _Fallback as why:
-        _log_once("tree_split_and_remove", str(why))
-        return _original("tree_split_and_remove")(self, flag_split, flag_remove)
-
-
 # ---- Splitter.split_and_remove -------------------------------------------------------------------------------------
 
 def _check_model(self, model, kwargs):
     if self.split_method != "uniform":
-        raise _Fallback(f"split_method = {self.split_method!r}")
+        raise Fallback(f"split_method = {self.split_method!r}")
     if int(self.N) not in _CHILDREN:
-        raise _Fallback(f"N = {self.N}")
+        raise Fallback(f"N = {self.N}")
     if set(kwargs) - {"scaling_factor"}:
-        raise _Fallback(f"arguments {sorted(set(kwargs) - {'scaling_factor'})}")
+        raise Fallback(f"arguments {sorted(set(kwargs) - {'scaling_factor'})}")
     if "tree_depth" in model.keys:
-        raise _Fallback("a tree_depth key")
-    act = getattr(model, "activation", None)
-    if act is None or act.scaling_activation is not torch.exp or act.scaling_inverse_activation is not torch.log \
-            or act.rotation_activation is not torch.nn.functional.normalize:
-        raise _Fallback("activations other than exp / log / normalize")
-    device = model.xyz.device
-    if device.type != "cuda":
-        raise _Fallback("tensors are not on the GPU")
+        raise Fallback("a tree_depth key")
+    check_activations(getattr(model, "activation", None), *_ACTIVATIONS)
+    device, p = device_and_rows(model.xyz)
     if model.xyz.dim() != 2:
-        raise _Fallback("a 3-D xyz (frames)")
-    p = int(model.xyz.shape[0])
+        raise Fallback("a 3-D xyz (frames)")
     for key in ("xyz", "scaling", "rotation"):
         t = getattr(model, key)
         if t.dtype != torch.float32 or tuple(t.shape) != (p, 4 if key == "rotation" else 3):
-            raise _Fallback(f"{key} of shape {tuple(t.shape)} / {t.dtype}")
+            raise Fallback(f"{key} of shape {tuple(t.shape)} / {t.dtype}")
     for key in model.keys:
         t = getattr(model, key, None)
         if t is None or t.shape[0] == 0:
             continue
         if t.device != device or int(t.shape[0]) != p or t.dtype not in _ELEM:
-            raise _Fallback(f"key {key} on {t.device} with {t.shape[0]} rows of {t.dtype}")
+            raise Fallback(f"key {key} on {t.device} with {t.shape[0]} rows of {t.dtype}")
     return device, p
 
 
-def _model_device(self, model, optimizer, flag_split, flag_remove, remove_split, kwargs):
+@dropins.dropin
+def split_and_remove(self, model, optimizer, flag_split, flag_remove, remove_split=True, **kwargs):
+    """Splitter.split_and_remove on the device; returns num_keep (a 0-d tensor, as the reference)."""
     device, p = _check_model(self, model, kwargs)
     if optimizer is not None:
         for state_key in optimizer.state_keys:
             for key, val in getattr(optimizer, state_key).items():
                 if val.device != device:
-                    raise _Fallback("moments that live on the CPU")
+                    raise Fallback("moments that live on the CPU")
                 if int(val.shape[0]) != p or val.dtype not in _ELEM:
-                    raise _Fallback(f"moment {state_key}.{key} of shape {tuple(val.shape)}")
+                    raise Fallback(f"moment {state_key}.{key} of shape {tuple(val.shape)}")
     for flag in (flag_split, flag_remove):
         if not torch.is_tensor(flag) or flag.device != device:
-            raise _Fallback("flags are not on the model's device")
+            raise Fallback("flags are not on the model's device")
     L = _lib.lib()
     children = int(self.N)
-    plan = Plan(flag_split, flag_remove, remove_split, children)
+    plan = Plan(flag_split, flag_remove, remove_split, children, who="split_and_remove")
     print(f'[{self.__class__.__name__}] split method {self.split_method}, remove {p} +{plan.num_split}x{self.N} '
           f'-{p - plan.num_keep - (plan.num_split if remove_split else 0)}')
     if plan.num_split:
@@ -304,82 +264,33 @@ def _move_group(plan, tensors, modes, prefilled):
         t.set_(dst)        # on the key itself, as splitter.py:178 does (a Parameter too: the callers hold no_grad)
 
 
-def split_and_remove(self, model, optimizer, flag_split, flag_remove, remove_split=True, **kwargs):
-    """Splitter.split_and_remove on the device; returns num_keep (a 0-d tensor, as the reference)."""
-    try:
-        with torch.no_grad():
-            return _model_device(self, model, optimizer, flag_split, flag_remove, remove_split, kwargs)
-    except _Fallback as why:
-        _log_once("split_and_remove", str(why))
-        return _original("split_and_remove")(self, model, optimizer, flag_split, flag_remove, remove_split=remove_split,
-                                             **kwargs)
-
-
 # ---- Splitter.split_and_remove_other -------------------------------------------------------------------------------
 
-def _other_device(self, model, keys, flag_split, flag_remove, remove_split):
+@dropins.dropin
+def split_and_remove_other(self, model, keys, flag_split, flag_remove, remove_split=True):
+    """Splitter.split_and_remove_other on the device: children get zero, those of ``radius3d_min`` copy the parent."""
     if int(self.N) not in _CHILDREN:
-        raise _Fallback(f"N = {self.N}")
+        raise Fallback(f"N = {self.N}")
     tensors, modes = [], []
     for key in keys:
         t = getattr(model, key, None)
         if t is None or t.shape[0] == 0:
             continue
         if t.device.type != "cuda" or t.device != flag_split.device:
-            raise _Fallback("tensors are not on the GPU")
+            raise Fallback("tensors are not on the GPU")
         if t.dim() != 1 or t.dtype not in _ELEM or int(t.shape[0]) != int(flag_split.shape[0]):
-            raise _Fallback(f"key {key} of shape {tuple(t.shape)} / {t.dtype}")
+            raise Fallback(f"key {key} of shape {tuple(t.shape)} / {t.dtype}")
         tensors.append(t)
         modes.append(_lib.MOVE_COPY_PARENT if key == 'radius3d_min' else _lib.MOVE_ZERO)   # splitter.py:215-219
     if not tensors:
         return
-    plan = Plan(flag_split, flag_remove, remove_split, int(self.N))
+    plan = Plan(flag_split, flag_remove, remove_split, int(self.N), who="split_and_remove_other")
     for first in range(0, len(tensors), 8):
         _move_group(plan, tensors[first:first + 8], modes[first:first + 8], [None] * len(tensors[first:first + 8]))
 
 
-def split_and_remove_other(self, model, keys, flag_split, flag_remove, remove_split=True):
-    """Splitter.split_and_remove_other on the device: children get zero, those of ``radius3d_min`` copy the parent."""
-    try:
-        with torch.no_grad():
-            return _other_device(self, model, keys, flag_split, flag_remove, remove_split)
-    except _Fallback as why:
-        _log_once("split_and_remove_other", str(why))
-        return _original("split_and_remove_other")(self, model, keys, flag_split, flag_remove, remove_split=remove_split)
-
-
 # ---- installation --------------------------------------------------------------------------------------------------
-
-def _original(name):
-    if name not in _originals:
-        from LoG.model.splitter import Splitter
-        from LoG.model.tensor_tree import TensorTree
-        cls, attr = (TensorTree, "split_and_remove") if name == "tree_split_and_remove" else (Splitter, name)
-        fn = getattr(cls, attr)
-        if fn in (tree_split_and_remove, split_and_remove, split_and_remove_other):
-            raise _lib.LograstError(f"log_amd.densify: the reference's {attr} was replaced before install() could save it")
-        _originals[name] = fn
-    return _originals[name]
-
 
 def install():
     """Patch the reference classes in place (needs LoG importable); the original methods are kept for the fall-backs."""
-    from LoG.model.splitter import Splitter
-    from LoG.model.tensor_tree import TensorTree
-    for name in ("tree_split_and_remove", "split_and_remove", "split_and_remove_other"):
-        _original(name)
-    TensorTree.split_and_remove = tree_split_and_remove
-    Splitter.split_and_remove = split_and_remove
-    Splitter.split_and_remove_other = split_and_remove_other
-    return Splitter
-
-
-def uninstall():
-    """Put the reference's methods back."""
-    from LoG.model.splitter import Splitter
-    from LoG.model.tensor_tree import TensorTree
-    if "tree_split_and_remove" in _originals:
-        TensorTree.split_and_remove = _originals["tree_split_and_remove"]
-    for name in ("split_and_remove", "split_and_remove_other"):
-        if name in _originals:
-            setattr(Splitter, name, _originals[name])
+    return dropins.install()["split_and_remove"][0]

@@ -21,73 +21,42 @@ not on the GPU or not fp32, activations other than exp / sigmoid / normalize (lo
 
 Install with ``log_amd.prepare.install()`` or ``log_amd.install_all(device_prepare=True)``."""
 import ctypes
-import logging
 
 import torch
 
 from . import _lib
 from . import rasterizer as _r
+from ._dropin import DropIns, Fallback, check_activations, device_and_rows, flag_u8, tensor, tree_buffers
 
-_originals = {}
-_logged = set()
-_METHODS = ("log_prepare", "gaussian_prepare", "clamp_scale", "step")
-_stats = {"calls": {}, "fallbacks": {}, "readbacks": {}}
-
-
-class _Fallback(Exception):
-    """Raised inside a drop-in for a case the kernels do not cover; the reference's method then runs."""
+_F32 = torch.float32
+_VIEW_ACTIVATIONS = ({"scaling_activation": torch.exp, "opacity_activation": torch.sigmoid,
+                      "rotation_activation": torch.nn.functional.normalize}, "activations other than exp / sigmoid / normalize")
+_CLAMP_ACTIVATIONS = ({"scaling_inverse_activation": torch.log}, "a scaling inverse activation other than log")
 
 
-def stats():
-    """{'calls': {method: n}, 'fallbacks': {(method, reason): n}, 'readbacks': {method: n}} since the last reset:
-    read-backs are the library's ``*_read`` calls (one stream synchronisation each) made on behalf of a method."""
-    return {k: dict(v) for k, v in _stats.items()}
+def _targets():
+    from LoG.model.level_of_gaussian import Gaussian, LoG
+    return {"log_prepare": (LoG, "prepare"), "gaussian_prepare": (Gaussian, "prepare"), "clamp_scale": (LoG, "clamp_scale"),
+            "step": (LoG, "step")}
 
 
-def reset_stats():
-    for v in _stats.values():
-        v.clear()
+dropins = DropIns("prepare", _targets)
+stats, reset_stats, uninstall = dropins.stats, dropins.reset_stats, dropins.uninstall
 
 
-def _count(kind, key, n=1):
-    _stats[kind][key] = _stats[kind].get(key, 0) + n
-
-
-def _fell_back(what, why):
-    _count("fallbacks", (what, why))
-    if (what, why) not in _logged:
-        _logged.add((what, why))
-        logging.getLogger("log_amd").warning("log_amd.prepare.%s: %s -- the reference's method runs instead (logged once)",
-                                             what, why)
-
-
-def _f32(t, device, shape, what):
-    """A model buffer as the kernels read it: on `device`, fp32, of the given trailing shape, contiguous."""
-    if not torch.is_tensor(t) or t.device != device:
-        raise _Fallback("tensors are not on the GPU" if device.type == "cuda" else "tensors on different devices")
-    if t.dtype != torch.float32:
-        raise _Fallback(f"{what} is not fp32")
-    if tuple(t.shape[1:]) != shape:
-        raise _Fallback(f"{what} of shape {tuple(t.shape)}")
-    return t.detach().contiguous()
-
-
-def _device_of(xyz):
-    if not torch.is_tensor(xyz) or xyz.device.type != "cuda":
-        raise _Fallback("tensors are not on the GPU")
+def _device_and_rows(xyz):
+    device, P = device_and_rows(xyz)
     if xyz.dim() != 2:
-        raise _Fallback("a 3-D xyz (frames)")
-    if int(xyz.shape[0]) >= 2 ** 31:
-        raise _Fallback("2^31 rows or more")
-    return xyz.device
+        raise Fallback("a 3-D xyz (frames)")
+    return device, P
 
 
 def _proj(camera, device):
     m = camera['full_proj_transform']
     if not torch.is_tensor(m) or m.device != device:
-        raise _Fallback("tensors are not on the GPU")
+        raise Fallback("tensors are not on the GPU")
     if m.dtype != torch.float32:
-        raise _Fallback("full_proj_transform is not fp32")
+        raise Fallback("full_proj_transform is not fp32")
     if m.numel() != 16:
         raise ValueError(f"full_proj_transform of shape {tuple(m.shape)}")
     return m.detach().contiguous()
@@ -112,7 +81,7 @@ def frustum_select(xyz, proj, padding, rows=None, raw=None, who="frustum_select"
         rows = rows.contiguous()
     n = P if rows is None else int(rows.shape[0])
     if n >= 2 ** 31:
-        raise _Fallback("2^31 rows or more")
+        raise Fallback("2^31 rows or more")
     sel = Selection()
     flag = torch.empty(n, dtype=torch.uint8, device=device)
     pos = torch.empty(n, dtype=torch.int64, device=device)
@@ -120,16 +89,13 @@ def frustum_select(xyz, proj, padding, rows=None, raw=None, who="frustum_select"
     outs = [None] * 4
     if raw is not None:
         outs = [torch.empty((n, w), dtype=torch.float32, device=device) for w in (3, 3, 4, 1)]
-    nbytes = L.lograst_frustum_scratch_bytes(n)
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=device)
     count = ctypes.c_uint32(0)
-    with torch.cuda.device(device):
-        stream = _r._stream_ptr(device)
-        _lib.check(L.lograst_frustum_select(n, P, _r._ptr(xyz), _r._ptr(rows), _r._ptr(proj), float(padding),
-                                            *[_r._ptr(t) for t in (raw or (None, None, None))], _r._ptr(flag), _r._ptr(pos),
-                                            _r._ptr(row_out), *[_r._ptr(t) for t in outs], _r._ptr(scratch), nbytes, stream))
-        _lib.check(L.lograst_frustum_read(_r._ptr(scratch), ctypes.byref(count), stream))
-    _count("readbacks", who)
+    dropins.launch_and_read(
+        who, device, L.lograst_frustum_scratch_bytes(n),
+        lambda scratch, nbytes, stream: L.lograst_frustum_select(
+            n, P, _r._ptr(xyz), _r._ptr(rows), _r._ptr(proj), float(padding), *[_r._ptr(t) for t in (raw or (None, None, None))],
+            _r._ptr(flag), _r._ptr(pos), _r._ptr(row_out), *[_r._ptr(t) for t in outs], scratch, nbytes, stream),
+        lambda scratch, stream: L.lograst_frustum_read(scratch, ctypes.byref(count), stream))
     k = int(count.value)
     sel.flag, sel.count, sel.pos = flag.view(torch.bool), k, pos[:k]
     sel.rows = row_out[:k] if row_out is not None else None
@@ -139,31 +105,16 @@ def frustum_select(xyz, proj, padding, rows=None, raw=None, who="frustum_select"
 
 # ---- Gaussian.prepare ----------------------------------------------------------------------------------------------
 
-def _gaussian_device(self, camera):
-    device = _device_of(self.xyz)
-    xyz = _f32(self.xyz, device, (3,), "xyz")
+@dropins.dropin
+def gaussian_prepare(self, rasterizer, camera):
+    """Gaussian.prepare on the device: ``visibility_flag = {'flag': bool[P], 'index': int64}``."""
+    device, P = _device_and_rows(self.xyz)
+    xyz = tensor(self.xyz, device, _F32, (P, 3), "xyz")
     sel = frustum_select(xyz, _proj(camera, device), 0.5, who="gaussian_prepare")
     self.visibility_flag = {'flag': sel.flag, 'index': sel.pos}
 
 
-def gaussian_prepare(self, rasterizer, camera):
-    """Gaussian.prepare on the device: ``visibility_flag = {'flag': bool[P], 'index': int64}``."""
-    _count("calls", "gaussian_prepare")
-    try:
-        with torch.no_grad():
-            return _gaussian_device(self, camera)
-    except _Fallback as why:
-        _fell_back("gaussian_prepare", str(why))
-        return _original("gaussian_prepare")(self, rasterizer, camera)
-
-
 # ---- LoG.prepare ---------------------------------------------------------------------------------------------------
-
-def _check_view_activations(act):
-    if act is None or act.scaling_activation is not torch.exp or act.opacity_activation is not torch.sigmoid \
-            or act.rotation_activation is not torch.nn.functional.normalize:
-        raise _Fallback("activations other than exp / sigmoid / normalize")
-
 
 def root_weight(rasterizer, sel):
     """LoG.render_to_check (:207-221) on the kept roots: the root render's point_weight."""
@@ -183,32 +134,24 @@ def lod_select(tree, gaussian, sel, weight, rasterizer, max_depth, opt_all_level
     fy = rs.image_height / (2.0 * rs.tanfovy)
     levels = max(0, min(int(tree.max_level), int(max_depth)))
     P = int(gaussian.xyz.shape[0])
-    want = {"node_index": torch.int32, "depth": torch.int8}
-    arrays = {}
-    for name, dt in want.items():
-        t = getattr(tree, name)
-        if t.device != device:
-            raise _Fallback("tree buffers are not on the model's device")
-        if t.dtype != dt or t.dim() != 1 or int(t.shape[0]) != P:
-            raise ValueError(f"tree buffer {name}: expected {dt}[{P}], got {t.dtype}{tuple(t.shape)}")
-        arrays[name] = t.contiguous()
+    arrays = tree_buffers(tree, device, P, ("node_index", "depth"))
     tr = tree.tree
     if tr.device != device:
-        raise _Fallback("tree buffers are not on the model's device")
+        raise Fallback("tree buffers are not on the model's device")
     if tr.dtype != torch.int32:
         raise ValueError("tree: expected int32[num_nodes, max_child]")
     tr = tr.contiguous()
     num_nodes, max_child = (int(tr.shape[0]), int(tr.shape[1])) if tr.dim() == 2 else (0, 1)
-    x = _f32(gaussian.xyz, device, (3,), "xyz")
-    s = _f32(gaussian.scaling, device, (3,), "scaling")
-    q = _f32(gaussian.rotation, device, (4,), "rotation")
+    x = tensor(gaussian.xyz, device, _F32, (P, 3), "xyz")
+    s = tensor(gaussian.scaling, device, _F32, (P, 3), "scaling")
+    q = tensor(gaussian.rotation, device, _F32, (P, 4), "rotation")
     pm, vm = _r._dev_f32(rs.projmatrix, device), _r._dev_f32(rs.viewmatrix, device)
     k = sel.count
     if weight is not None:
         weight = weight.detach().to(device=device, dtype=torch.float32).contiguous().reshape(-1)
         if int(weight.shape[0]) != k:
             raise ValueError(f"point_weight of {int(weight.shape[0])} entries for {k} roots")
-    flag_u8 = sel.flag.view(torch.uint8)
+    flags = sel.flag.view(torch.uint8)
     cap = max(P, 1)
     out = [torch.empty(cap, dtype=torch.int64, device=device) for _ in range(3)]     # the list, its leaves, its nodes
     nbytes = L.lograst_lod_select_scratch_bytes(k, num_nodes, max_child, cap)
@@ -221,13 +164,13 @@ def lod_select(tree, gaussian, sel, weight, rasterizer, max_depth, opt_all_level
         for lv in tries:
             _lib.check(L.lograst_lod_select(
                 P, num_nodes, max_child, _r._ptr(arrays["node_index"]), _r._ptr(tr), _r._ptr(arrays["depth"]), _r._ptr(x),
-                _r._ptr(s), _r._ptr(q), _r._ptr(sel.rows), k, _r._ptr(weight), _r._ptr(sel.pos), _r._ptr(flag_u8),
-                int(flag_u8.shape[0]), _r._ptr(pm), _r._ptr(vm), float(fx), float(fy), float(rs.tanfovx), float(rs.tanfovy),
+                _r._ptr(s), _r._ptr(q), _r._ptr(sel.rows), k, _r._ptr(weight), _r._ptr(sel.pos), _r._ptr(flags),
+                int(flags.shape[0]), _r._ptr(pm), _r._ptr(vm), float(fx), float(fy), float(rs.tanfovx), float(rs.tanfovy),
                 float(tree.min_resolution_pixel), lv, int(bool(opt_all_levels)), max(-129, min(int(current_depth), 128)),
                 _r._ptr(out[0]), cap, _r._ptr(out[1]), _r._ptr(out[2]), _r._ptr(scratch), nbytes, stream))
             _lib.check(L.lograst_lod_select_read(_r._ptr(scratch), ctypes.byref(n_all), ctypes.byref(n_leaf),
                                                  ctypes.byref(overflow), ctypes.byref(left), stream))
-            _count("readbacks", who)
+            dropins.count("readbacks", who)
             if left.value == 0:
                 break
     if overflow.value:
@@ -237,17 +180,17 @@ def lod_select(tree, gaussian, sel, weight, rasterizer, max_depth, opt_all_level
 
 def _log_device(self, rasterizer, camera):
     g = self.gaussian
-    device = _device_of(g.xyz)
-    _check_view_activations(getattr(g, "activation", None))
-    xyz = _f32(g.xyz, device, (3,), "xyz")
-    raw = (_f32(g.scaling, device, (3,), "scaling"), _f32(g.rotation, device, (4,), "rotation"))
+    device, P = _device_and_rows(g.xyz)
+    check_activations(getattr(g, "activation", None), *_VIEW_ACTIVATIONS)
+    xyz = tensor(g.xyz, device, _F32, (P, 3), "xyz")
+    raw = (tensor(g.scaling, device, _F32, (P, 3), "scaling"), tensor(g.rotation, device, _F32, (P, 4), "rotation"))
     opacity = g.opacity
-    if not torch.is_tensor(opacity) or opacity.dim() not in (1, 2) or opacity.numel() != xyz.shape[0]:
-        raise _Fallback("opacity that is not [P] or [P, 1]")
-    opacity = _f32(opacity.reshape(-1, 1), device, (1,), "opacity")
+    if not torch.is_tensor(opacity) or opacity.dim() not in (1, 2) or opacity.numel() != P:
+        raise Fallback("opacity that is not [P] or [P, 1]")
+    opacity = tensor(opacity.reshape(-1, 1), device, _F32, (P, 1), "opacity")
     roots = self.tree.root_index
     if roots.device != device or roots.dtype != torch.int32:
-        raise _Fallback("root_index that is not int32 on the model's device")
+        raise Fallback("root_index that is not int32 on the model's device")
     sel = frustum_select(xyz, _proj(camera, device), 0.5, rows=roots, raw=raw + (opacity,), who="log_prepare")
     if sel.count == 0:       # nothing to render or to descend from
         empty = torch.empty(0, dtype=torch.int64, device=device)
@@ -259,88 +202,58 @@ def _log_device(self, rasterizer, camera):
     g.visibility_flag = {'root_flag': flag, 'index': leaf, 'index_node': node}
 
 
+@dropins.register
 def log_prepare(self, rasterizer, camera):
     """LoG.prepare on the device: two read-backs per view (the number of roots in range, the two list sizes)."""
-    if self.tree.num_nodes == 0:
+    if self.tree.num_nodes == 0:       # a flat model: not a call of this drop-in
         return self.gaussian.prepare(rasterizer, camera)
-    _count("calls", "log_prepare")
-    try:
-        with torch.no_grad():
-            return _log_device(self, rasterizer, camera)
-    except _Fallback as why:
-        _fell_back("log_prepare", str(why))
-        return _original("log_prepare")(self, rasterizer, camera)
+    return dropins.run("log_prepare", _log_device, self, rasterizer, camera)
 
 
 # ---- LoG.clamp_scale / LoG.step ------------------------------------------------------------------------------------
 
 def _clamp_inputs(self, index, flag=None):
-    """Everything ``lograst_clamp_scale`` needs, checked BEFORE anything is written: a _Fallback here leaves the model as
+    """Everything ``lograst_clamp_scale`` needs, checked BEFORE anything is written: a Fallback here leaves the model as
     it was."""
     g = self.gaussian
-    device = _device_of(g.xyz)
-    act = getattr(g, "activation", None)
-    if act is None or act.scaling_inverse_activation is not torch.log:
-        raise _Fallback("a scaling inverse activation other than log")
-    scaling = g.scaling
-    if not torch.is_tensor(scaling) or scaling.device != device:
-        raise _Fallback("tensors are not on the GPU")
-    if scaling.dtype != torch.float32:
-        raise _Fallback("scaling is not fp32")
-    if scaling.dim() != 2 or int(scaling.shape[1]) != 3 or not scaling.is_contiguous():
-        raise _Fallback(f"scaling of shape {tuple(scaling.shape)} or not contiguous")
-    P = int(scaling.shape[0])
-    bounds = []
-    for name in ("radius3d_min", "radius3d_max"):
-        t = getattr(self.counter, name)
-        if not torch.is_tensor(t) or t.device != device:
-            raise _Fallback("tensors are not on the GPU")
-        if t.dtype != torch.float32:
-            raise _Fallback(f"{name} is not fp32")
-        if t.dim() != 1 or int(t.shape[0]) != P:
-            raise ValueError(f"{name}: expected fp32[{P}], got {tuple(t.shape)}")
-        bounds.append(t.detach().contiguous())
+    device, P = _device_and_rows(g.xyz)
+    check_activations(getattr(g, "activation", None), *_CLAMP_ACTIVATIONS)
+    if torch.is_tensor(g.scaling) and not g.scaling.is_contiguous():     # clamped in place: a contiguous copy will not do
+        raise Fallback("scaling that is not contiguous")
+    scaling = tensor(g.scaling, device, _F32, (P, 3), "scaling")
+    bounds = [tensor(getattr(self.counter, name), device, _F32, (P,), name) for name in ("radius3d_min", "radius3d_max")]
     if not torch.is_tensor(index) or index.device != device:
-        raise _Fallback("tensors are not on the GPU")
+        raise Fallback("tensors are not on the GPU")
     if index.dtype == torch.bool or index.dim() != 1:
-        raise _Fallback("an index that is not a 1-D list of rows")
+        raise Fallback("an index that is not a 1-D list of rows")
     m = int(index.shape[0])
     if m >= 2 ** 31:
-        raise _Fallback("2^31 rows or more")
+        raise Fallback("2^31 rows or more")
     index = index.detach().to(torch.int64).contiguous()
     if flag is not None:
-        if not torch.is_tensor(flag) or flag.device != device:
-            raise _Fallback("tensors are not on the GPU")
-        if flag.dim() != 1 or int(flag.shape[0]) != m:
-            raise ValueError(f"flag_vis of shape {tuple(flag.shape)} for {m} rows")
-        flag = flag.detach().contiguous()
-        flag = flag.view(torch.uint8) if flag.dtype == torch.bool else (flag != 0).view(torch.uint8)
+        flag = flag_u8(flag, device, m)
     return device, m, index, flag, P, scaling, bounds
 
 
 def _clamp_launch(device, m, index, flag, P, scaling, bounds):
     L = _r.HipBackend.require(device)
     with torch.cuda.device(device):
-        _lib.check(L.lograst_clamp_scale(m, _r._ptr(index), _r._ptr(flag), P, _r._ptr(scaling.detach()), _r._ptr(bounds[0]),
+        _lib.check(L.lograst_clamp_scale(m, _r._ptr(index), _r._ptr(flag), P, _r._ptr(scaling), _r._ptr(bounds[0]),
                                          _r._ptr(bounds[1]), _r._stream_ptr(device)))
 
 
+@dropins.dropin
 def clamp_scale(self, index):
     """LoG.clamp_scale on the device, in place, no read-back.  The rows of ``index`` are unique, as the reference's
     indexed assignment needs them to be."""
-    _count("calls", "clamp_scale")
-    try:
-        with torch.no_grad():
-            return _clamp_launch(*_clamp_inputs(self, index))
-    except _Fallback as why:
-        _fell_back("clamp_scale", str(why))
-        return _original("clamp_scale")(self, index)
+    _clamp_launch(*_clamp_inputs(self, index))
 
 
+@dropins.register
 def step(self):
     """LoG.step: the reference's control flow with the clamp on ``(index, flag_vis)`` -- no ``index[flag_vis]``, whose size
     the host would have to read back."""
-    _count("calls", "step")
+    dropins.count("calls", "step")
     vf = self.visibility_flag
     params = vf['params']
     index = vf['index']
@@ -353,9 +266,8 @@ def step(self):
     try:
         with torch.no_grad():
             clamp = _clamp_inputs(self, index, flag_vis)
-    except _Fallback as why:
-        _fell_back("step", str(why))
-        return _original("step")(self)
+    except Fallback as why:
+        return dropins.fall_back("step", why, self)
     self.optimizer.step(self.gaussian, index, params, flag_vis)
     # clip the scaling
     with torch.no_grad():
@@ -369,37 +281,6 @@ def step(self):
 
 # ---- installation --------------------------------------------------------------------------------------------------
 
-def _targets():
-    from LoG.model.level_of_gaussian import Gaussian, LoG
-    return {"log_prepare": (LoG, "prepare", log_prepare), "gaussian_prepare": (Gaussian, "prepare", gaussian_prepare),
-            "clamp_scale": (LoG, "clamp_scale", clamp_scale), "step": (LoG, "step", step)}
-
-
-def _original(name):
-    if name not in _originals:
-        cls, attr, ours = _targets()[name]
-        fn = getattr(cls, attr)
-        if fn is ours:
-            raise _lib.LograstError(f"log_amd.prepare: the reference's {attr} was replaced before install() could save it")
-        _originals[name] = fn
-    return _originals[name]
-
-
 def install():
     """Patch the reference classes in place (needs LoG importable); the original methods are kept for the fall-backs."""
-    targets = _targets()
-    for name in _METHODS:
-        _original(name)
-    for name in _METHODS:
-        cls, attr, ours = targets[name]
-        setattr(cls, attr, ours)
-    return targets["log_prepare"][0]
-
-
-def uninstall():
-    """Put the reference's methods back."""
-    targets = _targets()
-    for name in _METHODS:
-        if name in _originals:
-            cls, attr, _ = targets[name]
-            setattr(cls, attr, _originals[name])
+    return dropins.install()["log_prepare"][0]

@@ -175,7 +175,8 @@ def test_dropins_fall_back_to_the_reference_on_cpu_tensors(cpu_cuda_shims, caplo
         assert TensorTree.split_and_remove is densify.tree_split_and_remove
         assert Splitter.split_and_remove is densify.split_and_remove
         assert Splitter.split_and_remove_other is densify.split_and_remove_other
-        densify._logged.clear()
+        densify.dropins.logged.clear()
+        densify.reset_stats()
         with caplog.at_level("WARNING", logger="log_amd"):
             got = _state(_log_model(0, 400))
         densify.uninstall()
@@ -187,6 +188,10 @@ def test_dropins_fall_back_to_the_reference_on_cpu_tensors(cpu_cuda_shims, caplo
         assert got[k].dtype == want[k].dtype and torch.equal(got[k], want[k]), k
     logged = [r.getMessage() for r in caplog.records if "log_amd.densify" in r.getMessage()]
     assert len(logged) == 3 and all("not on the GPU" in m for m in logged), logged      # once per method, not per call
+    st = densify.stats()
+    methods = ("tree_split_and_remove", "split_and_remove", "split_and_remove_other")
+    assert set(st["calls"]) == set(methods) and min(st["calls"].values()) >= 1 and st["readbacks"] == {}
+    assert st["fallbacks"] == {(m, "tensors are not on the GPU"): st["calls"][m] for m in methods}       # every call fell back
 
 
 @needs_reference

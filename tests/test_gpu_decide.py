@@ -440,9 +440,6 @@ def test_every_fallback_reason_is_counted_and_leaves_the_model_alone():
     r = rounds[1]
     imeta, (ir,) = fixture("decide_init_scale1")
     calls = []
-    saved = dict(decide._originals)
-    decide._originals["update_depth_stage"] = lambda self, it: calls.append(("depth", it))
-    decide._originals["update_init_stage"] = lambda self, scale=1: calls.append(("init", scale))
     decide.reset_stats()
 
     def depth(change, **cfg):
@@ -460,7 +457,8 @@ def test_every_fallback_reason_is_counted_and_leaves_the_model_alone():
         change(log)
         decide.update_init_stage(log, scale=1)
         assert log.num_points == ir["p"] and log.counter.resets == []
-    try:
+    with decide.dropins.substituted(update_depth_stage=lambda self, it: calls.append(("depth", it)),
+                                    update_init_stage=lambda self, scale=1: calls.append(("init", scale))):
         depth(lambda log: setattr(log.gaussian, "scaling", log.gaussian.scaling.cpu()))
         depth(lambda log: setattr(log.counter, "visible_count", log.counter.visible_count.int()))
         depth(lambda log: setattr(log.gaussian.activation, "scaling_activation", torch.nn.functional.softplus))
@@ -471,9 +469,6 @@ def test_every_fallback_reason_is_counted_and_leaves_the_model_alone():
         init(lambda log: None, init_radius_split=-1)
         init(lambda log: setattr(log.counter, "weights_max", log.counter.weights_max.cpu()))
         init(lambda log: setattr(log.gaussian.activation, "opacity_activation", torch.tanh))
-    finally:
-        decide._originals.clear()
-        decide._originals.update(saved)
     assert calls == [("depth", 3)] * 6 + [("init", 1)] * 4
     reasons = decide.stats()["fallbacks"]
     assert set(reasons.values()) == {1} and len(reasons) == 10, reasons

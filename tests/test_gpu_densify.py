@@ -260,6 +260,21 @@ def test_traverse_on_a_densified_tree_matches_the_oracle(oracle_mod):
     assert deepest == 2          # the selection reached the children of the second round
 
 
+def test_one_host_synchronisation_per_call():
+    """The smallest fixture through the drop-ins: each call reads back once (the plan's counts) and none falls back."""
+    from log_amd import densify as dd
+    meta, (r,) = fixture("densify_firstsplit")
+    tree, splitter, g, opt, counter = stand_ins(meta, r)
+    dd.reset_stats()
+    fs, fr = dd.tree_split_and_remove(tree, dev(r["flag_split"]), dev(r["flag_remove"]))
+    assert dd.stats() == {"calls": {"tree_split_and_remove": 1}, "fallbacks": {}, "readbacks": {"tree_split_and_remove": 1}}
+    dd.reset_stats()
+    nk = dd.split_and_remove(splitter, g, opt, fs, fr, remove_split=False)
+    assert dd.stats() == {"calls": {"split_and_remove": 1}, "fallbacks": {}, "readbacks": {"split_and_remove": 1}}
+    assert int(nk) == int(r["num_keep"]) and g.xyz.shape[0] == r["src_row"].shape[0]
+    check_tree(tree, r, "firstsplit")
+
+
 # ---- the row move alone ----------------------------------------------------------------------------------------------
 
 def _plan(p, seed, children=4, remove_split=False, ps=0.05, pr=0.1):
@@ -327,12 +342,12 @@ def test_scan_second_level():
 def test_overlap_falls_back_and_counts():
     """Rows flagged for both while remove_split is off: the plan reports them and the drop-in refuses (the reference leaves
     the case undefined); with remove_split on they are simply split."""
-    from log_amd import densify as dd
+    from log_amd import _dropin, densify as dd
     fs = np.zeros(2000, bool)
     fr = np.zeros(2000, bool)
     fs[[3, 1500]] = True
     fr[[3, 1999]] = True
-    with pytest.raises(dd._Fallback, match="both split and remove"):
+    with pytest.raises(_dropin.Fallback, match="both split and remove"):
         dd.Plan(dev(fs), dev(fr), False, 2)
     plan = dd.Plan(dev(fs), dev(fr), True, 2)
     assert (plan.num_keep, plan.num_split, plan.overlap) == (1997, 2, 0)

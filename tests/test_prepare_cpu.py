@@ -187,7 +187,7 @@ def test_dropins_fall_back_to_the_reference_on_cpu_tensors(cpu_cuda_shims, caplo
     try:
         assert prepare.install() is LoG
         assert _methods() == (prepare.log_prepare, prepare.gaussian_prepare, prepare.clamp_scale, prepare.step)
-        prepare._logged.clear()
+        prepare.dropins.logged.clear()
         prepare.reset_stats()
         new = _log_model(0, 400)
         new.counter.radius3d_max.fill_(0.05)
@@ -221,15 +221,17 @@ def test_dropins_fall_back_to_the_reference_on_cpu_tensors(cpu_cuda_shims, caplo
 def test_fallback_reasons():
     """What the kernels do not cover is named before anything is launched."""
     import types
-    from log_amd import prepare
-    with pytest.raises(prepare._Fallback, match="not on the GPU"):
-        prepare._device_of(torch.zeros(4, 3))
+    from log_amd import _dropin, prepare
+    with pytest.raises(_dropin.Fallback, match="not on the GPU"):
+        prepare._device_and_rows(torch.zeros(4, 3))
     act = types.SimpleNamespace(scaling_activation=torch.sigmoid, opacity_activation=torch.sigmoid,
                                 rotation_activation=torch.nn.functional.normalize)
-    with pytest.raises(prepare._Fallback, match="activations other than exp / sigmoid / normalize"):
-        prepare._check_view_activations(act)
-    with pytest.raises(prepare._Fallback, match="activations"):
-        prepare._check_view_activations(None)
+    with pytest.raises(_dropin.Fallback, match="activations other than exp / sigmoid / normalize"):
+        _dropin.check_activations(act, *prepare._VIEW_ACTIVATIONS)
+    with pytest.raises(_dropin.Fallback, match="activations"):
+        _dropin.check_activations(None, *prepare._VIEW_ACTIVATIONS)
+    act.scaling_activation = torch.exp
+    _dropin.check_activations(act, *prepare._VIEW_ACTIVATIONS)
 
 
 @needs_reference
