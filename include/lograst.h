@@ -677,6 +677,35 @@ int lograst_loss_backward(int32_t batch, int32_t channels, int32_t height, int32
                           const float* gt, const int64_t* gt_strides, float l1_weight, const float* grad_loss,
                           const float* maps, float* grad_render, float* grad_render_l1, void* stream);
 
+/* The same loss with the L1 term on a per-image channel gain (LoG's view correction, renderer.py:243-245, without its
+ * render_correct tensor): l1 = mean | l1_gain[b, c] * render[b, c, y, x] - gt |, l1_gain fp32 [batch, channels] on the
+ * device, contiguous; the SSIM term is on render as above.  The product is one fp32 multiply and the subtraction a
+ * separate operation, so sign(0) = 0 holds exactly where gt == fp32(gain * render).
+ * lograst_loss_backward_gain writes ONE image gradient, grad_render = SSIM part + gain * (grad_loss * l1_scale * sign),
+ * and grad_gain[batch, channels] = grad_loss * l1_scale * sum over the plane of sign(gain * render - gt) * render,
+ * l1_scale = l1_weight / (batch * channels * height * width): per-workgroup sums in double, added per plane in a fixed
+ * order in double (scratch) and rounded to fp32 once -- no floating-point atomics, the same bits from run to run.
+ * scratch: lograst_loss_gain_scratch_bytes bytes, 8-byte aligned, serves either call. */
+size_t lograst_loss_gain_scratch_bytes(int32_t batch, int32_t channels, int32_t height, int32_t width);
+int lograst_loss_forward_gain(int32_t batch, int32_t channels, int32_t height, int32_t width, const float* render,
+                              const int64_t* render_strides, const float* gt, const int64_t* gt_strides, const float* l1_gain,
+                              float ssim_weight, float l1_weight, float* out3, float* maps, void* scratch, size_t scratch_bytes,
+                              void* stream);
+int lograst_loss_backward_gain(int32_t batch, int32_t channels, int32_t height, int32_t width, const float* render,
+                               const int64_t* render_strides, const float* gt, const int64_t* gt_strides, const float* l1_gain,
+                               float l1_weight, const float* grad_loss, const float* maps, float* grad_render, float* grad_gain,
+                               void* scratch, size_t scratch_bytes, void* stream);
+
+/* ---- Corrector.step (LoG/model/corrector.py:35-62): the AMSGrad step of ONE row of the view correction ----------------
+ * steps i32[views]; param, grad, exp_avg, exp_avg_sq, max_exp_avg_sq f32[views, width], contiguous, 1 <= width <= 64.
+ * One launch of one wave: steps[index] += 1; s = steps[index] - start_step; s < 0: nothing else is touched (grad stays).
+ * Otherwise t = clip(s / 100, 0, 1), lr = exp(log(lr_init) (1 - t) + log(lr_final) t) in double, the reference's
+ * _single_tensor_adam with max_exp_avg_sq (betas 0.9 / 0.999, eps 1e-15, bias corrections 1 - beta^s in fp32, a maximum
+ * that hands a NaN on) on the row, then grad[index] = 0.  Nothing comes back to the host; index is a host integer. */
+int lograst_corrector_step(int32_t views, int32_t width, int32_t index, int32_t start_step, double lr_init, double lr_final,
+                           int32_t* steps, float* param, float* grad, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq,
+                           void* stream);
+
 /* ---- the depth term of depth-supervised training (LoG/render/renderer.py:268-292 append_depth_loss with
  * LoG/render/loss.py:47-117 ScaleAndShiftInvariantLoss, one gradient scale) --------------------------------------------
  * pred, gt, acc: [height, width] fp32, each addressed through TWO ELEMENT STRIDES (y, x; host arrays of 2 int64).

@@ -17,7 +17,7 @@ def install_compute_radius():
 
 
 def install_all(fused_step=False, fused_loss=False, reuse_geometry=False, fused_depth_loss=False, device_densify=False,
-                device_prepare=False, device_decide=False):
+                device_prepare=False, device_decide=False, device_view_correction=False):
     """Everything a LoG process needs, in one call: the LoG.cuda.compute_radius module, then every
     drop-in method assigned onto LoG's own classes (needs LoG importable): LoG.get_all, TensorTree.traverse,
     Counter.update_by_output, SparseOptimizer.step.
@@ -41,7 +41,12 @@ def install_all(fused_step=False, fused_loss=False, reuse_geometry=False, fused_
     installed TensorTree.traverse.
     device_decide (opt-in): LoG.update_depth_stage and LoG.update_init_stage compute their split / remove flags, the top-k cut
     and every logged statistic on the device (log_amd.decide.install: one read-back of a fixed-size record per event), then
-    call the installed split_and_remove methods; without it the decisions stay the reference's torch code."""
+    call the installed split_and_remove methods; without it the decisions stay the reference's torch code.
+    device_view_correction (opt-in): Corrector.step becomes one launch with the row's step count and learning-rate schedule
+    on the device (no host synchronisation), Corrector.__getitem__ notes the rows it hands out, and
+    NaiveRendererAndLoss.calculate_loss gives them to the loss kernels as a per-image channel gain instead of reading
+    render_correct (log_amd.view_correction.install, which installs log_amd.loss as well: one image gradient, the gain's
+    gradient from the same kernel); without it the Corrector stays the reference's torch code."""
     install_compute_radius()
     from . import rasterizer
     rasterizer.set_geometry_reuse(bool(reuse_geometry))
@@ -63,4 +68,7 @@ def install_all(fused_step=False, fused_loss=False, reuse_geometry=False, fused_
     if device_decide:
         from . import decide
         installed.append(decide.install())
+    if device_view_correction:
+        from . import view_correction
+        installed.append(view_correction.install())
     return installed

@@ -169,6 +169,11 @@ _SIGNATURES = {
     "lograst_loss_forward": (ctypes.c_int, [c_int32] * 4 + [c_void_p] * 6 + [c_float, c_float, c_void_p, c_void_p, c_void_p,
                                             c_size_t, c_void_p]),
     "lograst_loss_backward": (ctypes.c_int, [c_int32] * 4 + [c_void_p] * 6 + [c_float] + [c_void_p] * 5),
+    "lograst_loss_gain_scratch_bytes": (c_size_t, [c_int32] * 4),
+    "lograst_loss_forward_gain": (ctypes.c_int, [c_int32] * 4 + [c_void_p] * 5 + [c_float, c_float, c_void_p, c_void_p, c_void_p,
+                                                 c_size_t, c_void_p]),
+    "lograst_loss_backward_gain": (ctypes.c_int, [c_int32] * 4 + [c_void_p] * 5 + [c_float] + [c_void_p] * 5 + [c_size_t, c_void_p]),
+    "lograst_corrector_step": (ctypes.c_int, [c_int32] * 4 + [ctypes.c_double, ctypes.c_double] + [c_void_p] * 7),
     "lograst_depth_loss_record_bytes": (c_size_t, [c_int32]),
     "lograst_depth_loss_forward": (ctypes.c_int, [c_int32, c_int32] + [c_void_p] * 6 + [c_int32, c_void_p, c_void_p,
                                                   ctypes.c_double, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p,

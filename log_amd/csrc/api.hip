@@ -1100,6 +1100,7 @@ static int lr_loss_args(LossArgs& a, int32_t batch, int32_t channels, int32_t he
   for (int k = 0; k < LS_WIN_TAPS; k++) { g[k] = std::exp(-(double)((k - 5) * (k - 5)) / (2.0 * 1.5 * 1.5)); sum += g[k]; }
   for (int k = 0; k < LS_WIN_TAPS; k++) a.w[k] = (float)(g[k] / sum);
   a.scale = 0.f; a.l1_scale = 0.f; a.maps = nullptr; a.partial = nullptr; a.ntx = a.nty = 0;
+  a.gain = nullptr; a.gain_partial = nullptr;
   return 0;
 }
 
@@ -1142,6 +1143,59 @@ int lograst_loss_backward(int32_t batch, int32_t channels, int32_t height, int32
   a.maps = const_cast<float*>(maps);
   g_prof_call++;
   LR_HIP(lr_launch_loss_bwd(a, grad_loss, grad_render, a.render_l1 ? grad_render_l1 : nullptr, (hipStream_t)stream));
+  return LOGRAST_OK;
+}
+
+// The same loss with the L1 term on gain[b, c] * render (LoG's view correction): no render_l1 tensor, one image gradient
+// and the gradient of the gain.
+size_t lograst_loss_gain_scratch_bytes(int32_t batch, int32_t channels, int32_t height, int32_t width) {
+  return lr_loss_gain_scratch_bytes(batch, channels, height, width);
+}
+
+int lograst_loss_forward_gain(int32_t batch, int32_t channels, int32_t height, int32_t width, const float* render,
+                              const int64_t* render_strides, const float* gt, const int64_t* gt_strides, const float* l1_gain,
+                              float ssim_weight, float l1_weight, float* out3, float* maps, void* scratch, size_t scratch_bytes,
+                              void* stream) {
+  LossArgs a;
+  const int rc = lr_loss_args(a, batch, channels, height, width, render, render_strides, nullptr, nullptr, gt, gt_strides);
+  if (rc < 0) return rc;
+  if (!out3) return lr_fail(LOGRAST_ERR_ARG, "out3 is NULL");
+  if (rc == 1) {
+    LR_HIP(hipMemsetAsync(out3, 0, 3 * sizeof(float), (hipStream_t)stream));
+    return LOGRAST_OK;
+  }
+  if (!l1_gain) return lr_fail(LOGRAST_ERR_ARG, "l1_gain is NULL");
+  if (!scratch || scratch_bytes < lr_loss_scratch_bytes(batch, channels, height, width) || (reinterpret_cast<uintptr_t>(scratch) & 7u))
+    return lr_fail(LOGRAST_ERR_ARG, "loss scratch too small (lograst_loss_gain_scratch_bytes) or not 8-byte aligned");
+  a.ntx = (width - 10 + 31) / 32; a.nty = (height - 10 + 31) / 32;
+  const double count = (double)batch * channels * (double)(height - 10) * (double)(width - 10);
+  a.scale = (float)(-(double)ssim_weight / count);
+  a.maps = maps;
+  a.partial = reinterpret_cast<float*>(scratch);
+  a.gain = l1_gain;
+  g_prof_call++;
+  LR_HIP(lr_launch_loss_fwd(a, ssim_weight, l1_weight, out3, (hipStream_t)stream));
+  return LOGRAST_OK;
+}
+
+int lograst_loss_backward_gain(int32_t batch, int32_t channels, int32_t height, int32_t width, const float* render,
+                               const int64_t* render_strides, const float* gt, const int64_t* gt_strides, const float* l1_gain,
+                               float l1_weight, const float* grad_loss, const float* maps, float* grad_render, float* grad_gain,
+                               void* scratch, size_t scratch_bytes, void* stream) {
+  LossArgs a;
+  const int rc = lr_loss_args(a, batch, channels, height, width, render, render_strides, nullptr, nullptr, gt, gt_strides);
+  if (rc < 0) return rc;
+  if (rc == 1) return LOGRAST_OK;
+  if (!grad_loss || !maps || !grad_render || !l1_gain || !grad_gain) return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
+  if (!scratch || scratch_bytes < lr_loss_gain_scratch_bytes(batch, channels, height, width) || (reinterpret_cast<uintptr_t>(scratch) & 7u))
+    return lr_fail(LOGRAST_ERR_ARG, "loss scratch too small (lograst_loss_gain_scratch_bytes) or not 8-byte aligned");
+  a.ntx = (width + 31) / 32; a.nty = (height + 31) / 32;
+  a.l1_scale = (float)((double)l1_weight / ((double)batch * channels * (double)height * (double)width));
+  a.maps = const_cast<float*>(maps);
+  a.gain = l1_gain;
+  a.gain_partial = reinterpret_cast<double*>(scratch);
+  g_prof_call++;
+  LR_HIP(lr_launch_loss_bwd_gain(a, grad_loss, grad_render, grad_gain, (hipStream_t)stream));
   return LOGRAST_OK;
 }
 
@@ -1215,6 +1269,26 @@ int lograst_sparse_adam(int32_t m, int32_t num_points, const int64_t* index, con
   a.bc2_sqrt = (float)bias_correction2_sqrt; a.eps = (float)eps;
   g_prof_call++;
   LR_HIP(lr_launch_sparse_adam(a, num_keys, (hipStream_t)stream));
+  return LOGRAST_OK;
+}
+
+// Corrector.step (corrector.py:35-62) for one row of the [views, width] buffers, the step count and the schedule on the device
+int lograst_corrector_step(int32_t views, int32_t width, int32_t index, int32_t start_step, double lr_init, double lr_final,
+                           int32_t* steps, float* param, float* grad, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq,
+                           void* stream) {
+  if (views < 1 || width < 1 || width > 64) return lr_fail(LOGRAST_ERR_ARG, "views must be >= 1 and width in 1 .. 64");
+  if (index < 0 || index >= views) return lr_fail(LOGRAST_ERR_ARG, "index outside [0, views)");
+  if (!(lr_init > 0.0) || !(lr_final > 0.0) || !std::isfinite(lr_init) || !std::isfinite(lr_final))
+    return lr_fail(LOGRAST_ERR_ARG, "lr_init and lr_final must be positive and finite");
+  if (!steps || !param || !grad || !exp_avg || !exp_avg_sq || !max_exp_avg_sq) return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
+  CorrectorArgs a;
+  a.steps = steps; a.param = param; a.grad = grad; a.exp_avg = exp_avg; a.exp_avg_sq = exp_avg_sq; a.max_exp_avg_sq = max_exp_avg_sq;
+  a.log_lr_init = std::log(lr_init); a.log_lr_final = std::log(lr_final);
+  a.index = index; a.width = width; a.start_step = start_step;
+  // betas 0.9 / 0.999 and eps 1e-15 of the reference's call, narrowed as lograst_sparse_adam narrows them
+  a.beta1 = (float)0.9; a.beta2 = (float)0.999; a.omb1 = (float)(1.0 - 0.9); a.omb2 = (float)(1.0 - 0.999); a.eps = (float)1e-15;
+  g_prof_call++;
+  LR_HIP(lr_launch_corrector_step(a, (hipStream_t)stream));
   return LOGRAST_OK;
 }
 

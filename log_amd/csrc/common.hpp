@@ -522,6 +522,15 @@ struct AdamArgs {
   float beta1, beta2, omb1, omb2, bc2_sqrt, eps;
 };
 
+// Corrector.step on one row (counter.hip: corrector_step_kernel; filled in by api.hip)
+struct CorrectorArgs {
+  int32_t* steps;                                                  // [V]
+  float *param, *grad, *exp_avg, *exp_avg_sq, *max_exp_avg_sq;     // [V, width]
+  double log_lr_init, log_lr_final;
+  int32_t index, width, start_step;
+  float beta1, beta2, omb1, omb2, eps;
+};
+
 // ---- fused get_all (sh.hip: ga_fwd_kernel / ga_bwd_kernel) ---------------------------------------------
 struct GatherArgs {
   const int64_t* index;
@@ -551,6 +560,8 @@ struct LossArgs {
   float* maps;                                                     // 3 x [B*C, H-10, W-10]
   float* partial;                                                  // forward: 2 floats per workgroup
   int32_t B, C, H, W, ntx, nty;                                    // ntx * nty tiles per plane (of outputs forward, of the image backward)
+  const float* gain;                                               // lograst_loss_*_gain: [B, C], the L1 term reads gain * render; else NULL
+  double* gain_partial;                                            // backward with gain: one double per workgroup
 };
 
 // ---- host-side launch bookkeeping (api.hip) ------------------------------------------------------

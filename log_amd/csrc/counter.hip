@@ -276,3 +276,43 @@ hipError_t lr_launch_sparse_adam(const AdamArgs& a, int num_keys, hipStream_t s)
   lr_prof_end(LRK_ADAM, s);
   return hipGetLastError();
 }
+
+// ---- Corrector.step, one row (corrector.py:35-62) --------------------------------------------------------------------
+// One wave, lane c = column c of row `index` of the [V, C] buffers.  steps[index] += 1; s = steps[index] - start_step;
+// s < 0: nothing else is touched (the gradient stays, as in the reference).  Otherwise the learning rate of the
+// reference's schedule in double -- t = clip(s / 100, 0, 1), lr = exp(log(lr_init) (1 - t) + log(lr_final) t) -- and the op
+// sequence of _single_tensor_adam with amsgrad as adam_kernel has it, with the scalars torch makes of an int32 step tensor:
+// bias_correction = 1 - powf(beta, (float)s) in fp32, step_size = (1 / bias_correction1) * (float)lr (a Python scalar
+// divided by a tensor is reciprocal() * scalar), eps = (float)1e-15.  Then grad[index] = 0.  Nothing is read back.
+__global__ void __launch_bounds__(64)
+corrector_step_kernel(CorrectorArgs a) {
+  const int c = (int)threadIdx.x;
+  const int32_t count = a.steps[a.index] + 1;          // every lane reads before lane 0 writes: one wave, in program order
+  if (c == 0) a.steps[a.index] = count;
+  const int32_t s = count - a.start_step;
+  if (s < 0 || c >= a.width) return;
+  double t = (double)s / 100.0;
+  t = t < 0.0 ? 0.0 : (t > 1.0 ? 1.0 : t);
+  const float lr = (float)exp(a.log_lr_init * (1.0 - t) + a.log_lr_final * t);
+  const float bc1 = 1.f - powf(a.beta1, (float)s), bc2 = 1.f - powf(a.beta2, (float)s);
+  const float step_size = (1.f / bc1) * lr;
+  const float bc2_sqrt = sqrtf(bc2);
+  const size_t o = (size_t)a.index * (size_t)a.width + (size_t)c;
+  const float g = a.grad[o];
+  const float m = lr_fma(g, a.omb1, a.exp_avg[o] * a.beta1);
+  const float v = lr_fma(a.omb2 * g, g, a.exp_avg_sq[o] * a.beta2);
+  const float vd = lr_max_nan(a.max_exp_avg_sq[o], v);
+  const float denom = sqrtf(vd) / bc2_sqrt + a.eps;
+  a.exp_avg[o] = m;
+  a.exp_avg_sq[o] = v;
+  a.max_exp_avg_sq[o] = vd;
+  a.param[o] = a.param[o] + (-step_size) * (m / denom);
+  a.grad[o] = 0.f;
+}
+
+hipError_t lr_launch_corrector_step(const CorrectorArgs& a, hipStream_t s) {
+  lr_prof_begin(LRK_ADAM, s);
+  hipLaunchKernelGGL(corrector_step_kernel, dim3(1), dim3(64), 0, s, a);
+  lr_prof_end(LRK_ADAM, s);
+  return hipGetLastError();
+}

@@ -112,11 +112,14 @@ hipError_t lr_launch_id_histogram(int n, const int32_t* pid, int npix, int32_t* 
                                   hipStream_t s);
 hipError_t lr_launch_counter(const CounterArgs& a, hipStream_t s);
 hipError_t lr_launch_sparse_adam(const AdamArgs& a, int num_keys, hipStream_t s);
+hipError_t lr_launch_corrector_step(const CorrectorArgs& a, hipStream_t s);
 
 // loss.hip
 size_t lr_loss_scratch_bytes(int B, int C, int H, int W);
 hipError_t lr_launch_loss_fwd(const LossArgs& a, float wa, float wb, float* out3, hipStream_t s);
 hipError_t lr_launch_loss_bwd(const LossArgs& a, const float* grad_loss, float* g_render, float* g_render_l1, hipStream_t s);
+size_t lr_loss_gain_scratch_bytes(int B, int C, int H, int W);
+hipError_t lr_launch_loss_bwd_gain(const LossArgs& a, const float* grad_loss, float* g_render, float* grad_gain, hipStream_t s);
 
 // depth_loss.hip
 #define DL_PATCH 64             // the patch side, the only one the kernels have

@@ -20,6 +20,13 @@
 //   maps[0] = d ssim / d mu1' at fixed centred second moments, maps[1] = d ssim / d s11, maps[2] = d ssim / d s12,
 // and the backward is  dL/drender(p) = g * sum_q w(p-q) * (maps0(q) + 2 (render(p)-0.5) maps1(q) + (gt(p)-0.5) maps2(q)).
 //
+// Gain.  The <true> instantiations of the two kernels (lograst_loss_*_gain) take the L1 term of gain[b, c] * render instead
+// of a second image: LoG's view correction (renderer.py:243-245) without its render_correct tensor.  The product is one
+// fp32 multiply and the subtraction of gt a separate operation (the library is built without contraction), so that
+// sign(0) = 0 falls on the pixels where gt == fp32(gain * render), as in the reference.  The backward leaves ONE image
+// gradient and, per workgroup, the double sum of sign * render, which loss_gain_reduce_kernel adds per (b, c) in a fixed
+// order.  The <false> instantiations are the kernels as they were.
+//
 // Determinism: fixed tap order (ascending tap index, horizontal then vertical), explicit fmaf only, per-workgroup
 // partial sums reduced in a fixed order by one workgroup in double -- no floating-point atomics anywhere.
 #include "common.hpp"
@@ -33,6 +40,15 @@
 #define LS_CENTER 0.5f
 #define LS_STAGE ((LS_IN * LS_IN + LS_THREADS - 1) / LS_THREADS)    // tile elements per thread (7)
 #define LS_HITEMS ((LS_IN * LS_T + LS_THREADS - 1) / LS_THREADS)    // horizontal-pass items per thread (6)
+
+// the backward with gain: one double per workgroup of IMAGE tiles -- never fewer than the forward's output tiles, so one
+// size serves both launches
+size_t lr_loss_gain_scratch_bytes(int B, int C, int H, int W) {
+  if (B <= 0 || C <= 0 || H < LS_WIN_TAPS || W < LS_WIN_TAPS) return 256;
+  const size_t ntx = (size_t)(W + LS_T - 1) / LS_T, nty = (size_t)(H + LS_T - 1) / LS_T;
+  const size_t bytes = 8 * ntx * nty * (size_t)B * (size_t)C;
+  return (bytes + 255) & ~(size_t)255;
+}
 
 size_t lr_loss_scratch_bytes(int B, int C, int H, int W) {
   if (B <= 0 || C <= 0 || H < LS_WIN_TAPS || W < LS_WIN_TAPS) return 256;
@@ -53,9 +69,18 @@ LR_DEV float ls_block_sum(float v, float* ws) {
   __syncthreads();
   return ((ws[0] + ws[1]) + ws[2]) + ws[3];
 }
+// the same in double (the gain gradient's partial sums)
+LR_DEV double ls_block_sum(double v, double* ws) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d);
+  if ((threadIdx.x & 63u) == 0) ws[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((ws[0] + ws[1]) + ws[2]) + ws[3];
+}
 
 // The moments travel in pairs -- (render, gt), (mu1, mu2), (e11, e22) -- one 8-byte LDS access and one packed fp32
 // instruction (v_pk_fma_f32 / v_pk_mul_f32) per pair; element for element the same IEEE operations as scalar code.
+template <bool GAIN>
 __global__ void __launch_bounds__(LS_THREADS)
 loss_fwd_kernel(LossArgs a) {
   __shared__ lr_f2 srg[LS_IN * LS_IN];                      // (render - 0.5, gt - 0.5)
@@ -73,8 +98,10 @@ loss_fwd_kernel(LossArgs a) {
   const int OW = a.W - LS_HALO, OH = a.H - LS_HALO;
   const float* rp = ls_plane(a.render, a.rs, b, c);
   const float* gp = ls_plane(a.gt, a.gs, b, c);
-  const float* lp = a.render_l1 ? ls_plane(a.render_l1, a.ls, b, c) : nullptr;
+  const float* lp = (!GAIN && a.render_l1) ? ls_plane(a.render_l1, a.ls, b, c) : nullptr;
   const int rsy = (int)a.rs[2], rsx = (int)a.rs[3], gsy = (int)a.gs[2], gsx = (int)a.gs[3], lsy = (int)a.ls[2], lsx = (int)a.ls[3];
+  float gain = 1.f;
+  if constexpr (GAIN) gain = a.gain[b * a.C + c];
 
   // stage the input tile: all of a thread's loads are requested before the first is used.  Every image pixel belongs to
   // exactly one tile's L1 sum (the last tile of a row / column also owns its halo).
@@ -95,7 +122,8 @@ loss_fwd_kernel(LossArgs a) {
 #pragma unroll
   for (int u = 0; u < LS_STAGE; u++) {
     const int i = tid + u * LS_THREADS;
-    if (own[u]) l1 += fabsf((lp ? lv[u] : rv[u]) - gv[u]);
+    if constexpr (GAIN) { if (own[u]) l1 += fabsf(gain * rv[u] - gv[u]); }
+    else if (own[u]) l1 += fabsf((lp ? lv[u] : rv[u]) - gv[u]);
     if (i < LS_IN * LS_IN) srg[i] = lr_f2{rv[u] - LS_CENTER, gv[u] - LS_CENTER};
   }
   __syncthreads();
@@ -223,6 +251,27 @@ loss_reduce_kernel(const float2* __restrict__ partial, uint32_t n, double inv_co
   }
 }
 
+// one workgroup per (b, c): thread t adds the plane's partials t, t + 256, ... in double, then a fixed tree over the threads;
+// grad_gain[b, c] = gl * l1_scale * sum, rounded to fp32 once
+#define LS_GAIN_RED_THREADS 256
+__global__ void __launch_bounds__(LS_GAIN_RED_THREADS)
+loss_gain_reduce_kernel(const double* __restrict__ partial, int C, uint32_t tiles, const float* __restrict__ grad_loss, float l1_scale,
+                        float* __restrict__ grad_gain) {
+  __shared__ double s[LS_GAIN_RED_THREADS];
+  const uint32_t b = blockIdx.x / (uint32_t)C, c = blockIdx.x - b * (uint32_t)C;
+  const double* p = partial + ((size_t)b * tiles) * (size_t)C + c;      // tile t of the plane: p[t * C]
+  double acc = 0.0;
+  for (uint32_t t = threadIdx.x; t < tiles; t += LS_GAIN_RED_THREADS) acc += p[(size_t)t * (size_t)C];
+  s[threadIdx.x] = acc;
+  __syncthreads();
+  for (uint32_t d = LS_GAIN_RED_THREADS / 2; d >= 1; d >>= 1) {
+    if (threadIdx.x < d) s[threadIdx.x] += s[threadIdx.x + d];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) grad_gain[blockIdx.x] = (float)(((double)grad_loss[0] * (double)l1_scale) * s[0]);
+}
+
+template <bool GAIN>
 __global__ void __launch_bounds__(LS_THREADS)
 loss_bwd_kernel(LossArgs a, const float* __restrict__ grad_loss, float* __restrict__ g_render, float* __restrict__ g_render_l1) {
   __shared__ lr_f2 sm01[LS_IN * LS_IN];                     // (maps0, maps1)
@@ -247,8 +296,10 @@ loss_bwd_kernel(LossArgs a, const float* __restrict__ grad_loss, float* __restri
   const int x = x0 + xo;
   const float* rp = ls_plane(a.render, a.rs, b, c);
   const float* gp = ls_plane(a.gt, a.gs, b, c);
-  const float* lp = a.render_l1 ? ls_plane(a.render_l1, a.ls, b, c) : nullptr;
+  const float* lp = (!GAIN && a.render_l1) ? ls_plane(a.render_l1, a.ls, b, c) : nullptr;
   const int rsy = (int)a.rs[2], rsx = (int)a.rs[3], gsy = (int)a.gs[2], gsx = (int)a.gs[3], lsy = (int)a.ls[2], lsx = (int)a.ls[3];
+  float gain = 1.f;
+  if constexpr (GAIN) gain = a.gain[b * a.C + c];
   float pr[LS_ROWS], pg[LS_ROWS], pl[LS_ROWS];
 #pragma unroll
   for (int j = 0; j < LS_ROWS; j++) {
@@ -316,28 +367,36 @@ loss_bwd_kernel(LossArgs a, const float* __restrict__ grad_loss, float* __restri
   }
 
   const float gl = grad_loss[0];
-  if (x >= a.W) return;
+  if constexpr (!GAIN) { if (x >= a.W) return; }                    // (with gain every thread reaches the workgroup sum)
   const int64_t out_plane = bc * ((int64_t)a.H * a.W);
+  float sr = 0.f;                                                   // with gain: sum of sign * render over this thread's pixels
 #pragma unroll
   for (int j = 0; j < LS_ROWS; j++) {
     const int y = y0 + yq + j;
-    if (y >= a.H) continue;
+    if (y >= a.H || (GAIN && x >= a.W)) continue;
     const float r = pr[j], g = pg[j];
     float G = gl * lr_fma(g - LS_CENTER, a2[j], lr_fma(2.f * (r - LS_CENTER), a01[j].y, a01[j].x));
-    const float d = (lp ? pl[j] : r) - g;
+    const float d = (GAIN ? gain * r : (lp ? pl[j] : r)) - g;
     const float sgn = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);       // sign(0) = 0, as torch.nn.L1Loss
     const float l1g = gl * (a.l1_scale * sgn);
     const int o = y * a.W + x;
-    if (lp) g_render_l1[out_plane + o] = l1g;
+    if constexpr (GAIN) { G += gain * l1g; sr += sgn * r; }
+    else if (lp) g_render_l1[out_plane + o] = l1g;
     else G += l1g;
     g_render[out_plane + o] = G;
+  }
+  if constexpr (GAIN) {
+    __shared__ double gws[4];
+    const double bsum = ls_block_sum((double)sr, gws);
+    if (tid == 0) a.gain_partial[blockIdx.x] = bsum;
   }
 }
 
 hipError_t lr_launch_loss_fwd(const LossArgs& a, float wa, float wb, float* out3, hipStream_t s) {
   const uint32_t blocks = (uint32_t)a.ntx * (uint32_t)a.nty * (uint32_t)a.B * (uint32_t)a.C;
   lr_prof_begin(LRK_LOSS_FWD, s);
-  hipLaunchKernelGGL(loss_fwd_kernel, dim3(blocks), dim3(LS_THREADS), 0, s, a);
+  if (a.gain) hipLaunchKernelGGL(loss_fwd_kernel<true>, dim3(blocks), dim3(LS_THREADS), 0, s, a);
+  else hipLaunchKernelGGL(loss_fwd_kernel<false>, dim3(blocks), dim3(LS_THREADS), 0, s, a);
   const double count = (double)a.B * a.C * (double)(a.H - LS_HALO) * (double)(a.W - LS_HALO);
   const double count_l1 = (double)a.B * a.C * (double)a.H * (double)a.W;
   hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(LS_RED_THREADS), 0, s, reinterpret_cast<const float2*>(a.partial), blocks, 1.0 / count,
@@ -349,7 +408,17 @@ hipError_t lr_launch_loss_fwd(const LossArgs& a, float wa, float wb, float* out3
 hipError_t lr_launch_loss_bwd(const LossArgs& a, const float* grad_loss, float* g_render, float* g_render_l1, hipStream_t s) {
   const uint32_t blocks = (uint32_t)a.ntx * (uint32_t)a.nty * (uint32_t)a.B * (uint32_t)a.C;
   lr_prof_begin(LRK_LOSS_BWD, s);
-  hipLaunchKernelGGL(loss_bwd_kernel, dim3(blocks), dim3(LS_THREADS), 0, s, a, grad_loss, g_render, g_render_l1);
+  hipLaunchKernelGGL(loss_bwd_kernel<false>, dim3(blocks), dim3(LS_THREADS), 0, s, a, grad_loss, g_render, g_render_l1);
+  lr_prof_end(LRK_LOSS_BWD, s);
+  return hipGetLastError();
+}
+
+hipError_t lr_launch_loss_bwd_gain(const LossArgs& a, const float* grad_loss, float* g_render, float* grad_gain, hipStream_t s) {
+  const uint32_t tiles = (uint32_t)a.ntx * (uint32_t)a.nty, planes = (uint32_t)a.B * (uint32_t)a.C;
+  lr_prof_begin(LRK_LOSS_BWD, s);
+  hipLaunchKernelGGL(loss_bwd_kernel<true>, dim3(tiles * planes), dim3(LS_THREADS), 0, s, a, grad_loss, g_render, (float*)nullptr);
+  hipLaunchKernelGGL(loss_gain_reduce_kernel, dim3(planes), dim3(LS_GAIN_RED_THREADS), 0, s, (const double*)a.gain_partial, (int)a.C,
+                     tiles, grad_loss, a.l1_scale, grad_gain);
   lr_prof_end(LRK_LOSS_BWD, s);
   return hipGetLastError();
 }

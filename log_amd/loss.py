@@ -3,7 +3,9 @@ LoG/render/renderer.py:253-266 (``calculate_loss``) and LoG/render/loss.py:6-44 
 kernel + a fixed-order reduction and one backward kernel (log_amd/csrc/loss.hip, C ABI ``lograst_loss_*``) instead of
 five grouped ``conv2d``, a dozen element-wise kernels and their autograd backward.
 
-* ``l1_ssim_loss(render, gt, render_l1=None, ssim_weight=0.2, l1_weight=0.8) -> (loss, l1, ssim)``
+* ``l1_ssim_loss(render, gt, render_l1=None, ssim_weight=0.2, l1_weight=0.8, l1_gain=None) -> (loss, l1, ssim)``;
+  ``l1_gain`` [B, C] puts the L1 term on ``l1_gain[b, c] * render`` inside the kernels (LoG's view correction without its
+  ``render_correct`` image: C ABI ``lograst_loss_*_gain``, one image gradient and the gradient of the gain)
 * ``ssim(img1, img2)`` = what ``SSIM(11, C).forward(img1, img2)`` returns (``1 - mean(ssim_map)``)
 * ``install()`` assigns drop-ins onto the reference's classes (``SSIM.forward``, ``NaiveRendererAndLoss.calculate_loss``);
   ``log_amd.install_all(fused_loss=True)`` calls it.
@@ -21,6 +23,7 @@ from .rasterizer import _ptr, _stream_ptr
 
 WINDOW = 11          # taps of the SSIM window (sigma 1.5), the only size the kernel has
 TILE = 32            # output pixels per workgroup tile side (loss.hip: LS_T)
+GAIN_REDUCE_THREADS = 256    # threads that add one plane's partial sums of the gain gradient (loss.hip: LS_GAIN_RED_THREADS)
 
 
 def window_taps():
@@ -103,17 +106,77 @@ class _L1SSIM(torch.autograd.Function):
                 g_l1 if ctx.l1_is_input and ctx.needs_input_grad[2] else None, None, None)
 
 
+class _L1SSIMGain(torch.autograd.Function):
+    """The loss with the L1 term on ``gain[b, c] * render``: gradients for render and for the gain."""
+
+    @staticmethod
+    def forward(ctx, render, gt, gain, ssim_weight, l1_weight):
+        L = _require(render, gt, None)
+        if ctx.needs_input_grad[1]:
+            raise _lib.LograstError("log_amd.loss: gt gets no gradient (detach it)")
+        device = render.device
+        B, C, H, W = (int(s) for s in render.shape)
+        if not torch.is_tensor(gain) or gain.device != device or gain.dtype != torch.float32 or tuple(gain.shape) != (B, C):
+            raise ValueError(f"l1_gain: expected a float32 tensor [{B}, {C}] on {device}, got "
+                             f"{getattr(gain, 'dtype', type(gain))} {tuple(getattr(gain, 'shape', ()))}")
+        r, g, k = render.detach(), gt.detach(), gain.detach().contiguous()
+        need_grad = any(ctx.needs_input_grad[i] for i in (0, 2))
+        out = torch.empty(3, dtype=torch.float32, device=device)
+        nmaps = 3 * B * C * max(H - WINDOW + 1, 0) * max(W - WINDOW + 1, 0)
+        maps = torch.empty(nmaps, dtype=torch.float32, device=device) if need_grad else None
+        nbytes = L.lograst_loss_gain_scratch_bytes(B, C, H, W)
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        with torch.cuda.device(device):
+            _lib.check(L.lograst_loss_forward_gain(
+                B, C, H, W, _ptr(r), _strides(r), _ptr(g), _strides(g), _ptr(k), float(ssim_weight), float(l1_weight),
+                _ptr(out), _ptr(maps), _ptr(scratch), nbytes, _stream_ptr(device)))
+        ctx.geom = (B, C, H, W, float(l1_weight))
+        ctx.tensors = (r, g, k, maps)
+        loss, stats = out[0], out[1:3]
+        ctx.mark_non_differentiable(stats)
+        return loss, stats
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_loss, _grad_stats):
+        B, C, H, W, l1_weight = ctx.geom
+        r, g, k, maps = ctx.tensors
+        device = r.device
+        L = _lib.lib()
+        gl = grad_loss.detach().to(device=device, dtype=torch.float32).reshape(1).contiguous()
+        g_render = torch.empty((B, C, H, W), dtype=torch.float32, device=device)
+        g_gain = torch.zeros((B, C), dtype=torch.float32, device=device)
+        nbytes = L.lograst_loss_gain_scratch_bytes(B, C, H, W)
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        with torch.cuda.device(device):
+            _lib.check(L.lograst_loss_backward_gain(
+                B, C, H, W, _ptr(r), _strides(r), _ptr(g), _strides(g), _ptr(k), l1_weight, _ptr(gl), _ptr(maps),
+                _ptr(g_render), _ptr(g_gain), _ptr(scratch), nbytes, _stream_ptr(device)))
+        return (g_render if ctx.needs_input_grad[0] else None, None, g_gain if ctx.needs_input_grad[2] else None, None, None)
+
+
+def _fused_gain(render, gt, gain, ssim_weight, l1_weight):
+    return _L1SSIMGain.apply(render, gt, gain, ssim_weight, l1_weight)
+
+
 def _fused(render, gt, render_l1, ssim_weight, l1_weight):
     if render_l1 is render:
         render_l1 = None
     return _L1SSIM.apply(render, gt, render_l1, ssim_weight, l1_weight)
 
 
-def l1_ssim_loss(render, gt, render_l1=None, ssim_weight=0.2, l1_weight=0.8):
+def l1_ssim_loss(render, gt, render_l1=None, ssim_weight=0.2, l1_weight=0.8, l1_gain=None):
     """-> (loss, l1, ssim): ``loss = ssim_weight * ssim + l1_weight * l1`` carries the graph (gradients for ``render`` and,
     when it is a tensor of its own, ``render_l1``); ``l1 = mean|render_l1 - gt|`` and ``ssim = 1 - mean(ssim_map(render,
     gt))`` are detached 0-dim views of the same device buffer.  All tensors [B, C, H, W] float32 on the device, any
-    strides; H, W >= 11."""
+    strides; H, W >= 11.
+    ``l1_gain`` (float32 [B, C] on the device, instead of ``render_l1``): ``l1 = mean|l1_gain[b, c] * render - gt|``, the
+    product taken inside the kernels; gradients for ``render`` (one image) and for ``l1_gain``."""
+    if l1_gain is not None:
+        if render_l1 is not None:
+            raise ValueError("l1_gain and render_l1 are mutually exclusive: the L1 term reads one of them")
+        loss, stats = _fused_gain(render, gt, l1_gain, ssim_weight, l1_weight)
+        return loss, stats[0], stats[1]
     loss, stats = _fused(render, gt, render_l1, ssim_weight, l1_weight)
     return loss, stats[0], stats[1]
 
