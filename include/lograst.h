@@ -116,11 +116,19 @@ typedef struct lograst_view {
    * (and gathering every record of a chunk) again.  A visit the masks leave out adds exactly zero to every sum: same
    * gradients up to the order of the float atomics.  Device, 32-byte aligned, hit_mask_words 64-bit words >= lograst_hit_mask_bytes(capacity, width, height) / 8,
    * uninitialised; the backward must be given the very buffer (contents untouched) of the forward whose tile_state it is
-   * handed.  Speed only: 30 M Gaussians, reverse walk 640 -> see DESIGN.md section 4. */
+   * handed.  Speed only: 30 M Gaussians, reverse walk 640 -> see DESIGN.md section 4.
+   * What lograst_backward does with a buffer it cannot use (the instance count lives on the device, so this is checked
+   * there, by every workgroup of the reverse walk, without a host synchronisation): if hit_mask_words holds fewer than
+   * 16 * ((instances >> 6) + tiles) words -- the slots this view's lists index -- or if hit_mask_form is not the form the
+   * forward recorded in tile_state when it wrote the masks, the walk reads NO word of the buffer and visits every entry of
+   * every chunk instead.  That is a superset of any mask, so the gradients are those of a backward without hit_masks
+   * (slower; no error is returned).  Contents changed after the forward are not detectable and give the sums of the
+   * visits they name. */
   uint64_t* hit_masks;
   uint64_t hit_mask_words;
   /* lograst_backward only: what lograst_forward_form() returned for the forward's view (1 row-split, 2 quadrant; 0 = do not
-   * use the masks).  The reverse walk takes the masks only when it runs in that same form (walk_form / LOGRAST_BWD_ROWS). */
+   * use the masks).  The reverse walk takes the masks only when it runs in that same form (walk_form / LOGRAST_BWD_ROWS)
+   * and the forward wrote them in it (above). */
   int32_t hit_mask_form;
 } lograst_view;
 

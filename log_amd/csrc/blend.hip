@@ -110,8 +110,11 @@ LR_DEV bool lr_lazy_range(const uint32_t* sorted, uint32_t tiles, int lazy, uint
   if (!lazy) return true;
   if (end - beg <= LR_LONG_LIST) return lazy == 1;
   // (down to a whole number of 64-entry chunks: the chunks of both passes are then the chunks of an uninterrupted walk,
-  // which is what the hit masks handed to the reverse walk are indexed by; the entries in between are simply walked later)
-  const uint32_t ordered = sorted[tile] & ~63u;
+  // which is what the hit masks handed to the reverse walk are indexed by; the entries in between are simply walked later.
+  // A list the first pass ordered to its end -- up to 7680 keys, or the network fallback -- is no partial list: it is walked
+  // to its last entry whatever its length, and nobody parks for the 63 entries or fewer behind its last whole chunk)
+  const uint32_t s = sorted[tile];
+  const uint32_t ordered = s >= end - beg ? s : (s & ~63u);
   if (lazy == 1) {
     if (ordered < end - beg) { end = beg + ordered; clamped = true; }
     return true;
@@ -165,11 +168,20 @@ LR_DEV void lr_lazy_resume(const LrView& v, size_t pix, bool& done, float& T, fl
 // at most capacity / 64 + tiles + 1 slots; a slot holds 16 words (row-split: [wave][block]) or 4 (quadrant: [wave]).
 // Which form wrote them: lograst_view.hit_mask_form of the backward's view (the caller knows what its forward launched:
 // lograst_forward_form); a reverse walk of the other form ignores the buffer and runs the tests as before.  The forward also
-// leaves the form in header word LR_HDR_MASKS (diagnostics).
+// leaves the form in header word LR_HDR_MASKS: a masked reverse walk holds its caller's claim against it (lr_masks_usable).
 #define LR_MBUF_CHUNKS 64u   // row-split forward: chunks of hit masks a wave collects in LDS between two bursts of stores
 #define LR_MASK_FORM_ROWS 1u
 #define LR_MASK_FORM_QUAD 2u
 LR_DEV size_t lr_mask_slot(uint32_t list_begin, uint32_t tile) { return (size_t)(list_begin >> 6) + tile; }
+// May a reverse walk of form `form` read the buffer it was handed?  (Launch-uniform: two scalar loads; the instance count
+// lives on the device, so the host cannot ask.)  Only if the forward that wrote this tile state left masks of that form
+// (LR_HDR_MASKS) and the buffer holds every slot its lists index -- at most (I >> 6) + tiles, 16 words each.  Otherwise the
+// walk reads no word of it and takes EVERY entry of a chunk as a visit: a superset of any mask, and a visit that no pixel
+// accumulated adds exact zeros, so the sums are those of a walk without masks (slower: include/lograst.h, hit_masks).
+LR_DEV bool lr_masks_usable(const LrView& v, const uint32_t* state, uint32_t tiles, uint32_t form) {
+  const uint32_t I = state[lr_offsets_off(tiles) + tiles];
+  return state[LR_HDR_MASKS] == form && ((uint64_t)(I >> 6) + tiles) * 16ull <= v.mask_words;
+}
 // bits of a REVERSED chunk mask (bit j = list position hi - 1 - j) whose position lies in front of `limit`
 LR_DEV uint64_t lr_mask_before(uint64_t m, int hi, int limit) {
   const int sh = hi - limit;                                 // positions hi - 1 - j < limit  <=>  j >= sh
@@ -417,7 +429,8 @@ lr_blend_bwd_kernel(LrView v, const float4* __restrict__ geom, const uint32_t* _
   const uint32_t* offsets = state + lr_offsets_off(tiles);
   const uint32_t beg = offsets[tile];
   const int lane = threadIdx.x & 63, quad = threadIdx.x >> 6;
-  constexpr bool use_masks = MASKS;   // the forward left its quadrant ballots in `masks` (the host checked the form: lr_launch_blend_bwd)
+  constexpr bool use_masks = MASKS;   // the caller says the forward left its quadrant ballots in `masks` (lr_launch_blend_bwd)
+  const bool masks_ok = use_masks && lr_masks_usable(v, state, tiles, LR_MASK_FORM_QUAD);   // (else: every entry is a visit)
   const int tx = tile % (uint32_t)v.gx, ty = tile / (uint32_t)v.gx;
   const int qx0 = tx * 16 + (quad & 1) * 8, qy0 = ty * 16 + (quad >> 1) * 8;
   const int px = qx0 + (lane & 7), py = qy0 + (lane >> 3);
@@ -460,9 +473,13 @@ lr_blend_bwd_kernel(LrView v, const float4* __restrict__ geom, const uint32_t* _
     const int pos = top - 1 - (int)(c * 64u) - lane;
     return (c < nchunks && pos >= 0 && pos < maxc) ? plist[beg + (uint32_t)pos] : 0xffffffffu;
   };
-  const uint64_t* const mbase = use_masks ? masks + 4 * lr_mask_slot(beg, tile) + __builtin_amdgcn_readfirstlane(quad) : nullptr;
+  // (a buffer that is not usable is not read: the load goes to the tile state's header instead and the result is all ones)
+  const uint64_t* const mbase = !use_masks ? nullptr : !masks_ok ? reinterpret_cast<const uint64_t*>(state)
+                                : masks + 4 * lr_mask_slot(beg, tile) + __builtin_amdgcn_readfirstlane(quad);
+  const size_t mstride = masks_ok ? 4u : 0u;
+  const uint64_t mfill = masks_ok ? 0ull : ~0ull;
   auto load_mask = [&](uint32_t c) -> uint64_t {             // (uniform address: a scalar load)
-    return (use_masks && c < nchunks) ? mbase[4 * (size_t)(((uint32_t)top >> 6) - 1u - c)] : 0ull;
+    return (use_masks && c < nchunks) ? (mbase[mstride * (size_t)(((uint32_t)top >> 6) - 1u - c)] | mfill) : 0ull;
   };
   uint32_t id_n = load_id(0), id_nn = load_id(1);
   uint64_t mk_n = load_mask(0), mk_nn = load_mask(1);
@@ -652,7 +669,8 @@ lr_blend_bwd_rows_kernel(LrView v, const float4* __restrict__ geom, const uint32
   const uint32_t beg = offsets[tile];
   const int lane = threadIdx.x & 63, wq = threadIdx.x >> 6;
   // the forward's block masks of this wave's chunks (hit masks, above), if it left any in this form
-  constexpr bool use_masks = MASKS;   // the forward left its block ballots in `masks` (the host checked the form: lr_launch_blend_bwd)
+  constexpr bool use_masks = MASKS;   // the caller says the forward left its block ballots in `masks` (lr_launch_blend_bwd)
+  const bool masks_ok = use_masks && lr_masks_usable(v, state, tiles, LR_MASK_FORM_ROWS);   // (else: every entry is a visit)
   const int row = lane >> 4, li = lane & 15;
   const int tx = tile % (uint32_t)v.gx, ty = tile / (uint32_t)v.gx;
   const int qx0 = tx * 16 + (wq & 1) * 8, qy0 = ty * 16 + (wq >> 1) * 8;
@@ -719,16 +737,20 @@ lr_blend_bwd_rows_kernel(LrView v, const float4* __restrict__ geom, const uint32
     const uint32_t got = plist[beg + (ok ? (uint32_t)pos : 0u)];
     return ok ? got : 0xffffffffu;
   };
-  const uint4* const mbase = use_masks ? reinterpret_cast<const uint4*>(masks + 16 * lr_mask_slot(beg, tile) +
-                                                                        4 * __builtin_amdgcn_readfirstlane(wq)) : nullptr;
+  // (a buffer that is not usable is not read: the loads go to the tile state's header instead and the result is all ones)
+  const uint4* const mbase = !use_masks ? nullptr : !masks_ok ? reinterpret_cast<const uint4*>(state)
+                             : reinterpret_cast<const uint4*>(masks + 16 * lr_mask_slot(beg, tile) +
+                                                              4 * __builtin_amdgcn_readfirstlane(wq));
+  const size_t mstride = masks_ok ? 8u : 0u;                 // (16 words = 8 uint4 per slot)
+  const uint64_t mfill = masks_ok ? 0ull : ~0ull;
   struct Masks4 { uint64_t m0, m1, m2, m3; };                // as the forward wrote them: bit j = list position 64 c + j
   auto load_masks = [&](uint32_t c) -> Masks4 {              // (uniform address: scalar loads, 32 bytes per wave and chunk)
     if (!use_masks) return Masks4{0ull, 0ull, 0ull, 0ull};
     const uint32_t cf = ((uint32_t)top >> 6) - 1u - min(c, nchunks - 1u);    // (past the end: the last chunk's once more)
-    const uint4* mp = mbase + 8 * (size_t)cf;                // (16 words = 8 uint4 per slot)
+    const uint4* mp = mbase + mstride * (size_t)cf;
     const uint4 lo = mp[0], hi4 = mp[1];
-    return Masks4{((uint64_t)lo.y << 32) | lo.x, ((uint64_t)lo.w << 32) | lo.z,
-                  ((uint64_t)hi4.y << 32) | hi4.x, ((uint64_t)hi4.w << 32) | hi4.z};
+    return Masks4{(((uint64_t)lo.y << 32) | lo.x) | mfill, (((uint64_t)lo.w << 32) | lo.z) | mfill,
+                  (((uint64_t)hi4.y << 32) | hi4.x) | mfill, (((uint64_t)hi4.w << 32) | hi4.z) | mfill};
   };
   auto wanted = [&](const Masks4& m) -> bool {               // does any row of this wave visit lane's entry?  (lane l of a
     return !use_masks || (((m.m0 | m.m1 | m.m2 | m.m3) >> (63 - lane)) & 1ull) != 0ull;   // reverse chunk = the forward's bit 63 - l)

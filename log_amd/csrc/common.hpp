@@ -46,7 +46,7 @@
 #define LR_HDR_KEYS_LO 11 // fingerprint of the key buffer the fill wrote into (pointer, capacity): lograst_finish_lists refuses any other
 #define LR_HDR_KEYS_HI 12
 #define LR_HDR_KEYS_CAP 13
-#define LR_HDR_MASKS 14 // which compositing form left its per-chunk support ballots in the caller's hit-mask buffer (0 none, 1 row-split, 2 quadrant: blend.hip)
+#define LR_HDR_MASKS 14 // which compositing form left its per-chunk hit masks in the caller's hit-mask buffer (0 none, 1 row-split, 2 quadrant: blend.hip; a masked reverse walk checks it)
 #define LR_HDR_OPEN 10 // some compositing wave parked at the end of an ordered part (else the second sort / compositing pair returns at once)
 #define LR_SORT_BLOCK 8192  // keys one workgroup sorts in LDS
 #define LR_LONG_LIST 4096   // longer lists are sorted with their keys streamed from memory (shorter ones: LDS-resident)

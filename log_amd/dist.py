@@ -389,6 +389,8 @@ class GradientBucket(_Flat):
                 part = pend[k0:k0 + 16]
                 n = min(int(t.numel()) for t in part)
                 assert all(int(t.numel()) == n for t in part), "mark_seen(defer=True): views of different lengths in one step"
+                if n > int(self._seen.numel()):
+                    raise RuntimeError("mark_seen(defer=True): %d radii for a bucket of %d rows" % (n, int(self._seen.numel())))
                 for t in part:
                     t.record_stream(stream)
                 ptrs = (ctypes.c_void_p * len(part))(*[t.data_ptr() for t in part])
@@ -415,6 +417,11 @@ class GradientBucket(_Flat):
             raise RuntimeError("this bucket was built with track_seen=False")
         self._seen_dirty = True
         fast = index is None and radii.is_cuda and radii.dtype == torch.int32 and radii.is_contiguous() and self._seen.is_cuda
+        if fast and int(radii.numel()) > int(self._seen.numel()):
+            # (the kernels write seen[0 .. n): e.g. compact / LoD radii handed over without `index`)
+            # RuntimeError: what the torch path below raises for the same mistake
+            raise RuntimeError("mark_seen: %d radii for a bucket of %d rows (pass `index` for a selection's radii)"
+                               % (int(radii.numel()), int(self._seen.numel())))
         if defer and fast:
             self._seen_pending.append(radii)
             return
@@ -518,7 +525,7 @@ class GradientBucket(_Flat):
                 into["rows"] += self.rows("rows", 0)
                 if clear:
                     self.rows("rows", 0).zero_()
-                if self.track_seen:
+                if self.track_seen and not seen_later:      # (seen_later: finish() sums the marked buckets once per step)
                     into["seen"] += self.seen[:self.Pr]
                 return into
             out["rows"] = self.rows("rows", 0)
@@ -842,12 +849,15 @@ class StepExchange:
             # (the sum over the buckets somebody marked: callers that mark one bucket for the whole step -- seen_bucket() --
             # pay one reduce-scatter of 4 bytes per row per step instead of one per group)
             b0 = self.buckets[0]
-            if b0.track_seen and _active(self.world):
+            if b0.track_seen:
                 dirty = [b.seen for b in self.buckets if getattr(b, "_seen_dirty", False)]
                 if dirty:
                     acc = dirty[0] if len(dirty) == 1 else torch.stack(dirty).sum(0)
-                    mine = torch.empty(b0.Pr, dtype=torch.float32, device=self.device)
-                    self._stream_shard["seen"] = _reduce_scatter(mine, acc, self.group)
+                    if _active(self.world):
+                        mine = torch.empty(b0.Pr, dtype=torch.float32, device=self.device)
+                        self._stream_shard["seen"] = _reduce_scatter(mine, acc, self.group)
+                    else:                  # one rank, no collective: the local sum (a copy: begin_step() zeroes the buckets')
+                        self._stream_shard["seen"] = acc[:b0.Pr].clone()
             return dict(self._stream_shard)
         total = dict(self._shards[0])
         if self.parts > 1:

@@ -27,7 +27,10 @@ def set_fused_step(enabled):
     are never written or read back; ``params[key].grad`` stays None and ``log_amd.sparse_optimizer.step`` is reduced to its
     bookkeeping for that step.  The update happens at backward time instead of at ``optimizer.step`` time -- the same result
     for the reference's trainer (one view: backward, then step; nothing reads the model in between), NOT for a loop that
-    accumulates several backwards per step.  -> previous value."""
+    accumulates several backwards per step: once the update of a step has been applied, a further backward into the same
+    optimizer's parameters before ``step`` raises ("fused step").  A backward that reaches ``get_all``
+    without a rasterizer backward of the same rows before it in the same pass (a regulariser on the activated outputs alone,
+    a render whose image received no gradient) is not fused: it leaves ordinary gradients for ``step``.  -> previous value."""
     global _fused_step
     prev, _fused_step = _fused_step, bool(enabled)
     return prev
@@ -52,11 +55,17 @@ class _Activate(torch.autograd.Function):
         pack = ctx.pack
         n = pack["n_param"]
         fused = pack.get("fused")
-        radii = _r.last_backward_radii() if fused else None
-        if fused and radii is not None and int(radii.numel()) >= n and radii.device == g_xyz.device:
+        if fused:
             from . import sparse_optimizer as _so
-            if _so.fused_update(fused, pack, n, radii, g_xyz, g_scaling, g_opacity, g_rotation, g_colors):
-                return (None,) * (1 + len(pack["param_keys"]))
+            _so.refuse_second_backward(fused)
+            # the visibility of THIS pack's render: published by a rasterizer backward earlier in this very pass, for the
+            # rows this pack gathered (same tensor, same row count), taken once.  Anything else -- a loss on the activated
+            # outputs alone, a render whose image received no gradient -- leaves the gradients to ``step`` and its flag_vis
+            rows = pack["raw"]["xyz"]
+            radii = _r.take_backward_radii(rows)
+            if radii is not None and int(radii.numel()) == int(rows.shape[0]) and radii.device == g_xyz.device:
+                if _so.fused_update(fused, pack, n, radii, g_xyz, g_scaling, g_opacity, g_rotation, g_colors):
+                    return (None,) * (1 + len(pack["param_keys"]))
         g = _r._backend.activate_backward(pack["raw"], n, pack["degree"], pack["campos"], g_scaling, g_opacity,
                                           g_rotation, g_colors)
         g["xyz"] = g_xyz[:n]

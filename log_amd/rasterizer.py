@@ -1053,12 +1053,37 @@ class HipBackend:
 
 
 _backend = HipBackend()
-_backward_view = threading.local()     # .radii: the radii of the forward whose backward ran last on this thread (see backward())
+_backward_view = threading.local()     # .cur: what the rasterizer backward running on this thread published (see backward())
 
 
-def last_backward_radii():
-    """The `radii` output of the rasterizer forward whose backward node ran last on this thread, or None."""
-    return getattr(_backward_view, "radii", None)
+def _publish_backward_view(radii, means3D):
+    """Called by the rasterizer's backward node: `radii` of its forward and the address of the means3D rows it rendered,
+    for the nodes further down the SAME backward pass.  The record is emptied when the pass ends (a callback of the
+    autograd engine, which may run on another thread: it empties the record itself, not this thread's slot) -- a later
+    backward that never reaches a rasterizer node finds nothing."""
+    rec = {"radii": radii, "means_ptr": int(means3D.data_ptr())}
+    _backward_view.cur = None
+    if radii is None:
+        return
+    try:
+        torch.autograd.Variable._execution_engine.queue_callback(rec.clear)
+    except RuntimeError:      # not inside an engine-driven backward: nothing can end the record's life, so none is left
+        return
+    _backward_view.cur = rec
+
+
+def take_backward_radii(means3D=None):
+    """The `radii` output of the rasterizer forward whose backward node ran before the caller's in this backward pass on
+    this thread -- handed out ONCE (the record is consumed) -- or None: no rasterizer backward with a gradient ran in this
+    pass, somebody took the radii already, or (means3D given) that render's means3D rows are not the tensor `means3D`."""
+    rec, _backward_view.cur = getattr(_backward_view, "cur", None), None
+    if not rec:
+        return None
+    radii, ptr = rec.get("radii"), rec.get("means_ptr")
+    rec.clear()
+    if radii is None or (means3D is not None and int(means3D.data_ptr()) != ptr):
+        return None
+    return radii
 
 
 # ---- multi-view gradient accumulation (new design, SURVEY 8e; not part of the reference's API) ---------------
@@ -1197,11 +1222,12 @@ class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_image, *unused):
         m, s, r = ctx.saved_tensors
-        if grad_image is None:   # only non-differentiable outputs were used downstream
+        if grad_image is None:   # no gradient reached the image: nothing flows on, and no visibility is published
+            _backward_view.cur = None
             return (None,) * 12
-        # which view's backward is running: nodes further down the same graph (log_amd.get_all's fused step) read the
+        # which view's backward is running: nodes further down the same graph (log_amd.get_all's fused step) take the
         # visibility of THIS render from here (the rasterizer's node runs before the nodes that produced its inputs)
-        _backward_view.radii = ctx.saved.get("radii") if isinstance(ctx.saved, dict) else None
+        _publish_backward_view(ctx.saved.get("radii") if isinstance(ctx.saved, dict) else None, m)
         m2_shape, o_shape = ctx.shapes
         sh, clamped = ctx.sh
         pw = ctx.saved.get("point_weight") if isinstance(ctx.saved, dict) else None
@@ -1349,6 +1375,25 @@ def ordered_lengths_of(saved, width, height):
     with torch.cuda.device(st.device):
         _lib.check(_lib.lib().lograst_ordered_lengths(_ptr(st), int(width), int(height), _ptr(out), _stream_ptr(st.device)))
     return out
+
+
+def parked_waves_of(saved, width, height):
+    """Test/debug accessor (synchronises): (open[tiles] int32, header word LR_HDR_OPEN) of a forward's tile state -- per
+    tile one bit for each of its four compositing waves that ran out of ordered entries with a pixel still open and parked
+    for the second sort / compositing pair, and the view's "somebody parked" flag (layout: log_amd/csrc/common.hpp,
+    sorted[] / open[]).  Only lists of more than 4096 keys of a view whose sort left lists at their first window have such a
+    word (elsewhere the array still holds the fill's cursors): every other tile reads as 0."""
+    tiles = ((int(width) + 15) // 16) * ((int(height) + 15) // 16)
+    st = saved["state"]
+    offs = tile_offsets_of(saved, width, height)
+    first = (offs.data_ptr() - st.data_ptr()) // 4
+    sorted_off = first + ((tiles + 1 + 15) & ~15)                       # lr_sorted_off = lr_offsets_off + lr_tpad
+    hdr = st[:16].cpu()
+    lazy, hdr_open = int(hdr[9]), int(hdr[10])                          # LR_HDR_LAZY, LR_HDR_OPEN
+    lens = (offs[1:].to(torch.int64) & 0xffffffff) - (offs[:-1].to(torch.int64) & 0xffffffff)
+    words = st[sorted_off + tiles:sorted_off + 2 * tiles]
+    streamed = (lens > 4096) if lazy else torch.zeros_like(lens, dtype=torch.bool)
+    return torch.where(streamed, words, torch.zeros_like(words)), hdr_open
 
 
 def finish_lists(saved, width, height):

@@ -49,6 +49,18 @@ def _lr_of(opt, key, steps):
     return opt.lr_dict[key]
 
 
+_SECOND = ("fused step (log_amd.get_all.set_fused_step): %s before optimizer.step() -- this step's Adam update was already "
+           "applied by an earlier backward and cannot be taken back or summed with; call step() after every backward, or "
+           "switch the fused step off for loops that accumulate several backwards per step")
+
+
+def refuse_second_backward(fused):
+    """A backward that reaches get_all's parameters while this step's fused update is already applied: its gradients could
+    only become a second Adam update of the same step (the moments would advance twice) -- refused, loudly."""
+    if getattr(fused["optimizer"], "_lograst_fused_pending", False):
+        raise RuntimeError(_SECOND % "a second backward reached get_all's parameters")
+
+
 def fused_update(fused, pack, n, radii, g_xyz, g_scaling, g_opacity, g_rotation, g_colors):
     """Called from the backward of ``log_amd.get_all`` (``set_fused_step(True)``): the step's Adam update of the rows with
     ``radii > 0``, applied by the kernel that computes their raw gradients.  Uses the scalars ``step`` would use (the step
@@ -57,7 +69,7 @@ def fused_update(fused, pack, n, radii, g_xyz, g_scaling, g_opacity, g_rotation,
     opt = fused["optimizer"]
     if getattr(opt, "_lograst_fused_pending", False) or getattr(opt, "_lograst_open_packs", 1) != 1:
         # more than one training get_all since the last step() (a batch of several views: their gradients must be SUMMED
-        # before Adam sees them), or a second backward through the same pack: everything goes the ordinary way
+        # before Adam sees them): everything goes the ordinary way
         return False
     bufs = fused["bufs"]
     try:
@@ -82,6 +94,9 @@ def fused_update(fused, pack, n, radii, g_xyz, g_scaling, g_opacity, g_rotation,
 def step(self, model, index, params, flag_vis):
     """Same signature and effects as SparseOptimizer.step: rows ``index[flag_vis]`` of every ``getattr(model, key)``
     with a gradient, and of its Adam moments, are updated; ``self.xyz_lr`` and ``self.global_steps`` advance."""
+    if getattr(self, "_lograst_fused_pending", False) and any(getattr(p_, "grad", None) is not None for p_ in params.values()):
+        # (nothing has been advanced: drop the gradients and call step() again for the bookkeeping of the applied update)
+        raise RuntimeError(_SECOND % "gradients were left on the step's parameters")
     steps = _host_steps(self) + 1            # read (first call only) BEFORE the device-side increment
     self.global_steps += 1
     self._lograst_steps = steps
@@ -92,10 +107,7 @@ def step(self, model, index, params, flag_vis):
         self._lograst_fused_pending = False
         if "xyz" in params:
             self.xyz_lr = self.xyz_scheduler_args(steps)
-        if all(getattr(p_, "grad", None) is None for p_ in params.values()):
-            return
-        # (gradients on the parameters all the same: a further backward ran before this step and went the ordinary way --
-        # its update is applied below, with this step's scalars)
+        return
     bc1 = 1 - BETA1 ** steps
     bc2 = 1 - BETA2 ** steps
     _migrate_state(self, next(iter(params.values())).device)

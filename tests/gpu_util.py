@@ -78,8 +78,11 @@ def hip_forward(cam, sc, bg, flavour=R.WODILATE, use_filter=True, dev="cuda:0", 
 
 
 def _lazy_list_check(saved, offs, I, W, H):
-    """-> dict(ordered_len[tiles], lazy_lists, lazy_prefix_mismatch, walk_beyond_ordered); finishes saved["plist"]."""
+    """-> dict(ordered_len[tiles], lazy_lists, lazy_prefix_mismatch, walk_beyond_ordered, open_words[tiles], hdr_open);
+    finishes saved["plist"]."""
     ordered = R.ordered_lengths_of(saved, W, H).cpu().numpy().astype(np.int64)
+    open_words, hdr_open = R.parked_waves_of(saved, W, H)     # (as the forward left them: before the tails are ordered)
+    open_words = open_words.cpu().numpy().astype(np.int64)
     lens = np.diff(offs.astype(np.int64))[: len(ordered)]
     before = saved["plist"][:I].cpu().numpy().astype(np.uint32)
     R.finish_lists(saved, W, H)
@@ -95,7 +98,8 @@ def _lazy_list_check(saved, offs, I, W, H):
     ys, xs = np.mgrid[0:H, 0:W]
     nc = saved["n_contrib"].cpu().numpy().astype(np.int64)
     beyond = int((nc > ordered[(ys // 16) * gx + xs // 16]).sum())
-    return dict(ordered_len=ordered, lazy_lists=int(partly.sum()), lazy_prefix_mismatch=mismatch, walk_beyond_ordered=beyond)
+    return dict(ordered_len=ordered, lazy_lists=int(partly.sum()), lazy_prefix_mismatch=mismatch, walk_beyond_ordered=beyond,
+                open_words=open_words, hdr_open=hdr_open)
 
 
 class Grads(dict):

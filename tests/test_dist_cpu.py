@@ -553,6 +553,31 @@ def test_row_sparse_exchange_equals_the_dense_one(tmp_path, world):
         assert torch.equal(got[r]["stream8_step1"]["full"], got[0]["stream8_step1"]["full"])
 
 
+@pytest.mark.parametrize("parts,streamed", [(4, True), (1, False), (2, False)])
+def test_one_rank_streamed_exchange_keeps_every_seen_count(parts, streamed):
+    """World 1 without a process group, row-sparse launches: the step's seen counts are the integer sum of radii > 0 over
+    ALL its views -- also those marked in bucket 0 after group 0's launch (seen_bucket(part, streamed=True)) --, the rows
+    the dense sum, and a step after begin_step() counts its own views alone."""
+    from dist_util import one_rank_streamed_steps
+    P = 1003
+    for step, (seen, rows, want_seen, want_rows) in enumerate(one_rank_streamed_steps("cpu", parts, streamed)):
+        assert int(want_seen.sum()) > 1500                                       # 8 views x 30 % of 1003 rows
+        assert np.array_equal(seen[:P].numpy().astype(np.int64), want_seen), (step, int(seen.sum()), int(want_seen.sum()))
+        assert float(seen[P:].sum()) == 0.0
+        assert torch.equal(rows, want_rows), step
+
+
+def test_mark_seen_rejects_more_radii_than_rows():
+    """The torch path of mark_seen (CPU buckets, or radii that are not int32 device tensors): radii longer than the
+    bucket's padded row count raise and leave the counts as they were."""
+    b = GradientBucket(1000, "cpu", world=1)
+    b.mark_seen(torch.ones(1000, dtype=torch.int32))
+    before = b.seen.clone()
+    with pytest.raises(RuntimeError):
+        b.mark_seen(torch.ones(b.Ppad + 64, dtype=torch.int32))
+    assert torch.equal(b.seen, before)
+
+
 def test_pack_rows_edge_cases():
     """The torch formulation of the row-sparse pack (what the gloo tests run; the device kernels are checked against it in
     tests/test_gpu_dist.py): an all-zero group, a bound above the group size, a row whose only non-zero entry is its last

@@ -117,3 +117,37 @@ def test_a_training_view_leaves_no_tensor_in_a_reference_cycle(double):
         gc.set_debug(0)
         gc.garbage.clear()
         gc.enable()
+
+
+def test_fused_step_takes_its_row_mask_from_its_own_render_only(double):
+    """``set_fused_step(True)`` outside the render -> loss -> backward -> step flow (tests/fused_step_util.py): a backward that
+    reaches get_all without a rasterizer backward of its own rows -- a regulariser on the activated rows alone, a render
+    whose image received no gradient -- must not apply Adam with the PREVIOUS view's visibility: it leaves ordinary
+    gradients, and step() with the caller's flag_vis gives what the unfused drop-ins give on a copy of the model
+    (parameters and moments, rtol 2e-6); a second backward before step() is refused instead of becoming a second update.
+    Host logic on the CPU: the oracle backend, with the fused kernel stood in for by the pair of calls it replaces
+    (tests/test_gpu_train_ops.py holds the kernel to that pair bit for bit)."""
+    import oracle_backend
+    from log_amd import rasterizer as R
+    import fused_step_util as F
+
+    class FusedDouble(oracle_backend.OracleBackend):
+        """+ what the fused step reads of the HIP backend: the forward's `radii` in the saved state, and the fused kernel."""
+
+        def forward(self, *args, **kw):
+            *out, saved = super().forward(*args, **kw)
+            return (*out, {"radii": out[1], "oracle": saved})
+
+        def backward(self, rs, flavour, use_filter, means3D, scales, rotations, saved, grad_image, **kw):
+            return super().backward(rs, flavour, use_filter, means3D, scales, rotations, saved["oracle"], grad_image, **kw)
+
+        def activate_backward_adam(self, raw, n, degree, campos, g_xyz, g_scaling, g_opacity, g_rotation, g_colors, index,
+                                   radii, entries, beta1, beta2, bias_correction2_sqrt, eps):
+            g = self.activate_backward(raw, n, degree, campos, g_scaling, g_opacity, g_rotation, g_colors)
+            g["xyz"] = g_xyz[:n]
+            self.sparse_adam(index, radii[:n] > 0, [(model, raw[k][:n], g[k], m1, m2, mx, step)
+                                                    for k, (model, m1, m2, mx, step) in entries.items()],
+                             beta1, beta2, bias_correction2_sqrt, eps)
+
+    oracle_backend.install(FusedDouble())                               # (the fixture puts the previous backend back)
+    F.run_cases("cpu", P=500, W=64, H=48, focal=120.0)

@@ -453,3 +453,46 @@ def test_pack_rows_with_a_hint_and_the_visible_count_kernel():
     b.mark_seen(views[2], defer=True)
     b.zero()                                                                             # ... and a reset drops them
     assert float(b.seen.abs().sum()) == 0.0
+
+
+@pytest.mark.parametrize("defer,views", [(False, 8), (True, 8), (True, 17)])
+def test_one_rank_streamed_exchange_keeps_every_seen_count(defer, views):
+    """tests/test_dist_cpu.py's world-1 streamed step on the device (no process group, parts = 4, every group marking
+    bucket 0): the counts go through lograst_add_visible (defer=False) and lograst_add_visible_n (defer=True: counted
+    together when finish() reads them; 17 pending views = one past the 16 a launch takes) and must come out as the exact
+    integer sum of radii > 0 over ALL of the step's views, the rows as the dense sum, in a first step and in a second one
+    that starts from begin_step()."""
+    import numpy as np
+    import torch
+    from dist_util import one_rank_streamed_steps
+    P = 1003
+    for step, (seen, rows, want_seen, want_rows) in enumerate(one_rank_streamed_steps("cuda:0", 4, True, defer=defer, views=views)):
+        assert int(want_seen.sum()) > 150 * views
+        assert np.array_equal(seen[:P].numpy().astype(np.int64), want_seen), (step, int(seen.sum()), int(want_seen.sum()))
+        assert float(seen[P:].sum()) == 0.0
+        assert torch.equal(rows, want_rows), step
+
+
+@pytest.mark.parametrize("defer", [False, True])
+def test_mark_seen_refuses_more_radii_than_rows(defer):
+    """int32 device radii longer than the bucket's padded row count (compact or level-of-detail radii handed over without
+    `index`): lograst_add_visible / lograst_add_visible_n write seen[0 .. n), so the call -- or, deferred, the read that
+    counts it -- must raise and leave the counts alone.  The bucket's count array is made a view of a longer allocation
+    for this test, so that even a missing guard writes inside owned memory: the tail then shows it."""
+    import torch
+    from log_amd.dist import GradientBucket
+    dev = torch.device("cuda:0")
+    b = GradientBucket(1000, dev, 1, row_major=True)
+    room = torch.zeros(b.Ppad + 256, dtype=torch.float32, device=dev)
+    b._seen = room[:b.Ppad]
+    good = (torch.arange(b.Ppad, device=dev) % 3 == 0).to(torch.int32)
+    b.mark_seen(good)
+    before = b.seen.clone()
+    too_long = torch.ones(b.Ppad + 64, dtype=torch.int32, device=dev)
+    with pytest.raises(RuntimeError, match="radii"):
+        b.mark_seen(too_long, defer=defer)
+        b.seen                                                          # (deferred: counted here)
+    torch.cuda.synchronize()
+    assert torch.equal(b.seen, before) and float(room[b.Ppad:].abs().sum()) == 0.0
+    b.mark_seen(good, defer=defer)                                      # the bucket goes on working
+    assert torch.equal(b.seen, 2.0 * before)

@@ -82,6 +82,12 @@ def _scene(name):
         # in the second pass (tests/test_gpu_scale.py: test_every_long_list_needs_its_tail, at the smallest size that parks)
         n = 9000
         return cam, _place(cam, rng.uniform(33, 46, n), rng.uniform(17, 30, n), 2.0 + 1e-4 * rng.permutation(n), 0.7, 0.02, rng)
+    if name == "flat":
+        # the same tile and count as `park`, at three distinct depths with thousands of ties each: the depth buckets of the
+        # long-list sort overflow and the list goes to the network, which orders it to its END in the first pass
+        # (tests/test_gpu_parity.py: the flat_depth_* recipe)
+        n = 9000
+        return cam, _place(cam, rng.uniform(33, 46, n), rng.uniform(17, 30, n), 2.0 + 1e-3 * rng.integers(0, 3, n), 0.7, 0.02, rng)
     if name == "apart":
         # one faint small splat in the middle of every 4x4 block: each reaches pixels of its own block only, so every
         # Gaussian has ONE contributing visit and no sum depends on the order of the atomics
@@ -244,3 +250,43 @@ def test_single_visit_rows_are_bit_identical(oracle_mod, flavour_name):
     g, g0 = r["g"][1], r["g"][0]
     for k in ("means2D", "conic", "opacities", "colors"):
         assert g[k].any() and (g[k].view(np.uint32) == g0[k].view(np.uint32)).all(), k
+
+
+@pytest.mark.parametrize("form", ["rows", "quadrant"])
+@pytest.mark.parametrize("name", ["flush", "flat", "park"])
+def test_a_list_ordered_to_its_end_parks_nobody(oracle_mod, name, form):
+    """A streamed list (more than 4096 keys) whose length is no multiple of 64 and whose pixels never stop.  `flush`
+    (4700 keys: the first window holds the whole list) and `flat` (9000 keys at three depths: the network fallback) are
+    ordered to their end by the first pass, so the first compositing pass must walk them to their last entry: no wave parks
+    for the entries behind the last whole 64-entry chunk (open[] and header word LR_HDR_OPEN stay zero, so the second sort /
+    compositing pair has nothing to do).  `park` is the control: 9000 keys at distinct depths are ordered over the first
+    window only, and there the waves must still park and resume.  Both compositing forms; forward bit for bit the
+    oracle's, and the reverse walk on the forward's hit masks within GRAD_TOL, as for every other scene."""
+    import gpu_util as G
+    cam, sc = _scene(name)
+    v, of = G.oracle_forward(oracle_mod, cam, sc, BG)
+    hf = G.hip_forward(cam, sc, BG, scratch_floats=16, fwd_form=form)
+    lens = np.diff(hf["tile_offsets"].astype(np.int64))
+    t = int(lens.argmax())
+    L = int(lens[t])
+    assert L % 64 != 0, L
+    assert (4096 < L <= 7680) if name == "flush" else L > 7680, L
+    assert (lens > 4096).sum() == 1                                     # the one list this test is about
+    assert hf["final_T"].min() > 1e-4                                   # no pixel ever stopped ...
+    assert hf["n_contrib"].max() > (L & ~63)                            # ... and some pixel's walk went into the last, partial chunk
+    st = G.compare_forward(hf, of)
+    for k in ("radii_mismatch", "rec_bits_mismatch", "offsets_mismatch", "list_mismatch", "n_contrib_mismatch",
+              "image_bits_mismatch", "final_T_bits_mismatch", "pid_mismatch"):
+        assert st[k] == 0, (k, st)
+    assert hf["lazy_lists"] == 0 and hf["ordered_len"][t] == L          # the walked list is in final order to its end
+    print("%s %s: L = %d, open[tile] = %#x, LR_HDR_OPEN = %d" % (name, form, L, hf["open_words"][t], hf["hdr_open"]))
+    if name == "park":
+        assert hf["hdr_open"] == 1 and hf["open_words"][t] != 0 and not np.delete(hf["open_words"], t).any()
+    else:
+        assert hf["hdr_open"] == 0 and not hf["open_words"].any(), (hf["hdr_open"], hf["open_words"][t])
+    dL = np.random.default_rng(4).standard_normal(of["image"].shape).astype(np.float32)
+    og = oracle_mod.backward(v, of, dL)
+    g = G.hip_backward(hf, dL, bwd_form=form)
+    assert g["bwd_masks"]
+    for k in ("means2D", "conic", "opacities", "colors"):
+        assert rel_l2(g[k], og[k]) < GRAD_TOL, (k, rel_l2(g[k], og[k]))

@@ -339,6 +339,18 @@ def test_fused_step_through_the_drop_ins():
         assert float(da.norm()) > 0
 
 
+def test_fused_step_takes_its_row_mask_from_its_own_render_only():
+    """The fused step next to flows it must not fuse (tests/fused_step_util.py; 3000 Gaussians, two 160 x 96 views that see
+    different rows; the ordinary step, case (a), is the test above): (b) a step whose loss touches the get_all outputs only,
+    (c) a render whose image receives no gradient -- each must leave ordinary gradients and, after step() with the caller's
+    flag_vis, equal the unfused drop-ins on a copy of the model in parameters and both moments (rtol 2e-6: the two start
+    from identical state and no rasterizer gradient enters the second step, so nothing but rounding may differ) --, and
+    (d) a second backward through one pack before step(): refused with an error that names the cause, the applied update
+    left exactly as it was."""
+    import fused_step_util as F
+    F.run_cases("cuda:0", P=3000, W=160, H=96, focal=300.0)
+
+
 @pytest.mark.parametrize("seed", range(6))
 def test_random_views_and_steps_against_reference_classes_on_device(seed):
     """The reference's recorded random cases (radii beyond int16, keys without gradient, amsgrad, K from 1 to 15) through the
