@@ -38,7 +38,7 @@ extern "C" {
  * version change (new entry points only): lograst_pack_rows_hinted, lograst_add_visible, lograst_add_visible_n.
  * 2: lograst_view gained cov3d_precomp / dl_dcov3d; 3: the backward accumulates into 64-byte rows (bwd_rows); lograst_view gained walk_form.  Added since without a version change (new entry points only): lograst_sparse_segment_floats / lograst_pack_rows / lograst_unpack_rows / lograst_ordered_lengths / lograst_finish_lists.
  * lograst_recomposite / lograst_record_bytes and the profiling slot "recolor" (LOGRAST_NUM_KERNELS 22 -> 23, appended) are
- * additions within version 4: no existing entry point, layout or default changed. */
+ * additions within version 4, as is lograst_backward_form: no existing entry point, layout or default changed. */
 #define LOGRAST_TILE 16        /* pixels per tile side (tile rects are part of the integer contract) */
 #define LOGRAST_REC_FLOATS 16  /* floats per projected-Gaussian record (64 B): see log_amd/csrc/project.hip */
 /* The reverse walk's accumulators: ONE 64-byte row per Gaussian -- slots 0-1 dL/d(ndc mean x, y), 2-4 dL/d(conic A, B, C),
@@ -157,6 +157,9 @@ size_t lograst_hit_mask_bytes(uint32_t capacity, int32_t width, int32_t height);
 /* which form the forward's compositing kernels take for this view (its walk_form + the LOGRAST_FWD_ROWS knob): 1 = row-split,
  * 2 = quadrant, negative = error.  Pass it back as hit_mask_form of the backward's view. */
 int lograst_forward_form(const lograst_view* view);
+/* which form the reverse walk of lograst_backward takes for this view of n Gaussians (its walk_form, the LOGRAST_BWD_ROWS
+ * knob, and n against LOGRAST_HELPER_MIN_N): 1 = row-split, 2 = quadrant, negative = error. */
+int lograst_backward_form(const lograst_view* view, int32_t n);
 size_t lograst_list_bytes(uint32_t capacity);
 
 /* ---- A0: LoG/cuda compute_radius --------------------------------------------------------------

@@ -98,6 +98,7 @@ _SIGNATURES = {
     "lograst_keys_bytes": (c_size_t, [c_uint32]),
     "lograst_hit_mask_bytes": (c_size_t, [c_uint32, c_int32, c_int32]),
     "lograst_forward_form": (ctypes.c_int, [ctypes.POINTER(LograstView)]),
+    "lograst_backward_form": (ctypes.c_int, [ctypes.POINTER(LograstView), ctypes.c_int32]),
     "lograst_list_bytes": (c_size_t, [c_uint32]),
     "lograst_tile_offsets": (c_void_p, [c_void_p, c_int32, c_int32]),
     "lograst_ordered_lengths": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p]),

@@ -289,6 +289,12 @@ int lograst_forward_form(const lograst_view* view) {
   if (rc) return rc;
   return lr_blend_fwd_form(v);
 }
+int lograst_backward_form(const lograst_view* view, int32_t n) {
+  LrView v;
+  int rc = lr_make_view(view, &v);
+  if (rc) return rc;
+  return lr_blend_bwd_form(v, lr_big_input(n));
+}
 size_t lograst_hit_mask_bytes(uint32_t capacity, int32_t width, int32_t height) {   // blend.hip: 16 words per (tile, 64-entry chunk) slot
   const size_t gx = (size_t)(width > 0 ? (width + LOGRAST_TILE - 1) / LOGRAST_TILE : 0), gy = (size_t)(height > 0 ? (height + LOGRAST_TILE - 1) / LOGRAST_TILE : 0);
   return 16 * sizeof(uint64_t) * ((size_t)capacity / 64 + gx * gy + 1);

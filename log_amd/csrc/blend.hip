@@ -1144,6 +1144,14 @@ int lr_blend_fwd_form(const LrView& v) {
   return rows ? (int)LR_MASK_FORM_ROWS : (int)LR_MASK_FORM_QUAD;
 }
 
+// Which form the reverse walk takes for this view: lr_launch_blend_bwd's rule, also behind lograst_backward_form.
+int lr_blend_bwd_form(const LrView& v, int big_input) {
+  const int rows_knob = lr_knob(LRKNOB_BWD_ROWS);
+  const int rows = rows_knob != 2 ? rows_knob
+                   : (v.walk_form == LOGRAST_FORM_ROWS ? 1 : (v.walk_form == LOGRAST_FORM_QUADRANT ? 0 : (big_input ? 1 : 0)));
+  return rows ? (int)LR_MASK_FORM_ROWS : (int)LR_MASK_FORM_QUAD;
+}
+
 void lr_launch_blend_fwd(const LrView& v, const void* geom, const uint32_t* state, uint32_t tiles,
                          const uint32_t* plist, uint32_t capacity, float* image, float* final_T, int* n_contrib,
                          int* pid, float* pwp, float* pw, float* zero_conic, int big_input, int lazy, uint64_t* masks,
@@ -1195,9 +1203,7 @@ void lr_launch_blend_bwd(const LrView& v, const void* geom, const uint32_t* stat
   // (Gaussian, quadrant) pair per visit; 2 (default): the caller's hint (lograst_view.walk_form: row-split for views of
   // tiny splats, few tile instances per Gaussian), else row-split on large inputs.  Measured, MI355X: 30 M tiny splats
   // 949 -> 700 us, with random opacities 1768 -> 1259; C2's 1 M 292 -> 307; a tree-ordered heavy-tailed view 448 -> 579.
-  const int rows_knob = lr_knob(LRKNOB_BWD_ROWS);
-  const int rows = rows_knob != 2 ? rows_knob
-                   : (v.walk_form == LOGRAST_FORM_ROWS ? 1 : (v.walk_form == LOGRAST_FORM_QUADRANT ? 0 : (big_input ? 1 : 0)));
+  const int rows = lr_blend_bwd_form(v, big_input) == (int)LR_MASK_FORM_ROWS;
   const int block_test = lr_knob(LRKNOB_BWD_BLOCK_TEST);
   lr_prof_begin(LRK_BLEND_BWD, s);
   // the forward's hit masks serve a reverse walk of the SAME form only (v.mask_form: what the caller says its forward launched)

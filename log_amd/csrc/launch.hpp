@@ -41,6 +41,7 @@ void lr_launch_blend_fwd(const LrView& v, const void* geom, const uint32_t* stat
                          int* pid, float* pwp, float* pw, float* zero_conic, int big_input, int lazy, uint64_t* masks,
                          hipStream_t s);
 int lr_blend_fwd_form(const LrView& v);
+int lr_blend_bwd_form(const LrView& v, int big_input);
 void lr_launch_blend_bwd(const LrView& v, const void* geom, const uint32_t* state, uint32_t tiles,
                          const uint32_t* plist, uint32_t capacity, const float* final_T, const int* n_contrib,
                          const float* dL_dimage, float* acc_rows, int big_input, const uint64_t* masks, hipStream_t s);

@@ -19,6 +19,7 @@ All arithmetic runs in hand-written HIP kernels (log_amd/csrc) through the C ABI
 """
 import contextlib
 import ctypes
+import math
 import threading
 from typing import NamedTuple
 
@@ -84,7 +85,6 @@ _debug_keep = False   # tests: keep dL/dconic of the last backward (HipBackend.l
 _hit_masks = True     # a training forward hands its compositing kernels a hit-mask buffer for the reverse walk (blend.hip)
 _zero_hit_masks = False   # tools/mask_stats.py: a zero-filled buffer, so that the slots nobody wrote read as "no visit"
 _keep_keys = False    # tests: the forward's key buffer stays alive in `saved` (finish_lists below needs it)
-_DEBUG_ADDR = bool(int(__import__('os').environ.get('LOGRAST_DEBUG_ADDR', '0')))
 
 
 def set_instance_capacity(n, max_tile_len=0):
@@ -221,7 +221,7 @@ class _ReuseSlot:
             return None, "geometry"
         if e["radii"]._version != e["radii_version"]:
             return None, "radii_modified"
-        if isinstance(e["saved"], dict) and e["saved"].get("instances", 1) == 0:
+        if isinstance(e["saved"], dict) and e["saved"]["instances"] == 0:
             return None, "no_instances"
         return e["saved"], None
 
@@ -369,11 +369,51 @@ def _dev_f32(t, device):
     return t.detach().to(device=device, dtype=torch.float32).contiguous()
 
 
+def _knob(name):
+    """The value the library holds for a knob (bytes name, as in lograst_knob_info)."""
+    val = ctypes.c_int32(0)
+    _lib.lib().lograst_get_knob(name, ctypes.byref(val))
+    return val.value
+
+
+def _tiles(width, height):
+    """How many 16 x 16 tiles cover a width x height image."""
+    return ((int(width) + 15) // 16) * ((int(height) + 15) // 16)
+
+
 # Blocks carved out of one allocation are read / written in lock step by one kernel; starting them at multiples of
 # n floats apart puts all streams on the same HBM channels (measured: the activation backward 0.12 -> 0.17 ms for
 # n = 1 M).  Each block is followed by this many floats (4352 B: keeps 16-byte alignment, breaks the stride).
 _BLOCK_SKEW = 1088
 _ITEMSIZE = {torch.float32: 4, torch.int32: 4, torch.uint8: 1, torch.int64: 8}
+
+
+def _carve_skewed(device, n, blocks):
+    """One fp32 allocation for blocks = [(name, row shape)]: -> {name: [n, *row shape] tensor}, the blocks in the order given,
+    each _BLOCK_SKEW floats behind the end of the one before (put the blocks whose rows move as float4 first: every block
+    starts 16-byte aligned only while all widths in front of it are multiples of 4)."""
+    sizes = [n * math.prod(row) for _, row in blocks]
+    flat = torch.empty(sum(sizes) + _BLOCK_SKEW * len(sizes), dtype=torch.float32, device=device)
+    out, off = {}, 0
+    for (name, row), size in zip(blocks, sizes):
+        out[name] = flat[off:off + size].view((n,) + row)
+        off += size + _BLOCK_SKEW
+    return out
+
+
+def _gather_blocks(K):
+    """gather_activate's outputs as _carve_skewed blocks (the quaternion blocks first: their rows are read and written
+    as float4); K = SH coefficients per Gaussian, 0 = no `shs`."""
+    return [(("raw", "rotation"), (4,)), (("act", "rotation"), (4,)), (("raw", "xyz"), (3,)), (("raw", "scaling"), (3,)),
+            (("raw", "colors"), (3,)), (("act", "scaling"), (3,)), (("act", "colors"), (3,)), (("raw", "opacity"), (1,)),
+            (("act", "opacity"), (1,))] + ([(("raw", "shs"), (K, 3))] if K else [])
+
+
+def _activate_backward_blocks(K, degree):
+    """activate_backward's gradients as _carve_skewed blocks: 16-byte aligned blocks first (quaternion rows and, for
+    3K % 4 == 0, the SH rows go out as float4)."""
+    return [("rotation", (4,))] + ([("shs", (K, 3))] if K and degree > 0 else []) + [("scaling", (3,)), ("colors", (3,)),
+                                                                                      ("opacity", (1,))]
 
 
 class _TileRows:
@@ -502,39 +542,10 @@ class HipBackend:
             self.last_forms = {}
         self.last_forms[kind] = "rows" if rows else "quadrant"
 
-    def _bwd_rows(self, walk_form, n):
-        """The rule of lr_launch_blend_bwd (log_amd/csrc/blend.hip) restated, the library exports none for the reverse
-        walk: knob LOGRAST_BWD_ROWS, else the view's hint, else row-split from LOGRAST_HELPER_MIN_N Gaussians."""
-        L = _lib.lib()
-        val = ctypes.c_int32(2)
-        L.lograst_get_knob(b"LOGRAST_BWD_ROWS", ctypes.byref(val))
-        if val.value != 2:
-            return val.value == 1
-        if walk_form != _lib.FORM_AUTO:
-            return walk_form == _lib.FORM_ROWS
-        L.lograst_get_knob(b"LOGRAST_HELPER_MIN_N", ctypes.byref(val))
-        return n >= val.value
-
-    @staticmethod
-    def _want_masks(L, scratch_floats):
-        """Does a forward that prepares `scratch_floats` accumulator floats per Gaussian get a hit-mask buffer?"""
-        want = bool(_hit_masks and scratch_floats)
-        if want:   # (knob LOGRAST_HIT_MASKS = 0: the library would ignore the buffer, and a backward under a different
-            kv = ctypes.c_int32(1)   # knob value must not find an unwritten one)
-            L.lograst_get_knob(b"LOGRAST_HIT_MASKS", ctypes.byref(kv))
-            want = kv.value != 0
-        return want
-
     def plan_key(self, saved):
         """The knob-dependent launch decisions that a recomposite must share with the forward whose lists it walks: whether
         long lists are ordered lazily, the large-input threshold, and the compositing form for that forward's walk_form."""
-        L = _lib.lib()
-        vals = []
-        for name in (b"LOGRAST_LAZY_SORT", b"LOGRAST_HELPER_MIN_N", b"LOGRAST_FWD_ROWS"):
-            v = ctypes.c_int32(0)
-            L.lograst_get_knob(name, ctypes.byref(v))
-            vals.append(v.value)
-        return tuple(vals)
+        return tuple(_knob(name) for name in (b"LOGRAST_LAZY_SORT", b"LOGRAST_HELPER_MIN_N", b"LOGRAST_FWD_ROWS"))
 
     @staticmethod
     def _carve(device, parts):
@@ -550,6 +561,54 @@ class HipBackend:
         arena = torch.empty(max(total, 1), dtype=torch.uint8, device=device)
         return {name: arena[off:off + n].view(dt).view(shape) for (name, dt, shape), (off, n) in zip(parts, spans)}
 
+    def _begin(self, L, view, flavour, device, N, own, scratch_floats):
+        """What forward() and recomposite() share once view.walk_form is set: -> (o, kept, scratch_floats, masks_for,
+        mask_form): the outputs, the _carve parts that outlive the call (`own`: the caller's, in front), the normalised
+        scratch_floats, the hit-mask buffer for a capacity, and the form those masks are written in (0: no masks)."""
+        H, W = view.height, view.width
+        i32, f32 = torch.int32, torch.float32
+        fwd_form = int(L.lograst_forward_form(ctypes.byref(view)))   # 1 = row-split, 2 = quadrant
+        self._note_form("fwd", fwd_form == 1)
+        # what the caller gets (image, radii, the fork's maps) / what backward needs / what dies with this call
+        # (every output is an allocation of its own, like the third-party packages': views of one arena would share a
+        # version counter -- an in-place op on `radii` would invalidate `image` for autograd -- and any one of them kept
+        # alive would pin all the others' memory)
+        o = {"image": torch.empty(3, H, W, dtype=f32, device=device), "radii": torch.empty(N, dtype=i32, device=device)}
+        if flavour.extras:
+            o.update(pid=torch.empty(H, W, dtype=i32, device=device), pwp=torch.empty(H, W, dtype=f32, device=device),
+                     pw=torch.empty(N, dtype=f32, device=device))
+        kept = own + [("final_T", f32, (H, W)), ("n_contrib", i32, (H, W))]
+        scratch_floats = _lib.BWD_ROW_FLOATS if scratch_floats and N else 0
+        if scratch_floats:
+            kept.append(("bwd_scratch", f32, (N * scratch_floats,)))
+        # a training forward gets a hit-mask buffer (knob LOGRAST_HIT_MASKS = 0: the library would ignore the buffer, and a
+        # backward under a different knob value must not find an unwritten one)
+        want_masks = bool(_hit_masks and scratch_floats) and _knob(b"LOGRAST_HIT_MASKS") != 0
+
+        def masks_for(cap):
+            """The hit-mask buffer of a training forward with room for `cap` tile instances (uninitialised)."""
+            if not want_masks:
+                return None
+            m = (torch.zeros if _zero_hit_masks else torch.empty)(L.lograst_hit_mask_bytes(cap, W, H) // 8, dtype=torch.int64,
+                                                                  device=device)
+            view.hit_masks, view.hit_mask_words = m.data_ptr(), m.numel()
+            return m
+        return o, kept, scratch_floats, masks_for, fwd_form if want_masks else 0
+
+    @staticmethod
+    def _finish(view, o, k, state, plist, tile_rows, instances, pin, capacity, max_len, masks, mask_form, keys):
+        """What forward() and recomposite() return; the last entry is `saved`, the record a forward leaves its backward (and
+        a later recomposite, the test accessors below, bench.py): every key is present in every record."""
+        saved = dict(radii=o["radii"], geom=k["geom"].view(torch.float32), state=state, plist=plist, final_T=k["final_T"],
+                     n_contrib=k["n_contrib"], point_weight=o.get("pw"), tile_rows=tile_rows, instances=int(instances),
+                     walk_form_pin=pin, hit_masks=masks, hit_mask_form=mask_form,
+                     # the accumulator rows the forward cleared: the first backward takes them and leaves None
+                     bwd_scratch=k.get("bwd_scratch"),
+                     # what this stage 2 ran with (a recomposite walks the lists under the same decisions)
+                     capacity=int(capacity), max_len=int(max_len), fwd_walk_form=int(view.walk_form),
+                     keys=keys)   # keep_keys(True) only: the (depth, id) key buffer, for finish_lists
+        return o["image"], o["radii"], o.get("pid"), o.get("pwp"), o.get("pw"), saved
+
     def forward(self, rs, flavour, use_filter, means3D, scales, rotations, opacities, colors, scratch_floats=0,
                 cov3D=None):
         """scratch_floats: non-zero = allocate the backward's accumulator rows (16 fp32 = 64 B per Gaussian,
@@ -563,39 +622,16 @@ class HipBackend:
         view, keep = self.make_view(rs, flavour, use_filter, device, cov3D=cov3D)
         stream = _stream_ptr(device)
         status = _status_block(device)
-        i32, f32, u8 = torch.int32, torch.float32, torch.uint8
-        # what the caller gets (image, radii, the fork's maps) / what backward needs / what dies with this call
-        # (every output is an allocation of its own, like the third-party packages': views of one arena would share a
-        # version counter -- an in-place op on `radii` would invalidate `image` for autograd -- and any one of them kept
-        # alive would pin all the others' memory)
-        o = {"image": torch.empty(3, H, W, dtype=f32, device=device), "radii": torch.empty(N, dtype=i32, device=device)}
-        if flavour.extras:
-            o.update(pid=torch.empty(H, W, dtype=i32, device=device), pwp=torch.empty(H, W, dtype=f32, device=device),
-                     pw=torch.empty(N, dtype=f32, device=device))
-        kept = [("geom", u8, (L.lograst_geom_bytes(N),)), ("state", u8, (L.lograst_tile_state_bytes(W, H, N),)),
-                ("final_T", f32, (H, W)), ("n_contrib", i32, (H, W))]
-        scratch_floats = _lib.BWD_ROW_FLOATS if scratch_floats and N else 0
-        if scratch_floats:
-            kept.append(("bwd_scratch", f32, (N * scratch_floats,)))
-        instances = None
-        want_masks = self._want_masks(L, scratch_floats)
-
-        def masks_for(cap):
-            """The hit-mask buffer of a training forward with room for `cap` tile instances (uninitialised)."""
-            if not want_masks:
-                return None
-            m = (torch.zeros if _zero_hit_masks else torch.empty)(L.lograst_hit_mask_bytes(cap, W, H) // 8, dtype=torch.int64,
-                                                                  device=device)
-            view.hit_masks, view.hit_mask_words = m.data_ptr(), m.numel()
-            return m
+        i32, u8 = torch.int32, torch.uint8
         ckey = (device.index, W, H, _tile_rows.get())
-        hist_ratio = _cap_model.ratio(ckey)
         # which form the compositing kernel takes: instances per Gaussian as the recent forwards of this resolution had
         # them (speculative / exact mode), or the caller's capacity (sync-free mode)
         pin = _pinned_form()
-        view.walk_form = pin or self.walk_form(_capacity_hint if _capacity_hint is not None else hist_ratio * N, N)
-        fwd_form = int(L.lograst_forward_form(ctypes.byref(view)))   # 1 = row-split, 2 = quadrant
-        self._note_form("fwd", fwd_form == 1)
+        view.walk_form = pin or self.walk_form(_capacity_hint if _capacity_hint is not None else _cap_model.ratio(ckey) * N, N)
+        o, kept, scratch_floats, masks_for, mask_form = self._begin(
+            L, view, flavour, device, N,
+            [("geom", u8, (L.lograst_geom_bytes(N),)), ("state", u8, (L.lograst_tile_state_bytes(W, H, N),))], scratch_floats)
+        instances = None
 
         def lists_for(cap, plist=None):
             """point list, key buffer and hit masks of a stage 2 with room for `cap` tile instances.  The list is an
@@ -623,8 +659,7 @@ class HipBackend:
                 k = self._carve(device, kept)
                 retry = True
                 if _speculative and N > 0:   # both stages with a guessed capacity; the host reads the real one afterwards
-                    tiles = ((W + 15) // 16) * ((H + 15) // 16)
-                    capacity, max_len = _cap_model.guess(ckey, N, tiles)
+                    capacity, max_len = _cap_model.guess(ckey, N, _tiles(W, H))
                     plist, keys, masks = lists_for(capacity)
                     _lib.check(L.lograst_forward_speculative(*stage1_args(k), *stage2_args(k, keys, plist, capacity, max_len)[:-1],
                                                              ctypes.byref(n_host), ctypes.byref(m_host), stream))
@@ -640,20 +675,8 @@ class HipBackend:
                                                         *stage2_args(k, keys, plist, capacity, max_len)))
         if instances is None:
             instances = capacity          # exact mode: the real count; sync-free: the caller's (tight) upper bound
-        if _DEBUG_ADDR:
-            print("fwd state@%x keys@%x capacity=%d stream=%x" % (k["state"].data_ptr(), keys.data_ptr(), capacity, stream.value or 0), flush=True)
-        kept_keys = (keys, capacity) if _keep_keys else None
-        del keys, keep
-        saved = dict(radii=o["radii"], geom=k["geom"].view(f32), state=k["state"].view(i32), plist=plist,
-                     final_T=k["final_T"], n_contrib=k["n_contrib"], bwd_scratch=k.get("bwd_scratch"),
-                     point_weight=o.get("pw"), tile_rows=(view.tile_row_begin, view.tile_row_end), instances=int(instances),
-                     walk_form_pin=pin, hit_masks=masks if want_masks else None,
-                     hit_mask_form=fwd_form if want_masks else 0,
-                     # what this stage 2 ran with (a recomposite walks the lists under the same decisions)
-                     capacity=int(capacity), max_len=int(max_len), fwd_walk_form=int(view.walk_form))
-        if kept_keys is not None:
-            saved["keys"], saved["capacity"] = kept_keys
-        return o["image"], o["radii"], o.get("pid"), o.get("pwp"), o.get("pw"), saved
+        return self._finish(view, o, k, k["state"].view(i32), plist, (view.tile_row_begin, view.tile_row_end), instances, pin,
+                            capacity, max_len, masks, mask_form, keys if _keep_keys else None)
 
     def recomposite(self, rs, flavour, use_filter, saved, colors, scratch_floats=0):
         """The forward of the same Gaussians with other colours, from the `saved` dict of a forward that ran (full image,
@@ -665,27 +688,12 @@ class HipBackend:
         device = colors.device
         L = self.require(device)
         N = colors.shape[0]
-        H, W = int(rs.image_height), int(rs.image_width)
         view, keep = self.make_view(rs, flavour, use_filter, device)
         view.walk_form = int(saved["fwd_walk_form"])     # the form the first walk ran in (the history may have moved since)
-        fwd_form = int(L.lograst_forward_form(ctypes.byref(view)))
-        self._note_form("fwd", fwd_form == 1)
-        i32, f32, u8 = torch.int32, torch.float32, torch.uint8
-        o = {"image": torch.empty(3, H, W, dtype=f32, device=device), "radii": torch.empty(N, dtype=i32, device=device)}
-        if flavour.extras:
-            o.update(pid=torch.empty(H, W, dtype=i32, device=device), pwp=torch.empty(H, W, dtype=f32, device=device),
-                     pw=torch.empty(N, dtype=f32, device=device))
-        kept = [("geom", u8, (L.lograst_record_bytes(N),)), ("final_T", f32, (H, W)), ("n_contrib", i32, (H, W))]
-        scratch_floats = _lib.BWD_ROW_FLOATS if scratch_floats and N else 0
-        if scratch_floats:
-            kept.append(("bwd_scratch", f32, (N * scratch_floats,)))
+        o, kept, scratch_floats, masks_for, mask_form = self._begin(
+            L, view, flavour, device, N, [("geom", torch.uint8, (L.lograst_record_bytes(N),))], scratch_floats)
         capacity, max_len = int(saved["capacity"]), int(saved["max_len"])
-        masks = None
-        want_masks = self._want_masks(L, scratch_floats)
-        if want_masks:   # a buffer of this call's own: the first call's backward has not run yet
-            masks = (torch.zeros if _zero_hit_masks else torch.empty)(L.lograst_hit_mask_bytes(capacity, W, H) // 8,
-                                                                      dtype=torch.int64, device=device)
-            view.hit_masks, view.hit_mask_words = masks.data_ptr(), masks.numel()
+        masks = masks_for(capacity)   # a buffer of this call's own: the first call's backward has not run yet
         with torch.cuda.device(device):
             k = self._carve(device, kept)
             _lib.check(L.lograst_recomposite(
@@ -693,13 +701,8 @@ class HipBackend:
                 capacity, max_len, _ptr(colors), _ptr(k["geom"]), _ptr(o["radii"]), _ptr(o["image"]), _ptr(k["final_T"]),
                 _ptr(k["n_contrib"]), _ptr(o.get("pid")), _ptr(o.get("pwp")), _ptr(o.get("pw")), _ptr(k.get("bwd_scratch")),
                 scratch_floats, _ptr(_status_block(device)), _stream_ptr(device)))
-        del keep
-        out = dict(radii=o["radii"], geom=k["geom"].view(f32), state=saved["state"], plist=saved["plist"],
-                   final_T=k["final_T"], n_contrib=k["n_contrib"], bwd_scratch=k.get("bwd_scratch"),
-                   point_weight=o.get("pw"), tile_rows=saved["tile_rows"], instances=saved["instances"],
-                   walk_form_pin=saved["walk_form_pin"], hit_masks=masks, hit_mask_form=fwd_form if want_masks else 0,
-                   capacity=capacity, max_len=max_len, fwd_walk_form=int(view.walk_form))
-        return o["image"], o["radii"], o.get("pid"), o.get("pwp"), o.get("pw"), out
+        return self._finish(view, o, k, saved["state"], saved["plist"], saved["tile_rows"], saved["instances"],
+                            saved["walk_form_pin"], capacity, max_len, masks, mask_form, None)
 
     def backward(self, rs, flavour, use_filter, means3D, scales, rotations, saved, grad_image, sink=None, cov3D=None):
         """sink: optional dict of running-sum tensors (means3D, scales, rotations, opacities, colors) that this call
@@ -714,7 +717,7 @@ class HipBackend:
                 raise ValueError("a gradient sink has no cov3D_precomp entry")
             g_cov = torch.empty(N, 6, dtype=torch.float32, device=device)
         view, keep = self.make_view(rs, flavour, use_filter, device, cov3D=cov3D, g_cov3D=g_cov)
-        view.tile_row_begin, view.tile_row_end = saved.get("tile_rows", (0, 0))   # the band the forward rendered
+        view.tile_row_begin, view.tile_row_end = saved["tile_rows"]   # the band the forward rendered
         f32 = dict(dtype=torch.float32, device=device)
         grad_image = grad_image.to(torch.float32).contiguous()
         need = _lib.BWD_ROW_FLOATS
@@ -723,20 +726,20 @@ class HipBackend:
         # torch.zeros.  In the 5-tuple flavour the forward cleared the rows of the contributing Gaussians only
         # (point_weight > 0); the chain rule skips all the others (LOGRAST_BWD_CONIC_TOUCHED_ONLY) -- and hands out the
         # separate outputs: dL/dmeans2D, and dL/dopacity / dL/dcolour (written, or added into the sink's running sums).
-        acc = saved.pop("bwd_scratch", None)
-        pw = saved.get("point_weight")
+        acc, saved["bwd_scratch"] = saved["bwd_scratch"], None
+        pw = saved["point_weight"]
         flags = 1
         if acc is None or acc.numel() < need * N:
             acc = torch.zeros(N * need, **f32)
         elif pw is not None:
             flags |= 4
         # tiny splats -> the row-split reverse walk; a form pinned for the forward holds for its backward
-        view.walk_form = saved.get("walk_form_pin", 0) or self.walk_form(saved.get("instances", 0), N)
-        self._note_form("bwd", self._bwd_rows(view.walk_form, N))
-        hm = saved.get("hit_masks")      # the forward's support ballots (lograst_view.hit_masks): the reverse walk reads them
+        view.walk_form = saved["walk_form_pin"] or self.walk_form(saved["instances"], N)
+        self._note_form("bwd", L.lograst_backward_form(ctypes.byref(view), N) == 1)
+        hm = saved["hit_masks"]      # the forward's support ballots (lograst_view.hit_masks): the reverse walk reads them
         if hm is not None:
             view.hit_masks, view.hit_mask_words = hm.data_ptr(), hm.numel()
-            view.hit_mask_form = max(int(saved.get("hit_mask_form", 0)), 0)
+            view.hit_mask_form = max(int(saved["hit_mask_form"]), 0)
         g_conic = acc          # (the C ABI's `bwd_rows`)
         g_means2D = torch.empty(N, 3, **f32)
         if sink is None:
@@ -925,6 +928,22 @@ class HipBackend:
                 *[_ptr(buffers[name]) for name in want], _ptr(flag), _stream_ptr(device)))
         return flag.view(torch.bool)
 
+    @staticmethod
+    def _adam_key(slot, device, entry, rows, grad):
+        """Fills one LograstAdamKey from entry = (model_param, exp_avg, exp_avg_sq, max_exp_avg_sq | None, step_size) and the
+        addresses of the rows being stepped and of their gradient (None: the launch computes it); -> floats per row."""
+        model_p, m1, m2, mmax, step_size = entry
+        width = int(model_p[0].numel()) if model_p.shape[0] else 1
+        for t in (model_p, m1, m2) + ((mmax,) if mmax is not None else ()):
+            if t.device != device or t.dtype != torch.float32 or not t.is_contiguous() or t.shape != model_p.shape:
+                raise ValueError("parameters and Adam moments must be contiguous fp32 tensors on the parameter's "
+                                 "device (log_amd.sparse_optimizer.step moves host-resident moments there)")
+        slot.model_param, slot.param, slot.grad = model_p.data_ptr(), rows, grad
+        slot.exp_avg, slot.exp_avg_sq = m1.data_ptr(), m2.data_ptr()
+        slot.max_exp_avg_sq = mmax.data_ptr() if mmax is not None else None
+        slot.width, slot.step_size = width, float(step_size)
+        return width
+
     def sparse_adam(self, index, flag_vis, entries, beta1, beta2, bias_correction2_sqrt, eps):
         """N4c (log_amd/sparse_optimizer.py).  entries: (model_param, param, grad, exp_avg, exp_avg_sq,
         max_exp_avg_sq | None, step_size) per key."""
@@ -941,21 +960,13 @@ class HipBackend:
             for first in range(0, len(entries), 8):
                 chunk = entries[first:first + 8]
                 keys = (_lib.LograstAdamKey * len(chunk))()
-                for slot, (model_p, param, grad, m1, m2, mmax, step_size) in zip(keys, chunk):
+                for slot, (model_p, param, grad, *moments) in zip(keys, chunk):
                     num_points = int(model_p.shape[0])
-                    width = int(model_p[0].numel()) if num_points else 1
-                    for t in (model_p, m1, m2) + ((mmax,) if mmax is not None else ()):
-                        if t.device != device or t.dtype != torch.float32 or not t.is_contiguous() or t.shape != model_p.shape:
-                            raise ValueError("parameters and Adam moments must be contiguous fp32 tensors on the parameter's "
-                                             "device (log_amd.sparse_optimizer.step moves host-resident moments there)")
                     p, g = _dev_f32(param, device), _dev_f32(grad, device)
+                    width = self._adam_key(slot, device, (model_p, *moments), p.data_ptr(), g.data_ptr())
                     if int(p.numel()) != m * width or int(g.numel()) != m * width:
                         raise ValueError("param / grad rows do not match index")
                     keep += [p, g]
-                    slot.model_param, slot.param, slot.grad = model_p.data_ptr(), p.data_ptr(), g.data_ptr()
-                    slot.exp_avg, slot.exp_avg_sq = m1.data_ptr(), m2.data_ptr()
-                    slot.max_exp_avg_sq = mmax.data_ptr() if mmax is not None else None
-                    slot.width, slot.step_size = width, float(step_size)
                 _lib.check(L.lograst_sparse_adam(m, num_points, _ptr(idx), _ptr(fv), len(chunk), keys, float(beta1),
                                                  float(beta2), float(bias_correction2_sqrt), float(eps),
                                                  _stream_ptr(device)))
@@ -970,16 +981,9 @@ class HipBackend:
         n, P = int(idx.numel()), int(bufs["xyz"].shape[0])
         src = {k: _dev_f32(v, device) for k, v in bufs.items()}
         K = int(src["shs"].shape[1]) if "shs" in src else 0
-        # one allocation for all outputs (the quaternion blocks first: their rows are read and written as float4)
-        widths = [("raw", "rotation", 4), ("act", "rotation", 4), ("raw", "xyz", 3), ("raw", "scaling", 3),
-                  ("raw", "colors", 3), ("act", "scaling", 3), ("act", "colors", 3), ("raw", "opacity", 1),
-                  ("act", "opacity", 1)] + ([("raw", "shs", 3 * K)] if K else [])
-        flat = torch.empty(sum(n * w + _BLOCK_SKEW for _, _, w in widths), dtype=torch.float32, device=device)
-        raw, act, off = {}, {}, 0
-        for kind, key, w in widths:
-            view = flat[off:off + n * w].view((n, K, 3) if key == "shs" else (n, w))
-            (raw if kind == "raw" else act)[key] = view
-            off += n * w + _BLOCK_SKEW
+        raw, act = {}, {}
+        for (kind, key), block in _carve_skewed(device, n, _gather_blocks(K)).items():   # one allocation for all outputs
+            (raw if kind == "raw" else act)[key] = block
         cp = _dev_f32(campos, device).reshape(-1) if campos is not None else None
         with torch.cuda.device(device):
             _lib.check(L.lograst_gather_activate(
@@ -1010,18 +1014,10 @@ class HipBackend:
         for slot, key in zip(keys, ("xyz", "scaling", "opacity", "rotation", "colors", "shs")):
             if key not in entries:
                 continue
-            model_p, m1, m2, mmax, step_size = entries[key]
-            width = int(model_p[0].numel()) if num_points else 1
-            for t in (model_p, m1, m2) + ((mmax,) if mmax is not None else ()):
-                if t.device != device or t.dtype != torch.float32 or not t.is_contiguous() or t.shape != model_p.shape:
-                    raise ValueError("parameters and Adam moments must be contiguous fp32 tensors on the parameter's device")
             p = raw[key]
+            width = self._adam_key(slot, device, entries[key], p.data_ptr(), None)
             if not p.is_contiguous() or int(p.numel()) < n * width:
                 raise ValueError("gathered parameter rows do not match")
-            slot.model_param, slot.param, slot.grad = model_p.data_ptr(), p.data_ptr(), None
-            slot.exp_avg, slot.exp_avg_sq = m1.data_ptr(), m2.data_ptr()
-            slot.max_exp_avg_sq = mmax.data_ptr() if mmax is not None else None
-            slot.width, slot.step_size = width, float(step_size)
         with torch.cuda.device(device):
             _lib.check(L.lograst_activate_backward_adam(
                 int(n), _ptr(raw["xyz"]), _ptr(raw["scaling"]), _ptr(raw["opacity"]), _ptr(raw["rotation"]), K, int(degree),
@@ -1034,13 +1030,7 @@ class HipBackend:
         device = raw["xyz"].device
         L = self.require(device)
         K = int(raw["shs"].shape[1]) if "shs" in raw else 0
-        # one allocation; 16-byte aligned blocks first (quaternion rows and, for 3K % 4 == 0, the SH rows go out as float4)
-        widths = [("rotation", 4)] + ([("shs", 3 * K)] if K and degree > 0 else []) + [("scaling", 3), ("colors", 3), ("opacity", 1)]
-        flat = torch.empty(sum(n * w + _BLOCK_SKEW for _, w in widths), dtype=torch.float32, device=device)
-        g, off = {}, 0
-        for key, w in widths:
-            g[key] = flat[off:off + n * w].view((n, K, 3) if key == "shs" else (n, w))
-            off += n * w + _BLOCK_SKEW
+        g = _carve_skewed(device, int(n), _activate_backward_blocks(K, degree))
         ups = [_dev_f32(t, device) for t in (g_scaling, g_opacity, g_rotation, g_colors)]
         cp = _dev_f32(campos, device).reshape(-1) if campos is not None else None
         with torch.cuda.device(device):
@@ -1205,10 +1195,10 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.cov = cov
         ctx.rs, ctx.flavour, ctx.use_filter = rs, flavour, use_filter
         ctx.set_materialize_grads(False)   # no zero-filled gradients for radii / the fork maps (4 fill kernels per view)
-        ctx.saved = saved
+        ctx.saved = saved   # the backend's own record: opaque here
         # the backward trusts the forward's point_weight (which Gaussians it may skip, which dL/dconic rows are cleared):
         # an in-place change of that output between forward and backward is refused, like autograd does for saved tensors
-        ctx.pw_version = pw._version if pw is not None else None
+        ctx.radii, ctx.pw, ctx.pw_version = radii, pw, pw._version if pw is not None else None
         ctx.leaves = (means3D, colors, opacities, scales, rotations) if (sh is None and cov is None) else None
         ctx.sh = (sh, clamped)
         ctx.shapes = (means2D.shape, opacities.shape)
@@ -1227,61 +1217,51 @@ class _RasterizeGaussians(torch.autograd.Function):
             return (None,) * 12
         # which view's backward is running: nodes further down the same graph (log_amd.get_all's fused step) take the
         # visibility of THIS render from here (the rasterizer's node runs before the nodes that produced its inputs)
-        _publish_backward_view(ctx.saved.get("radii") if isinstance(ctx.saved, dict) else None, m)
+        _publish_backward_view(ctx.radii, m)
         m2_shape, o_shape = ctx.shapes
         sh, clamped = ctx.sh
-        pw = ctx.saved.get("point_weight") if isinstance(ctx.saved, dict) else None
-        if pw is not None and ctx.pw_version is not None and pw._version != ctx.pw_version:
+        if ctx.pw is not None and ctx.pw._version != ctx.pw_version:
             raise RuntimeError("the rasterizer's point_weight output was modified in place between forward and backward; "
                                "the backward uses it to skip Gaussians that contributed to no pixel -- clone it first")
-        if ctx.cov is not None:
-            g_m3, g_m2, g_c, g_o, g_cov, _ = _backend.backward(ctx.rs, ctx.flavour, ctx.use_filter, m, None, None,
-                                                               ctx.saved, grad_image, cov3D=ctx.cov)
-            g_sh = None
-            if sh is not None:
-                g_sh = _backend.sh_backward(m, ctx.rs.campos, sh, int(ctx.rs.sh_degree), clamped, g_c.contiguous(), g_m3)
-                g_c = None
-            return g_m3, g_m2.reshape(m2_shape), g_c, g_sh, g_o.reshape(o_shape), None, None, None, None, None, g_cov, None
-        sink = _grad_sink
-        if sink is None and ctx.leaves is not None and (
+        # where the gradients go: back to autograd (sink None), or added into running sums -- one row per Gaussian, or one
+        # tensor per input (with native SH: the colour gradient into a scratch, from there into the running dL/dshs)
+        n = m.shape[0]
+        sink = _grad_sink if ctx.cov is None else None
+        if sink is None and ctx.leaves is not None and (   # (leaves: None under cov3D_precomp or native SH)
                 _inplace_leaf_grads or all(getattr(t, _INPLACE_TAG, False) for t in ctx.leaves if t is not None)):
             sink = _leaf_grad_sink(ctx.leaves, m.device)
         if sink is not None and "rows" in sink:
-            n = m.shape[0]
             if sh is not None:
                 raise ValueError("the row-major gradient sink has no native-SH form (pass colors_precomp)")
             if sink["rows"].shape[0] != n or sink["rows"].device != m.device:
                 raise ValueError("gradient sink does not match the rasterizer inputs")
-            _, g_m2, _, _, _, _ = _backend.backward(ctx.rs, ctx.flavour, ctx.use_filter, m, s, r, ctx.saved, grad_image,
-                                                    sink=sink)
-            return None, g_m2.reshape(m2_shape), None, None, None, None, None, None, None, None, None, None
-        if sink is not None and (sh is None or "shs" in sink):
-            n = m.shape[0]
+        elif sink is not None and (sh is None or "shs" in sink):
             if not (sink["means3D"].shape == (n, 3) and sink["scales"].shape == (n, 3) and
                     sink["rotations"].shape == (n, 4) and sink["opacities"].numel() == n and
                     (sh is not None or sink["colors"].shape == (n, 3)) and sink["means3D"].device == m.device):
                 raise ValueError("gradient sink does not match the rasterizer inputs")
-            if sh is None:
-                _, g_m2, _, _, _, _ = _backend.backward(ctx.rs, ctx.flavour, ctx.use_filter, m, s, r, ctx.saved,
-                                                        grad_image, sink=sink)
-            else:
+            if sh is not None:
                 # colours are an intermediate here: their gradient goes to a zeroed scratch, then through the SH
                 # polynomial into the running dL/dshs (and the direction term into the running dL/dmeans3D)
                 if sink["shs"].shape != sh.shape or not sink["shs"].is_contiguous():
                     raise ValueError("gradient sink 'shs' must be a contiguous tensor shaped like shs")
-                g_c = torch.zeros(n, 3, dtype=torch.float32, device=m.device)
-                _, g_m2, _, _, _, _ = _backend.backward(ctx.rs, ctx.flavour, ctx.use_filter, m, s, r, ctx.saved,
-                                                        grad_image, sink=dict(sink, colors=g_c))
-                _backend.sh_backward(m, ctx.rs.campos, sh, int(ctx.rs.sh_degree), clamped, g_c, sink["means3D"],
-                                     into=sink["shs"])
-            return None, g_m2.reshape(m2_shape), None, None, None, None, None, None, None, None, None, None
-        g_m3, g_m2, g_c, g_o, g_s, g_r = _backend.backward(ctx.rs, ctx.flavour, ctx.use_filter, m, s, r, ctx.saved,
-                                                           grad_image)
-        g_sh = None
-        if sh is not None:
+                sink = dict(sink, colors=torch.zeros(n, 3, dtype=torch.float32, device=m.device))
+        else:
+            sink = None   # (a sink without an "shs" entry under native SH: the gradients go back to autograd)
+        g_m3, g_m2, g_c, g_o, g_s, g_r = _backend.backward(ctx.rs, ctx.flavour, ctx.use_filter, m,
+                                                           *((s, r) if ctx.cov is None else (None, None)), ctx.saved,
+                                                           grad_image, sink=sink, cov3D=ctx.cov)
+        g_sh = g_cov = None
+        if ctx.cov is not None:   # (the backend's last two results are then (dL/dcov3D, None))
+            g_cov, g_s = g_s, None
+        if sh is not None and sink is None:
             g_sh = _backend.sh_backward(m, ctx.rs.campos, sh, int(ctx.rs.sh_degree), clamped, g_c.contiguous(), g_m3)
             g_c = None
-        return g_m3, g_m2.reshape(m2_shape), g_c, g_sh, g_o.reshape(o_shape), g_s, g_r, None, None, None, None, None
+        elif sh is not None:
+            _backend.sh_backward(m, ctx.rs.campos, sh, int(ctx.rs.sh_degree), clamped, sink["colors"], sink["means3D"],
+                                 into=sink["shs"])
+        return (g_m3, g_m2.reshape(m2_shape), g_c, g_sh, g_o.reshape(o_shape) if g_o is not None else None, g_s, g_r,
+                None, None, None, g_cov, None)
 
 
 class GaussianRasterizer(nn.Module):
@@ -1369,7 +1349,7 @@ def ordered_lengths_of(saved, width, height):
     """Test/debug accessor: per tile, how many leading positions of its list are in final order (lists of more than
     4096 keys are ordered over their first window only unless a pixel needed more: include/lograst.h,
     lograst_ordered_lengths)."""
-    tiles = ((int(width) + 15) // 16) * ((int(height) + 15) // 16)
+    tiles = _tiles(width, height)
     st = saved["state"]
     out = torch.empty(tiles, dtype=torch.int32, device=st.device)
     with torch.cuda.device(st.device):
@@ -1383,7 +1363,7 @@ def parked_waves_of(saved, width, height):
     for the second sort / compositing pair, and the view's "somebody parked" flag (layout: log_amd/csrc/common.hpp,
     sorted[] / open[]).  Only lists of more than 4096 keys of a view whose sort left lists at their first window have such a
     word (elsewhere the array still holds the fill's cursors): every other tile reads as 0."""
-    tiles = ((int(width) + 15) // 16) * ((int(height) + 15) // 16)
+    tiles = _tiles(width, height)
     st = saved["state"]
     offs = tile_offsets_of(saved, width, height)
     first = (offs.data_ptr() - st.data_ptr()) // 4
@@ -1400,7 +1380,7 @@ def finish_lists(saved, width, height):
     """Test/debug: orders every tile list of a forward made under keep_keys(True) to its end, in place
     (lograst_finish_lists): saved["plist"] is then what LOGRAST_LAZY_SORT=0 would have produced."""
     st = saved["state"]
-    if saved.get("keys") is None:
+    if saved["keys"] is None:
         raise RuntimeError("finish_lists: this forward did not keep its key buffer -- run it under keep_keys(True) "
                            "(the forward treats `keys` as dead scratch otherwise)")
     with torch.cuda.device(st.device):
@@ -1411,8 +1391,7 @@ def finish_lists(saved, width, height):
 def tile_offsets_of(saved, width, height):
     """Test/debug accessor: the per-tile exclusive offsets (tiles+1 entries) inside a tile_state tensor
     (layout: log_amd/csrc/common.hpp)."""
-    gx, gy = (int(width) + 15) // 16, (int(height) + 15) // 16
-    tiles = gx * gy
+    tiles = _tiles(width, height)
     st = saved["state"]
     L = _lib.lib()
     first = (L.lograst_tile_offsets(ctypes.c_void_p(st.data_ptr()), int(width), int(height)) - st.data_ptr()) // 4

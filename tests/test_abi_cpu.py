@@ -227,3 +227,36 @@ def test_knob_precedence_override_environment_default():
     assert len(out["all"]) == 22 and out["env"] == [0, 16] and out["reset"] == [0, 16]
     for name, dflt, rc, value in out["all"]:
         assert rc == 0 and value == dflt, (name, value, dflt)
+
+
+def test_backward_form_is_the_written_out_table():
+    """lograst_backward_form (the reverse walk's form, as lr_launch_blend_bwd decides it) over knob LOGRAST_BWD_ROWS x the
+    view's walk_form x n on either side of LOGRAST_HELPER_MIN_N: 1 = row-split, 2 = quadrant.  The view's pointers are fake
+    (never dereferenced, as with lograst_forward_form); a NULL view or a walk_form outside the enumeration is an error code,
+    not a form."""
+    from log_amd import _lib
+    L = _lib.lib()
+    v = _lib.LograstView()
+    v.width, v.height, v.tanfovx, v.tanfovy, v.scale_modifier = 64, 48, 0.5, 0.5, 1.0
+    v.filter_mode, v.ndc_cull, v.extras = _lib.FILTER_CLAMP, 1, 1
+    v.viewmatrix, v.projmatrix, v.bg = 0x1000, 0x2000, 0x3000
+    min_n = ctypes.c_int32(-1)
+    assert L.lograst_get_knob(b"LOGRAST_HELPER_MIN_N", ctypes.byref(min_n)) == 0 and min_n.value >= 1
+    small, big = min_n.value - 1, min_n.value
+    AUTO, ROWS, QUAD = _lib.FORM_AUTO, _lib.FORM_ROWS, 2
+    expected = {  # (knob, walk_form, n) -> form
+        (0, AUTO, small): 2, (0, AUTO, big): 2, (0, ROWS, small): 2, (0, ROWS, big): 2, (0, QUAD, small): 2, (0, QUAD, big): 2,
+        (1, AUTO, small): 1, (1, AUTO, big): 1, (1, ROWS, small): 1, (1, ROWS, big): 1, (1, QUAD, small): 1, (1, QUAD, big): 1,
+        (2, AUTO, small): 2, (2, AUTO, big): 1, (2, ROWS, small): 1, (2, ROWS, big): 1, (2, QUAD, small): 2, (2, QUAD, big): 2,
+    }
+    assert len(expected) == 18
+    try:
+        for (knob, form, n), want in expected.items():
+            assert L.lograst_set_knob(b"LOGRAST_BWD_ROWS", knob) == 0
+            v.walk_form = form
+            assert L.lograst_backward_form(ctypes.byref(v), n) == want, (knob, form, n)
+        v.walk_form = 3
+        assert L.lograst_backward_form(ctypes.byref(v), big) == -1 and b"walk_form" in L.lograst_last_error()
+        assert L.lograst_backward_form(None, big) == -1 and b"view" in L.lograst_last_error()
+    finally:
+        assert L.lograst_reset_knobs() == 0

@@ -151,3 +151,36 @@ def test_fused_step_takes_its_row_mask_from_its_own_render_only(double):
 
     oracle_backend.install(FusedDouble())                               # (the fixture puts the previous backend back)
     F.run_cases("cpu", P=500, W=64, H=48, focal=120.0)
+
+
+@pytest.mark.parametrize("n", [0, 1, 1000])
+def test_skewed_carve_offsets_alignment_and_shapes(n):
+    """The one-allocation outputs of gather_activate (with and without `shs`, K = 16) and of activate_backward: every block
+    starts n * w + 1088 floats behind the start of the one before, in the order written out here; the blocks whose rows move
+    as float4 (the quaternions; activate_backward's `shs`, 3K floats) start 16-byte aligned; shapes are (n, w), (n, K, 3) for
+    `shs`.  gather_activate's raw `shs` block comes last, 25 n + 9 * 1088 floats in: 16-byte aligned only for n % 4 == 0 (its
+    kernel stores it one 12-byte triple at a time) -- pinned as it is."""
+    from log_amd import rasterizer as R
+    K = 16
+    gather = [(("raw", "rotation"), 4), (("act", "rotation"), 4), (("raw", "xyz"), 3), (("raw", "scaling"), 3),
+              (("raw", "colors"), 3), (("act", "scaling"), 3), (("act", "colors"), 3), (("raw", "opacity"), 1),
+              (("act", "opacity"), 1)]
+    grads = [("rotation", 4), ("scaling", 3), ("colors", 3), ("opacity", 1)]
+    cases = [(R._gather_blocks(0), gather), (R._gather_blocks(K), gather + [(("raw", "shs"), 3 * K)]),
+             (R._activate_backward_blocks(K, 3), grads[:1] + [("shs", 3 * K)] + grads[1:]),
+             (R._activate_backward_blocks(K, 0), grads), (R._activate_backward_blocks(0, 3), grads)]
+    for blocks, want in cases:
+        out = R._carve_skewed(torch.device("cpu"), n, blocks)
+        assert list(out) == [name for name, _ in want]
+        base, off = out[want[0][0]].untyped_storage(), 0
+        assert base.data_ptr() % 16 == 0 and out[want[0][0]].storage_offset() == 0
+        for name, w in want:
+            t = out[name]
+            assert t.shape == ((n, K, 3) if w == 3 * K else (n, w)) and t.dtype == torch.float32 and t.is_contiguous()
+            assert t.untyped_storage().data_ptr() == base.data_ptr() and t.storage_offset() == off, (name, n)   # one allocation
+            if name == ("raw", "shs"):
+                assert off == 25 * n + 9 * 1088 and (4 * off % 16 == 0) == (n % 4 == 0)
+            elif w == 4 or w == 3 * K:
+                assert 4 * off % 16 == 0, (name, n)
+            off += n * w + 1088
+        assert base.nbytes() == 4 * off

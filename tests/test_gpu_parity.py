@@ -338,7 +338,7 @@ def test_backward_does_not_trust_a_hit_mask_buffer_it_cannot_use(oracle_mod, for
         return g
 
     g_ok = backward(saved, form)                                        # (takes the forward's accumulator rows: the copies below get fresh ones)
-    assert "bwd_scratch" not in saved
+    assert saved["bwd_scratch"] is None
     # (b) before (a) spoils the buffer: the right masks, claimed to be of the other form, walked in that form
     g_b = backward(dict(saved, hit_mask_form=code[other]), other)
     # (a) the front half of the allocation, the rest zeroed
@@ -476,6 +476,56 @@ def test_backward_scratch_lifecycle():
     with torch.no_grad():
         img2 = rast(means2D=m2, shs=None, cov3D_precomp=None, **leaves)[0]
     assert (img2 == img).all() and not img2.requires_grad
+
+
+@pytest.mark.parametrize("min_n", [None, 32])
+@pytest.mark.parametrize("flavour_name", ["wodilate", "upstream"])
+def test_second_backward_over_one_forward(oracle_mod, flavour_name, min_n):
+    """Two backwards through one forward (retain_graph), each held to what test_backward_vs_oracle asks of one: the first
+    takes the accumulator rows its forward cleared (the record's `bwd_scratch`, None afterwards), the second finds None and
+    clears rows of its own.  min_n = 32: LOGRAST_HELPER_MIN_N below the 64 Gaussians, so the 5-tuple package's forward
+    clears only the rows of contributing Gaussians and its first backward skips the others (touched-only); the second, on
+    fully cleared rows, does not.  32 x 32 pixels (2 x 2 tiles); one of the 64 Gaussians reaches no pixel."""
+    import diff_gaussian_rasterization as up
+    import diff_gaussian_rasterization_wodilate as wo
+    import gpu_util as G
+    from log_amd import rasterizer as R, tune
+    cam, sc = small_case(n=64, W=32, H=32, focal=40.0, seed=1)
+    bg = (0.3, 0.6, 0.9)
+    fl = _flavour(flavour_name)
+    v, of = G.oracle_forward(oracle_mod, cam, sc, bg, flavour=fl)
+    dL = np.random.default_rng(1).random(of["image"].shape, dtype=np.float32)
+    og, g64 = oracle_mod.backward(v, of, dL), oracle_mod.backward_f64(v, of, dL)
+    dev = torch.device("cuda:0")
+    t = lambda a: torch.tensor(np.ascontiguousarray(a, np.float32), device=dev, requires_grad=True)
+    leaves = dict(means3D=t(sc["xyz"]), colors_precomp=t(sc["colors"]), opacities=t(sc["opacity"]),
+                  scales=t(sc["scaling"]), rotations=t(sc["rotation"]))
+    m2 = torch.zeros_like(leaves["means3D"], requires_grad=True)
+    rast = (wo if flavour_name == "wodilate" else up).GaussianRasterizer(raster_settings=G.settings(cam, bg, dev))
+    if min_n is not None:
+        tune.set_knob("LOGRAST_HELPER_MIN_N", min_n)
+    try:
+        img = rast(means2D=m2, shs=None, cov3D_precomp=None, **leaves)[0]
+        saved = img.grad_fn.saved
+        assert saved["bwd_scratch"] is not None and saved["hit_masks"] is not None
+        assert (saved["point_weight"] is not None) == (flavour_name == "wodilate")
+        for nth in ("first", "second"):
+            for x in list(leaves.values()) + [m2]:
+                x.grad = None
+            img.backward(gradient=torch.tensor(dL, device=dev), retain_graph=True)
+            assert saved["bwd_scratch"] is None
+            g = lambda x: x.grad.cpu().numpy()
+            hg = dict(means3D=g(leaves["means3D"]), scales=g(leaves["scales"]), rotations=g(leaves["rotations"]),
+                      colors=g(leaves["colors_precomp"]), opacities=g(leaves["opacities"]).reshape(-1, 1), means2D=g(m2),
+                      conic=R._backend.last_conic_grad.cpu().numpy())
+            if saved["point_weight"] is not None:                    # (as gpu_util.hip_backward: rows nobody cleared or read)
+                hg["conic"][saved["point_weight"].cpu().numpy() == 0] = 0
+            for k in ("means2D", "conic", "opacities", "colors"):
+                print("%s %s %s %s: %.2e" % (flavour_name, min_n, nth, k, rel_l2(hg[k], og[k])))
+                assert rel_l2(hg[k], og[k]) < GRAD_TOL, (nth, k, rel_l2(hg[k], og[k]))
+            G.assert_gradients_anchored(G.gradient_anchor_stats(hg, og, g64), tol=GRAD_TOL, max_excluded=0.10, all_rows_tol=None)
+    finally:
+        tune.reset_knobs()
 
 
 def test_module_autograd_contract():

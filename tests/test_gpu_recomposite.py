@@ -73,7 +73,9 @@ class Pair:
     """Two calls through the public package, the way LoG makes them, and one backward over both."""
 
     def __init__(self, cam, sc, reuse, package="wodilate", between=None, other_object=False, second_kw=None,
-                 second_ctx=None, cov3D=False, grad=(True, True), backward=True, sink_rows=False, dev="cuda:0"):
+                 second_ctx=None, cov3D=False, grad=(True, True), backward=True, sink_rows=False, dev="cuda:0", order=None):
+        """order: None = one backward over the sum of both calls' losses; (1, 2) / (2, 1) = one backward per call, in that
+        order (the leaves' .grad hold the same sums either way)."""
         import contextlib
         import gpu_util as G
         from log_amd import rasterizer as R
@@ -124,12 +126,16 @@ class Pair:
                         self.out2 = rast2(**kw2)
                 self.stats = R.geometry_reuse_stats()
                 if backward:
-                    loss = 0
+                    losses = {}
                     if grad[0]:
-                        loss = loss + (self.out1[0] * torch.from_numpy(self.w1).to(dev)).sum()
+                        losses[1] = (self.out1[0] * torch.from_numpy(self.w1).to(dev)).sum()
                     if grad[1]:
-                        loss = loss + (self.out2[0] * torch.from_numpy(self.w2).to(dev)).sum()
-                    loss.backward()
+                        losses[2] = (self.out2[0] * torch.from_numpy(self.w2).to(dev)).sum()
+                    if order is None:
+                        sum(losses.values()).backward()
+                    else:
+                        for i in order:
+                            losses[i].backward()
         finally:
             R.set_geometry_reuse(prev)
         torch.cuda.synchronize()
@@ -171,6 +177,9 @@ def _check_pair(oracle_mod, cam, sc, a, b, oracle_grads=True):
     b.out2[1].add_(1)
     assert np.array_equal(_bits(b.out1[1]), _bits(a.out1[1]))
     b.out2[1].sub_(1)
+    s1, s2 = b.out1[0].grad_fn.saved, b.out2[0].grad_fn.saved                    # a forward's record and a recomposite's
+    assert set(s1) == set(s2) and s2["state"] is s1["state"] and s2["plist"] is s1["plist"]
+    assert s1["bwd_scratch"] is None and s2["bwd_scratch"] is None               # each backward took its own accumulator rows
     sc2 = _depth_scene(cam, sc)
     v, of2 = G.oracle_forward(oracle_mod, cam, sc2, BG, flavour=a.flavour)
     assert np.array_equal(_bits(b.out2[0]), of2["image"].view(np.uint32))
@@ -223,6 +232,16 @@ def test_dense_tile_lists(oracle_mod):
     """Case 3: lists in the LDS sort classes and long lists that are never streamed lazily."""
     cam, sc = _dense_tile()
     a, b = Pair(cam, sc, False), Pair(cam, sc, True)
+    _check_pair(oracle_mod, cam, sc, a, b)
+
+
+@pytest.mark.parametrize("order", [(1, 2), (2, 1)])
+@pytest.mark.parametrize("package", ["wodilate", "upstream"])
+def test_backward_on_either_record_in_either_order(oracle_mod, package, order):
+    """The forward's record and the recomposite's hold the same keys (_check_pair), and the unchanged backward runs on
+    either one first: 64 Gaussians on 2 x 2 tiles, one backward per call."""
+    cam, sc = small_case(n=64, W=32, H=32, focal=40.0, seed=1)
+    a, b = Pair(cam, sc, False, package, order=order), Pair(cam, sc, True, package, order=order)
     _check_pair(oracle_mod, cam, sc, a, b)
 
 

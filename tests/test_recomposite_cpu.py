@@ -367,3 +367,41 @@ def test_reference_depth_pass_with_install_all_reuse(oracle_mod):
             sys.modules.pop(k, None)
         for p in added:
             sys.path.remove(p)
+
+
+def test_forward_and_recomposite_leave_the_same_record():
+    """HipBackend.forward and HipBackend.recomposite build `saved` with one function: the same keys whichever of the two made
+    it and whatever was optional (no training buffers, no kept key buffer, the upstream flavour's missing point_weight), and
+    among them every key that bench.py, the GPU tests and tools/ index."""
+    from log_amd import _lib
+    from log_amd.rasterizer import HipBackend
+    n, H, W = 5, 4, 6
+    u8 = lambda k: torch.zeros(k, dtype=torch.uint8)
+    view = _lib.LograstView()
+    view.walk_form = _lib.FORM_ROWS
+
+    def record(training, extras, keys):
+        o = {"image": torch.zeros(3, H, W), "radii": torch.zeros(n, dtype=torch.int32)}
+        if extras:
+            o.update(pid=torch.zeros(H, W, dtype=torch.int32), pwp=torch.zeros(H, W), pw=torch.zeros(n))
+        k = {"geom": u8(64 * n), "state": u8(256), "final_T": torch.zeros(H, W), "n_contrib": torch.zeros(H, W, dtype=torch.int32)}
+        if training:
+            k["bwd_scratch"] = torch.zeros(16 * n)
+        masks = torch.zeros(32, dtype=torch.int64) if training else None
+        out = HipBackend._finish(view, o, k, k["state"].view(torch.int32), torch.zeros(9, dtype=torch.int32), (0, 0), 7, 0, 9, 3,
+                                 masks, 1 if training else 0, u8(144) if keys else None)
+        assert out[0] is o["image"] and out[1] is o["radii"] and out[4] is o.get("pw")
+        return out[-1]
+
+    fwd = record(True, True, True)                       # a training forward of the fork under keep_keys(True)
+    plain = record(False, False, False)                  # an upstream forward under no_grad
+    assert set(fwd) == set(plain)
+    assert set(fwd) >= {"n_contrib", "final_T", "geom", "radii", "plist", "state", "hit_masks", "hit_mask_form", "point_weight",
+                        "keys", "bwd_scratch", "tile_rows", "instances", "walk_form_pin", "capacity", "max_len", "fwd_walk_form"}
+    assert all(plain[k] is None for k in ("keys", "bwd_scratch", "hit_masks", "point_weight")) and plain["hit_mask_form"] == 0
+    assert all(fwd[k] is not None for k in ("keys", "bwd_scratch", "hit_masks", "point_weight")) and fwd["hit_mask_form"] == 1
+    assert fwd["geom"].dtype == torch.float32 and fwd["state"].dtype == torch.int32 and fwd["fwd_walk_form"] == _lib.FORM_ROWS
+    # the autograd node keeps nothing of the record's layout: a backend may hand it any object (tests/oracle_backend.py: a tuple)
+    import inspect
+    from log_amd import rasterizer as R
+    assert "ctx.saved[" not in inspect.getsource(R._RasterizeGaussians) and ".saved.get" not in inspect.getsource(R)
