@@ -16,7 +16,7 @@ is a view into it), so a step needs exactly one exchange.  Two forms:
     replace).  The reference updates only the rows seen this step (``flag_vis``, sparse_optimizer.py:167): the bucket
     carries a per-row ``seen`` count next to the gradients for exactly that.
 
-Two refinements of the exchange, both optional and both leaving the result unchanged:
+Three refinements of the exchange, each optional and each leaving the result unchanged:
 
   * **touched-row blocks** (``block_rows`` > 0, ``compact=True``): a level-of-detail step touches a fraction of the model's
     rows, and a row no view saw has an exactly zero gradient and does not move.  The ranks first agree on which
@@ -37,6 +37,7 @@ Two refinements of the exchange, both optional and both leaving the 
 
 With world_size == 1 nothing is communicated and results are bit-identical to the single-GPU path.
 """
+import contextlib
 import math
 import os
 
@@ -70,7 +71,7 @@ def split_rows(grads):
 
 
 def shard_views(n_views, rank, world):
-    """Round-robin view ownership."""
+    """The views of `rank`: view v belongs to rank v % world."""
     return list(range(rank, n_views, world))
 
 
@@ -122,6 +123,21 @@ def _all_gather(out, inp, group=None):
 SPARSE_FLOATS = ROW_FLOATS + 1     # a packed row of the row-sparse exchange: 16 running sums | row index (int32 bits)
 
 
+def _clamp(k, limit):
+    """A list length the collectives are sized for: at least one entry (nothing touched: one of padding), at most all."""
+    return min(max(int(k), 1), limit)
+
+
+def _row_bound(rows, kmax, group):
+    """Rows per segment of a row-sparse collective over rows [G, R, 16]: the caller's bound `kmax`, or (None) the longest
+    list of non-zero rows any group holds on any rank, exactly -- one max-reduce and one device -> host read."""
+    if kmax is None:
+        cnt = (rows != 0).any(dim=2).sum(1).max().reshape(1)
+        dist.all_reduce(cnt, op=dist.ReduceOp.MAX, group=group)
+        kmax = cnt.item()
+    return _clamp(kmax, rows.shape[1])
+
+
 def _pack_rows(rows, kmax, clear=False, hint=None):
     """clear: the packed rows are zeroed in `rows` afterwards (pack and clear; rows dropped by an exceeded kmax stay).
     hint: see _pack_segments (the rows to pack are those with a non-zero hint word, whatever they hold).
@@ -131,12 +147,13 @@ def _pack_rows(rows, kmax, clear=False, hint=None):
     bound; `overflow` (a device flag) is raised when a group holds more than kmax such rows (the excess is dropped)."""
     G, R, C = rows.shape
     dev = rows.device
-    nz = torch.count_nonzero(rows, dim=2) > 0                     # [G, R]
-    if hint is not None:
-        h = torch.zeros(G * R, dtype=torch.bool, device=dev)
+    if hint is None:
+        nz = torch.count_nonzero(rows, dim=2) > 0                 # [G, R]
+    else:                             # (a hinted row is packed whatever it holds; the others are not looked at)
+        nz = torch.zeros(G * R, dtype=torch.bool, device=dev)
         n = min(int(hint.numel()), G * R)
-        h[:n] = hint.reshape(-1)[:n].view(torch.int32) != 0
-        nz = h.view(G, R)             # (a hinted row is packed whatever it holds; the others are not looked at)
+        nz[:n] = hint.reshape(-1)[:n].view(torch.int32) != 0
+        nz = nz.view(G, R)
     csum = torch.cumsum(nz.view(-1).to(torch.int32), 0).view(G, R)
     before = torch.cat([csum.new_zeros(1), csum[:-1, -1]])        # non-zero rows in front of each group
     rank = csum - 1 - before[:, None]                             # position of a non-zero row inside its group's list
@@ -167,11 +184,18 @@ def _unpack_add(dest, packed):
 # The torch formulation above is what the CPU tests run (gloo); on a 30 M-row bucket it takes 6 ms to pack, 30 ms to add
 # 8 M received rows (index_add_) and 180 ms to put the gathered rows back -- the kernels stream (a segment there is
 # header | values | indices, lograst_sparse_segment_floats(kmax) floats: include/lograst.h).
+def _native():
+    """-> (check, library, _ptr, _stream_ptr): liblograst.so with the error check of its return codes and the rasterizer's
+    marshalling of tensors and of the current stream.  Imported on first use: importing this module loads no library."""
+    from . import _lib
+    from .rasterizer import _ptr, _stream_ptr
+    return _lib.check, _lib.lib(), _ptr, _stream_ptr
+
+
 def _segment_floats(kmax, device):
     if device.type != "cuda":
         return int(kmax) * SPARSE_FLOATS
-    from . import _lib
-    return int(_lib.lib().lograst_sparse_segment_floats(int(kmax)))
+    return int(_native()[1].lograst_sparse_segment_floats(int(kmax)))
 
 
 def _pack_segments(rows, kmax, clear=False, hint=None):
@@ -183,26 +207,20 @@ def _pack_segments(rows, kmax, clear=False, hint=None):
     if rows.device.type != "cuda":
         packed, _, over = _pack_rows(rows, kmax, clear=clear, hint=hint)
         return packed.reshape(-1), over
-    import ctypes
-    from . import _lib
-    L = _lib.lib()
+    check, L, ptr, stream_ptr = _native()
     G, R, _ = rows.shape
     assert rows.is_contiguous() or not clear, "pack and clear works on the bucket's own storage"
     rows = rows.contiguous()
-    seg = int(L.lograst_sparse_segment_floats(int(kmax)))
-    packed = torch.empty(G * seg, dtype=torch.float32, device=rows.device)
+    packed = torch.empty(G * _segment_floats(kmax, rows.device), dtype=torch.float32, device=rows.device)
     flag = torch.zeros(1, dtype=torch.int32, device=rows.device)
     with torch.cuda.device(rows.device):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(rows.device).cuda_stream)
         if hint is not None:
             assert hint.is_contiguous() and hint.element_size() == 4 and hint.device == rows.device
-            _lib.check(L.lograst_pack_rows_hinted(ctypes.c_void_p(rows.data_ptr()), G, R, int(kmax), ctypes.c_void_p(packed.data_ptr()),
-                                                  ctypes.c_void_p(flag.data_ptr()), 1 if clear else 0,
-                                                  ctypes.c_void_p(hint.data_ptr()), int(hint.numel()), stream))
+            check(L.lograst_pack_rows_hinted(ptr(rows), G, R, int(kmax), ptr(packed), ptr(flag), 1 if clear else 0,
+                                             ptr(hint), int(hint.numel()), stream_ptr(rows.device)))
         else:
             fn = L.lograst_pack_rows_clear if clear else L.lograst_pack_rows
-            _lib.check(fn(ctypes.c_void_p(rows.data_ptr()), G, R, int(kmax), ctypes.c_void_p(packed.data_ptr()),
-                          ctypes.c_void_p(flag.data_ptr()), stream))
+            check(fn(ptr(rows), G, R, int(kmax), ptr(packed), ptr(flag), stream_ptr(rows.device)))
     return packed, flag[0] != 0
 
 
@@ -223,15 +241,11 @@ def _unpack_segments(dest, packed, segments, kmax, per_segment_rows=0, zero=Fals
         else:
             _unpack_add(dest, segs)
         return dest
-    import ctypes
-    from . import _lib
-    L = _lib.lib()
+    check, L, ptr, stream_ptr = _native()
     rows_per_group = int(per_segment_rows) if per_segment_rows else int(dest.shape[0])
     with torch.cuda.device(dest.device):
-        _lib.check(L.lograst_unpack_rows(ctypes.c_void_p(dest.data_ptr()), ctypes.c_void_p(packed.data_ptr()), int(segments),
-                                         int(kmax), rows_per_group, int(per_segment_rows),
-                                         (2 if zero else 0) if per_segment_rows else 1,
-                                         ctypes.c_void_p(torch.cuda.current_stream(dest.device).cuda_stream)))
+        check(L.lograst_unpack_rows(ptr(dest), ptr(packed), int(segments), int(kmax), rows_per_group, int(per_segment_rows),
+                                    (2 if zero else 0) if per_segment_rows else 1, stream_ptr(dest.device)))
     return dest
 
 
@@ -248,7 +262,6 @@ def _all_to_all(out, inp, group=None):
     else:
         dist.all_to_all_single(out, inp, group=group)
     return out
-
 
 
 def _shape(name, rows, cols):
@@ -313,19 +326,15 @@ class TouchedBlocks:
         self.bitmap = bitmap                                   # bool [world, nb]
         self.world, self.nb = bitmap.shape
         self.counts = bitmap.sum(1)
-        if kmax is None:
-            self.kmax = max(int(self.counts.max().item()), 1)   # (nothing touched: one block of padding)
-            self.overflow = None
-        else:
-            self.kmax = min(max(int(kmax), 1), self.nb)
-            self.overflow = self.counts.max() > self.kmax       # device bool, no synchronisation
+        self.kmax = _clamp(self.counts.max().item() if kmax is None else kmax, self.nb)
+        self.overflow = None if kmax is None else self.counts.max() > self.kmax       # device bool, no synchronisation
         self.bound = kmax
         self.order = torch.argsort((~bitmap).to(torch.uint8), dim=1, stable=True)[:, :self.kmax].contiguous()
 
     def union(self, other):
         """Blocks touched by either.  Bounded form: the union of two lists of at most K blocks can hold up to 2 K, so the
-        union is sized for the SUM of the parts' bounds (round-4 advisory: with max(K, K) an owner whose parts touched
-        disjoint blocks published only its first K -- the other updated rows never reached the replicas); its own
+        union is sized for the SUM of the parts' bounds (sized for max(K, K), an owner whose parts touched disjoint
+        blocks would publish only its first K, and the other updated rows would never reach the replicas); its own
         overflow flag (impossible unless a part overflowed) is folded in all the same."""
         out = TouchedBlocks(self.bitmap | other.bitmap,
                             kmax=None if self.bound is None else min(self.kmax + other.kmax, self.nb))
@@ -353,8 +362,11 @@ class GradientBucket(_Flat):
         # views that saw the row this step (one float when not tracked: mark_seen / the touched-block exchange then refuse)
         self._seen = torch.zeros(self.Ppad if self.track_seen else 1, dtype=torch.float32, device=device)
         self._seen_pending = []      # radii tensors of mark_seen(defer=True), not yet counted (see the `seen` property)
+        self._seen_dirty = False     # somebody marked the counts since the last reset
         self._seen_reduced = False
         self.touched = None                                   # TouchedBlocks of the last compact exchange (else None)
+        self.touch_hint, self._hint_calls = None, 0           # mark_touched
+        self.sparse_overflow, self.sparse_kmax = None, 0      # the last row-sparse exchange's device flag and rows per segment
 
     def attach(self, params):
         """params: dict name -> leaf tensor (requires_grad).  Their .grad become views of the bucket,
@@ -379,9 +391,7 @@ class GradientBucket(_Flat):
         pend, self._seen_pending = self._seen_pending, []
         if not pend:
             return
-        import ctypes
-        from . import _lib
-        L = _lib.lib()
+        check, L, ptr, stream_ptr = _native()
         dev = self._seen.device
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev)
@@ -393,18 +403,25 @@ class GradientBucket(_Flat):
                     raise RuntimeError("mark_seen(defer=True): %d radii for a bucket of %d rows" % (n, int(self._seen.numel())))
                 for t in part:
                     t.record_stream(stream)
-                ptrs = (ctypes.c_void_p * len(part))(*[t.data_ptr() for t in part])
-                _lib.check(L.lograst_add_visible_n(ctypes.c_void_p(self._seen.data_ptr()), ptrs, len(part), n,
-                                                   ctypes.c_void_p(stream.cuda_stream)))
+                table = torch.tensor([t.data_ptr() for t in part], dtype=torch.int64)      # host array of addresses, read by the call
+                check(L.lograst_add_visible_n(ptr(self._seen), ptr(table), len(part), n, stream_ptr(dev)))
 
-    def zero(self):
-        self.flat.zero_()
+    def reset_step(self, rows):
+        """The per-step state back to where a step starts.  rows: the gradient rows are zero-filled as well -- False for a
+        caller that knows them zero (the streamed exchange's packs cleared them): then only seen counts that somebody marked
+        are zero-filled, and nothing else of the bucket's size is touched."""
+        if rows:
+            self.flat.zero_()
         self._seen_pending = []
-        self._seen.zero_()
+        if rows or (self.track_seen and self._seen_dirty):
+            self._seen.zero_()
         self._seen_reduced = False
         self._seen_dirty = False
         self.touched = None
         self._take_hint()
+
+    def zero(self):
+        self.reset_step(rows=True)
 
     def mark_seen(self, radii, index=None, defer=False):
         """Record which rows one view touched: radii > 0 (what the reference's step calls flag_vis,
@@ -427,12 +444,9 @@ class GradientBucket(_Flat):
             return
         self._flush_seen()
         if fast:
-            import ctypes
-            from . import _lib
+            check, L, ptr, stream_ptr = _native()
             with torch.cuda.device(radii.device):
-                _lib.check(_lib.lib().lograst_add_visible(
-                    ctypes.c_void_p(self._seen.data_ptr()), ctypes.c_void_p(radii.data_ptr()), int(radii.numel()),
-                    ctypes.c_void_p(torch.cuda.current_stream(radii.device).cuda_stream)))
+                check(L.lograst_add_visible(ptr(self._seen), ptr(radii), int(radii.numel()), stream_ptr(radii.device)))
             return
         vis = (radii > 0).to(torch.float32)
         if index is None:
@@ -447,16 +461,13 @@ class GradientBucket(_Flat):
         the view did not touch (94 % of them at the 30 M headline).  A second call before the bucket is exchanged (several
         views in one group) withdraws the hint: the pack scans the rows themselves, as without it.  The tensor must stay
         alive and unchanged until the exchange of this bucket has run."""
-        if getattr(self, "_hint_calls", 0) == 0 and point_weight is not None and point_weight.dim() == 1 \
-                and point_weight.element_size() == 4 and point_weight.is_contiguous():
-            self.touch_hint = point_weight
-        else:
-            self.touch_hint = None
-        self._hint_calls = getattr(self, "_hint_calls", 0) + 1
+        usable = self._hint_calls == 0 and point_weight is not None and point_weight.dim() == 1 \
+            and point_weight.element_size() == 4 and point_weight.is_contiguous()
+        self.touch_hint = point_weight if usable else None
+        self._hint_calls += 1
 
     def _take_hint(self):
-        h = getattr(self, "touch_hint", None)
-        self.touch_hint, self._hint_calls = None, 0
+        h, self.touch_hint, self._hint_calls = self.touch_hint, None, 0
         return h
 
     def _sum_seen(self, group):
@@ -469,14 +480,8 @@ class GradientBucket(_Flat):
         if not _active(self.world):
             return self.flat
         self._sum_seen(group)
-        if dist.get_backend(group) == "gloo":
-            # gloo has no reduce_scatter_tensor: same result via all_reduce (CPU tests only)
-            dist.all_reduce(self.flat, op=dist.ReduceOp.SUM, group=group)
-            return self.flat
         mine = torch.empty(self.flat.numel() // self.world, dtype=self.flat.dtype, device=self.flat.device)
-        dist.reduce_scatter_tensor(mine, self.flat, op=dist.ReduceOp.SUM, group=group)
-        dist.all_gather_into_tensor(self.flat, mine, group=group)
-        return self.flat
+        return _all_gather(self.flat, _reduce_scatter(mine, self.flat, group), group)
 
     def touched_blocks(self, group=None, kmax=None):
         """The step's TouchedBlocks: local `seen` per block, max-reduced over the ranks (world * nb int32: tiny).
@@ -493,68 +498,76 @@ class GradientBucket(_Flat):
         """Share of this rank's rows with a non-zero gradient (row-major buckets; a device scalar)."""
         return (self.blocks["rows"].view(self.Ppad, ROW_FLOATS) != 0).any(dim=1).float().mean()
 
+    def _own_rows(self, seen=True):
+        """What every exchange form delivers in a world without a process group: this rank's own rows of every column
+        block and (seen) its own seen counts -- views of the bucket, nothing moves."""
+        out = {name: self.rows(name, 0) for name, _ in self.layout}
+        if seen and self.track_seen:
+            out["seen"] = self.seen[:self.Pr]
+        return out
+
+    def _seen_shard(self, counts, group, into=None):
+        """The seen counts' exchange: `counts` [P_pad] -> [Pr], this rank's rows of their sum over the ranks -- a dense
+        reduce-scatter (4 bytes per row, dense by nature: every visible row counts); without a process group the local
+        slice.  Added to the running sums `into`, or returned fresh."""
+        active = _active(self.world)
+        if active:
+            mine = _reduce_scatter(torch.empty(self.Pr, dtype=torch.float32, device=counts.device), counts, group)
+        else:
+            mine = counts[:self.Pr]
+        if into is not None:
+            into += mine
+            return into
+        return mine if active else mine.clone()      # (fresh: never a view of a bucket's own counts, which a reset zeroes)
+
     def reduce_scatter_rows_sparse(self, rank, group=None, kmax=None, into=None, clear=False, seen_later=False):
         """Row-sparse form of ``reduce_scatter_rows`` (row-major buckets without SH columns): -> the same dict -- "rows"
         [Pr, 16] = the sum over ranks of this rank's rows, "seen" [Pr] -- but only the rows with a non-zero gradient
         travel: packed per owner as (16 sums | row index), padded to `kmax` rows per (sender, owner) pair, one all-to-all
-        with equal splits; the owner adds what it receives into a zeroed shard.  The seen counts (4 bytes per row, dense
-        by nature: every visible row counts) keep their dense reduce-scatter.
-        kmax=None: the longest list over all pairs of the whole job, exactly (one max-reduce + one read-back); kmax=K: a
-        bound kept from an earlier step, no read-back; ``self.sparse_overflow`` (device flag, summed into
+        with equal splits; the owner adds what it receives into a zeroed shard.  The seen counts keep their dense
+        reduce-scatter (``_seen_shard``).
+        kmax=None: the longest list over all pairs of the whole job, exactly (``_row_bound``); kmax=K: a bound kept from an
+        earlier step, no read-back; ``self.sparse_overflow`` (device flag, summed into
         ``StepExchange.compact_overflowed()``) says if some list was longer -- rows were dropped, repeat the step.
         Same addends as the dense form, summed in rank order -- ((r0 + r1) + r2) + ... -- instead of ring order: on the
         device lograst_unpack_rows adds the received segments one after the other with plain read-modify-writes (rows inside
-        a segment are unique; no float atomics since round 5), on the CPU index_add_ walks them in the same order, so the
-        reduced gradients are reproducible run to run on any number of ranks.
-        into (round 6, the STREAMED exchange of ``StepExchange(parts > 1)``): a dict {"rows": [Pr, 16](, "seen": [Pr])} of
-        running sums that this group's received rows (and seen counts) are ADDED to instead of a fresh zeroed shard -- the
-        step's shard then holds, row by row, (((0 + g0) + g1) + ...) with every g = ((r0 + r1) + ...) added segment by
-        segment.  clear: the rows this call packs are zeroed in the bucket ("pack and clear"): the bucket is all zero again
-        and needs no zero-fill before the next step (unless a bound was outgrown: then zero() and repeat the step).
+        a segment are unique: no float atomics), on the CPU index_add_ walks them in the same order, so the reduced
+        gradients are reproducible run to run on any number of ranks.
+        into (the STREAMED exchange of ``StepExchange(parts > 1)``): a dict {"rows": [Pr, 16](, "seen": [Pr])} of running
+        sums that this group's received rows (and seen counts) are ADDED to instead of a fresh zeroed shard -- the step's
+        shard then holds, row by row, (((0 + g0) + g1) + ...) with every g = ((r0 + r1) + ...) added segment by segment.
+        clear: the rows this call packs are zeroed in the bucket ("pack and clear"): the bucket is all zero again and needs
+        no zero-fill before the next step (unless a bound was outgrown: then zero() and repeat the step).
         seen_later: the seen counts are NOT exchanged here (StepExchange's streamed form sends them once per step, from
-        finish(): a dense 4-byte-per-row reduce-scatter per GROUP moved as many bytes as the packed rows themselves).
+        finish(): a dense 4-byte-per-row reduce-scatter per GROUP moves as many bytes as the packed rows themselves).
         A hint left by ``mark_touched`` is consumed by this call."""
         assert self.row_major and [n for n, _ in self.layout] == ["rows"], "row-sparse exchange: row-major bucket without SH columns"
         self.touched = None
-        dev, W, Pr = self.flat.device, self.world, self.Pr
-        out = {}
-        if not _active(self.world):
-            self._take_hint()
-            self.sparse_overflow, self.sparse_kmax = None, 0
-            if into is not None:           # world 1, streamed: the group's rows join the running sums, the bucket is cleared
-                into["rows"] += self.rows("rows", 0)
-                if clear:
-                    self.rows("rows", 0).zero_()
-                if self.track_seen and not seen_later:      # (seen_later: finish() sums the marked buckets once per step)
-                    into["seen"] += self.seen[:self.Pr]
-                return into
-            out["rows"] = self.rows("rows", 0)
-            if self.track_seen:
-                out["seen"] = self.seen[:self.Pr]
-            return out
-        rows = self.blocks["rows"].view(W, Pr, ROW_FLOATS)
-        if kmax is None:
-            cnt = (rows != 0).any(dim=2).sum(1).max().reshape(1)
-            dist.all_reduce(cnt, op=dist.ReduceOp.MAX, group=group)
-            kmax = max(int(cnt.item()), 1)
-        kmax = min(max(int(kmax), 1), Pr)
         hint = self._take_hint()
+        with_seen = self.track_seen and not seen_later
+        if not _active(self.world):
+            self.sparse_overflow, self.sparse_kmax = None, 0
+            if into is None:
+                return self._own_rows()
+            own = self.rows("rows", 0)             # streamed: the group's rows join the running sums, the bucket is cleared
+            into["rows"] += own
+            if clear:
+                own.zero_()
+            if with_seen:
+                self._seen_shard(self.seen, group, into["seen"])
+            return into
+        rows = self.blocks["rows"].view(self.world, self.Pr, ROW_FLOATS)
+        kmax = _row_bound(rows, kmax, group)
         if hint is not None and hint.is_cuda:
             hint.record_stream(torch.cuda.current_stream(hint.device))      # (read here, possibly on a side stream)
-        packed, over = _pack_segments(rows, kmax, clear=clear, hint=hint)
+        packed, self.sparse_overflow = _pack_segments(rows, kmax, clear=clear, hint=hint)
+        self.sparse_kmax = kmax
         recv = torch.empty_like(packed)
         _all_to_all(recv, packed, group)
-        shard = into["rows"] if into is not None else torch.zeros(Pr, ROW_FLOATS, dtype=torch.float32, device=dev)
-        out["rows"] = _unpack_segments(shard, recv, W, kmax)
-        if self.track_seen and not seen_later:
-            mine = torch.empty(Pr, dtype=torch.float32, device=dev)
-            _reduce_scatter(mine, self.seen, group)
-            if into is not None:
-                into["seen"] += mine
-                out["seen"] = into["seen"]
-            else:
-                out["seen"] = mine
-        self.sparse_overflow, self.sparse_kmax = over, kmax
+        shard = into["rows"] if into is not None else torch.zeros(self.Pr, ROW_FLOATS, dtype=torch.float32, device=self.flat.device)
+        out = {"rows": _unpack_segments(shard, recv, self.world, kmax)}
+        if with_seen:
+            out["seen"] = self._seen_shard(self.seen, group, None if into is None else into["seen"])
         return out
 
     def _columns(self):
@@ -568,10 +581,7 @@ class GradientBucket(_Flat):
         block_rows > 0), the rest of the returned rows are zeros -- which is what their sum is."""
         self.touched = None
         if not _active(self.world):
-            out = {name: self.rows(name, 0) for name, _ in self.layout}
-            if self.track_seen:
-                out["seen"] = self.seen[:self.Pr]
-            return out
+            return self._own_rows()
         dev, out = self.flat.device, {}
         tb = self.touched_blocks(group, kmax=kmax) if compact and self.block_rows > 0 and self.track_seen else None
         if tb is not None and tb.fraction >= self.DENSE_ABOVE:
@@ -680,19 +690,19 @@ class StepExchange:
     bucket memory (30 M Gaussians x 14 columns: 1.7 GB each out of 288).  The sum is the same set of addends as one
     bucket's, grouped by part.
 
-    Round 6, the STREAMED row-sparse exchange (``launch(g, sparse=True)`` with parts > 1; round-5 verdict, next #5): a dense
-    group exchange is as large as the whole step's, so grouping never paid for views that touch rows all over the model --
-    but ONE view's gradients live in 6 % of the rows against the 24 % of a rank's eight views (tools/touched_rows.py).  Per
-    group: the touched rows are packed per owner and CLEARED in the bucket (pack and clear: no bucket is ever zero-filled
-    again), one all-to-all moves them under the next group's rendering, and the owner adds them straight into the step's
-    ONE running shard -- no per-group dense shards, no sum in finish().  Exposed: the last group's all-to-all (1 / parts of
-    the rows a rank touches, counting rows several groups touch once per group) and the closing all-gather.  The sum of a row
-    is (((0 + g0) + g1) + ...), each g = ((r0 + r1) + ...): fixed by construction, reproducible on any number of ranks."""
+    The STREAMED row-sparse exchange (``launch(g, sparse=True)`` with parts > 1): a dense group exchange is as large as the
+    whole step's, so grouping does not pay for views that touch rows all over the model -- but ONE view's gradients live in
+    6 % of the rows against the 24 % of a rank's eight views (tools/touched_rows.py).  Per group: the touched rows are packed
+    per owner and CLEARED in the bucket (pack and clear: no bucket is ever zero-filled again), one all-to-all moves them
+    under the next group's rendering, and the owner adds them straight into the step's ONE running shard -- no per-group
+    dense shards, no sum in finish().  Exposed: the last group's all-to-all (1 / parts of the rows a rank touches, counting
+    rows several groups touch once per group) and the closing all-gather.  The sum of a row is (((0 + g0) + g1) + ...),
+    each g = ((r0 + r1) + ...): fixed by construction, reproducible on any number of ranks."""
 
     def __init__(self, num_points, device, world=1, rank=0, sh_coeffs=0, parts=1, block_rows=0, group=None,
                  track_seen=True, timing=False, row_major=False):
-        """timing: record device events around every collective and around the join in finish(), so that a run reports
-        how much of the exchange ran under the rendering and how much was exposed (``timing_summary``)."""
+        """timing: a pair of device events brackets every collective and the join in finish(), so that a run reports how
+        much of the exchange ran under the rendering and how much was exposed (``timing_summary``)."""
         self.world, self.rank, self.parts, self.group = max(int(world), 1), int(rank), max(int(parts), 1), group
         self._timing = bool(timing)
         self._ev = {"reduce_scatter": [], "join": [], "all_gather": []}
@@ -703,11 +713,12 @@ class StepExchange:
         self._shards = [None] * self.parts
         self.touched = None
         # device flag: a bounded touched-block / row-sparse exchange dropped rows (compact_overflowed).  ONE persistent
-        # tensor, OR-ed in place on the stream that produced the addend (round-4 advisory: a fresh `a | b` issued on the
-        # compute stream read a side-stream temporary without waiting for it, after its block had gone back to the pool)
+        # tensor, OR-ed in place on the stream that produced the addend (a fresh `a | b` issued on the compute stream would
+        # read a side-stream temporary without waiting for it, after its block has gone back to the pool)
         self._overflow = torch.zeros((), dtype=torch.bool, device=self.device)
         self._overflow_used = False
-        self.gather_kmax = 0
+        self.gather_kmax = 0           # rows per owner of the last row-sparse all_gather_grads
+        self._gathered_prev = None     # (result tensor, received segments, rows per owner) of the last all_gather_grads(into=...)
         self._stream_shard = None      # the streamed sparse exchange's running sums of this step (launch(sparse=True), parts > 1)
         self.streamed = False          # the last step's sparse launches were streamed: buckets cleared by their own packs
 
@@ -724,45 +735,35 @@ class StepExchange:
     def last_view_of(self, part, n_views):
         return max(v for v in range(n_views) if self.bucket_of(v, n_views) is self.buckets[part])
 
-    def zero(self):
+    def _reset_step(self, rows):
         for b in self.buckets:
-            b.zero()
+            b.reset_step(rows)
         self._shards = [None] * self.parts
         self.touched = None
         self._stream_shard = None
+
+    def zero(self):
+        self._reset_step(rows=True)
 
     def begin_step(self):
         """Between steps of the STREAMED sparse exchange: the buckets' rows were cleared by their own packs, so only the
-        small per-step state is reset (seen counts, shard list) -- instead of zero()'s full zero-fill of every bucket."""
-        for b in self.buckets:
-            b._seen_pending = []
-            if b.track_seen and getattr(b, "_seen_dirty", True):       # (only the counts somebody marked since the last reset)
-                b._seen.zero_()
-            b._seen_dirty = False
-            b.touched = None
-            b._take_hint()
-        self._shards = [None] * self.parts
-        self.touched = None
-        self._stream_shard = None
+        small per-step state is reset (the seen counts somebody marked, the shard list) -- instead of zero()'s full
+        zero-fill of every bucket."""
+        self._reset_step(rows=False)
 
+    @contextlib.contextmanager
     def _timed(self, kind, stream):
-        """Context manager: a pair of timing events on `stream` around the block (no-op unless timing on a HIP device)."""
-        ex = self
-
-        class _T:
-            def __enter__(self_t):
-                self_t.on = ex._timing and ex.device.type == "cuda"
-                if self_t.on:
-                    self_t.a = torch.cuda.Event(enable_timing=True)
-                    self_t.b = torch.cuda.Event(enable_timing=True)
-                    self_t.a.record(stream)
-
-            def __exit__(self_t, *exc):
-                if self_t.on:
-                    self_t.b.record(stream)
-                    ex._ev[kind].append((self_t.a, self_t.b))
-                return False
-        return _T()
+        """A pair of timing events on `stream` bracketing the block (nothing unless timing on a HIP device)."""
+        if not (self._timing and self.device.type == "cuda"):
+            yield
+            return
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(stream)
+        try:
+            yield
+        finally:
+            b.record(stream)
+            self._ev[kind].append((a, b))
 
     def reset_timing(self):
         for v in self._ev.values():
@@ -785,32 +786,38 @@ class StepExchange:
         ``GradientBucket.reduce_scatter_rows_sparse``); check ``compact_overflowed()`` where the step synchronises anyway.
         sparse: the row-sparse form (only rows with a non-zero gradient travel)."""
         b = self.buckets[part]
-        stream_it = bool(sparse) and self.parts > 1
-        self.streamed = stream_it
-
-        def run_streamed():
-            if self._stream_shard is None:         # first group of the step: the running sums start at zero
-                sh = {"rows": torch.zeros(b.Pr, ROW_FLOATS, dtype=torch.float32, device=self.device)}
-                if b.track_seen:
-                    sh["seen"] = torch.zeros(b.Pr, dtype=torch.float32, device=self.device)
-                self._stream_shard = sh
-            b.reduce_scatter_rows_sparse(self.rank, self.group, kmax=kmax, into=self._stream_shard, clear=True, seen_later=True)
-            return self._stream_shard
-        run = (run_streamed if stream_it else
-               (lambda: b.reduce_scatter_rows_sparse(self.rank, self.group, kmax=kmax)) if sparse else
-               (lambda: b.reduce_scatter_rows(self.rank, self.group, compact=compact, kmax=kmax)))
-        def run_and_note():
-            self._shards[part] = run()
-            over = getattr(b, "sparse_overflow", None) if sparse else (b.touched.overflow if b.touched is not None else None)
+        self.streamed = bool(sparse) and self.parts > 1
+        form = self._streamed_form if self.streamed else self._sparse_form if sparse else self._dense_form
+        with self._on_side_stream("reduce_scatter"):
+            self._shards[part], over = form(b, compact, kmax)
             self._note_overflow(over)       # on the stream that wrote `over`: in order behind its producer
 
+    # the exchange forms of launch(): -> (this rank's shard of bucket `b`, the device flag of an outgrown bound or None)
+    def _dense_form(self, b, compact, kmax):
+        shard = b.reduce_scatter_rows(self.rank, self.group, compact=compact, kmax=kmax)
+        return shard, None if b.touched is None else b.touched.overflow
+
+    def _sparse_form(self, b, compact, kmax):
+        return b.reduce_scatter_rows_sparse(self.rank, self.group, kmax=kmax), b.sparse_overflow
+
+    def _streamed_form(self, b, compact, kmax):
+        if self._stream_shard is None:             # first group of the step: the running sums start at zero
+            self._stream_shard = {"rows": torch.zeros(b.Pr, ROW_FLOATS, dtype=torch.float32, device=self.device)}
+            if b.track_seen:
+                self._stream_shard["seen"] = torch.zeros(b.Pr, dtype=torch.float32, device=self.device)
+        b.reduce_scatter_rows_sparse(self.rank, self.group, kmax=kmax, into=self._stream_shard, clear=True, seen_later=True)
+        return self._stream_shard, b.sparse_overflow
+
+    @contextlib.contextmanager
+    def _on_side_stream(self, kind):
+        """The block is issued on the side stream, behind the compute stream's work so far, between timing events of
+        `kind` (no side stream: where it stands)."""
         if self.side is None:
-            run_and_note()
-        else:
-            self.side.wait_stream(torch.cuda.current_stream(self.device))
-            with torch.cuda.stream(self.side):
-                with self._timed("reduce_scatter", self.side):
-                    run_and_note()
+            yield
+            return
+        self.side.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(self.side), self._timed(kind, self.side):
+            yield
 
     def _note_overflow(self, over):
         """OR a device flag into the step's persistent overflow flag, on the CURRENT stream (the caller issues this on the
@@ -848,16 +855,10 @@ class StepExchange:
             # streamed sparse exchange: the groups' rows were added as they arrived; the step's seen counts travel ONCE, now
             # (the sum over the buckets somebody marked: callers that mark one bucket for the whole step -- seen_bucket() --
             # pay one reduce-scatter of 4 bytes per row per step instead of one per group)
-            b0 = self.buckets[0]
-            if b0.track_seen:
-                dirty = [b.seen for b in self.buckets if getattr(b, "_seen_dirty", False)]
-                if dirty:
-                    acc = dirty[0] if len(dirty) == 1 else torch.stack(dirty).sum(0)
-                    if _active(self.world):
-                        mine = torch.empty(b0.Pr, dtype=torch.float32, device=self.device)
-                        self._stream_shard["seen"] = _reduce_scatter(mine, acc, self.group)
-                    else:                  # one rank, no collective: the local sum (a copy: begin_step() zeroes the buckets')
-                        self._stream_shard["seen"] = acc[:b0.Pr].clone()
+            dirty = [b.seen for b in self.buckets if b._seen_dirty]
+            if dirty:
+                acc = dirty[0] if len(dirty) == 1 else torch.stack(dirty).sum(0)
+                self._stream_shard["seen"] = self.buckets[0]._seen_shard(acc, self.group)
             return dict(self._stream_shard)
         total = dict(self._shards[0])
         if self.parts > 1:
@@ -886,21 +887,16 @@ class StepExchange:
         exchange's next step."""
         b0 = self.buckets[0]
         if not _active(self.world):
-            for name, _ in b0.layout:
-                b0.rows(name, 0).copy_(total[name])
+            for name, own in b0._own_rows(seen=False).items():
+                own.copy_(total[name])
             return b0.flat
+        main = torch.cuda.current_stream(self.device) if self.device.type == "cuda" else None
         if sparse_kmax is not None and "rows" in total:
-            # (only the "rows" block travels here: SH columns would silently stay un-gathered -- round-4 advisory)
+            # (only the "rows" block travels here: SH columns would silently stay un-gathered)
             assert [n for n, _ in b0.layout] == ["rows"], "row-sparse all-gather: row-major bucket without SH columns"
-            main = torch.cuda.current_stream(self.device) if self.device.type == "cuda" else None
             with self._timed("all_gather", main):
                 shard = total["rows"].reshape(1, b0.Pr, ROW_FLOATS)
-                k = sparse_kmax
-                if not k or k == "exact":
-                    cnt = (shard != 0).any(dim=2).sum().reshape(1)
-                    dist.all_reduce(cnt, op=dist.ReduceOp.MAX, group=self.group)
-                    k = max(int(cnt.item()), 1)
-                k = min(int(k), b0.Pr)
+                k = _row_bound(shard, None if not sparse_kmax or sparse_kmax == "exact" else sparse_kmax, self.group)
                 packed, over = _pack_segments(shard.contiguous(), k)
                 recv = torch.empty(self.world * packed.numel(), dtype=torch.float32, device=self.device)
                 _all_gather(recv, packed, self.group)
@@ -912,7 +908,7 @@ class StepExchange:
                 else:
                     full = into.view(-1)
                     assert full.numel() == self.world * b0.Pr * ROW_FLOATS and full.is_contiguous()
-                    prev = getattr(self, "_gathered_prev", None)
+                    prev = self._gathered_prev
                     if prev is not None and prev[0] is into:
                         _unpack_segments(full.view(self.world * b0.Pr, ROW_FLOATS), prev[1], self.world, prev[2],
                                          per_segment_rows=b0.Pr, zero=True)
@@ -921,7 +917,6 @@ class StepExchange:
                     self._gathered_prev = (into, recv, k)
                 _unpack_segments(full.view(self.world * b0.Pr, ROW_FLOATS), recv, self.world, k, per_segment_rows=b0.Pr)
             return b0.flat if into is None else into
-        main = torch.cuda.current_stream(self.device) if self.device.type == "cuda" else None
         with self._timed("all_gather", main):
             for name, c in b0.layout:
                 _all_gather(b0.blocks[name], total[name].reshape(-1), self.group)
@@ -933,16 +928,15 @@ class StepExchange:
 # in the projection kernel, so a rank bins, sorts and composites only what reaches its rows); no compositing across
 # ranks is needed.  Exchange per view: an all-gather of the bands (3 * H * W * 4 bytes in total) and the same gradient
 # sum as above.
-TILE = 16
-
-
 def band_rows(rank, world, height):
     """Tile rows [begin, end) owned by `rank`: contiguous, sizes differing by at most one row of tiles."""
+    from .rasterizer import TILE
     gy = (int(height) + TILE - 1) // TILE
     return rank * gy // world, (rank + 1) * gy // world
 
 
 def band_pixels(rank, world, height):
+    from .rasterizer import TILE
     b, e = band_rows(rank, world, height)
     return b * TILE, min(e * TILE, int(height))
 

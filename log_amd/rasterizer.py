@@ -376,9 +376,12 @@ def _knob(name):
     return val.value
 
 
+TILE = 16     # pixels per tile side (log_amd/csrc: the binning, compositing and band kernels)
+
+
 def _tiles(width, height):
-    """How many 16 x 16 tiles cover a width x height image."""
-    return ((int(width) + 15) // 16) * ((int(height) + 15) // 16)
+    """How many TILE x TILE tiles cover a width x height image."""
+    return ((int(width) + TILE - 1) // TILE) * ((int(height) + TILE - 1) // TILE)
 
 
 # Blocks carved out of one allocation are read / written in lock step by one kernel; starting them at multiples of

@@ -438,7 +438,7 @@ def _sparse_worker(rank, world, port, out):
             total = ex.finish()
             flat = ex.all_gather_grads(total, **kw_ag)
             res[mode] = dict(rows=total["rows"].clone(), seen=total["seen"].clone(), full=ex.buckets[0].views["rows"].clone(),
-                             over=ex.compact_overflowed(), kmax=getattr(ex.buckets[0], "sparse_kmax", 0), gk=ex.gather_kmax)
+                             over=ex.compact_overflowed(), kmax=ex.buckets[0].sparse_kmax, gk=ex.gather_kmax)
         # non-integer gradients (round-4 verdict, next #7): the row-sparse sum is the RANK-ORDERED sum ((r0 + r1) + r2)
         # of every group, bit for bit -- the test rebuilds it from the ranks' own buckets
         ex = StepExchange(P, "cpu", world, rank, parts=2, row_major=True)
@@ -454,46 +454,12 @@ def _sparse_worker(rank, world, port, out):
         ex.all_gather_grads(total, sparse_kmax="exact")
         res["float"] = dict(local=local, rows=total["rows"].clone(), full=ex.buckets[0].blocks["rows"].clone(),
                             Pr=ex.buckets[0].Pr, over=ex.compact_overflowed(), cleared=cleared, streamed=ex.streamed)
-        # round 6: the STREAMED exchange, one group per view (parts = 8), against ONE group holding the sum of the same eight
-        # views (integer-valued gradients: exact in any order, so the two must agree bit for bit), sized exactly and from bounds
-        per_view = []
-        for v in range(8):
-            gen = torch.Generator().manual_seed(5000 + 100 * rank + v)
-            touched = torch.randperm(P, generator=gen)[:60]                      # 6 % of the rows per view, overlapping between views
-            per_view.append((touched, torch.randint(-8, 9, (60, 14), generator=gen).float(),
-                             (torch.rand(P, generator=gen) < 0.3).to(torch.int32)))
-        for mode, parts, kw_rs, kw_ag in (("one_group", 1, dict(sparse=True), dict(sparse_kmax="exact")),
-                                          ("stream8", 8, dict(sparse=True), dict(sparse_kmax="exact")),
-                                          ("stream8_bound", 8, dict(sparse=True, kmax=64), dict(sparse_kmax=500)),
-                                          # each view's bucket packed from a HINT (the view's point_weight stand-in: non-zero
-                                          # exactly at the rows it touched) and the seen counts marked in ONE bucket for the step
-                                          ("stream8_hint", 8, dict(sparse=True), dict(sparse_kmax="exact"))):
-            ex = StepExchange(P, "cpu", world, rank, parts=parts, row_major=True)
-            result = torch.full((world * ex.buckets[0].Pr, 16), float("nan")) if parts > 1 else None   # (the first gather zero-fills it)
-            for step in range(2):                                                # two steps: the second one starts from begin_step(), no zero()
-                if step:
-                    ex.begin_step()
-                for v, (touched, vals, seen) in enumerate(per_view):
-                    b = ex.bucket_of(v, 8)
-                    b.views["rows"][touched, :14] += vals * (step + 1)
-                    if mode == "stream8_hint":
-                        hint = torch.zeros(P)
-                        hint[touched] = 0.25
-                        b.mark_touched(hint)
-                        ex.seen_bucket(ex.buckets.index(b), True).mark_seen(seen)
-                    else:
-                        b.mark_seen(seen)
-                    if v == ex.last_view_of(ex.buckets.index(b), 8):
-                        ex.launch(ex.buckets.index(b), **kw_rs)
-                total = ex.finish()
-                left = [float(b.blocks["rows"].abs().sum()) for b in ex.buckets]
-                ex.all_gather_grads(total, into=result, **kw_ag)                 # (streamed: a persistent result, bucket 0 stays clean)
-                full = ex.buckets[0].blocks["rows"].clone() if result is None else result.reshape(-1).clone()
-                after = [float(b.blocks["rows"].abs().sum()) for b in ex.buckets]
-                res["%s_step%d" % (mode, step)] = dict(rows=total["rows"].clone(), seen=total["seen"].clone(), full=full, left=left,
-                                                       after=after, over=ex.compact_overflowed(), streamed=ex.streamed)
-                if parts == 1:
-                    ex.zero()                                                    # (the one-group form keeps its sums: zero-filled as before)
+        # the STREAMED exchange, one group per view (parts = 8), against ONE group holding the sum of the same eight views
+        # (integer-valued gradients: exact in any order, so the two must agree bit for bit), sized exactly and from bounds
+        from dist_util import STREAMED_MODES, streamed_steps, streamed_views
+        per_view = streamed_views(rank, P)
+        for mode, parts, kw_rs, kw_ag in STREAMED_MODES:
+            res.update(streamed_steps(mode, parts, kw_rs, kw_ag, per_view, "cpu", world, rank, P=P))
         torch.save(res, os.path.join(out, f"s{rank}.pt"))
     finally:
         dist.destroy_process_group()
@@ -565,6 +531,23 @@ def test_one_rank_streamed_exchange_keeps_every_seen_count(parts, streamed):
         assert np.array_equal(seen[:P].numpy().astype(np.int64), want_seen), (step, int(seen.sum()), int(want_seen.sum()))
         assert float(seen[P:].sum()) == 0.0
         assert torch.equal(rows, want_rows), step
+
+
+def test_fresh_exchange_has_all_its_state():
+    """Before any launch an exchange and a bucket hold every field their methods and callers read: nothing overflowed, both
+    resets run, and finish() on an untouched exchange returns all-zero rows and seen counts."""
+    from log_amd.dist import StepExchange
+    ex = StepExchange(1003, "cpu", world=1, parts=3, row_major=True)
+    for b in ex.buckets + [GradientBucket(1003, "cpu", world=1, row_major=True)]:
+        assert b.sparse_kmax == 0 and b.sparse_overflow is None and b.touch_hint is None and b.touched is None
+    assert ex.gather_kmax == 0 and ex.streamed is False and ex.touched is None
+    assert ex.compact_overflowed() is False
+    ex.begin_step()
+    ex.zero()
+    total = ex.finish()
+    assert total["rows"].shape == (ex.buckets[0].Pr, 16) and total["seen"].shape == (ex.buckets[0].Pr,)
+    assert float(total["rows"].abs().sum()) == 0.0 and float(total["seen"].abs().sum()) == 0.0
+    assert ex.compact_overflowed() is False
 
 
 def test_mark_seen_rejects_more_radii_than_rows():

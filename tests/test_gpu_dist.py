@@ -258,6 +258,71 @@ def test_step_exchange_one_rank_over_rccl(tmp_path, mode):
     assert torch.equal(got["seen"][:rows.numel()], rows)
 
 
+def _streamed_worker(rank, world, port, out, backend):
+    """tests/test_dist_cpu.py's streamed row-sparse protocol (tests/dist_util.py) with the buckets on the device."""
+    import torch
+    import torch.distributed as dist
+    from dist_util import STREAMED_MODES, STREAMED_TOO_SMALL, streamed_steps, streamed_views
+    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
+    if backend == "nccl":                         # (one rank over RCCL: see _exchange_worker)
+        os.environ["LOGRAST_DIST_SINGLE_RANK"] = "1"
+        os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+        torch.cuda.set_device(0)
+        dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda:0"))
+    else:
+        dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        per_view, res = streamed_views(rank), {}
+        for mode, parts, kw_rs, kw_ag in STREAMED_MODES:
+            res.update(streamed_steps(mode, parts, kw_rs, kw_ag, per_view, "cuda:0", world, rank))
+        mode, parts, kw_rs, kw_ag = STREAMED_TOO_SMALL
+        res.update(streamed_steps(mode, parts, kw_rs, kw_ag, per_view, "cuda:0", world, rank, steps=1))
+        torch.cuda.synchronize()
+        torch.save(res, os.path.join(out, f"t{rank}.pt"))
+    finally:
+        dist.destroy_process_group()
+
+
+@pytest.mark.parametrize("backend,world", [("nccl", 1), ("gloo", 2)])
+def test_streamed_row_sparse_exchange_on_the_device(tmp_path, backend, world):
+    """The active row-sparse and streamed branches of log_amd/dist.py with device buckets (the device pack, pack and clear,
+    hinted pack, the all-to-all, the unpack into the running shard, the zeroing unpack of all_gather_grads(into=...)): eight
+    synthetic views of 60 rows over P = 1003 (padding rows live), integer-valued gradients, two steps of which the second
+    starts from begin_step().  One group per view -- sized exactly, from bounds, packed from hints with deferred seen
+    counts -- equals one group for all views bit for bit, and both equal plain torch sums; every bucket is all zero after a
+    streamed step; a bound of 4 rows is reported as outgrown.  One rank over RCCL (all_to_all_single and its neighbours),
+    and two ranks over gloo sharing the device (the all-gather fallback of the all-to-all)."""
+    import socket
+    import torch
+    import torch.multiprocessing as mp
+    from dist_util import streamed_plain_sums
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
+    mp.spawn(_streamed_worker, args=(world, port, str(tmp_path), backend), nprocs=world, join=True)
+    got = [torch.load(os.path.join(tmp_path, f"t{r}.pt")) for r in range(world)]
+    for step in range(2):
+        want_rows, want_seen = streamed_plain_sums(world, step)
+        Pr = want_rows.shape[0] // world
+        assert float(want_rows.abs().sum()) > 0 and float(want_seen.sum()) > 0.25 * 8 * 1003 * world
+        for r in range(world):
+            one = got[r]["one_group_step%d" % step]
+            assert not one["over"] and not one["streamed"]
+            assert torch.equal(one["rows"], want_rows[r * Pr:(r + 1) * Pr]), (r, step)
+            assert torch.equal(one["seen"], want_seen[r * Pr:(r + 1) * Pr]), (r, step)
+            assert torch.equal(one["full"], want_rows.reshape(-1)), (r, step)
+            for mode in ("stream8", "stream8_bound", "stream8_hint"):
+                m = got[r]["%s_step%d" % (mode, step)]
+                assert m["streamed"] and not m["over"], (r, mode, step)
+                assert m["left"] == [0.0] * 8 and m["after"] == [0.0] * 8, (mode, m["left"], m["after"])
+                assert torch.equal(m["rows"], one["rows"]) and torch.equal(m["seen"], one["seen"]), (r, mode, step)
+                assert torch.equal(m["full"], one["full"]), (r, mode, step)
+                assert torch.equal(m["full"], got[0]["%s_step%d" % (mode, step)]["full"]), (r, mode, step)
+    for r in range(world):
+        small = got[r]["stream8_small_step0"]
+        assert small["streamed"] and small["over"] is True, r
+
+
 def test_bench_one_rank_over_rccl():
     """bench.py's multi-GPU step (view groups, the exchange on the side stream, the closing all-gather) through a one-rank
     RCCL group, dense and row-sparse (streamed): it runs, reports the exchange, and raises no overflow."""
