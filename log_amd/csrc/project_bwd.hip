@@ -130,7 +130,8 @@ template <bool ACCUMULATE, bool COV, bool AOS, bool SINKROWS>
 // 30 M-row launch 402 -> 477 us.)
 LR_DEV void lr_pbwd_live_row(const LrView& v, int i, const float* means, const float* scales, const float* rots,
                              const float* g_mean2d, const float* g_conic, const float4* rows, float* o_mean2d,
-                             float* o_opac, float* o_col, float* g_means3d, float* g_scales, float* g_rots) {
+                             float* o_opac, float* o_col, float* g_means3d, float* g_scales, float* g_rots,
+                             float* m2d_slice = nullptr, int slice_base = 0, bool staged = false) {
     float gm[3], gs[3] = {0.f, 0.f, 0.f}, gq[4] = {0.f, 0.f, 0.f, 0.f};
     float gnx, gny, gA, gB, gC;
     // running sums (ACCUMULATE): every old value is requested up front, next to the row's inputs -- the row is a chain of
@@ -159,7 +160,12 @@ LR_DEV void lr_pbwd_live_row(const LrView& v, int i, const float* means, const f
       const float4 a0 = rows[4 * (size_t)i], a1 = rows[4 * (size_t)i + 1];
       const float cb = reinterpret_cast<const float*>(rows + 4 * (size_t)i + 2)[0];
       gnx = a0.x; gny = a0.y; gA = a0.z; gB = a0.w; gC = a1.x;
-      o_mean2d[3 * (size_t)i + 0] = gnx; o_mean2d[3 * (size_t)i + 1] = gny; o_mean2d[3 * (size_t)i + 2] = 0.f;
+      if (staged) {   // the workgroup's slice of dL/dmeans2D sits in LDS and leaves as whole lines (lr_project_bwd_kernel)
+        float* const o = m2d_slice + 3 * (i - slice_base);
+        o[0] = gnx; o[1] = gny; o[2] = 0.f;
+      } else {
+        o_mean2d[3 * (size_t)i + 0] = gnx; o_mean2d[3 * (size_t)i + 1] = gny; o_mean2d[3 * (size_t)i + 2] = 0.f;
+      }
       if (SINKROWS) {
         sr2.z += a1.y; sr2.w += a1.z; sr3.x += a1.w; sr3.y += cb;   // slots 10 opacity, 11-13 colour
       } else {
@@ -215,7 +221,8 @@ LR_DEV void lr_pbwd_live_row(const LrView& v, int i, const float* means, const f
 // Gaussians, running sums / fresh gradients: default 374 / 736 us, 4 waves (128 VGPRs, no scratch) 391 / 865, 5 (spills)
 // 473 / 877, 6: 518 / 918 -- more resident workgroups make the scattered rows' traffic worse, not better.  A band view
 // (nearly all flag pass: a fraction of a percent of 100 M rows is live) gains from four: 738 -> 638 us -- the row-major
-// sink's kernel exists in both forms and band views launch the second.
+// sink's kernel exists in both forms and band views launch the second (unless they take the compact-list form below, the
+// default; the current compiler spills 10 VGPRs in it, 22 before the staged slice: profiles/chain_rule_dmeans2d_lines.md).
 template <bool ACCUMULATE, bool TOUCHED, bool COV, bool AOS, bool SINKROWS = false, int WAVES = 1>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES)))
 lr_project_bwd_kernel(LrView v, int N, const float* __restrict__ means, const float* __restrict__ scales,
@@ -227,6 +234,18 @@ lr_project_bwd_kernel(LrView v, int N, const float* __restrict__ means, const fl
                       float* __restrict__ g_rots, int clear_inside) {
   __shared__ uint32_t live_list[LR_PBWD_ROWS];
   __shared__ uint32_t live_count;
+  // STAGE (the instantiations the large-input running-sum route launches; taken when clear_inside == 0): the workgroup's
+  // slice of dL/dmeans2D -- 1024 rows x 12 bytes = 12 288 contiguous bytes, a multiple of 64 -- is built in LDS (zeros,
+  // then the live rows' values) and leaves with 16-byte stores that cover whole 64-byte lines.  The memory side charges
+  // write transactions, a partial line as much as a full one: before, lr_zero_floats_kernel streamed the array's zeros in a
+  // launch of its own and every live row then re-opened one or two of those lines with a 12-byte store.  Measured, 30 M rows
+  // (profiles/chain_rule_dmeans2d_lines.md): the kernel itself 344 -> 352 us WITH the array's 360 MB, the 66 us zero pass
+  // gone (the stage 432 -> 356 us; opacity = rand 642 -> 507); scattered write requests per live row 1.80 -> 0.92.  LDS per
+  // workgroup 4 -> 16 KB (nine workgroups per CU by LDS, three by registers).  Handing the row's values out behind the chain
+  // rule instead of in front of it (no store between the row's gathers) cost 8 more VGPRs and 7-10 us: not kept.
+  constexpr bool STAGE = AOS && ACCUMULATE;
+  __shared__ __attribute__((aligned(16))) float m2d_slice[STAGE ? 3 * LR_PBWD_ROWS : 4];
+  const bool staged = STAGE && !clear_inside;
   const int tid = threadIdx.x, base = blockIdx.x * LR_PBWD_ROWS;
   if (tid == 0) live_count = 0u;
   // the live flags of the workgroup's rows, requested before anything else and all at once: most workgroups hold no live
@@ -242,13 +261,17 @@ lr_project_bwd_kernel(LrView v, int N, const float* __restrict__ means, const fl
     rad_k[k] = TOUCHED ? 1 : (i < N ? radii[i] : 0);
     pw_k[k] = (TOUCHED && i < N) ? pw[i] : 1.f;
   }
+  typedef float lr_f4v __attribute__((ext_vector_type(4)));
+  if (staged) {   // zeros for the whole slice, in LDS, while the flag loads are in flight (three 16-byte LDS stores per thread)
+#pragma unroll
+    for (int k = 0; k < 3 * LR_PBWD_ROWS / 4 / 256; k++)
+      reinterpret_cast<lr_f4v*>(m2d_slice)[k * 256 + tid] = lr_f4v{0.f, 0.f, 0.f, 0.f};
+  }
   if (AOS && clear_inside) {
     // the per-view / per-call outputs are defined for every row: the block's whole slice is cleared with full-width
     // stores first (row-by-row 12-byte stores from the flag pass below cost the 30 M view 0.2 ms), the live rows
-    // overwrite theirs after the barrier.  (On large inputs lr_zero_floats_kernel streams the zeros before this kernel
-    // runs: lr_launch_project_bwd.)
+    // overwrite theirs after the barrier.  (Large inputs with running sums take the staged form above instead.)
     const int rows_here = min(LR_PBWD_ROWS, N - base);
-    typedef float lr_f4v __attribute__((ext_vector_type(4)));
     // (a scalar head up to the first 16-byte boundary, then full-width stores, then a scalar tail: the C ABI asks only
     // for 4-byte alignment of these outputs -- round-4 advisory; torch's allocations always take the head-less path)
     auto clear = [&](float* p0, int floats) {
@@ -305,7 +328,33 @@ lr_project_bwd_kernel(LrView v, int N, const float* __restrict__ means, const fl
   const uint32_t n = live_count;
   for (uint32_t j = (uint32_t)tid; j < n; j += 256u)
     lr_pbwd_live_row<ACCUMULATE, COV, AOS, SINKROWS>(v, (int)live_list[j], means, scales, rots, g_mean2d, g_conic, rows,
-                                                     o_mean2d, o_opac, o_col, g_means3d, g_scales, g_rots);
+                                                     o_mean2d, o_opac, o_col, g_means3d, g_scales, g_rots,
+                                                     STAGE ? m2d_slice : nullptr, base, staged);
+  if (staged) {
+    // the slice leaves: every row of the block is defined here (zero unless live), 16 bytes per lane and 1 KB per wave and
+    // store instruction -- whole lines (three instructions for a full block); non-temporal like the zero pass it replaces
+    // (360 MB per 30 M-row view that nothing reads back soon).  The C ABI asks only for 4-byte alignment: then a scalar head
+    // up to the first 16-byte boundary and a scalar tail (the LDS side of the middle part reads four floats one by one);
+    // torch's allocations take the head-less path.
+    __syncthreads();
+    const int rows_here = min(LR_PBWD_ROWS, N - base);
+    float* const p0 = o_mean2d + 3 * (size_t)base;
+    int floats = 3 * rows_here;
+    const int head = min(floats, (int)(((16u - (uint32_t)(reinterpret_cast<uintptr_t>(p0) & 15u)) & 15u) >> 2));
+    if (tid < head) p0[tid] = m2d_slice[tid];
+    floats -= head;
+    const int n4 = floats >> 2;
+    lr_f4v* const q = reinterpret_cast<lr_f4v*>(p0 + head);
+    if (head == 0) {
+      for (int t = tid; t < n4; t += 256) __builtin_nontemporal_store(reinterpret_cast<const lr_f4v*>(m2d_slice)[t], q + t);
+    } else {
+      for (int t = tid; t < n4; t += 256) {
+        const float* const l = m2d_slice + head + 4 * t;
+        __builtin_nontemporal_store(lr_f4v{l[0], l[1], l[2], l[3]}, q + t);
+      }
+    }
+    for (int t = (n4 << 2) + tid; t < floats; t += 256) p0[head + t] = m2d_slice[head + t];
+  }
 }
 
 
@@ -394,12 +443,14 @@ void lr_launch_project_bwd(const LrView& v, int N, const float* means, const flo
   const dim3 grid((N + LR_PBWD_ROWS - 1) / LR_PBWD_ROWS), block(256);
   const float4* rows4 = reinterpret_cast<const float4*>(rows);
   // dL/dmeans2D is a per-view output, defined for every row.  When the other gradients are running sums (nothing else is
-  // written for a dead row) and the input is large, its zeros are streamed by lr_zero_floats_kernel (non-temporal 16-byte
-  // stores) in front of the chain rule instead of by its workgroups between their flag reads and their barrier: a band
-  // view of 100 M rows 1040 -> 730 us (with the radii read gone), the 30 M view unchanged (415 us).  With fresh gradients
-  // (every output zeroed for every dead row: 68 bytes per row) the same split LOSES (30 M: 763 -> 858 us): kept inside.
+  // written for a dead row) and the input is large (clear_inside == 0), the kernel's workgroups neither clear their slice
+  // between their flag reads and their barrier nor overwrite live rows with 12-byte stores: the slice is staged in LDS and
+  // leaves as whole lines (lr_project_bwd_kernel: STAGE) -- no zero pass in front of the kernel.  Only the compact-list
+  // form below, which has no per-block slice, still has lr_zero_floats_kernel stream the zeros first (non-temporal 16-byte
+  // stores; a band view of 100 M rows 1040 -> 730 us against clearing inside, with the radii read gone).  With fresh
+  // gradients (every output zeroed for every dead row: 68 bytes per row) a separate zero pass LOSES (30 M: 763 -> 858 us):
+  // cleared inside.
   const int clear_inside = (rows && (accumulate || sink_rows) && big_input) ? 0 : 1;
-  if (!clear_inside) lr_launch_zero_floats(o_mean2d, 3 * (size_t)N, s);
   // Large inputs, running sums, the forward's point_weight at hand, no cov3d_precomp: the live rows through a compact list
   // (see lr_pbwd_compact_kernel) -- on BAND views, where a per cent of the rows is live and the one-kernel form is nearly
   // all flag pass (100 M rows, band 3 of 8: 929 -> 490 us).  On full views the chain rule is bound by its scattered lines
@@ -409,6 +460,7 @@ void lr_launch_project_bwd(const LrView& v, int N, const float* means, const flo
   const int list_knob = lr_knob(LRKNOB_PBWD_LIST);
   const bool band_view = v.ty0 > 0 || v.ty1 < v.gy;
   if ((list_knob == 2 || (list_knob == 1 && band_view)) && !clear_inside && pw && !v.cov3d && N >= 8) {
+    lr_launch_zero_floats(o_mean2d, 3 * (size_t)N, s);
     float4* rows_w = const_cast<float4*>(rows4);   // (the accumulator rows are the caller's scratch: slots 12-15 are this path's)
     lr_launch_zero_words(reinterpret_cast<uint32_t*>(rows_w + 3), 4, s);
     hipLaunchKernelGGL(lr_pbwd_compact_kernel, dim3((N + LR_PBWD_CHUNK - 1) / LR_PBWD_CHUNK), dim3(1024), 0, s, pw, N, rows_w);
