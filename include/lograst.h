@@ -743,6 +743,35 @@ int lograst_depth_loss_backward(int32_t height, int32_t width, const float* pred
                                 const float* gt, const int64_t* gt_strides, const float* acc, const int64_t* acc_strides,
                                 int32_t n, const void* records, const float* grad_loss, float* grad_pred, void* stream);
 
+/* ---- evaluation: what a validation image costs after it is rendered (LoG/utils/trainer.py:313-332 make_validation,
+ * LoG/utils/metric.py psnr and ssim, LoG/render/renderer.py:19-23 tensor_to_bgr) ----------------------------------------
+ * Images are [channels, height, width] fp32, 1 <= channels <= 4, each addressed through THREE ELEMENT STRIDES (c, y, x;
+ * host arrays of 3 int64, y and x strides not negative), so a view of an HWC image is read in place.
+ * lograst_image_to_bgr8 writes out = uint8 [height, width, channels] (4-byte aligned), the channel order reversed, each
+ * byte (uint8) trunc(fp32(min(max(x, 0), 1) * 255.f)): the bytes of tensor_to_bgr for every input that is not a nan.
+ * lograst_eval_metrics: with LOGRAST_EVAL_FIT_GAIN, gain[c] = fp32(sum gt * pred / sum pred^2) over the columns
+ * [0, width / 2) (double sums in a fixed order; nan or inf where the reference's division gives one) and
+ * p = min(max(fp32(gain[c] * pred), 0), 1), a nan staying a nan; without it p = pred, not clamped.  d = p - gt.  The record
+ * (128 bytes, 8-byte aligned, 16 doubles ON THE DEVICE) gets [0] sum |d|, [1] sum d^2, [2] with LOGRAST_EVAL_SSIM the sum of
+ * the SSIM map of metric.py:33-103 over p and gt (11 taps, sigma 1.5, zero padding: height * width outputs per channel;
+ * variances clamped at 0, the covariance limited to sqrt(s00 * s11); c1 = (0.01 max_val)^2, c2 = (0.03 max_val)^2), else 0,
+ * [3] the element count, [4..7] gain (1 without the fit, 0 beyond `channels`), [8..11] sum gt * pred, [12..15] sum pred^2.
+ * corrected (or NULL): fp32 [channels, height, width] contiguous, gets p.  bgr8 (or NULL): uint8 [2 * height, width,
+ * channels], the 8-bit form (as lograst_image_to_bgr8) of p above gt, each byte of p converted from the value `corrected`
+ * holds.  No floating-point atomics: the same input gives the same bits.
+ * lograst_eval_read copies the record to the host and synchronises the stream: the one synchronisation.
+ * NULL pointers, channels outside 1..4, height or width below 1, too small a scratch buffer, 2^31 elements or more and a
+ * plane whose strides reach beyond 32-bit offsets are errors, reported before any device work. */
+#define LOGRAST_EVAL_FIT_GAIN 1
+#define LOGRAST_EVAL_SSIM 2
+size_t lograst_eval_scratch_bytes(int32_t channels, int32_t height, int32_t width);
+int lograst_image_to_bgr8(int32_t channels, int32_t height, int32_t width, const float* image, const int64_t* strides3,
+                          uint8_t* out, void* stream);
+int lograst_eval_metrics(int32_t channels, int32_t height, int32_t width, const float* pred, const int64_t* pred_strides3,
+                         const float* gt, const int64_t* gt_strides3, int32_t flags, double max_val, float* corrected,
+                         uint8_t* bgr8, void* record, void* scratch, size_t scratch_bytes, void* stream);
+int lograst_eval_read(const void* record, double* out16, void* stream);
+
 /* ---- densification decisions: LoG.update_depth_stage / update_init_stage up to the flags -------------------------
  * (LoG/model/level_of_gaussian.py:400-427, :454-508).  One event is: lograst_decide_depth or lograst_decide_init (the
  * flags, every count and statistic the reference logs and, for the depth stage, the top-k cut, all on `stream`), then

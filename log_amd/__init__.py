@@ -17,7 +17,7 @@ def install_compute_radius():
 
 
 def install_all(fused_step=False, fused_loss=False, reuse_geometry=False, fused_depth_loss=False, device_densify=False,
-                device_prepare=False, device_decide=False, device_view_correction=False):
+                device_prepare=False, device_decide=False, device_view_correction=False, device_evaluate=False):
     """Everything a LoG process needs, in one call: the LoG.cuda.compute_radius module, then every
     drop-in method assigned onto LoG's own classes (needs LoG importable): LoG.get_all, TensorTree.traverse,
     Counter.update_by_output, SparseOptimizer.step.
@@ -46,7 +46,11 @@ def install_all(fused_step=False, fused_loss=False, reuse_geometry=False, fused_
     on the device (no host synchronisation), Corrector.__getitem__ notes the rows it hands out, and
     NaiveRendererAndLoss.calculate_loss gives them to the loss kernels as a per-image channel gain instead of reading
     render_correct (log_amd.view_correction.install, which installs log_amd.loss as well: one image gradient, the gain's
-    gradient from the same kernel); without it the Corrector stays the reference's torch code."""
+    gradient from the same kernel); without it the Corrector stays the reference's torch code.
+    device_evaluate (opt-in): Trainer.make_validation, LoG.utils.metric.psnr / ssim and BaseRender.tensor_to_bgr compute the
+    view-correction fit, L1, PSNR, the metric's SSIM and the 8-bit image on the device (log_amd.evaluate.install: one
+    read-back of a 128-byte record per image, plus the 8-bit copy when an image is written); without it evaluation stays
+    the reference's torch and numpy code."""
     install_compute_radius()
     from . import rasterizer
     rasterizer.set_geometry_reuse(bool(reuse_geometry))
@@ -71,4 +75,7 @@ def install_all(fused_step=False, fused_loss=False, reuse_geometry=False, fused_
     if device_view_correction:
         from . import view_correction
         installed.append(view_correction.install())
+    if device_evaluate:
+        from . import evaluate
+        installed.append(evaluate.install())
     return installed

@@ -1,4 +1,4 @@
-"""What every module of drop-ins with a fall-back shares (densify, prepare, decide): the ``Fallback`` exception, the
+"""What every module of drop-ins with a fall-back shares (densify, prepare, decide, evaluate): the ``Fallback`` exception, the
 registry that saves the reference's methods, installs ours, counts and logs, the checks of what the kernels cover, and the
 launch whose result the host reads back.  A module keeps what is its own: what it checks, launches and prints.
 
@@ -12,6 +12,7 @@ The other modules keep their own conventions: lod, counter, sparse_optimizer and
 fall-back; loss and depth_loss wrap theirs behind a predicate."""
 import contextlib
 import functools
+import inspect
 import logging
 
 import torch
@@ -33,6 +34,7 @@ class DropIns:
         self.module, self._targets = module, targets
         self._ours = {}                # name -> our function
         self._saved = {}               # name -> the reference's method, saved on first need
+        self._static = set()           # the names whose target is a staticmethod
         self.logged = set()            # the (method, reason) pairs that have had their warning
         self._stats = {"calls": {}, "fallbacks": {}, "readbacks": {}}
 
@@ -89,6 +91,8 @@ class DropIns:
         if name not in self._saved:
             cls, attr = self._targets()[name]
             fn = getattr(cls, attr)
+            if isinstance(inspect.getattr_static(cls, attr, None), staticmethod):
+                self._static.add(name)         # a plain setattr would make an instance method of it: see _put
             if fn in self._ours.values():
                 raise _lib.LograstError(f"log_amd.{self.module}: the reference's {attr} was replaced before install() "
                                         f"could save it")
@@ -106,20 +110,26 @@ class DropIns:
             self._saved.clear()
             self._saved.update(saved)
 
+    def _put(self, target, name, fn):
+        setattr(*target, staticmethod(fn) if name in self._static else fn)
+
     def install(self):
-        """Saves the reference's methods, then puts ours in their place -> targets()."""
+        """Saves the reference's methods, then puts ours in their place -> targets().  A registered name that targets()
+        leaves out (its module cannot be imported) is skipped."""
         targets = self._targets()
-        for name in self._ours:
+        names = [name for name in self._ours if name in targets]
+        for name in names:
             self.original(name)
-        for name, fn in self._ours.items():
-            setattr(*targets[name], fn)
+        for name in names:
+            self._put(targets[name], name, self._ours[name])
         return targets
 
     def uninstall(self):
         """Put the reference's methods back."""
         targets = self._targets()
         for name, fn in self._saved.items():
-            setattr(*targets[name], fn)
+            if name in targets:
+                self._put(targets[name], name, fn)
 
     # ---- a launch whose result the host needs ----
 

@@ -55,6 +55,7 @@ class LograstDecideStat(ctypes.Structure):
 
 
 DECIDE_DEPTH_BINS = 256   # LOGRAST_DECIDE_DEPTH_BINS
+EVAL_FIT_GAIN, EVAL_SSIM = 1, 2   # LOGRAST_EVAL_*
 
 
 class LograstDecideRecord(ctypes.Structure):
@@ -180,6 +181,11 @@ _SIGNATURES = {
                                                   ctypes.c_double, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p,
                                                   c_size_t, c_void_p]),
     "lograst_depth_loss_backward": (ctypes.c_int, [c_int32, c_int32] + [c_void_p] * 6 + [c_int32] + [c_void_p] * 4),
+    "lograst_eval_scratch_bytes": (c_size_t, [c_int32] * 3),
+    "lograst_image_to_bgr8": (ctypes.c_int, [c_int32] * 3 + [c_void_p] * 4),
+    "lograst_eval_metrics": (ctypes.c_int, [c_int32] * 3 + [c_void_p] * 4 + [c_int32, ctypes.c_double] + [c_void_p] * 4
+                             + [c_size_t, c_void_p]),
+    "lograst_eval_read": (ctypes.c_int, [c_void_p, ctypes.POINTER(ctypes.c_double), c_void_p]),
     "lograst_sparse_adam": (ctypes.c_int, [c_int32, c_int32, c_void_p, c_void_p, c_int32,
                                            ctypes.POINTER(LograstAdamKey), ctypes.c_double, ctypes.c_double,
                                            ctypes.c_double, ctypes.c_double, c_void_p]),

@@ -1077,6 +1077,13 @@ size_t lograst_loss_scratch_bytes(int32_t batch, int32_t channels, int32_t heigh
   return lr_loss_scratch_bytes(batch, channels, height, width);
 }
 
+// the window: exp(-(x-5)^2 / (2 * 1.5^2)) in double, normalised, rounded to fp32 once (the loss's and the metric's)
+static void lr_ssim_window(float* w) {
+  double g[LS_WIN_TAPS], sum = 0.0;
+  for (int k = 0; k < LS_WIN_TAPS; k++) { g[k] = std::exp(-(double)((k - 5) * (k - 5)) / (2.0 * 1.5 * 1.5)); sum += g[k]; }
+  for (int k = 0; k < LS_WIN_TAPS; k++) w[k] = (float)(g[k] / sum);
+}
+
 // Geometry and input checks shared by the two entry points; fills everything of LossArgs but the tile grid.
 static int lr_loss_args(LossArgs& a, int32_t batch, int32_t channels, int32_t height, int32_t width, const float* render,
                         const int64_t* rs, const float* render_l1, const int64_t* ls, const float* gt, const int64_t* gs) {
@@ -1101,10 +1108,7 @@ static int lr_loss_args(LossArgs& a, int32_t batch, int32_t channels, int32_t he
   a.render = render; a.gt = gt;
   a.render_l1 = (render_l1 && !same) ? render_l1 : nullptr;
   a.B = batch; a.C = channels; a.H = height; a.W = width;
-  // the window: exp(-(x-5)^2 / (2 * 1.5^2)) in double, normalised, rounded to fp32 once
-  double g[LS_WIN_TAPS], sum = 0.0;
-  for (int k = 0; k < LS_WIN_TAPS; k++) { g[k] = std::exp(-(double)((k - 5) * (k - 5)) / (2.0 * 1.5 * 1.5)); sum += g[k]; }
-  for (int k = 0; k < LS_WIN_TAPS; k++) a.w[k] = (float)(g[k] / sum);
+  lr_ssim_window(a.w);
   a.scale = 0.f; a.l1_scale = 0.f; a.maps = nullptr; a.partial = nullptr; a.ntx = a.nty = 0;
   a.gain = nullptr; a.gain_partial = nullptr;
   return 0;
@@ -1248,6 +1252,68 @@ int lograst_depth_loss_backward(int32_t height, int32_t width, const float* pred
   if (reinterpret_cast<uintptr_t>(records) & 7u) return lr_fail(LOGRAST_ERR_ARG, "depth loss records must be 8-byte aligned");
   g_prof_call++;
   LR_HIP(lr_launch_depth_loss_bwd(a, n, reinterpret_cast<const double*>(records), grad_loss, grad_pred, (hipStream_t)stream));
+  return LOGRAST_OK;
+}
+
+// ---- evaluation: validation metrics and 8-bit export (evaluate.hip) ----------------------------------------
+size_t lograst_eval_scratch_bytes(int32_t channels, int32_t height, int32_t width) {
+  return lr_eval_scratch_bytes(channels, height, width);
+}
+
+// Checks shared by the entry points; everything here runs before any device work.
+static int lr_eval_geometry(int32_t channels, int32_t height, int32_t width) {
+  if (channels < 1 || channels > 4) return lr_fail(LOGRAST_ERR_ARG, "channels must be 1..4");
+  if (height < 1 || width < 1) return lr_fail(LOGRAST_ERR_ARG, "height and width must be at least 1");
+  if ((int64_t)channels * (int64_t)height * width > 0x7fffffffLL) return lr_fail(LOGRAST_ERR_ARG, "more than 2^31 - 1 image elements");
+  return 0;
+}
+
+static int lr_eval_strides(int64_t* dst, const int64_t* st, int32_t height, int32_t width) {
+  const int64_t sy = st[1] < 0 ? -st[1] : st[1], sx = st[2] < 0 ? -st[2] : st[2];
+  if (st[1] < 0 || st[2] < 0 || sy > 0x7fffffffLL || sx > 0x7fffffffLL || (int64_t)(height - 1) * sy + (int64_t)(width - 1) * sx > 0x7fffffffLL)
+    return lr_fail(LOGRAST_ERR_ARG, "y / x strides are negative or reach beyond 2^31 - 1 elements inside one image plane");
+  for (int i = 0; i < 3; i++) dst[i] = st[i];
+  return 0;
+}
+
+int lograst_image_to_bgr8(int32_t channels, int32_t height, int32_t width, const float* image, const int64_t* strides3,
+                          uint8_t* out, void* stream) {
+  if (lr_eval_geometry(channels, height, width)) return LOGRAST_ERR_ARG;
+  if (!image || !strides3 || !out) return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
+  if (reinterpret_cast<uintptr_t>(out) & 3u) return lr_fail(LOGRAST_ERR_ARG, "out must be 4-byte aligned");
+  EvalArgs a = {};
+  if (lr_eval_strides(a.ps, strides3, height, width)) return LOGRAST_ERR_ARG;
+  a.pred = image; a.C = channels; a.H = height; a.W = width; a.bgr8 = out;
+  g_prof_call++;
+  LR_HIP(lr_launch_eval_bgr8(a, (hipStream_t)stream));
+  return LOGRAST_OK;
+}
+
+int lograst_eval_metrics(int32_t channels, int32_t height, int32_t width, const float* pred, const int64_t* pred_strides3,
+                         const float* gt, const int64_t* gt_strides3, int32_t flags, double max_val, float* corrected,
+                         uint8_t* bgr8, void* record, void* scratch, size_t scratch_bytes, void* stream) {
+  if (lr_eval_geometry(channels, height, width)) return LOGRAST_ERR_ARG;
+  if (!pred || !pred_strides3 || !gt || !gt_strides3 || !record) return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
+  if (flags & ~(LOGRAST_EVAL_FIT_GAIN | LOGRAST_EVAL_SSIM)) return lr_fail(LOGRAST_ERR_ARG, "unknown flag");
+  if (reinterpret_cast<uintptr_t>(record) & 7u) return lr_fail(LOGRAST_ERR_ARG, "record must be 8-byte aligned");
+  if (!scratch || scratch_bytes < lr_eval_scratch_bytes(channels, height, width) || (reinterpret_cast<uintptr_t>(scratch) & 7u))
+    return lr_fail(LOGRAST_ERR_ARG, "eval scratch too small (lograst_eval_scratch_bytes) or not 8-byte aligned");
+  EvalArgs a = {};
+  if (lr_eval_strides(a.ps, pred_strides3, height, width) || lr_eval_strides(a.gs, gt_strides3, height, width)) return LOGRAST_ERR_ARG;
+  a.pred = pred; a.gt = gt; a.C = channels; a.H = height; a.W = width;
+  lr_ssim_window(a.w);
+  a.c1 = (float)((0.01 * max_val) * (0.01 * max_val));
+  a.c2 = (float)((0.03 * max_val) * (0.03 * max_val));
+  a.corrected = corrected; a.bgr8 = bgr8; a.record = reinterpret_cast<double*>(record);
+  g_prof_call++;
+  LR_HIP(lr_launch_eval_metrics(a, (flags & LOGRAST_EVAL_FIT_GAIN) != 0, (flags & LOGRAST_EVAL_SSIM) != 0, scratch, (hipStream_t)stream));
+  return LOGRAST_OK;
+}
+
+int lograst_eval_read(const void* record, double* out16, void* stream) {
+  if (!record || !out16) return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
+  LR_HIP(hipMemcpyAsync(out16, record, 16 * sizeof(double), hipMemcpyDeviceToHost, (hipStream_t)stream));
+  LR_HIP(hipStreamSynchronize((hipStream_t)stream));
   return LOGRAST_OK;
 }
 

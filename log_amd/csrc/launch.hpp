@@ -137,6 +137,22 @@ hipError_t lr_launch_depth_loss_fwd(const DepthLossArgs& a, int n, const int64_t
 hipError_t lr_launch_depth_loss_bwd(const DepthLossArgs& a, int n, const double* records, const float* grad_loss,
                                     float* grad_pred, hipStream_t s);
 
+// evaluate.hip
+struct EvalArgs {
+  const float* pred; const float* gt;       // [C, H, W] each
+  int64_t ps[3], gs[3];                     // element strides (c, y, x)
+  int32_t C, H, W, ntx;
+  float w[LS_WIN_TAPS];                     // the SSIM window (the loss's table)
+  float c1, c2;                             // (0.01 max_val)^2, (0.03 max_val)^2
+  float* corrected;                         // [C, H, W] contiguous, or NULL
+  uint8_t* bgr8;                            // metrics: [2 H, W, C]; the export alone: [H, W, C]; or NULL
+  double* record;                           // 16 doubles (layout: evaluate.hip)
+  double* gain_partial; double* partial;    // inside the scratch
+};
+size_t lr_eval_scratch_bytes(int C, int H, int W);
+hipError_t lr_launch_eval_bgr8(const EvalArgs& a, hipStream_t s);
+hipError_t lr_launch_eval_metrics(EvalArgs a, bool fit_gain, bool ssim, void* scratch, hipStream_t s);
+
 // densify.hip
 #define LR_MOVE_COPY_PARENT 0   // rows >= num_keep copy src[src_row[d]] like the kept rows
 #define LR_MOVE_ZERO 1          // rows >= num_keep are zero
