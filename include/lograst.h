@@ -520,6 +520,19 @@ int lograst_lod_select_read(const void* scratch, uint32_t* count_all_host, uint3
 int lograst_clamp_scale(int32_t m, const int64_t* index, const uint8_t* flag, int32_t num_points, float* scaling,
                         const float* radius3d_min, const float* radius3d_max, void* stream);
 
+/* lograst_init_radius3d = the initialisation pass, LoG.init with Gaussian.init_radius3d
+ * (/root/reference/LoG/model/level_of_gaussian.py:328-332, :55-63) over ALL p points and `num_views` cameras in one launch.
+ * xyz [p, 3], scaling [p, 3] and rotation [p, 4] are the RAW parameters: the kernel applies exp and normalize as
+ * lograst_lod_traverse does.  cameras (device): num_views x 36 floats -- projmatrix[16], viewmatrix[16], focal_x, focal_y,
+ * tanfovx, tanfovy, the arguments of lograst_compute_radius.  Per point and camera, in order: r = the radius of
+ * lograst_compute_radius; where r > 0: r3d = exp(scaling[i, 0]) * (3.f / r) and radius3d_min[i] = minimum(radius3d_min[i],
+ * r3d) as torch.minimum has it (a NaN on either side stays).  A row that no camera sees keeps its bits.  The minimum does
+ * not depend on the order or the grouping of the cameras.
+ * radius3d_min: in/out f32[p], or NULL.  valid (u8[p]: r > 0) and radius3d (f32[p]: r3d, exp(scaling[i, 0]) where r <= 0)
+ * are Gaussian.init_radius3d's results, or NULL; they need num_views == 1.  p == 0 or num_views == 0: nothing happens. */
+int lograst_init_radius3d(int32_t p, const float* xyz, const float* scaling, const float* rotation, int32_t num_views,
+                          const float* cameras, float* radius3d_min, uint8_t* valid, float* radius3d, void* stream);
+
 /* ---- "next" row N4: what LoG does with the rasterizer's outputs after every view ----------------------------
  * (a) lograst_id_histogram replaces `torch.unique(point_id_pixel, sorted=True, return_counts=True)` + dropping the
  *     leading -1 (/root/reference/LoG/render/renderer.py:156-159): ids_out (i32) = the distinct ids >= 0 in

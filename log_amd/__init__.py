@@ -17,7 +17,7 @@ def install_compute_radius():
 
 
 def install_all(fused_step=False, fused_loss=False, reuse_geometry=False, fused_depth_loss=False, device_densify=False,
-                device_prepare=False, device_decide=False, device_view_correction=False, device_evaluate=False):
+                device_prepare=False, device_decide=False, device_view_correction=False, device_evaluate=False, device_init=False):
     """Everything a LoG process needs, in one call: the LoG.cuda.compute_radius module, then every
     drop-in method assigned onto LoG's own classes (needs LoG importable): LoG.get_all, TensorTree.traverse,
     Counter.update_by_output, SparseOptimizer.step.
@@ -50,7 +50,11 @@ def install_all(fused_step=False, fused_loss=False, reuse_geometry=False, fused_
     device_evaluate (opt-in): Trainer.make_validation, LoG.utils.metric.psnr / ssim and BaseRender.tensor_to_bgr compute the
     view-correction fit, L1, PSNR, the metric's SSIM and the 8-bit image on the device (log_amd.evaluate.install: one
     read-back of a 128-byte record per image, plus the 8-bit copy when an image is written); without it evaluation stays
-    the reference's torch and numpy code."""
+    the reference's torch and numpy code.
+    device_init (opt-in): LoG.init, Gaussian.init_radius3d and LoG.at_init_final run the initialisation pass of Trainer.init
+    on the device (log_amd.init_pass.install with views_per_launch left at 1: one launch per view over all points, no host
+    synchronisation, the state after every call the reference's); without it the pass stays the reference's torch code
+    around the installed compute_radius."""
     install_compute_radius()
     from . import rasterizer
     rasterizer.set_geometry_reuse(bool(reuse_geometry))
@@ -78,4 +82,7 @@ def install_all(fused_step=False, fused_loss=False, reuse_geometry=False, fused_
     if device_evaluate:
         from . import evaluate
         installed.append(evaluate.install())
+    if device_init:
+        from . import init_pass
+        installed.append(init_pass.install())
     return installed

@@ -162,6 +162,7 @@ _SIGNATURES = {
                            + [c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "lograst_lod_select_read": (ctypes.c_int, [c_void_p] + [ctypes.POINTER(c_uint32)] * 4 + [c_void_p]),
     "lograst_clamp_scale": (ctypes.c_int, [c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "lograst_init_radius3d": (ctypes.c_int, [c_int32, c_void_p, c_void_p, c_void_p, c_int32] + [c_void_p] * 5),
     "lograst_id_histogram_scratch_bytes": (c_size_t, [c_int32]),
     "lograst_id_histogram": (ctypes.c_int, [c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "lograst_id_histogram_read": (ctypes.c_int, [c_void_p, ctypes.POINTER(c_uint32), c_void_p]),

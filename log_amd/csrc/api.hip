@@ -1029,6 +1029,19 @@ int lograst_clamp_scale(int32_t m, const int64_t* index, const uint8_t* flag, in
   return LOGRAST_OK;
 }
 
+int lograst_init_radius3d(int32_t p, const float* xyz, const float* scaling, const float* rotation, int32_t num_views,
+                          const float* cameras, float* radius3d_min, uint8_t* valid, float* radius3d, void* stream) {
+  if (p < 0 || num_views < 0) return lr_fail(LOGRAST_ERR_ARG, "negative point or view count");
+  if ((valid || radius3d) && num_views != 1)
+    return lr_fail(LOGRAST_ERR_ARG, "valid / radius3d are the results of one view: num_views must be 1");
+  if (p == 0 || num_views == 0) return LOGRAST_OK;
+  if (!xyz || !scaling || !rotation || !cameras) return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
+  g_prof_call++;
+  LR_HIP(lr_launch_init_radius3d(p, xyz, scaling, rotation, num_views, cameras, radius3d_min, valid, radius3d,
+                                 (hipStream_t)stream));
+  return LOGRAST_OK;
+}
+
 size_t lograst_id_histogram_scratch_bytes(int32_t n) { return lr_hist_scratch_bytes(n); }
 
 int lograst_id_histogram(int32_t n, const int32_t* point_id_pixel, int32_t num_pixels, int32_t* ids_out,

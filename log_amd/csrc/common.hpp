@@ -273,22 +273,31 @@ LR_DEV float lr_radius_from_cov(float a, float c, float det) {
 
 // A0 for one Gaussian: the body of compute_radius_cuda (/root/reference/LoG/cuda/compute_radius_kernel.cu:107-156)
 // -- float radius (no ceil), |ndc| > 1.3 cull only, fork low-pass max(., 0.3), det == 0 -> 0.  Shared by
-// lr_radius_kernel (project.hip) and the level-of-detail traversal (lod.hip).
-LR_DEV float lr_radius_one(const float p[3], const float s[3], const float q[4], const float* __restrict__ proj,
-                           const float* __restrict__ view, float fx, float fy, float tanfovx, float tanfovy) {
+// lr_radius_kernel (project.hip) and the level-of-detail traversal (lod.hip); in its two halves -- the cull, which needs
+// the centre alone, and the radius of a Gaussian that passed it, from its world-space covariance -- by the
+// initialisation pass (init.hip), which computes the covariance once for many cameras.
+LR_DEV bool lr_radius_in_ndc(const float p[3], const float* __restrict__ proj) {
   float hx = lr_dot3p(proj[0], proj[4], proj[8], p[0], p[1], p[2], proj[12]);
   float hy = lr_dot3p(proj[1], proj[5], proj[9], p[0], p[1], p[2], proj[13]);
   float hw = lr_dot3p(proj[3], proj[7], proj[11], p[0], p[1], p[2], proj[15]);
   float pw = 1.0f / (hw + 0.0000001f);
   float nx = hx * pw, ny = hy * pw;
+  return !(nx < -1.3f || nx > 1.3f || ny < -1.3f || ny > 1.3f);
+}
+LR_DEV float lr_radius_of_cov(const float p[3], const float Sg[6], const float* __restrict__ view, float fx, float fy,
+                              float tanfovx, float tanfovy) {
+  LrEwa e;
+  lr_ewa(p, Sg, view, fx, fy, tanfovx, tanfovy, LOGRAST_FILTER_CLAMP, e);
+  float det = e.a * e.c - e.b * e.b;
+  return det != 0.0f ? lr_radius_from_cov(e.a, e.c, det) : 0.f;
+}
+LR_DEV float lr_radius_one(const float p[3], const float s[3], const float q[4], const float* __restrict__ proj,
+                           const float* __restrict__ view, float fx, float fy, float tanfovx, float tanfovy) {
   float out = 0.f;
-  if (!(nx < -1.3f || nx > 1.3f || ny < -1.3f || ny > 1.3f)) {
+  if (lr_radius_in_ndc(p, proj)) {
     float R[9], Sg[6];
     lr_cov3d(s, q, R, Sg);
-    LrEwa e;
-    lr_ewa(p, Sg, view, fx, fy, tanfovx, tanfovy, LOGRAST_FILTER_CLAMP, e);
-    float det = e.a * e.c - e.b * e.b;
-    if (det != 0.0f) out = lr_radius_from_cov(e.a, e.c, det);
+    out = lr_radius_of_cov(p, Sg, view, fx, fy, tanfovx, tanfovy);
   }
   return out;
 }

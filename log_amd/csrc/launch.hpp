@@ -107,6 +107,13 @@ hipError_t lr_launch_partition(const int64_t* list, const uint32_t* n_dev, uint3
 hipError_t lr_launch_clamp_scale(int m, const int64_t* index, const uint8_t* flag, int num_points, float* scaling,
                                  const float* rmin, const float* rmax, hipStream_t s);
 
+// init.hip
+// cameras: V x 36 floats on the device (proj[16], view[16], fx, fy, tanfovx, tanfovy); radius3d_min in/out or NULL;
+// valid / radius3d: NULL unless V == 1
+hipError_t lr_launch_init_radius3d(int P, const float* xyz, const float* scaling, const float* rotation, int V,
+                                   const float* cameras, float* radius3d_min, uint8_t* valid, float* radius3d,
+                                   hipStream_t s);
+
 // counter.hip
 size_t lr_hist_scratch_bytes(int n);
 hipError_t lr_launch_id_histogram(int n, const int32_t* pid, int npix, int32_t* ids, int64_t* counts, void* scratch,
