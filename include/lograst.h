@@ -591,6 +591,47 @@ int lograst_activate_backward_adam(int32_t n, const float* raw_xyz, const float*
                                    const lograst_adam_key* keys, double beta1, double beta2, double bias_correction2_sqrt,
                                    double eps, void* stream);
 
+/* ---- steps over several views of the LoG model (Python side: log_amd/multi_view.py) ------------------------------------
+ * The reference steps over ONE view: LoG.get_all writes visibility_flag['params'] per view and LoG.step reads the last
+ * (level_of_gaussian.py:262-296, :379-398).  Here every view's activation backward is added into sums laid out by MODEL
+ * row, and one Adam step is taken over the rows some view saw.  Neither call allocates; all work on `stream`.
+ *
+ * A target is one key's block of per-model-row sums: row p starts at base + p * row_stride_floats.  The attribute-major
+ * blocks of log_amd.dist have row_stride_floats = the key's width; its row-major form is 16-float rows with the key's first
+ * column as `base` (and a separate shs block).  base == NULL: the key is not accumulated.  Offsets are 64-bit:
+ * lograst_accumulate_target_floats(num_points, row_stride_floats, width) = the floats such a block spans
+ * ((num_points - 1) * row_stride_floats + width, 0 for no rows; computed as the kernels compute an element's offset). */
+typedef struct lograst_acc_target {
+  float* base;
+  int32_t row_stride_floats;
+} lograst_acc_target;
+size_t lograst_accumulate_target_floats(int32_t num_points, int32_t row_stride_floats, int32_t width);
+
+/* For every r < n with radii[r] > 0 and 0 <= index[r] < num_points: the raw gradients of row r exactly as
+ * lograst_activate_backward computes them (same op sequences; dl_dact_xyz passes through; coefficients above the active
+ * degree get zero) are ADDED into row index[r] of targets[6] (order xyz, scaling, opacity, rotation, colors, shs; widths 3,
+ * 3, 1, 4, 3, 3 * sh_coeffs; row_stride_floats >= width) and seen[index[r]] (i32[num_points]) is incremented.  Other rows
+ * are not written.  Plain read-modify-writes, no atomics: index (i64[n]) has no duplicates (the contract of
+ * lograst_counter_update) and the views follow each other on the stream, so the same views in the same order give the same
+ * bits: after each view a sum is fp32(sum + gradient). */
+int lograst_activate_backward_accumulate(int32_t n, const float* raw_xyz, const float* raw_scaling, const float* raw_opacity,
+                                         const float* raw_rotation, int32_t sh_coeffs, int32_t active_degree,
+                                         const float* camera_center, const float* dl_dact_xyz, const float* dl_dact_scaling,
+                                         const float* dl_dact_opacity, const float* dl_dact_rotation,
+                                         const float* dl_dact_colors, int32_t num_points, const int64_t* index,
+                                         const int32_t* radii, const lograst_acc_target* targets, int32_t* seen,
+                                         void* stream);
+
+/* For every row p < num_points with seen[p] > 0: Adam on model row p and its moments with the op sequence and the scalars
+ * of lograst_sparse_adam -- given the same gradient bits, the same result bits; amsgrad where max_exp_avg_sq != NULL -- then
+ * the row's accumulated gradient is overwritten with zeros, seen[p] = 0 and moved_out[p] = 1 (u8[num_points], or NULL).
+ * Rows with seen[p] == 0 get moved_out[p] = 0; nothing else of theirs is read or written.  keys[6] in the order and with the
+ * widths above: model_param is updated in place, `param` is ignored, `grad` is the key's accumulated block with rows
+ * grad_row_stride_floats[key] apart; model_param == NULL skips the key. */
+int lograst_accumulated_adam(int32_t num_points, int32_t* seen, const lograst_adam_key* keys,
+                             const int32_t* grad_row_stride_floats, double beta1, double beta2,
+                             double bias_correction2_sqrt, double eps, uint8_t* moved_out, void* stream);
+
 /* ---- densification: TensorTree.split_and_remove + Splitter.split_and_remove(_other) on the device ----------------
  * (LoG/model/tensor_tree.py:65-129, LoG/model/splitter.py:5-31, :95-220).  One call of the reference method is:
  * lograst_densify_plan, lograst_densify_read (the only host synchronisation: the caller allocates the new buffers from

@@ -17,7 +17,8 @@ def install_compute_radius():
 
 
 def install_all(fused_step=False, fused_loss=False, reuse_geometry=False, fused_depth_loss=False, device_densify=False,
-                device_prepare=False, device_decide=False, device_view_correction=False, device_evaluate=False, device_init=False):
+                device_prepare=False, device_decide=False, device_view_correction=False, device_evaluate=False, device_init=False,
+                views_per_step=None):
     """Everything a LoG process needs, in one call: the LoG.cuda.compute_radius module, then every
     drop-in method assigned onto LoG's own classes (needs LoG importable): LoG.get_all, TensorTree.traverse,
     Counter.update_by_output, SparseOptimizer.step.
@@ -54,7 +55,10 @@ def install_all(fused_step=False, fused_loss=False, reuse_geometry=False, fused_
     device_init (opt-in): LoG.init, Gaussian.init_radius3d and LoG.at_init_final run the initialisation pass of Trainer.init
     on the device (log_amd.init_pass.install with views_per_launch left at 1: one launch per view over all points, no host
     synchronisation, the state after every call the reference's); without it the pass stays the reference's torch code
-    around the installed compute_radius."""
+    around the installed compute_radius.
+    views_per_step (opt-in, an integer K >= 1): LoG.step takes ONE Adam step per K calls, over every row that one of the K
+    views saw, from gradients that the backward of LoG.get_all added by model row (log_amd.multi_view.install, installed
+    after device_prepare so that its fall-back is that module's step); None installs nothing: every step is one view wide."""
     install_compute_radius()
     from . import rasterizer
     rasterizer.set_geometry_reuse(bool(reuse_geometry))
@@ -73,6 +77,9 @@ def install_all(fused_step=False, fused_loss=False, reuse_geometry=False, fused_
     if device_prepare:
         from . import prepare
         installed.append(prepare.install())
+    if views_per_step is not None:
+        from . import multi_view
+        installed.append(multi_view.install(views_per_step=views_per_step))
     if device_decide:
         from . import decide
         installed.append(decide.install())

@@ -40,9 +40,12 @@ class DropIns:
 
     # ---- the public functions ----
 
-    def register(self, fn):
-        """Decorator: ``fn`` is what install() puts in place of the reference's method of that name."""
-        self._ours[fn.__name__] = fn
+    def register(self, fn=None, *, name=None):
+        """Decorator: ``fn`` is what install() puts in place of the reference's method of that name (``name``: where the
+        function's own name is another)."""
+        if fn is None:
+            return lambda f: self.register(f, name=name)
+        self._ours[name or fn.__name__] = fn
         return fn
 
     def dropin(self, body):

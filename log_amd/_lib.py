@@ -39,6 +39,11 @@ class LograstAdamKey(ctypes.Structure):
                 ("exp_avg_sq", c_void_p), ("max_exp_avg_sq", c_void_p), ("width", c_int32), ("step_size", c_float)]
 
 
+class LograstAccTarget(ctypes.Structure):
+    """struct lograst_acc_target (include/lograst.h)."""
+    _fields_ = [("base", c_void_p), ("row_stride_floats", c_int32)]
+
+
 class LograstMoveKey(ctypes.Structure):
     """struct lograst_move_key (include/lograst.h)."""
     _fields_ = [("src", c_void_p), ("dst", c_void_p), ("elem_size", c_int32), ("columns", c_int32),
@@ -209,6 +214,13 @@ _SIGNATURES = {
     "lograst_activate_backward_adam": (ctypes.c_int, [c_int32] + [c_void_p] * 4 + [c_int32, c_int32] + [c_void_p] * 6 +
                                        [c_int32, c_void_p, c_void_p, ctypes.POINTER(LograstAdamKey), ctypes.c_double,
                                         ctypes.c_double, ctypes.c_double, ctypes.c_double, c_void_p]),
+    "lograst_accumulate_target_floats": (c_size_t, [c_int32] * 3),
+    "lograst_activate_backward_accumulate": (ctypes.c_int, [c_int32] + [c_void_p] * 4 + [c_int32, c_int32] + [c_void_p] * 6 +
+                                             [c_int32, c_void_p, c_void_p, ctypes.POINTER(LograstAccTarget), c_void_p,
+                                              c_void_p]),
+    "lograst_accumulated_adam": (ctypes.c_int, [c_int32, c_void_p, ctypes.POINTER(LograstAdamKey),
+                                                ctypes.POINTER(c_int32), ctypes.c_double, ctypes.c_double,
+                                                ctypes.c_double, ctypes.c_double, c_void_p, c_void_p]),
     "lograst_gather_activate": (ctypes.c_int, [c_int32, c_int32] + [c_void_p] * 7 + [c_int32, c_int32] + [c_void_p] * 12),
     "lograst_activate_backward": (ctypes.c_int, [c_int32] + [c_void_p] * 4 + [c_int32, c_int32] + [c_void_p] * 11),
     "lograst_profile_enable": (None, [ctypes.c_int]),

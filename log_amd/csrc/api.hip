@@ -1666,6 +1666,86 @@ int lograst_activate_backward_adam(int32_t n, const float* raw_xyz, const float*
   return LOGRAST_OK;
 }
 
+// ---- steps over several views (accumulate.hip) ----------------------------------------------------------------------------
+size_t lograst_accumulate_target_floats(int32_t num_points, int32_t row_stride_floats, int32_t width) {
+  if (num_points <= 0 || row_stride_floats < 0 || width < 0) return 0;
+  return lr_acc_offset((int64_t)num_points - 1, row_stride_floats, width);
+}
+
+static const int kAccWidths[6] = {3, 3, 1, 4, 3, 0};   // xyz, scaling, opacity, rotation, colors; shs: 3 * sh_coeffs
+
+int lograst_activate_backward_accumulate(int32_t n, const float* raw_xyz, const float* raw_scaling, const float* raw_opacity,
+                                         const float* raw_rotation, int32_t sh_coeffs, int32_t active_degree,
+                                         const float* camera_center, const float* dl_dact_xyz, const float* dl_dact_scaling,
+                                         const float* dl_dact_opacity, const float* dl_dact_rotation,
+                                         const float* dl_dact_colors, int32_t num_points, const int64_t* index,
+                                         const int32_t* radii, const lograst_acc_target* targets, int32_t* seen,
+                                         void* stream) {
+  int rc = lr_ga_check(n, sh_coeffs, active_degree, camera_center);
+  if (rc) return rc;
+  if (n == 0) return LOGRAST_OK;
+  if (num_points <= 0) return lr_fail(LOGRAST_ERR_ARG, "rows of an empty model");
+  if (!raw_xyz || !raw_scaling || !raw_opacity || !raw_rotation || !dl_dact_xyz || !dl_dact_scaling || !dl_dact_opacity ||
+      !dl_dact_rotation || !dl_dact_colors || !index || !radii || !targets || !seen)
+    return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
+  if ((reinterpret_cast<uintptr_t>(raw_rotation) | reinterpret_cast<uintptr_t>(dl_dact_rotation)) & 15u)
+    return lr_fail(LOGRAST_ERR_ARG, "raw_rotation / dl_dact_rotation must be 16-byte aligned");
+  ActBwdArgs a;
+  memset(&a, 0, sizeof(a));
+  a.r_xyz = raw_xyz; a.r_scaling = raw_scaling; a.r_opacity = raw_opacity; a.r_rotation = raw_rotation;
+  a.campos = camera_center;
+  a.g_a_scaling = dl_dact_scaling; a.g_a_opacity = dl_dact_opacity; a.g_a_rotation = dl_dact_rotation;
+  a.g_a_colors = dl_dact_colors;
+  a.n = n; a.K = sh_coeffs; a.deg = active_degree;
+  AccArgs t;
+  memset(&t, 0, sizeof(t));
+  for (int i = 0; i < ACC_KEYS; i++) {
+    if (!targets[i].base) continue;
+    const int w = i == 5 ? 3 * sh_coeffs : kAccWidths[i];
+    if (i == 5 && sh_coeffs == 0) return lr_fail(LOGRAST_ERR_ARG, "shs target without SH coefficients");
+    if (targets[i].row_stride_floats < w)
+      return lr_fail(LOGRAST_ERR_ARG, "lograst_activate_backward_accumulate: a target's row stride is smaller than its key's width (3, 3, 1, 4, 3, 3 * sh_coeffs)");
+    t.t[i].base = targets[i].base; t.t[i].stride = targets[i].row_stride_floats;
+  }
+  t.g_a_xyz = dl_dact_xyz; t.index = index; t.radii = radii; t.seen = seen; t.num_points = num_points;
+  g_prof_call++;
+  LR_HIP(lr_launch_activate_bwd_accumulate(a, t, (hipStream_t)stream));
+  return LOGRAST_OK;
+}
+
+int lograst_accumulated_adam(int32_t num_points, int32_t* seen, const lograst_adam_key* keys,
+                             const int32_t* grad_row_stride_floats, double beta1, double beta2,
+                             double bias_correction2_sqrt, double eps, uint8_t* moved_out, void* stream) {
+  if (num_points < 0) return lr_fail(LOGRAST_ERR_ARG, "negative count");
+  if (num_points == 0) return LOGRAST_OK;
+  if (!seen || !keys || !grad_row_stride_floats) return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
+  AdamArgs f;
+  memset(&f, 0, sizeof(f));
+  AccStepArgs t;
+  memset(&t, 0, sizeof(t));
+  for (int i = 0; i < ACC_KEYS; i++) {
+    const lograst_adam_key& k = keys[i];
+    if (!k.model_param) continue;                            // key not optimised
+    if (i == 5 ? (k.width < 3 || k.width > 45 || k.width % 3) : k.width != kAccWidths[i])
+      return lr_fail(LOGRAST_ERR_ARG, "lograst_accumulated_adam: key widths are 3, 3, 1, 4, 3, 3 * sh_coeffs (xyz, scaling, opacity, rotation, colors, shs)");
+    if (!k.grad || !k.exp_avg || !k.exp_avg_sq) return lr_fail(LOGRAST_ERR_ARG, "NULL pointer in key");
+    if (grad_row_stride_floats[i] < k.width) return lr_fail(LOGRAST_ERR_ARG, "lograst_accumulated_adam: a gradient row stride is smaller than its key's width");
+    f.key[i].model = (float*)k.model_param; f.key[i].param = nullptr; f.key[i].grad = (const float*)k.grad;
+    f.key[i].exp_avg = (float*)k.exp_avg; f.key[i].exp_avg_sq = (float*)k.exp_avg_sq;
+    f.key[i].max_exp_avg_sq = (float*)k.max_exp_avg_sq;
+    f.key[i].width = k.width; f.key[i].neg_step_size = -k.step_size;
+    t.gstride[i] = grad_row_stride_floats[i];
+  }
+  f.num_points = num_points;
+  // the reference's Python scalars are doubles that torch narrows to fp32 when they meet an fp32 tensor
+  f.beta1 = (float)beta1; f.beta2 = (float)beta2; f.omb1 = (float)(1.0 - beta1); f.omb2 = (float)(1.0 - beta2);
+  f.bc2_sqrt = (float)bias_correction2_sqrt; f.eps = (float)eps;
+  t.seen = seen; t.moved = moved_out;
+  g_prof_call++;
+  LR_HIP(lr_launch_accumulated_adam(f, t, (hipStream_t)stream));
+  return LOGRAST_OK;
+}
+
 static int lr_sh_check(int32_t n, int32_t degree, int32_t max_coeffs) {
   if (n < 0) return lr_fail(LOGRAST_ERR_ARG, "negative Gaussian count");
   if (degree < 0 || degree > 3) return lr_fail(LOGRAST_ERR_ARG, "SH degree must be 0..3");

@@ -558,6 +558,32 @@ struct ActBwdArgs {
   int n, K, deg;
 };
 
+// ---- steps over several views (accumulate.hip; filled in by api.hip) ------------------------------------
+// Element (row, column) of a strided per-model-row block.  num_points < 2^31 rows of up to 2^31 - 1 floats: the product
+// needs 64 bits, so every offset of accumulate.hip -- and the host's size check, lograst_accumulate_target_floats -- is
+// this one expression.
+__host__ __device__ inline size_t lr_acc_offset(int64_t row, int32_t stride, int32_t col) {
+  return (size_t)row * (size_t)stride + (size_t)col;
+}
+#define ACC_KEYS 6   // xyz, scaling, opacity, rotation, colors, shs
+struct AccTarget {
+  float* base;         // NULL: the key is not accumulated
+  int32_t stride;      // floats from one model row to the next
+};
+struct AccArgs {
+  AccTarget t[ACC_KEYS];
+  const float* g_a_xyz;       // dL/d(xyz), passed through
+  const int64_t* index;       // [n]: the model row of every compact row, no duplicates
+  const int32_t* radii;       // [n]: rows with radii <= 0 are skipped
+  int32_t* seen;              // [num_points]
+  int32_t num_points;
+};
+struct AccStepArgs {
+  int32_t gstride[ACC_KEYS];  // AdamKey.grad = the accumulated block of the key, rows this many floats apart
+  int32_t* seen;              // [num_points], cleared where it was > 0
+  uint8_t* moved;             // [num_points] = seen > 0, or NULL
+};
+
 // ---- fused L1 + SSIM loss (loss.hip; filled in by api.hip) ----------------------------------------------
 #define LS_WIN_TAPS 11
 struct LossArgs {

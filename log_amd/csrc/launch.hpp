@@ -79,6 +79,10 @@ hipError_t lr_launch_activate_bwd(const ActBwdArgs& a, hipStream_t s);
 hipError_t lr_launch_activate_bwd_adam(const ActBwdArgs& a, const AdamArgs& f, const float* g_a_xyz, const int32_t* radii,
                                        hipStream_t s);
 
+// accumulate.hip
+hipError_t lr_launch_activate_bwd_accumulate(const ActBwdArgs& a, const AccArgs& t, hipStream_t s);
+hipError_t lr_launch_accumulated_adam(const AdamArgs& f, const AccStepArgs& t, hipStream_t s);
+
 // lod.hip
 size_t lr_lod_scratch_bytes(int num_roots, int num_nodes, int max_child);
 hipError_t lr_launch_lod(int num_points, int num_nodes, int max_child, const int32_t* node_index, const int32_t* tree,

@@ -388,6 +388,15 @@ def _tiles(width, height):
 # n floats apart puts all streams on the same HBM channels (measured: the activation backward 0.12 -> 0.17 ms for
 # n = 1 M).  Each block is followed by this many floats (4352 B: keeps 16-byte alignment, breaks the stride).
 _BLOCK_SKEW = 1088
+# the keys of the accumulate kernels (include/lograst.h: lograst_acc_target), in the library's order, and their floats per row
+ACCUMULATE_KEYS = ("xyz", "scaling", "opacity", "rotation", "colors", "shs")
+_ACCUMULATE_WIDTHS = {"xyz": 3, "scaling": 3, "opacity": 1, "rotation": 4, "colors": 3}
+
+
+def accumulate_width(key, sh_coeffs):
+    return 3 * int(sh_coeffs) if key == "shs" else _ACCUMULATE_WIDTHS[key]
+
+
 _ITEMSIZE = {torch.float32: 4, torch.int32: 4, torch.uint8: 1, torch.int64: 8}
 
 
@@ -1043,6 +1052,77 @@ class HipBackend:
                 _ptr(g["opacity"]), _ptr(g["rotation"]), _ptr(g["colors"]), _ptr(g.get("shs")), _stream_ptr(device)))
         del ups
         return g
+
+    @staticmethod
+    def _row_block(t, device, num_points, width, what):
+        """A key's per-model-row block as the accumulate kernels address it: fp32 on ``device``, ``num_points`` rows whose
+        ``width`` floats are contiguous, any row stride >= width -> (address, row stride in floats)."""
+        if t.device != device or t.dtype != torch.float32:
+            raise ValueError(f"{what}: fp32 on the rows' device is needed")
+        if t.dim() < 2 or int(t.shape[0]) != num_points or math.prod(t.shape[1:]) != width:
+            raise ValueError(f"{what}: {tuple(t.shape)} where {num_points} rows of {width} floats are needed")
+        if num_points > 1 and t[0].numel() and not t[0].is_contiguous():
+            raise ValueError(f"{what}: the floats of a row must be contiguous")
+        stride = int(t.stride(0)) if num_points > 1 else width
+        if stride < width:
+            raise ValueError(f"{what}: rows overlap")
+        return t.data_ptr(), stride
+
+    def activate_backward_accumulate(self, raw, n, degree, campos, g_xyz, g_scaling, g_opacity, g_rotation, g_colors, index,
+                                     radii, targets, seen):
+        """One view's activation backward added by model row (lograst_activate_backward_accumulate; log_amd.multi_view).
+        targets: {key: [P, ...] fp32 view, rows any stride apart} for the keys that are accumulated (of xyz / scaling /
+        opacity / rotation / colors / shs); seen: int32[P].  log_amd.multi_view.accumulate checks the sizes."""
+        device = raw["xyz"].device
+        L = self.require(device)
+        K = int(raw["shs"].shape[1]) if "shs" in raw else 0
+        P = int(seen.numel())
+        ups = [_dev_f32(t, device) for t in (g_xyz, g_scaling, g_opacity, g_rotation, g_colors)]
+        cp = _dev_f32(campos, device).reshape(-1) if campos is not None else None
+        idx = index.detach().to(torch.int64).contiguous()
+        rad = radii.detach().to(torch.int32).contiguous()
+        if int(idx.numel()) < n or int(rad.numel()) < n:
+            raise ValueError("index / radii are shorter than the rows that are parameters")
+        if seen.device != device or seen.dtype != torch.int32 or not seen.is_contiguous():
+            raise ValueError("seen must be a contiguous int32 tensor on the rows' device")
+        slots = (_lib.LograstAccTarget * 6)()
+        for slot, key in zip(slots, ACCUMULATE_KEYS):
+            if key in targets:
+                slot.base, slot.row_stride_floats = self._row_block(targets[key], device, P, accumulate_width(key, K),
+                                                                    f"target {key}")
+        with torch.cuda.device(device):
+            _lib.check(L.lograst_activate_backward_accumulate(
+                int(n), _ptr(raw["xyz"]), _ptr(raw["scaling"]), _ptr(raw["opacity"]), _ptr(raw["rotation"]), K, int(degree),
+                _ptr(cp), _ptr(ups[0]), _ptr(ups[1]), _ptr(ups[2]), _ptr(ups[3]), _ptr(ups[4]), P, _ptr(idx), _ptr(rad),
+                slots, _ptr(seen), _stream_ptr(device)))
+        del ups
+
+    def accumulated_adam(self, seen, entries, beta1, beta2, bias_correction2_sqrt, eps, moved_out=None):
+        """One Adam step over the rows with seen > 0 (lograst_accumulated_adam; log_amd.multi_view).  entries: {key:
+        (model_param, accumulated gradient [P, ...] view, exp_avg, exp_avg_sq, max_exp_avg_sq | None, step_size)};
+        moved_out: uint8[P] or None."""
+        device = seen.device
+        L = self.require(device)
+        P = int(seen.numel())
+        if seen.dtype != torch.int32 or not seen.is_contiguous():
+            raise ValueError("seen must be a contiguous int32 tensor")
+        if moved_out is not None and (moved_out.device != device or moved_out.dtype != torch.uint8
+                                      or not moved_out.is_contiguous() or int(moved_out.numel()) != P):
+            raise ValueError("moved_out must be a contiguous uint8 tensor with one entry per model row")
+        keys = (_lib.LograstAdamKey * 6)()
+        strides = (ctypes.c_int32 * 6)()
+        for i, key in enumerate(ACCUMULATE_KEYS):
+            if key not in entries:
+                continue
+            model_p, grad, *rest = entries[key]
+            if int(model_p.shape[0]) != P:
+                raise ValueError(f"{key}: {int(model_p.shape[0])} model rows, {P} counts in seen")
+            width = self._adam_key(keys[i], device, (model_p, *rest), None, None)
+            keys[i].grad, strides[i] = self._row_block(grad, device, P, width, f"accumulated gradient of {key}")
+        with torch.cuda.device(device):
+            _lib.check(L.lograst_accumulated_adam(P, _ptr(seen), keys, strides, float(beta1), float(beta2),
+                                                  float(bias_correction2_sqrt), float(eps), _ptr(moved_out),
+                                                  _stream_ptr(device)))
 
 
 _backend = HipBackend()
