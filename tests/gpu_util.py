@@ -78,9 +78,13 @@ def hip_forward(cam, sc, bg, flavour=R.WODILATE, use_filter=True, dev="cuda:0", 
 
 
 def _lazy_list_check(saved, offs, I, W, H):
-    """-> dict(ordered_len[tiles], lazy_lists, lazy_prefix_mismatch, walk_beyond_ordered, open_words[tiles], hdr_open);
-    finishes saved["plist"]."""
+    """-> dict(ordered_len[tiles], lazy_lists, lazy_prefix_mismatch, walk_beyond_ordered, open_words[tiles], hdr_open,
+    first_window[tiles]); finishes saved["plist"].
+    first_window: where the FIRST sort pass stopped ordering a streamed list (the raw sorted[] word; the second pass leaves it
+    where the parked waves resume, so it is still there when ordered_len already says "to its end"); the list's length for
+    every other tile."""
     ordered = R.ordered_lengths_of(saved, W, H).cpu().numpy().astype(np.int64)
+    first_window = _sorted_words(saved, offs, W, H)
     open_words, hdr_open = R.parked_waves_of(saved, W, H)     # (as the forward left them: before the tails are ordered)
     open_words = open_words.cpu().numpy().astype(np.int64)
     lens = np.diff(offs.astype(np.int64))[: len(ordered)]
@@ -99,7 +103,36 @@ def _lazy_list_check(saved, offs, I, W, H):
     nc = saved["n_contrib"].cpu().numpy().astype(np.int64)
     beyond = int((nc > ordered[(ys // 16) * gx + xs // 16]).sum())
     return dict(ordered_len=ordered, lazy_lists=int(partly.sum()), lazy_prefix_mismatch=mismatch, walk_beyond_ordered=beyond,
-                open_words=open_words, hdr_open=hdr_open)
+                open_words=open_words, hdr_open=hdr_open, first_window=first_window)
+
+
+def _sorted_words(saved, offs, W, H):
+    """sorted[tiles] of a forward's tile state (log_amd/csrc/common.hpp: lr_sorted_off = lr_offsets_off + the padded
+    offsets) for the streamed lists of a lazily sorted view, min'ed with the length as lograst_ordered_lengths does."""
+    st = saved["state"]
+    tiles = len(offs) - 1
+    first = (R.tile_offsets_of(saved, W, H).data_ptr() - st.data_ptr()) // 4
+    sorted_off = first + ((tiles + 1 + 15) & ~15)
+    words = st[sorted_off:sorted_off + tiles].cpu().numpy().astype(np.int64) & 0xffffffff
+    lens = np.diff(offs.astype(np.int64))
+    lazy = int(st[9].item()) != 0                              # LR_HDR_LAZY
+    return np.where(lazy & (lens > 4096), np.minimum(words, lens), lens)
+
+
+def visits(hf):
+    """bool [I, 16]: does (wave w, block row r) = column 4 w + r visit list entry i?  Decoded from the hit-mask buffer a
+    row-split training forward wrote (zero-filled before -- log_amd.rasterizer._zero_hit_masks -- so that the slots nobody
+    wrote read as no visit).  Slot of (tile, chunk c): (offsets[tile] >> 6) + tile + c, 16 words [wave][row] each, bit j =
+    list position 64 c + j."""
+    saved = hf["_torch"][-1]
+    assert saved["hit_masks"] is not None and saved["hit_mask_form"] == 1
+    words = saved["hit_masks"].cpu().numpy().view(np.uint64).reshape(-1, 16)
+    offs = hf["tile_offsets"].astype(np.int64)
+    lens = np.diff(offs)
+    tile = np.repeat(np.arange(len(lens)), lens)
+    pos = np.arange(hf["I"]) - offs[tile]
+    slot = (offs[tile] >> 6) + tile + (pos >> 6)
+    return ((words[slot] >> (pos & 63).astype(np.uint64)[:, None]) & np.uint64(1)).astype(bool)
 
 
 class Grads(dict):

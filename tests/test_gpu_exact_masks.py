@@ -102,21 +102,6 @@ def _flavour(name):
     return {"wodilate": R.WODILATE, "upstream": R.UPSTREAM}[name]
 
 
-def _visits(hf):
-    """bool [I, 16]: does (wave w, block row r) = column 4 w + r visit list entry i?  Decoded from the buffer the forward
-    wrote (zero-filled before: the slots nobody wrote read as no visit).  Slot of (tile, chunk c): (offsets[tile] >> 6) +
-    tile + c, 16 words [wave][row] each, bit j = list position 64 c + j."""
-    saved = hf["_torch"][-1]
-    assert saved["hit_masks"] is not None and saved["hit_mask_form"] == 1
-    words = saved["hit_masks"].cpu().numpy().view(np.uint64).reshape(-1, 16)
-    offs = hf["tile_offsets"].astype(np.int64)
-    lens = np.diff(offs)
-    tile = np.repeat(np.arange(len(lens)), lens)
-    pos = np.arange(hf["I"]) - offs[tile]
-    slot = (offs[tile] >> 6) + tile + (pos >> 6)
-    return ((words[slot] >> (pos & 63).astype(np.uint64)[:, None]) & np.uint64(1)).astype(bool)
-
-
 _CACHE = {}
 
 
@@ -144,7 +129,7 @@ def _run(oracle_mod, name, flavour_name):
     finally:
         R._zero_hit_masks = prev_zero
         tune.reset_knobs()
-    vis = {k: _visits(hf[k]) for k in (1, 0)}
+    vis = {k: G.visits(hf[k]) for k in (1, 0)}
     hf[1]["_torch"][-1]["hit_masks"].zero_()
     g["zeroed"] = G.hip_backward(hf[1], dL, bwd_form="rows")
     out = dict(cam=cam, sc=sc, of=of, og=og, hf=hf, g=g, vis=vis)
