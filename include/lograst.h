@@ -761,6 +761,46 @@ int lograst_loss_backward_gain(int32_t batch, int32_t channels, int32_t height, 
                                float l1_weight, const float* grad_loss, const float* maps, float* grad_render, float* grad_gain,
                                void* scratch, size_t scratch_bytes, void* stream);
 
+/* The same loss with masks (LoG/render/renderer.py:253-266 calculate_loss with mask_ignore, :343-370 MaskForeground):
+ * mask, foreground: fp32 [batch, height, width], each through THREE ELEMENT STRIDES (b, y, x), either may be NULL but
+ * not both (without masks use the entry points above).  Per image element, one fp32 operation each and in this order:
+ *   g = gt * f + (1 - f) * background[c]      with foreground (background: fp32 [channels] on the device); else g = gt
+ *   x = g * m + render * (1 - m)              with mask; else x = render
+ *   ssim = 1 - mean(ssim_map(x, g));  l1 = mean |x - g|, or |render_l1 - g|, or |l1_gain[b, c] * render - g| (render_l1 and
+ *   l1_gain exclude each other and read the PLAIN render, as the reference's render_correct does); the means are over
+ *   all elements -- nothing is renormalised by a mask.
+ * With foreground, gt_out [batch, channels, height, width] (contiguous) receives g and is REQUIRED: it is the gt of the
+ * backward.  lograst_loss_backward_masked takes that composited gt (or the caller's gt without foreground) and the mask
+ * (without a mask the plain backward entry points on the composited gt are the backward): grad_render = (1 - m) * (SSIM
+ * part + L1 part) when the L1 term reads x; (1 - m) * SSIM part with render_l1 (grad_render_l1 = L1 part) and
+ * (1 - m) * SSIM part + gain * L1 part with l1_gain (grad_gain as lograst_loss_backward_gain).  Masks, foreground and
+ * background get no gradient.  scratch: lograst_loss_masked_scratch_bytes, 8-byte aligned, serves either call (the
+ * backward reads it only with l1_gain). */
+size_t lograst_loss_masked_scratch_bytes(int32_t batch, int32_t channels, int32_t height, int32_t width);
+int lograst_loss_forward_masked(int32_t batch, int32_t channels, int32_t height, int32_t width, const float* render,
+                                const int64_t* render_strides, const float* render_l1, const int64_t* render_l1_strides,
+                                const float* gt, const int64_t* gt_strides, const float* l1_gain, const float* mask,
+                                const int64_t* mask_strides, const float* foreground, const int64_t* foreground_strides,
+                                const float* background, float* gt_out, float ssim_weight, float l1_weight, float* out3,
+                                float* maps, void* scratch, size_t scratch_bytes, void* stream);
+int lograst_loss_backward_masked(int32_t batch, int32_t channels, int32_t height, int32_t width, const float* render,
+                                 const int64_t* render_strides, const float* render_l1, const int64_t* render_l1_strides,
+                                 const float* gt, const int64_t* gt_strides, const float* l1_gain, const float* mask,
+                                 const int64_t* mask_strides, float l1_weight, const float* grad_loss, const float* maps,
+                                 float* grad_render, float* grad_render_l1, float* grad_gain, void* scratch, size_t scratch_bytes,
+                                 void* stream);
+
+/* The bounding box of a foreground mask (MaskForeground.bound_from_mask, renderer.py:319-326) in one pass: mask fp32
+ * [batch, height, width] through three element strides; record (lograst_mask_bounds_bytes, 4-byte aligned) receives per
+ * image eight int32 {xmin, ymin, xmax, ymax, count, 0, 0, 0} over the pixels with mask > threshold (strict: a NaN is
+ * not foreground); an image without such a pixel leaves {width, height, -1, -1, 0}.  The call initialises the record
+ * itself on the same stream and allocates nothing; integer atomics only, so the result is exact and repeatable.
+ * lograst_mask_bounds_read copies batch * 8 int32 to the host and synchronises the stream (the one synchronisation). */
+size_t lograst_mask_bounds_bytes(int32_t batch);
+int lograst_mask_bounds(int32_t batch, int32_t height, int32_t width, const float* mask, const int64_t* mask_strides,
+                        float threshold, void* record, size_t record_bytes, void* stream);
+int lograst_mask_bounds_read(const void* record, int32_t batch, int32_t* host_out, void* stream);
+
 /* ---- Corrector.step (LoG/model/corrector.py:35-62): the AMSGrad step of ONE row of the view correction ----------------
  * steps i32[views]; param, grad, exp_avg, exp_avg_sq, max_exp_avg_sq f32[views, width], contiguous, 1 <= width <= 64.
  * One launch of one wave: steps[index] += 1; s = steps[index] - start_step; s < 0: nothing else is touched (grad stays).

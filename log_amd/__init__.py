@@ -18,7 +18,7 @@ def install_compute_radius():
 
 def install_all(fused_step=False, fused_loss=False, reuse_geometry=False, fused_depth_loss=False, device_densify=False,
                 device_prepare=False, device_decide=False, device_view_correction=False, device_evaluate=False, device_init=False,
-                views_per_step=None):
+                views_per_step=None, masked_loss=False):
     """Everything a LoG process needs, in one call: the LoG.cuda.compute_radius module, then every
     drop-in method assigned onto LoG's own classes (needs LoG importable): LoG.get_all, TensorTree.traverse,
     Counter.update_by_output, SparseOptimizer.step.
@@ -58,7 +58,11 @@ def install_all(fused_step=False, fused_loss=False, reuse_geometry=False, fused_
     around the installed compute_radius.
     views_per_step (opt-in, an integer K >= 1): LoG.step takes ONE Adam step per K calls, over every row that one of the K
     views saw, from gradients that the backward of LoG.get_all added by model row (log_amd.multi_view.install, installed
-    after device_prepare so that its fall-back is that module's step); None installs nothing: every step is one view wide."""
+    after device_prepare so that its fall-back is that module's step); None installs nothing: every step is one view wide.
+    masked_loss (opt-in): a mask_ignore in calculate_loss is blended inside the loss kernels, and MaskForeground.forward /
+    bound_from_mask take the mask's bounding box from one kernel, crop by views and composite the ground truth inside the
+    same loss call (log_amd.masked_loss.install, which installs log_amd.loss as well: two read-backs per foreground step,
+    the bounds and loss_dict); without it masks stay torch code around the loss."""
     install_compute_radius()
     from . import rasterizer
     rasterizer.set_geometry_reuse(bool(reuse_geometry))
@@ -86,6 +90,9 @@ def install_all(fused_step=False, fused_loss=False, reuse_geometry=False, fused_
     if device_view_correction:
         from . import view_correction
         installed.append(view_correction.install())
+    if masked_loss:
+        from . import masked_loss as masked
+        installed.append(masked.install())
     if device_evaluate:
         from . import evaluate
         installed.append(evaluate.install())

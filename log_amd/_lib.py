@@ -181,6 +181,14 @@ _SIGNATURES = {
     "lograst_loss_forward_gain": (ctypes.c_int, [c_int32] * 4 + [c_void_p] * 5 + [c_float, c_float, c_void_p, c_void_p, c_void_p,
                                                  c_size_t, c_void_p]),
     "lograst_loss_backward_gain": (ctypes.c_int, [c_int32] * 4 + [c_void_p] * 5 + [c_float] + [c_void_p] * 5 + [c_size_t, c_void_p]),
+    "lograst_loss_masked_scratch_bytes": (c_size_t, [c_int32] * 4),
+    "lograst_loss_forward_masked": (ctypes.c_int, [c_int32] * 4 + [c_void_p] * 13 + [c_float, c_float, c_void_p, c_void_p,
+                                                   c_void_p, c_size_t, c_void_p]),
+    "lograst_loss_backward_masked": (ctypes.c_int, [c_int32] * 4 + [c_void_p] * 9 + [c_float] + [c_void_p] * 6
+                                     + [c_size_t, c_void_p]),
+    "lograst_mask_bounds_bytes": (c_size_t, [c_int32]),
+    "lograst_mask_bounds": (ctypes.c_int, [c_int32] * 3 + [c_void_p, c_void_p, c_float, c_void_p, c_size_t, c_void_p]),
+    "lograst_mask_bounds_read": (ctypes.c_int, [c_void_p, c_int32, c_void_p, c_void_p]),
     "lograst_corrector_step": (ctypes.c_int, [c_int32] * 4 + [ctypes.c_double, ctypes.c_double] + [c_void_p] * 7),
     "lograst_depth_loss_record_bytes": (c_size_t, [c_int32]),
     "lograst_depth_loss_forward": (ctypes.c_int, [c_int32, c_int32] + [c_void_p] * 6 + [c_int32, c_void_p, c_void_p,

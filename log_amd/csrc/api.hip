@@ -1124,6 +1124,8 @@ static int lr_loss_args(LossArgs& a, int32_t batch, int32_t channels, int32_t he
   lr_ssim_window(a.w);
   a.scale = 0.f; a.l1_scale = 0.f; a.maps = nullptr; a.partial = nullptr; a.ntx = a.nty = 0;
   a.gain = nullptr; a.gain_partial = nullptr;
+  a.mask = nullptr; a.fg = nullptr; a.bg = nullptr; a.gt_out = nullptr;
+  for (int i = 0; i < 3; i++) a.ms[i] = a.fs[i] = 0;
   return 0;
 }
 
@@ -1219,6 +1221,111 @@ int lograst_loss_backward_gain(int32_t batch, int32_t channels, int32_t height, 
   a.gain_partial = reinterpret_cast<double*>(scratch);
   g_prof_call++;
   LR_HIP(lr_launch_loss_bwd_gain(a, grad_loss, grad_render, grad_gain, (hipStream_t)stream));
+  return LOGRAST_OK;
+}
+
+// The same loss with an ignore mask blended into the SSIM input and / or the ground truth composited over a background
+// (the MASKED instantiations), and the bounding box of a foreground mask.
+size_t lograst_loss_masked_scratch_bytes(int32_t batch, int32_t channels, int32_t height, int32_t width) {
+  return lr_loss_gain_scratch_bytes(batch, channels, height, width);      // >= lr_loss_scratch_bytes: serves either call
+}
+
+// mask [B, H, W] through three element strides: the same 32-bit in-plane offsets as the images
+static int lr_loss_mask_strides(int64_t* dst, const float* p, const int64_t* st, int32_t height, int32_t width, const char* what) {
+  for (int i = 0; i < 3; i++) dst[i] = 0;
+  if (!p) return 0;
+  if (!st) return lr_fail(LOGRAST_ERR_ARG, what);
+  const int64_t sy = st[1] < 0 ? -st[1] : st[1], sx = st[2] < 0 ? -st[2] : st[2];
+  if (sy > 0x7fffffffLL || sx > 0x7fffffffLL || (int64_t)(height - 1) * sy + (int64_t)(width - 1) * sx > 0x7fffffffLL)
+    return lr_fail(LOGRAST_ERR_ARG, "y / x strides reach beyond 2^31 - 1 elements inside one image plane");
+  for (int i = 0; i < 3; i++) dst[i] = st[i];
+  return 0;
+}
+
+int lograst_loss_forward_masked(int32_t batch, int32_t channels, int32_t height, int32_t width, const float* render,
+                                const int64_t* render_strides, const float* render_l1, const int64_t* render_l1_strides,
+                                const float* gt, const int64_t* gt_strides, const float* l1_gain, const float* mask,
+                                const int64_t* mask_strides, const float* foreground, const int64_t* foreground_strides,
+                                const float* background, float* gt_out, float ssim_weight, float l1_weight, float* out3,
+                                float* maps, void* scratch, size_t scratch_bytes, void* stream) {
+  LossArgs a;
+  if (render_l1 && l1_gain) return lr_fail(LOGRAST_ERR_ARG, "render_l1 and l1_gain are mutually exclusive: the L1 term reads one of them");
+  if (!mask && !foreground) return lr_fail(LOGRAST_ERR_ARG, "mask and foreground are both NULL: use lograst_loss_forward / _gain");
+  if (foreground && (!background || !gt_out)) return lr_fail(LOGRAST_ERR_ARG, "foreground needs background and gt_out");
+  const int rc = lr_loss_args(a, batch, channels, height, width, render, render_strides, render_l1, render_l1_strides, gt, gt_strides);
+  if (rc < 0) return rc;
+  if (!out3) return lr_fail(LOGRAST_ERR_ARG, "out3 is NULL");
+  if (rc == 1) {
+    LR_HIP(hipMemsetAsync(out3, 0, 3 * sizeof(float), (hipStream_t)stream));
+    return LOGRAST_OK;
+  }
+  if (lr_loss_mask_strides(a.ms, mask, mask_strides, height, width, "mask without strides") < 0) return LOGRAST_ERR_ARG;
+  if (lr_loss_mask_strides(a.fs, foreground, foreground_strides, height, width, "foreground without strides") < 0) return LOGRAST_ERR_ARG;
+  if (!scratch || scratch_bytes < lograst_loss_masked_scratch_bytes(batch, channels, height, width) || (reinterpret_cast<uintptr_t>(scratch) & 7u))
+    return lr_fail(LOGRAST_ERR_ARG, "loss scratch too small (lograst_loss_masked_scratch_bytes) or not 8-byte aligned");
+  a.ntx = (width - 10 + 31) / 32; a.nty = (height - 10 + 31) / 32;
+  const double count = (double)batch * channels * (double)(height - 10) * (double)(width - 10);
+  a.scale = (float)(-(double)ssim_weight / count);
+  a.maps = maps;
+  a.partial = reinterpret_cast<float*>(scratch);
+  a.gain = l1_gain;
+  a.mask = mask; a.fg = foreground; a.bg = foreground ? background : nullptr; a.gt_out = foreground ? gt_out : nullptr;
+  g_prof_call++;
+  LR_HIP(lr_launch_loss_fwd_masked(a, ssim_weight, l1_weight, out3, (hipStream_t)stream));
+  return LOGRAST_OK;
+}
+
+int lograst_loss_backward_masked(int32_t batch, int32_t channels, int32_t height, int32_t width, const float* render,
+                                 const int64_t* render_strides, const float* render_l1, const int64_t* render_l1_strides,
+                                 const float* gt, const int64_t* gt_strides, const float* l1_gain, const float* mask,
+                                 const int64_t* mask_strides, float l1_weight, const float* grad_loss, const float* maps,
+                                 float* grad_render, float* grad_render_l1, float* grad_gain, void* scratch, size_t scratch_bytes,
+                                 void* stream) {
+  LossArgs a;
+  if (render_l1 && l1_gain) return lr_fail(LOGRAST_ERR_ARG, "render_l1 and l1_gain are mutually exclusive: the L1 term reads one of them");
+  if (!mask) return lr_fail(LOGRAST_ERR_ARG, "mask is NULL: use lograst_loss_backward / _gain on the composited gt");
+  const int rc = lr_loss_args(a, batch, channels, height, width, render, render_strides, render_l1, render_l1_strides, gt, gt_strides);
+  if (rc < 0) return rc;
+  if (rc == 1) return LOGRAST_OK;
+  if (!grad_loss || !maps || !grad_render || (l1_gain && !grad_gain)) return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
+  if (a.render_l1 && !grad_render_l1) return lr_fail(LOGRAST_ERR_ARG, "render_l1 is a tensor of its own but grad_render_l1 is NULL");
+  if (lr_loss_mask_strides(a.ms, mask, mask_strides, height, width, "mask without strides") < 0) return LOGRAST_ERR_ARG;
+  if (l1_gain && (!scratch || scratch_bytes < lograst_loss_masked_scratch_bytes(batch, channels, height, width) ||
+                  (reinterpret_cast<uintptr_t>(scratch) & 7u)))
+    return lr_fail(LOGRAST_ERR_ARG, "loss scratch too small (lograst_loss_masked_scratch_bytes) or not 8-byte aligned");
+  a.ntx = (width + 31) / 32; a.nty = (height + 31) / 32;
+  a.l1_scale = (float)((double)l1_weight / ((double)batch * channels * (double)height * (double)width));
+  a.maps = const_cast<float*>(maps);
+  a.gain = l1_gain;
+  a.gain_partial = reinterpret_cast<double*>(scratch);
+  a.mask = mask;
+  g_prof_call++;
+  LR_HIP(lr_launch_loss_bwd_masked(a, grad_loss, grad_render, a.render_l1 ? grad_render_l1 : nullptr, grad_gain, (hipStream_t)stream));
+  return LOGRAST_OK;
+}
+
+size_t lograst_mask_bounds_bytes(int32_t batch) { return (size_t)(batch > 0 ? batch : 1) * MB_RECORD_INTS * sizeof(int32_t); }
+
+int lograst_mask_bounds(int32_t batch, int32_t height, int32_t width, const float* mask, const int64_t* mask_strides,
+                        float threshold, void* record, size_t record_bytes, void* stream) {
+  if (batch < 0 || height < 0 || width < 0) return lr_fail(LOGRAST_ERR_ARG, "negative batch, height or width");
+  if ((int64_t)batch * height > 0x7fffffffLL) return lr_fail(LOGRAST_ERR_ARG, "more than 2^31 - 1 image rows");
+  if (batch == 0) return LOGRAST_OK;
+  if (!record || record_bytes < lograst_mask_bounds_bytes(batch) || (reinterpret_cast<uintptr_t>(record) & 3u))
+    return lr_fail(LOGRAST_ERR_ARG, "mask bounds record too small (lograst_mask_bounds_bytes) or not 4-byte aligned");
+  if ((int64_t)height * width > 0 && (!mask || !mask_strides)) return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
+  static const int64_t none[3] = {0, 0, 0};
+  LR_HIP(lr_launch_mask_bounds(batch, height, width, mask, mask_strides ? mask_strides : none, threshold,
+                               reinterpret_cast<int32_t*>(record), (hipStream_t)stream));
+  return LOGRAST_OK;
+}
+
+int lograst_mask_bounds_read(const void* record, int32_t batch, int32_t* host_out, void* stream) {
+  if (batch < 0) return lr_fail(LOGRAST_ERR_ARG, "negative batch");
+  if (batch == 0) return LOGRAST_OK;
+  if (!record || !host_out) return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
+  LR_HIP(hipMemcpyAsync(host_out, record, (size_t)batch * MB_RECORD_INTS * sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
+  LR_HIP(hipStreamSynchronize((hipStream_t)stream));
   return LOGRAST_OK;
 }
 

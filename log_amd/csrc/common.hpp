@@ -597,6 +597,11 @@ struct LossArgs {
   int32_t B, C, H, W, ntx, nty;                                    // ntx * nty tiles per plane (of outputs forward, of the image backward)
   const float* gain;                                               // lograst_loss_*_gain: [B, C], the L1 term reads gain * render; else NULL
   double* gain_partial;                                            // backward with gain: one double per workgroup
+  // lograst_loss_*_masked only (the MASKED instantiations; NULL / 0 everywhere else)
+  const float* mask; const float* fg;                              // [B, H, W] ignore mask / foreground mask, either may be NULL
+  int64_t ms[3], fs[3];                                            // element strides (b, y, x)
+  const float* bg;                                                 // [C] background of the composite (with fg)
+  float* gt_out;                                                   // forward: [B, C, H, W] contiguous composited gt, or NULL
 };
 
 // ---- host-side launch bookkeeping (api.hip) ------------------------------------------------------

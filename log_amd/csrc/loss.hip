@@ -27,6 +27,15 @@
 // gradient and, per workgroup, the double sum of sign * render, which loss_gain_reduce_kernel adds per (b, c) in a fixed
 // order.  The <false> instantiations are the kernels as they were.
 //
+// Masks.  The second template flag (lograst_loss_*_masked) takes LoG's mask_ignore blend and MaskForeground's composite
+// (renderer.py:255, :356) into the staging of the tile: g = gt * f + (1 - f) * bg[c], x = g * m + render * (1 - m), one fp32
+// operation each in the order of the torch expressions, so the results carry the bits of the torch code around the unmasked
+// kernels.  The moments are those of (x, g); the L1 term reads x, or render_l1 / gain * render unblended, as the reference's
+// render_correct is; the pixel's owner writes g (gt_out), which is the gt of the backward; the backward recomputes x and
+// scales what x receives by (1 - m).  In the forward either mask may be NULL (uniform per launch); the masked backward
+// always has the ignore mask.  Everything of it stands behind
+// `if constexpr (MASKED)`: the <.., false> instantiations are the kernels as they were.
+//
 // Determinism: fixed tap order (ascending tap index, horizontal then vertical), explicit fmaf only, per-workgroup
 // partial sums reduced in a fixed order by one workgroup in double -- no floating-point atomics anywhere.
 #include "common.hpp"
@@ -80,7 +89,7 @@ LR_DEV double ls_block_sum(double v, double* ws) {
 
 // The moments travel in pairs -- (render, gt), (mu1, mu2), (e11, e22) -- one 8-byte LDS access and one packed fp32
 // instruction (v_pk_fma_f32 / v_pk_mul_f32) per pair; element for element the same IEEE operations as scalar code.
-template <bool GAIN>
+template <bool GAIN, bool MASKED>
 __global__ void __launch_bounds__(LS_THREADS)
 loss_fwd_kernel(LossArgs a) {
   __shared__ lr_f2 srg[LS_IN * LS_IN];                      // (render - 0.5, gt - 0.5)
@@ -102,10 +111,21 @@ loss_fwd_kernel(LossArgs a) {
   const int rsy = (int)a.rs[2], rsx = (int)a.rs[3], gsy = (int)a.gs[2], gsx = (int)a.gs[3], lsy = (int)a.ls[2], lsx = (int)a.ls[3];
   float gain = 1.f;
   if constexpr (GAIN) gain = a.gain[b * a.C + c];
+  // MASKED: the ignore mask and the foreground mask of image b (either may be NULL: uniform per launch), shared by the
+  // C workgroups of a tile, which are adjacent in blockIdx
+  const float* mp = nullptr;
+  const float* fp = nullptr;
+  int msy = 0, msx = 0, fsy = 0, fsx = 0;
+  float bgc = 0.f;
+  if constexpr (MASKED) {
+    if (a.mask) { mp = a.mask + (int64_t)b * a.ms[0]; msy = (int)a.ms[1]; msx = (int)a.ms[2]; }
+    if (a.fg) { fp = a.fg + (int64_t)b * a.fs[0]; fsy = (int)a.fs[1]; fsx = (int)a.fs[2]; bgc = a.bg[c]; }
+  }
 
   // stage the input tile: all of a thread's loads are requested before the first is used.  Every image pixel belongs to
   // exactly one tile's L1 sum (the last tile of a row / column also owns its halo).
   float rv[LS_STAGE], gv[LS_STAGE], lv[LS_STAGE];
+  [[maybe_unused]] float mv[LS_STAGE], fv[LS_STAGE];        // MASKED only
   bool own[LS_STAGE];
 #pragma unroll
   for (int u = 0; u < LS_STAGE; u++) {
@@ -117,14 +137,34 @@ loss_fwd_kernel(LossArgs a) {
     rv[u] = in ? rp[y * rsy + x * rsx] : LS_CENTER;
     gv[u] = in ? gp[y * gsy + x * gsx] : LS_CENTER;
     lv[u] = (lp && own[u]) ? lp[y * lsy + x * lsx] : 0.f;
+    if constexpr (MASKED) {
+      mv[u] = (mp && in) ? mp[y * msy + x * msx] : 0.f;
+      fv[u] = (fp && in) ? fp[y * fsy + x * fsx] : 1.f;
+    }
   }
   float l1 = 0.f;
 #pragma unroll
   for (int u = 0; u < LS_STAGE; u++) {
     const int i = tid + u * LS_THREADS;
-    if constexpr (GAIN) { if (own[u]) l1 += fabsf(gain * rv[u] - gv[u]); }
-    else if (own[u]) l1 += fabsf((lp ? lv[u] : rv[u]) - gv[u]);
-    if (i < LS_IN * LS_IN) srg[i] = lr_f2{rv[u] - LS_CENTER, gv[u] - LS_CENTER};
+    if constexpr (MASKED) {
+      // gt = gt * f + (1 - f) * bg, then the SSIM input x = gt * m + render * (1 - m): one fp32 operation each, in the
+      // order of the reference's torch expressions; out-of-image elements stay LS_CENTER for both
+      const int ly = i / LS_IN, lx = i - ly * LS_IN;
+      const int y = y0 + ly, x = x0 + lx;
+      const bool in = i < LS_IN * LS_IN && y < a.H && x < a.W;
+      float g = gv[u], xs = rv[u];
+      if (in) {
+        if (fp) g = (g * fv[u]) + ((1.f - fv[u]) * bgc);
+        if (a.gt_out && own[u]) a.gt_out[(((int64_t)b * a.C + c) * a.H + y) * a.W + x] = g;
+        if (mp) xs = (g * mv[u]) + (xs * (1.f - mv[u]));
+      }
+      if (own[u]) l1 += fabsf((GAIN ? gain * rv[u] : (lp ? lv[u] : xs)) - g);   // gain and render_l1 read the plain render
+      if (i < LS_IN * LS_IN) srg[i] = lr_f2{xs - LS_CENTER, g - LS_CENTER};
+    } else {
+      if constexpr (GAIN) { if (own[u]) l1 += fabsf(gain * rv[u] - gv[u]); }
+      else if (own[u]) l1 += fabsf((lp ? lv[u] : rv[u]) - gv[u]);
+      if (i < LS_IN * LS_IN) srg[i] = lr_f2{rv[u] - LS_CENTER, gv[u] - LS_CENTER};
+    }
   }
   __syncthreads();
 
@@ -271,7 +311,7 @@ loss_gain_reduce_kernel(const double* __restrict__ partial, int C, uint32_t tile
   if (threadIdx.x == 0) grad_gain[blockIdx.x] = (float)(((double)grad_loss[0] * (double)l1_scale) * s[0]);
 }
 
-template <bool GAIN>
+template <bool GAIN, bool MASKED>
 __global__ void __launch_bounds__(LS_THREADS)
 loss_bwd_kernel(LossArgs a, const float* __restrict__ grad_loss, float* __restrict__ g_render, float* __restrict__ g_render_l1) {
   __shared__ lr_f2 sm01[LS_IN * LS_IN];                     // (maps0, maps1)
@@ -301,6 +341,12 @@ loss_bwd_kernel(LossArgs a, const float* __restrict__ grad_loss, float* __restri
   float gain = 1.f;
   if constexpr (GAIN) gain = a.gain[b * a.C + c];
   float pr[LS_ROWS], pg[LS_ROWS], pl[LS_ROWS];
+  // MASKED only: the ignore mask, never NULL here (a.gt is the composited gt; a composite without a blend takes the
+  // unmasked backward on it)
+  [[maybe_unused]] float pm[LS_ROWS];
+  const float* mp = nullptr;
+  int msy = 0, msx = 0;
+  if constexpr (MASKED) { mp = a.mask + (int64_t)b * a.ms[0]; msy = (int)a.ms[1]; msx = (int)a.ms[2]; }
 #pragma unroll
   for (int j = 0; j < LS_ROWS; j++) {
     const int y = y0 + yq + j;
@@ -308,6 +354,7 @@ loss_bwd_kernel(LossArgs a, const float* __restrict__ grad_loss, float* __restri
     pr[j] = in ? rp[y * rsy + x * rsx] : 0.f;
     pg[j] = in ? gp[y * gsy + x * gsx] : 0.f;
     pl[j] = (in && lp) ? lp[y * lsy + x * lsx] : 0.f;
+    if constexpr (MASKED) pm[j] = in ? mp[y * msy + x * msx] : 0.f;
   }
 
   // maps at q = p - 10 .. p (zero outside the valid region); all loads requested before the first is used
@@ -375,15 +422,31 @@ loss_bwd_kernel(LossArgs a, const float* __restrict__ grad_loss, float* __restri
     const int y = y0 + yq + j;
     if (y >= a.H || (GAIN && x >= a.W)) continue;
     const float r = pr[j], g = pg[j];
-    float G = gl * lr_fma(g - LS_CENTER, a2[j], lr_fma(2.f * (r - LS_CENTER), a01[j].y, a01[j].x));
-    const float d = (GAIN ? gain * r : (lp ? pl[j] : r)) - g;
-    const float sgn = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);       // sign(0) = 0, as torch.nn.L1Loss
-    const float l1g = gl * (a.l1_scale * sgn);
-    const int o = y * a.W + x;
-    if constexpr (GAIN) { G += gain * l1g; sr += sgn * r; }
-    else if (lp) g_render_l1[out_plane + o] = l1g;
-    else G += l1g;
-    g_render[out_plane + o] = G;
+    if constexpr (MASKED) {
+      // the SSIM input is the blend x (recomputed with the forward's operations); render gets (1 - m) of what x gets,
+      // the gain's and render_l1's L1 terms read the plain render and pass unscaled
+      const float keep = 1.f - pm[j];
+      const float xs = (g * pm[j]) + (r * keep);
+      float G = gl * lr_fma(g - LS_CENTER, a2[j], lr_fma(2.f * (xs - LS_CENTER), a01[j].y, a01[j].x));
+      const float d = (GAIN ? gain * r : (lp ? pl[j] : xs)) - g;
+      const float sgn = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
+      const float l1g = gl * (a.l1_scale * sgn);
+      const int o = y * a.W + x;
+      if constexpr (GAIN) { G = (keep * G) + gain * l1g; sr += sgn * r; }
+      else if (lp) { g_render_l1[out_plane + o] = l1g; G = keep * G; }
+      else { G += l1g; G = keep * G; }
+      g_render[out_plane + o] = G;
+    } else {
+      float G = gl * lr_fma(g - LS_CENTER, a2[j], lr_fma(2.f * (r - LS_CENTER), a01[j].y, a01[j].x));
+      const float d = (GAIN ? gain * r : (lp ? pl[j] : r)) - g;
+      const float sgn = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);       // sign(0) = 0, as torch.nn.L1Loss
+      const float l1g = gl * (a.l1_scale * sgn);
+      const int o = y * a.W + x;
+      if constexpr (GAIN) { G += gain * l1g; sr += sgn * r; }
+      else if (lp) g_render_l1[out_plane + o] = l1g;
+      else G += l1g;
+      g_render[out_plane + o] = G;
+    }
   }
   if constexpr (GAIN) {
     __shared__ double gws[4];
@@ -395,8 +458,8 @@ loss_bwd_kernel(LossArgs a, const float* __restrict__ grad_loss, float* __restri
 hipError_t lr_launch_loss_fwd(const LossArgs& a, float wa, float wb, float* out3, hipStream_t s) {
   const uint32_t blocks = (uint32_t)a.ntx * (uint32_t)a.nty * (uint32_t)a.B * (uint32_t)a.C;
   lr_prof_begin(LRK_LOSS_FWD, s);
-  if (a.gain) hipLaunchKernelGGL(loss_fwd_kernel<true>, dim3(blocks), dim3(LS_THREADS), 0, s, a);
-  else hipLaunchKernelGGL(loss_fwd_kernel<false>, dim3(blocks), dim3(LS_THREADS), 0, s, a);
+  if (a.gain) hipLaunchKernelGGL((loss_fwd_kernel<true, false>), dim3(blocks), dim3(LS_THREADS), 0, s, a);
+  else hipLaunchKernelGGL((loss_fwd_kernel<false, false>), dim3(blocks), dim3(LS_THREADS), 0, s, a);
   const double count = (double)a.B * a.C * (double)(a.H - LS_HALO) * (double)(a.W - LS_HALO);
   const double count_l1 = (double)a.B * a.C * (double)a.H * (double)a.W;
   hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(LS_RED_THREADS), 0, s, reinterpret_cast<const float2*>(a.partial), blocks, 1.0 / count,
@@ -408,7 +471,7 @@ hipError_t lr_launch_loss_fwd(const LossArgs& a, float wa, float wb, float* out3
 hipError_t lr_launch_loss_bwd(const LossArgs& a, const float* grad_loss, float* g_render, float* g_render_l1, hipStream_t s) {
   const uint32_t blocks = (uint32_t)a.ntx * (uint32_t)a.nty * (uint32_t)a.B * (uint32_t)a.C;
   lr_prof_begin(LRK_LOSS_BWD, s);
-  hipLaunchKernelGGL(loss_bwd_kernel<false>, dim3(blocks), dim3(LS_THREADS), 0, s, a, grad_loss, g_render, g_render_l1);
+  hipLaunchKernelGGL((loss_bwd_kernel<false, false>), dim3(blocks), dim3(LS_THREADS), 0, s, a, grad_loss, g_render, g_render_l1);
   lr_prof_end(LRK_LOSS_BWD, s);
   return hipGetLastError();
 }
@@ -416,9 +479,122 @@ hipError_t lr_launch_loss_bwd(const LossArgs& a, const float* grad_loss, float* 
 hipError_t lr_launch_loss_bwd_gain(const LossArgs& a, const float* grad_loss, float* g_render, float* grad_gain, hipStream_t s) {
   const uint32_t tiles = (uint32_t)a.ntx * (uint32_t)a.nty, planes = (uint32_t)a.B * (uint32_t)a.C;
   lr_prof_begin(LRK_LOSS_BWD, s);
-  hipLaunchKernelGGL(loss_bwd_kernel<true>, dim3(tiles * planes), dim3(LS_THREADS), 0, s, a, grad_loss, g_render, (float*)nullptr);
+  hipLaunchKernelGGL((loss_bwd_kernel<true, false>), dim3(tiles * planes), dim3(LS_THREADS), 0, s, a, grad_loss, g_render, (float*)nullptr);
   hipLaunchKernelGGL(loss_gain_reduce_kernel, dim3(planes), dim3(LS_GAIN_RED_THREADS), 0, s, (const double*)a.gain_partial, (int)a.C,
                      tiles, grad_loss, a.l1_scale, grad_gain);
   lr_prof_end(LRK_LOSS_BWD, s);
+  return hipGetLastError();
+}
+
+// The MASKED instantiations (lograst_loss_*_masked): a.mask and / or a.fg set, a.gain selects GAIN.
+hipError_t lr_launch_loss_fwd_masked(const LossArgs& a, float wa, float wb, float* out3, hipStream_t s) {
+  const uint32_t blocks = (uint32_t)a.ntx * (uint32_t)a.nty * (uint32_t)a.B * (uint32_t)a.C;
+  lr_prof_begin(LRK_LOSS_FWD, s);
+  if (a.gain) hipLaunchKernelGGL((loss_fwd_kernel<true, true>), dim3(blocks), dim3(LS_THREADS), 0, s, a);
+  else hipLaunchKernelGGL((loss_fwd_kernel<false, true>), dim3(blocks), dim3(LS_THREADS), 0, s, a);
+  const double count = (double)a.B * a.C * (double)(a.H - LS_HALO) * (double)(a.W - LS_HALO);
+  const double count_l1 = (double)a.B * a.C * (double)a.H * (double)a.W;
+  hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(LS_RED_THREADS), 0, s, reinterpret_cast<const float2*>(a.partial), blocks, 1.0 / count,
+                     1.0 / count_l1, wa, wb, out3);
+  lr_prof_end(LRK_LOSS_FWD, s);
+  return hipGetLastError();
+}
+
+hipError_t lr_launch_loss_bwd_masked(const LossArgs& a, const float* grad_loss, float* g_render, float* g_render_l1, float* grad_gain,
+                                     hipStream_t s) {
+  const uint32_t tiles = (uint32_t)a.ntx * (uint32_t)a.nty, planes = (uint32_t)a.B * (uint32_t)a.C;
+  lr_prof_begin(LRK_LOSS_BWD, s);
+  if (a.gain) {
+    hipLaunchKernelGGL((loss_bwd_kernel<true, true>), dim3(tiles * planes), dim3(LS_THREADS), 0, s, a, grad_loss, g_render, (float*)nullptr);
+    hipLaunchKernelGGL(loss_gain_reduce_kernel, dim3(planes), dim3(LS_GAIN_RED_THREADS), 0, s, (const double*)a.gain_partial, (int)a.C,
+                       tiles, grad_loss, a.l1_scale, grad_gain);
+  } else {
+    hipLaunchKernelGGL((loss_bwd_kernel<false, true>), dim3(tiles * planes), dim3(LS_THREADS), 0, s, a, grad_loss, g_render, g_render_l1);
+  }
+  lr_prof_end(LRK_LOSS_BWD, s);
+  return hipGetLastError();
+}
+
+// ---- bounding box of a foreground mask (MaskForeground.bound_from_mask, renderer.py:319-326) ------------------------
+// One pass over a strided fp32 mask [B, H, W]: per image the int32 record {xmin, ymin, xmax, ymax, count, 0, 0, 0} of the
+// pixels with mask > threshold (strict: a NaN is not foreground).  A workgroup takes MB_ROWS row(s) of one image, lane after
+// lane along x (consecutive dwords of a row with stride 1); the five integers are reduced over the wave by shuffles, over
+// the four waves through LDS, and one thread commits them with integer atomicMin / atomicMax / atomicAdd: exact and
+// independent of the order.
+#define MB_THREADS 256
+#define MB_ROWS 4                  // rows per workgroup: 270 workgroups at 1080p (one row each: four times the atomics on one
+                                   // record, measured twice as slow)
+#define MB_UNROLL 4                // loads in flight per thread
+
+__global__ void mask_bounds_init_kernel(int32_t* __restrict__ record, int B, int H, int W) {
+  for (int b = (int)threadIdx.x; b < B; b += (int)blockDim.x) {
+    int32_t* r = record + (size_t)b * MB_RECORD_INTS;
+    r[0] = W; r[1] = H; r[2] = -1; r[3] = -1;
+    r[4] = 0; r[5] = 0; r[6] = 0; r[7] = 0;
+  }
+}
+
+__global__ void __launch_bounds__(MB_THREADS)
+mask_bounds_kernel(const float* __restrict__ mask, int64_t sb, int64_t sy, int64_t sx, int H, int W, int strips, float threshold,
+                   int32_t* __restrict__ record) {
+  __shared__ int32_t red[4][5];
+  const int b = (int)(blockIdx.x / (uint32_t)strips), strip = (int)(blockIdx.x - (uint32_t)b * (uint32_t)strips);
+  const float* mp = mask + (int64_t)b * sb;
+  const int yb = strip * MB_ROWS, ye = min(yb + MB_ROWS, H);
+  int xmin = W, ymin = H, xmax = -1, ymax = -1, count = 0;
+  for (int y = yb; y < ye; y++) {
+    const float* row = mp + (int64_t)y * sy;
+    for (int xb = (int)threadIdx.x; xb < W; xb += MB_UNROLL * MB_THREADS) {
+      float v[MB_UNROLL];                                           // all of a round's loads are requested before the first is used
+#pragma unroll
+      for (int u = 0; u < MB_UNROLL; u++) {
+        const int x = xb + u * MB_THREADS;
+        v[u] = x < W ? row[(int64_t)x * sx] : threshold;            // (threshold > threshold is false)
+      }
+#pragma unroll
+      for (int u = 0; u < MB_UNROLL; u++) {
+        const int x = xb + u * MB_THREADS;
+        if (v[u] > threshold) {
+          xmin = min(xmin, x); xmax = max(xmax, x);
+          ymin = min(ymin, y); ymax = max(ymax, y);
+          count++;
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    xmin = min(xmin, __shfl_down(xmin, d)); ymin = min(ymin, __shfl_down(ymin, d));
+    xmax = max(xmax, __shfl_down(xmax, d)); ymax = max(ymax, __shfl_down(ymax, d));
+    count += __shfl_down(count, d);
+  }
+  const int wave = (int)(threadIdx.x >> 6);
+  if ((threadIdx.x & 63u) == 0) { red[wave][0] = xmin; red[wave][1] = ymin; red[wave][2] = xmax; red[wave][3] = ymax; red[wave][4] = count; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int w = 1; w < 4; w++) {
+      xmin = min(xmin, red[w][0]); ymin = min(ymin, red[w][1]);
+      xmax = max(xmax, red[w][2]); ymax = max(ymax, red[w][3]);
+      count += red[w][4];
+    }
+    if (count > 0) {
+      // The record only ever tightens, so a bound that an earlier read of it already meets needs no atomic (a stale read
+      // costs an atomic, never a result): a box-shaped mask leaves most workgroups the count alone.
+      int32_t* r = record + (size_t)b * MB_RECORD_INTS;
+      if (xmin < __hip_atomic_load(r + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(r + 0, xmin);
+      if (ymin < __hip_atomic_load(r + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(r + 1, ymin);
+      if (xmax > __hip_atomic_load(r + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(r + 2, xmax);
+      if (ymax > __hip_atomic_load(r + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(r + 3, ymax);
+      atomicAdd(r + 4, count);
+    }
+  }
+}
+
+hipError_t lr_launch_mask_bounds(int B, int H, int W, const float* mask, const int64_t* ms, float threshold, int32_t* record, hipStream_t s) {
+  const int strips = (H + MB_ROWS - 1) / MB_ROWS;
+  hipLaunchKernelGGL(mask_bounds_init_kernel, dim3(1), dim3(64), 0, s, record, B, H, W);
+  if (strips > 0 && W > 0) hipLaunchKernelGGL(mask_bounds_kernel, dim3((uint32_t)B * (uint32_t)strips), dim3(MB_THREADS), 0, s, mask, ms[0], ms[1], ms[2], H, W, strips,
+                     threshold, record);
   return hipGetLastError();
 }

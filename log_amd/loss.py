@@ -202,15 +202,25 @@ def _make_ssim_forward(original):
     return forward
 
 
+def _modules_covered(self):
+    """The renderer's loss modules are the ones the kernels compute: SSIM(11) without padding and a mean L1Loss."""
+    ssim_mod = getattr(self, "ssim_loss", None)
+    return (getattr(ssim_mod, "window_size", None) == WINDOW and getattr(ssim_mod, "padding", 0) == 0
+            and isinstance(getattr(self, "l1_loss", None), torch.nn.L1Loss) and self.l1_loss.reduction == "mean")
+
+
+_masked_branch = None     # log_amd.masked_loss.set_enabled(True) puts its mask_ignore branch here; None: the torch blend below
+
+
 def _make_calculate_loss(original):
     def calculate_loss(self, gt_image, render, output, mask_ignore=None):
         """renderer.py:253-266 with the two losses in one kernel and ONE read-back for loss_dict."""
-        ssim_mod = getattr(self, "ssim_loss", None)
         if not (_fusable(gt_image, render) and gt_image.shape == render.shape and not gt_image.requires_grad
-                and getattr(ssim_mod, "window_size", None) == WINDOW and getattr(ssim_mod, "padding", 0) == 0
-                and isinstance(getattr(self, "l1_loss", None), torch.nn.L1Loss) and self.l1_loss.reduction == "mean"):
+                and _modules_covered(self)):
             return original(self, gt_image, render, output, mask_ignore)
         if mask_ignore is not None:
+            if _masked_branch is not None and _masked_branch(gt_image, render, output, mask_ignore):
+                return
             render = gt_image * mask_ignore[:, None] + render * (1 - mask_ignore[:, None])
         render_l1 = output["render_correct"][:, :3] if "render_correct" in output.keys() else render
         if not (_fusable(render_l1) and render_l1.shape == render.shape):

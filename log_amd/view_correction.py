@@ -15,7 +15,8 @@
   is one image gradient instead of two and their sum.  ``view_correction.grad`` comes out dense ``[V, 3]`` with the
   gradient in the handed-out rows, as the reference leaves it.  A ``mask_ignore`` blend goes to the SSIM input only, as in
   the reference: the SSIM term then comes from the kernels without gain on the blend, the L1 term from the kernels with
-  gain on the plain render.
+  gain on the plain render -- or, with ``log_amd.masked_loss.set_enabled(True)``, both from ONE call of the masked kernels
+  with gain and mask.
 
 What this does not cover goes to the method that was there before ``install()``, counted by reason in ``stats()``:
 ``step`` for tensors off the GPU or not float32 (or not contiguous), ``use_amsgrad`` false, ``view_correction.grad is None``
@@ -30,6 +31,7 @@ import torch
 
 from . import _lib
 from . import loss as _loss
+from . import masked_loss as _masked
 from . import rasterizer as _r
 from ._dropin import DropIns, Fallback
 
@@ -157,6 +159,8 @@ def calculate_loss(self, gt_image, render, output, mask_ignore=None):
         return dropins.fall_back("calculate_loss", why, self, gt_image, render, output, mask_ignore)
     if mask_ignore is None:
         loss, values = _loss._fused_gain(render, gt_image, gain, 0.2, 0.8)
+    elif _masked.enabled() and _masked._mask_fits(mask_ignore, render):
+        loss, values, _ = _masked._fused_masked(render, gt_image, mask_ignore, None, None, None, gain, 0.2, 0.8)
     else:
         blend = gt_image * mask_ignore[:, None] + render * (1 - mask_ignore[:, None])
         ssim = _loss._fused(blend, gt_image, None, 1.0, 0.0)[0]
