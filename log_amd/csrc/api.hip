@@ -1086,8 +1086,19 @@ int lograst_counter_update(int32_t nv, const int64_t* visible_index, const float
 }
 
 // ---- fused L1 + SSIM loss (loss.hip) ----------------------------------------------------------------------
+// Three forms, one host body per direction: the plain loss; _gain, with the L1 term on gain[b, c] * render (LoG's view
+// correction): no render_l1 tensor, one image gradient and the gradient of the gain; _masked, with an ignore mask blended into
+// the SSIM input and / or the ground truth composited over a background (the MASKED instantiations).
 size_t lograst_loss_scratch_bytes(int32_t batch, int32_t channels, int32_t height, int32_t width) {
   return lr_loss_scratch_bytes(batch, channels, height, width);
+}
+
+size_t lograst_loss_gain_scratch_bytes(int32_t batch, int32_t channels, int32_t height, int32_t width) {
+  return lr_loss_gain_scratch_bytes(batch, channels, height, width);
+}
+
+size_t lograst_loss_masked_scratch_bytes(int32_t batch, int32_t channels, int32_t height, int32_t width) {
+  return lr_loss_gain_scratch_bytes(batch, channels, height, width);      // >= lr_loss_scratch_bytes: serves either call
 }
 
 // the window: exp(-(x-5)^2 / (2 * 1.5^2)) in double, normalised, rounded to fp32 once (the loss's and the metric's)
@@ -1097,149 +1108,162 @@ static void lr_ssim_window(float* w) {
   for (int k = 0; k < LS_WIN_TAPS; k++) w[k] = (float)(g[k] / sum);
 }
 
-// Geometry and input checks shared by the two entry points; fills everything of LossArgs but the tile grid.
-static int lr_loss_args(LossArgs& a, int32_t batch, int32_t channels, int32_t height, int32_t width, const float* render,
-                        const int64_t* rs, const float* render_l1, const int64_t* ls, const float* gt, const int64_t* gs) {
-  if (batch < 0 || channels < 0) return lr_fail(LOGRAST_ERR_ARG, "negative batch or channel count");
-  if (height < LS_WIN_TAPS || width < LS_WIN_TAPS)
+// Inside one image plane the kernels address with 32-bit offsets y * stride_y + x * stride_x (the loss's images and masks, the
+// evaluation's images): true when no pixel of the plane lies beyond 2^31 - 1 elements, a negative stride taken by magnitude.
+static bool lr_plane_in_32bit(int64_t stride_y, int64_t stride_x, int32_t height, int32_t width) {
+  const int64_t sy = stride_y < 0 ? -stride_y : stride_y, sx = stride_x < 0 ? -stride_x : stride_x;
+  return sy <= 0x7fffffffLL && sx <= 0x7fffffffLL && (int64_t)(height - 1) * sy + (int64_t)(width - 1) * sx <= 0x7fffffffLL;
+}
+
+// What one call of an entry point hands to the shared bodies.  The leading members are what (nearly) every entry point has,
+// in the order of its parameters: `LossCall c = {batch, ..., stream}` leaves what follows zero -- a pointer the entry point
+// does not have is NULL.
+struct LossCall {
+  int32_t batch, channels, height, width;
+  const float* render; const int64_t* rs;
+  const float* render_l1; const int64_t* ls;
+  const float* gt; const int64_t* gs;
+  const float* gain;
+  void* scratch; size_t scratch_bytes;
+  void* stream;
+  bool gain_required;                                      // _gain: a NULL l1_gain is an error, not the plain loss
+  const float* mask; const int64_t* ms;
+  const float* fg; const int64_t* fs; const float* bg; float* gt_out;
+  size_t scratch_min; const char* scratch_fn;              // the size the entry point accepts, the sizing function its message names
+  const char* precondition;                                // the entry point's own precondition that does not hold, or NULL
+};
+
+static int lr_loss_scratch(const LossCall& c) {
+  if (c.scratch && c.scratch_bytes >= c.scratch_min && !(reinterpret_cast<uintptr_t>(c.scratch) & 7u)) return 0;
+  return lr_fail(LOGRAST_ERR_ARG, std::string("loss scratch too small (") + c.scratch_fn + ") or not 8-byte aligned");
+}
+
+// Geometry and image checks of both directions; fills the geometry, the images and the window of LossArgs and leaves the
+// rest zero.  -> 1 for the empty batch, < 0 after lr_fail.
+static int lr_loss_args(LossArgs& a, const LossCall& c) {
+  a = LossArgs{};
+  if (c.precondition) return lr_fail(LOGRAST_ERR_ARG, c.precondition);
+  if (c.batch < 0 || c.channels < 0) return lr_fail(LOGRAST_ERR_ARG, "negative batch or channel count");
+  if (c.height < LS_WIN_TAPS || c.width < LS_WIN_TAPS)
     return lr_fail(LOGRAST_ERR_ARG, "image smaller than the 11-pixel window of the SSIM (height and width must be >= 11)");
-  if ((int64_t)batch * channels * (int64_t)height * width > 0x7fffffffLL) return lr_fail(LOGRAST_ERR_ARG, "more than 2^31 - 1 image elements");
-  if ((int64_t)batch * channels == 0) return 1;
-  if (!render || !gt || !rs || !gs || (render_l1 && !ls)) return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
-  // inside a (b, c) plane the kernels address with 32-bit offsets y * stride_y + x * stride_x
-  for (const int64_t* st : {rs, gs, render_l1 ? ls : rs}) {
-    const int64_t sy = st[2] < 0 ? -st[2] : st[2], sx = st[3] < 0 ? -st[3] : st[3];
-    if (sy > 0x7fffffffLL || sx > 0x7fffffffLL || (int64_t)(height - 1) * sy + (int64_t)(width - 1) * sx > 0x7fffffffLL)
+  if ((int64_t)c.batch * c.channels * (int64_t)c.height * c.width > 0x7fffffffLL)
+    return lr_fail(LOGRAST_ERR_ARG, "more than 2^31 - 1 image elements");
+  if ((int64_t)c.batch * c.channels == 0) return 1;
+  if (!c.render || !c.gt || !c.rs || !c.gs || (c.render_l1 && !c.ls)) return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
+  for (const int64_t* st : {c.rs, c.gs, c.render_l1 ? c.ls : c.rs})
+    if (!lr_plane_in_32bit(st[2], st[3], c.height, c.width))
       return lr_fail(LOGRAST_ERR_ARG, "y / x strides reach beyond 2^31 - 1 elements inside one image plane");
-  }
-  bool same = render_l1 == render;
+  bool same = c.render_l1 == c.render;
   for (int i = 0; i < 4; i++) {
-    a.rs[i] = rs[i]; a.gs[i] = gs[i];
-    a.ls[i] = render_l1 ? ls[i] : 0;
-    same = same && (!render_l1 || ls[i] == rs[i]);
+    a.rs[i] = c.rs[i]; a.gs[i] = c.gs[i];
+    a.ls[i] = c.render_l1 ? c.ls[i] : 0;
+    same = same && (!c.render_l1 || c.ls[i] == c.rs[i]);
   }
-  a.render = render; a.gt = gt;
-  a.render_l1 = (render_l1 && !same) ? render_l1 : nullptr;
-  a.B = batch; a.C = channels; a.H = height; a.W = width;
+  a.render = c.render; a.gt = c.gt;
+  a.render_l1 = (c.render_l1 && !same) ? c.render_l1 : nullptr;
+  a.B = c.batch; a.C = c.channels; a.H = c.height; a.W = c.width;
   lr_ssim_window(a.w);
-  a.scale = 0.f; a.l1_scale = 0.f; a.maps = nullptr; a.partial = nullptr; a.ntx = a.nty = 0;
-  a.gain = nullptr; a.gain_partial = nullptr;
-  a.mask = nullptr; a.fg = nullptr; a.bg = nullptr; a.gt_out = nullptr;
-  for (int i = 0; i < 3; i++) a.ms[i] = a.fs[i] = 0;
   return 0;
+}
+
+// mask [B, H, W] through three element strides: the same 32-bit in-plane offsets as the images
+static int lr_loss_mask_strides(int64_t* dst, const float* p, const int64_t* st, int32_t height, int32_t width, const char* what) {
+  if (!p) return 0;
+  if (!st) return lr_fail(LOGRAST_ERR_ARG, what);
+  if (!lr_plane_in_32bit(st[1], st[2], height, width))
+    return lr_fail(LOGRAST_ERR_ARG, "y / x strides reach beyond 2^31 - 1 elements inside one image plane");
+  for (int i = 0; i < 3; i++) dst[i] = st[i];
+  return 0;
+}
+
+static int lr_loss_forward(const LossCall& c, float ssim_weight, float l1_weight, float* out3, float* maps) {
+  LossArgs a;
+  const int rc = lr_loss_args(a, c);
+  if (rc < 0) return rc;
+  if (!out3) return lr_fail(LOGRAST_ERR_ARG, "out3 is NULL");
+  if (rc == 1) {
+    LR_HIP(hipMemsetAsync(out3, 0, 3 * sizeof(float), (hipStream_t)c.stream));
+    return LOGRAST_OK;
+  }
+  if (c.gain_required && !c.gain) return lr_fail(LOGRAST_ERR_ARG, "l1_gain is NULL");
+  if (lr_loss_mask_strides(a.ms, c.mask, c.ms, c.height, c.width, "mask without strides") < 0) return LOGRAST_ERR_ARG;
+  if (lr_loss_mask_strides(a.fs, c.fg, c.fs, c.height, c.width, "foreground without strides") < 0) return LOGRAST_ERR_ARG;
+  if (lr_loss_scratch(c) < 0) return LOGRAST_ERR_ARG;
+  a.ntx = (c.width - 10 + 31) / 32; a.nty = (c.height - 10 + 31) / 32;
+  const double count = (double)c.batch * c.channels * (double)(c.height - 10) * (double)(c.width - 10);
+  a.scale = (float)(-(double)ssim_weight / count);
+  a.maps = maps;
+  a.partial = reinterpret_cast<float*>(c.scratch);
+  a.gain = c.gain;
+  a.mask = c.mask; a.fg = c.fg; a.bg = c.fg ? c.bg : nullptr; a.gt_out = c.fg ? c.gt_out : nullptr;
+  g_prof_call++;
+  LR_HIP(lr_launch_loss_fwd(a, ssim_weight, l1_weight, out3, (hipStream_t)c.stream));
+  return LOGRAST_OK;
+}
+
+// the scratch holds the partial sums of the gain's gradient: looked at only with a gain
+static int lr_loss_backward(const LossCall& c, float l1_weight, const float* grad_loss, const float* maps, float* grad_render,
+                            float* grad_render_l1, float* grad_gain) {
+  LossArgs a;
+  const int rc = lr_loss_args(a, c);
+  if (rc < 0) return rc;
+  if (rc == 1) return LOGRAST_OK;
+  if (!grad_loss || !maps || !grad_render || (c.gain_required && !c.gain) || (c.gain && !grad_gain))
+    return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
+  if (a.render_l1 && !grad_render_l1) return lr_fail(LOGRAST_ERR_ARG, "render_l1 is a tensor of its own but grad_render_l1 is NULL");
+  if (lr_loss_mask_strides(a.ms, c.mask, c.ms, c.height, c.width, "mask without strides") < 0) return LOGRAST_ERR_ARG;
+  if (c.gain && lr_loss_scratch(c) < 0) return LOGRAST_ERR_ARG;
+  a.ntx = (c.width + 31) / 32; a.nty = (c.height + 31) / 32;
+  a.l1_scale = (float)((double)l1_weight / ((double)c.batch * c.channels * (double)c.height * (double)c.width));
+  a.maps = const_cast<float*>(maps);
+  a.gain = c.gain;
+  a.gain_partial = reinterpret_cast<double*>(c.scratch);
+  a.mask = c.mask;
+  g_prof_call++;
+  LR_HIP(lr_launch_loss_bwd(a, grad_loss, grad_render, a.render_l1 ? grad_render_l1 : nullptr, grad_gain, (hipStream_t)c.stream));
+  return LOGRAST_OK;
 }
 
 int lograst_loss_forward(int32_t batch, int32_t channels, int32_t height, int32_t width, const float* render,
                          const int64_t* render_strides, const float* render_l1, const int64_t* render_l1_strides,
                          const float* gt, const int64_t* gt_strides, float ssim_weight, float l1_weight, float* out3,
                          float* maps, void* scratch, size_t scratch_bytes, void* stream) {
-  LossArgs a;
-  const int rc = lr_loss_args(a, batch, channels, height, width, render, render_strides, render_l1, render_l1_strides, gt, gt_strides);
-  if (rc < 0) return rc;
-  if (!out3) return lr_fail(LOGRAST_ERR_ARG, "out3 is NULL");
-  if (rc == 1) {
-    LR_HIP(hipMemsetAsync(out3, 0, 3 * sizeof(float), (hipStream_t)stream));
-    return LOGRAST_OK;
-  }
-  if (!scratch || scratch_bytes < lr_loss_scratch_bytes(batch, channels, height, width) || (reinterpret_cast<uintptr_t>(scratch) & 7u))
-    return lr_fail(LOGRAST_ERR_ARG, "loss scratch too small (lograst_loss_scratch_bytes) or not 8-byte aligned");
-  a.ntx = (width - 10 + 31) / 32; a.nty = (height - 10 + 31) / 32;
-  const double count = (double)batch * channels * (double)(height - 10) * (double)(width - 10);
-  a.scale = (float)(-(double)ssim_weight / count);
-  a.maps = maps;
-  a.partial = reinterpret_cast<float*>(scratch);
-  g_prof_call++;
-  LR_HIP(lr_launch_loss_fwd(a, ssim_weight, l1_weight, out3, (hipStream_t)stream));
-  return LOGRAST_OK;
+  LossCall c = {batch, channels, height, width, render, render_strides, render_l1, render_l1_strides, gt, gt_strides, nullptr,
+                scratch, scratch_bytes, stream};
+  c.scratch_min = lr_loss_scratch_bytes(batch, channels, height, width); c.scratch_fn = "lograst_loss_scratch_bytes";
+  return lr_loss_forward(c, ssim_weight, l1_weight, out3, maps);
 }
 
 int lograst_loss_backward(int32_t batch, int32_t channels, int32_t height, int32_t width, const float* render,
                           const int64_t* render_strides, const float* render_l1, const int64_t* render_l1_strides,
                           const float* gt, const int64_t* gt_strides, float l1_weight, const float* grad_loss,
                           const float* maps, float* grad_render, float* grad_render_l1, void* stream) {
-  LossArgs a;
-  const int rc = lr_loss_args(a, batch, channels, height, width, render, render_strides, render_l1, render_l1_strides, gt, gt_strides);
-  if (rc < 0) return rc;
-  if (rc == 1) return LOGRAST_OK;
-  if (!grad_loss || !maps || !grad_render) return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
-  if (a.render_l1 && !grad_render_l1) return lr_fail(LOGRAST_ERR_ARG, "render_l1 is a tensor of its own but grad_render_l1 is NULL");
-  a.ntx = (width + 31) / 32; a.nty = (height + 31) / 32;
-  a.l1_scale = (float)((double)l1_weight / ((double)batch * channels * (double)height * (double)width));
-  a.maps = const_cast<float*>(maps);
-  g_prof_call++;
-  LR_HIP(lr_launch_loss_bwd(a, grad_loss, grad_render, a.render_l1 ? grad_render_l1 : nullptr, (hipStream_t)stream));
-  return LOGRAST_OK;
-}
-
-// The same loss with the L1 term on gain[b, c] * render (LoG's view correction): no render_l1 tensor, one image gradient
-// and the gradient of the gain.
-size_t lograst_loss_gain_scratch_bytes(int32_t batch, int32_t channels, int32_t height, int32_t width) {
-  return lr_loss_gain_scratch_bytes(batch, channels, height, width);
+  LossCall c = {batch, channels, height, width, render, render_strides, render_l1, render_l1_strides, gt, gt_strides, nullptr,
+                nullptr, 0, stream};
+  return lr_loss_backward(c, l1_weight, grad_loss, maps, grad_render, grad_render_l1, nullptr);
 }
 
 int lograst_loss_forward_gain(int32_t batch, int32_t channels, int32_t height, int32_t width, const float* render,
                               const int64_t* render_strides, const float* gt, const int64_t* gt_strides, const float* l1_gain,
                               float ssim_weight, float l1_weight, float* out3, float* maps, void* scratch, size_t scratch_bytes,
                               void* stream) {
-  LossArgs a;
-  const int rc = lr_loss_args(a, batch, channels, height, width, render, render_strides, nullptr, nullptr, gt, gt_strides);
-  if (rc < 0) return rc;
-  if (!out3) return lr_fail(LOGRAST_ERR_ARG, "out3 is NULL");
-  if (rc == 1) {
-    LR_HIP(hipMemsetAsync(out3, 0, 3 * sizeof(float), (hipStream_t)stream));
-    return LOGRAST_OK;
-  }
-  if (!l1_gain) return lr_fail(LOGRAST_ERR_ARG, "l1_gain is NULL");
-  if (!scratch || scratch_bytes < lr_loss_scratch_bytes(batch, channels, height, width) || (reinterpret_cast<uintptr_t>(scratch) & 7u))
-    return lr_fail(LOGRAST_ERR_ARG, "loss scratch too small (lograst_loss_gain_scratch_bytes) or not 8-byte aligned");
-  a.ntx = (width - 10 + 31) / 32; a.nty = (height - 10 + 31) / 32;
-  const double count = (double)batch * channels * (double)(height - 10) * (double)(width - 10);
-  a.scale = (float)(-(double)ssim_weight / count);
-  a.maps = maps;
-  a.partial = reinterpret_cast<float*>(scratch);
-  a.gain = l1_gain;
-  g_prof_call++;
-  LR_HIP(lr_launch_loss_fwd(a, ssim_weight, l1_weight, out3, (hipStream_t)stream));
-  return LOGRAST_OK;
+  LossCall c = {batch, channels, height, width, render, render_strides, nullptr, nullptr, gt, gt_strides, l1_gain, scratch, scratch_bytes,
+                stream};
+  c.gain_required = true;
+  // the forward needs the forward's size; the message names the function whose size serves this call and its backward
+  c.scratch_min = lr_loss_scratch_bytes(batch, channels, height, width); c.scratch_fn = "lograst_loss_gain_scratch_bytes";
+  return lr_loss_forward(c, ssim_weight, l1_weight, out3, maps);
 }
 
 int lograst_loss_backward_gain(int32_t batch, int32_t channels, int32_t height, int32_t width, const float* render,
                                const int64_t* render_strides, const float* gt, const int64_t* gt_strides, const float* l1_gain,
                                float l1_weight, const float* grad_loss, const float* maps, float* grad_render, float* grad_gain,
                                void* scratch, size_t scratch_bytes, void* stream) {
-  LossArgs a;
-  const int rc = lr_loss_args(a, batch, channels, height, width, render, render_strides, nullptr, nullptr, gt, gt_strides);
-  if (rc < 0) return rc;
-  if (rc == 1) return LOGRAST_OK;
-  if (!grad_loss || !maps || !grad_render || !l1_gain || !grad_gain) return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
-  if (!scratch || scratch_bytes < lr_loss_gain_scratch_bytes(batch, channels, height, width) || (reinterpret_cast<uintptr_t>(scratch) & 7u))
-    return lr_fail(LOGRAST_ERR_ARG, "loss scratch too small (lograst_loss_gain_scratch_bytes) or not 8-byte aligned");
-  a.ntx = (width + 31) / 32; a.nty = (height + 31) / 32;
-  a.l1_scale = (float)((double)l1_weight / ((double)batch * channels * (double)height * (double)width));
-  a.maps = const_cast<float*>(maps);
-  a.gain = l1_gain;
-  a.gain_partial = reinterpret_cast<double*>(scratch);
-  g_prof_call++;
-  LR_HIP(lr_launch_loss_bwd_gain(a, grad_loss, grad_render, grad_gain, (hipStream_t)stream));
-  return LOGRAST_OK;
-}
-
-// The same loss with an ignore mask blended into the SSIM input and / or the ground truth composited over a background
-// (the MASKED instantiations), and the bounding box of a foreground mask.
-size_t lograst_loss_masked_scratch_bytes(int32_t batch, int32_t channels, int32_t height, int32_t width) {
-  return lr_loss_gain_scratch_bytes(batch, channels, height, width);      // >= lr_loss_scratch_bytes: serves either call
-}
-
-// mask [B, H, W] through three element strides: the same 32-bit in-plane offsets as the images
-static int lr_loss_mask_strides(int64_t* dst, const float* p, const int64_t* st, int32_t height, int32_t width, const char* what) {
-  for (int i = 0; i < 3; i++) dst[i] = 0;
-  if (!p) return 0;
-  if (!st) return lr_fail(LOGRAST_ERR_ARG, what);
-  const int64_t sy = st[1] < 0 ? -st[1] : st[1], sx = st[2] < 0 ? -st[2] : st[2];
-  if (sy > 0x7fffffffLL || sx > 0x7fffffffLL || (int64_t)(height - 1) * sy + (int64_t)(width - 1) * sx > 0x7fffffffLL)
-    return lr_fail(LOGRAST_ERR_ARG, "y / x strides reach beyond 2^31 - 1 elements inside one image plane");
-  for (int i = 0; i < 3; i++) dst[i] = st[i];
-  return 0;
+  LossCall c = {batch, channels, height, width, render, render_strides, nullptr, nullptr, gt, gt_strides, l1_gain, scratch, scratch_bytes,
+                stream};
+  c.gain_required = true;
+  c.scratch_min = lr_loss_gain_scratch_bytes(batch, channels, height, width); c.scratch_fn = "lograst_loss_gain_scratch_bytes";
+  return lr_loss_backward(c, l1_weight, grad_loss, maps, grad_render, nullptr, grad_gain);
 }
 
 int lograst_loss_forward_masked(int32_t batch, int32_t channels, int32_t height, int32_t width, const float* render,
@@ -1248,31 +1272,14 @@ int lograst_loss_forward_masked(int32_t batch, int32_t channels, int32_t height,
                                 const int64_t* mask_strides, const float* foreground, const int64_t* foreground_strides,
                                 const float* background, float* gt_out, float ssim_weight, float l1_weight, float* out3,
                                 float* maps, void* scratch, size_t scratch_bytes, void* stream) {
-  LossArgs a;
-  if (render_l1 && l1_gain) return lr_fail(LOGRAST_ERR_ARG, "render_l1 and l1_gain are mutually exclusive: the L1 term reads one of them");
-  if (!mask && !foreground) return lr_fail(LOGRAST_ERR_ARG, "mask and foreground are both NULL: use lograst_loss_forward / _gain");
-  if (foreground && (!background || !gt_out)) return lr_fail(LOGRAST_ERR_ARG, "foreground needs background and gt_out");
-  const int rc = lr_loss_args(a, batch, channels, height, width, render, render_strides, render_l1, render_l1_strides, gt, gt_strides);
-  if (rc < 0) return rc;
-  if (!out3) return lr_fail(LOGRAST_ERR_ARG, "out3 is NULL");
-  if (rc == 1) {
-    LR_HIP(hipMemsetAsync(out3, 0, 3 * sizeof(float), (hipStream_t)stream));
-    return LOGRAST_OK;
-  }
-  if (lr_loss_mask_strides(a.ms, mask, mask_strides, height, width, "mask without strides") < 0) return LOGRAST_ERR_ARG;
-  if (lr_loss_mask_strides(a.fs, foreground, foreground_strides, height, width, "foreground without strides") < 0) return LOGRAST_ERR_ARG;
-  if (!scratch || scratch_bytes < lograst_loss_masked_scratch_bytes(batch, channels, height, width) || (reinterpret_cast<uintptr_t>(scratch) & 7u))
-    return lr_fail(LOGRAST_ERR_ARG, "loss scratch too small (lograst_loss_masked_scratch_bytes) or not 8-byte aligned");
-  a.ntx = (width - 10 + 31) / 32; a.nty = (height - 10 + 31) / 32;
-  const double count = (double)batch * channels * (double)(height - 10) * (double)(width - 10);
-  a.scale = (float)(-(double)ssim_weight / count);
-  a.maps = maps;
-  a.partial = reinterpret_cast<float*>(scratch);
-  a.gain = l1_gain;
-  a.mask = mask; a.fg = foreground; a.bg = foreground ? background : nullptr; a.gt_out = foreground ? gt_out : nullptr;
-  g_prof_call++;
-  LR_HIP(lr_launch_loss_fwd_masked(a, ssim_weight, l1_weight, out3, (hipStream_t)stream));
-  return LOGRAST_OK;
+  LossCall c = {batch, channels, height, width, render, render_strides, render_l1, render_l1_strides, gt, gt_strides, l1_gain,
+                scratch, scratch_bytes, stream};
+  c.mask = mask; c.ms = mask_strides; c.fg = foreground; c.fs = foreground_strides; c.bg = background; c.gt_out = gt_out;
+  c.scratch_min = lograst_loss_masked_scratch_bytes(batch, channels, height, width); c.scratch_fn = "lograst_loss_masked_scratch_bytes";
+  c.precondition = render_l1 && l1_gain ? "render_l1 and l1_gain are mutually exclusive: the L1 term reads one of them"
+                   : !mask && !foreground ? "mask and foreground are both NULL: use lograst_loss_forward / _gain"
+                   : foreground && (!background || !gt_out) ? "foreground needs background and gt_out" : nullptr;
+  return lr_loss_forward(c, ssim_weight, l1_weight, out3, maps);
 }
 
 int lograst_loss_backward_masked(int32_t batch, int32_t channels, int32_t height, int32_t width, const float* render,
@@ -1281,27 +1288,13 @@ int lograst_loss_backward_masked(int32_t batch, int32_t channels, int32_t height
                                  const int64_t* mask_strides, float l1_weight, const float* grad_loss, const float* maps,
                                  float* grad_render, float* grad_render_l1, float* grad_gain, void* scratch, size_t scratch_bytes,
                                  void* stream) {
-  LossArgs a;
-  if (render_l1 && l1_gain) return lr_fail(LOGRAST_ERR_ARG, "render_l1 and l1_gain are mutually exclusive: the L1 term reads one of them");
-  if (!mask) return lr_fail(LOGRAST_ERR_ARG, "mask is NULL: use lograst_loss_backward / _gain on the composited gt");
-  const int rc = lr_loss_args(a, batch, channels, height, width, render, render_strides, render_l1, render_l1_strides, gt, gt_strides);
-  if (rc < 0) return rc;
-  if (rc == 1) return LOGRAST_OK;
-  if (!grad_loss || !maps || !grad_render || (l1_gain && !grad_gain)) return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
-  if (a.render_l1 && !grad_render_l1) return lr_fail(LOGRAST_ERR_ARG, "render_l1 is a tensor of its own but grad_render_l1 is NULL");
-  if (lr_loss_mask_strides(a.ms, mask, mask_strides, height, width, "mask without strides") < 0) return LOGRAST_ERR_ARG;
-  if (l1_gain && (!scratch || scratch_bytes < lograst_loss_masked_scratch_bytes(batch, channels, height, width) ||
-                  (reinterpret_cast<uintptr_t>(scratch) & 7u)))
-    return lr_fail(LOGRAST_ERR_ARG, "loss scratch too small (lograst_loss_masked_scratch_bytes) or not 8-byte aligned");
-  a.ntx = (width + 31) / 32; a.nty = (height + 31) / 32;
-  a.l1_scale = (float)((double)l1_weight / ((double)batch * channels * (double)height * (double)width));
-  a.maps = const_cast<float*>(maps);
-  a.gain = l1_gain;
-  a.gain_partial = reinterpret_cast<double*>(scratch);
-  a.mask = mask;
-  g_prof_call++;
-  LR_HIP(lr_launch_loss_bwd_masked(a, grad_loss, grad_render, a.render_l1 ? grad_render_l1 : nullptr, grad_gain, (hipStream_t)stream));
-  return LOGRAST_OK;
+  LossCall c = {batch, channels, height, width, render, render_strides, render_l1, render_l1_strides, gt, gt_strides, l1_gain,
+                scratch, scratch_bytes, stream};
+  c.mask = mask; c.ms = mask_strides;
+  c.scratch_min = lograst_loss_masked_scratch_bytes(batch, channels, height, width); c.scratch_fn = "lograst_loss_masked_scratch_bytes";
+  c.precondition = render_l1 && l1_gain ? "render_l1 and l1_gain are mutually exclusive: the L1 term reads one of them"
+                   : !mask ? "mask is NULL: use lograst_loss_backward / _gain on the composited gt" : nullptr;
+  return lr_loss_backward(c, l1_weight, grad_loss, maps, grad_render, grad_render_l1, grad_gain);
 }
 
 size_t lograst_mask_bounds_bytes(int32_t batch) { return (size_t)(batch > 0 ? batch : 1) * MB_RECORD_INTS * sizeof(int32_t); }
@@ -1389,8 +1382,7 @@ static int lr_eval_geometry(int32_t channels, int32_t height, int32_t width) {
 }
 
 static int lr_eval_strides(int64_t* dst, const int64_t* st, int32_t height, int32_t width) {
-  const int64_t sy = st[1] < 0 ? -st[1] : st[1], sx = st[2] < 0 ? -st[2] : st[2];
-  if (st[1] < 0 || st[2] < 0 || sy > 0x7fffffffLL || sx > 0x7fffffffLL || (int64_t)(height - 1) * sy + (int64_t)(width - 1) * sx > 0x7fffffffLL)
+  if (st[1] < 0 || st[2] < 0 || !lr_plane_in_32bit(st[1], st[2], height, width))
     return lr_fail(LOGRAST_ERR_ARG, "y / x strides are negative or reach beyond 2^31 - 1 elements inside one image plane");
   for (int i = 0; i < 3; i++) dst[i] = st[i];
   return 0;

@@ -128,14 +128,12 @@ hipError_t lr_launch_corrector_step(const CorrectorArgs& a, hipStream_t s);
 
 // loss.hip
 size_t lr_loss_scratch_bytes(int B, int C, int H, int W);
-hipError_t lr_launch_loss_fwd(const LossArgs& a, float wa, float wb, float* out3, hipStream_t s);
-hipError_t lr_launch_loss_bwd(const LossArgs& a, const float* grad_loss, float* g_render, float* g_render_l1, hipStream_t s);
 size_t lr_loss_gain_scratch_bytes(int B, int C, int H, int W);
-hipError_t lr_launch_loss_bwd_gain(const LossArgs& a, const float* grad_loss, float* g_render, float* grad_gain, hipStream_t s);
-// ... with a.mask and / or a.fg: the MASKED instantiations (a.gain selects GAIN)
-hipError_t lr_launch_loss_fwd_masked(const LossArgs& a, float wa, float wb, float* out3, hipStream_t s);
-hipError_t lr_launch_loss_bwd_masked(const LossArgs& a, const float* grad_loss, float* g_render, float* g_render_l1, float* grad_gain,
-                                     hipStream_t s);
+// a.gain selects the GAIN instantiations (and the reduction into grad_gain); a.mask or a.fg the MASKED forward, a.mask the
+// MASKED backward
+hipError_t lr_launch_loss_fwd(const LossArgs& a, float wa, float wb, float* out3, hipStream_t s);
+hipError_t lr_launch_loss_bwd(const LossArgs& a, const float* grad_loss, float* g_render, float* g_render_l1, float* grad_gain,
+                              hipStream_t s);
 #define MB_RECORD_INTS 8        // per image: xmin, ymin, xmax, ymax, count, 0, 0, 0
 hipError_t lr_launch_mask_bounds(int B, int H, int W, const float* mask, const int64_t* ms, float threshold, int32_t* record, hipStream_t s);
 

@@ -455,11 +455,15 @@ loss_bwd_kernel(LossArgs a, const float* __restrict__ grad_loss, float* __restri
   }
 }
 
+// The instantiation follows the arguments: a.gain selects GAIN; a.mask or a.fg selects MASKED in the forward, a.mask in the
+// backward (a composite alone leaves its gt_out, and the backward is the unmasked one on it).
 hipError_t lr_launch_loss_fwd(const LossArgs& a, float wa, float wb, float* out3, hipStream_t s) {
   const uint32_t blocks = (uint32_t)a.ntx * (uint32_t)a.nty * (uint32_t)a.B * (uint32_t)a.C;
+  const bool masked = a.mask || a.fg;
   lr_prof_begin(LRK_LOSS_FWD, s);
-  if (a.gain) hipLaunchKernelGGL((loss_fwd_kernel<true, false>), dim3(blocks), dim3(LS_THREADS), 0, s, a);
-  else hipLaunchKernelGGL((loss_fwd_kernel<false, false>), dim3(blocks), dim3(LS_THREADS), 0, s, a);
+  auto kernel = a.gain ? (masked ? loss_fwd_kernel<true, true> : loss_fwd_kernel<true, false>)
+                       : (masked ? loss_fwd_kernel<false, true> : loss_fwd_kernel<false, false>);
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(LS_THREADS), 0, s, a);
   const double count = (double)a.B * a.C * (double)(a.H - LS_HALO) * (double)(a.W - LS_HALO);
   const double count_l1 = (double)a.B * a.C * (double)a.H * (double)a.W;
   hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(LS_RED_THREADS), 0, s, reinterpret_cast<const float2*>(a.partial), blocks, 1.0 / count,
@@ -468,49 +472,17 @@ hipError_t lr_launch_loss_fwd(const LossArgs& a, float wa, float wb, float* out3
   return hipGetLastError();
 }
 
-hipError_t lr_launch_loss_bwd(const LossArgs& a, const float* grad_loss, float* g_render, float* g_render_l1, hipStream_t s) {
-  const uint32_t blocks = (uint32_t)a.ntx * (uint32_t)a.nty * (uint32_t)a.B * (uint32_t)a.C;
-  lr_prof_begin(LRK_LOSS_BWD, s);
-  hipLaunchKernelGGL((loss_bwd_kernel<false, false>), dim3(blocks), dim3(LS_THREADS), 0, s, a, grad_loss, g_render, g_render_l1);
-  lr_prof_end(LRK_LOSS_BWD, s);
-  return hipGetLastError();
-}
-
-hipError_t lr_launch_loss_bwd_gain(const LossArgs& a, const float* grad_loss, float* g_render, float* grad_gain, hipStream_t s) {
+// g_render_l1 where a.render_l1 is set, grad_gain (the reduction of the workgroups' partial sums) where a.gain is: else NULL
+hipError_t lr_launch_loss_bwd(const LossArgs& a, const float* grad_loss, float* g_render, float* g_render_l1, float* grad_gain,
+                              hipStream_t s) {
   const uint32_t tiles = (uint32_t)a.ntx * (uint32_t)a.nty, planes = (uint32_t)a.B * (uint32_t)a.C;
   lr_prof_begin(LRK_LOSS_BWD, s);
-  hipLaunchKernelGGL((loss_bwd_kernel<true, false>), dim3(tiles * planes), dim3(LS_THREADS), 0, s, a, grad_loss, g_render, (float*)nullptr);
-  hipLaunchKernelGGL(loss_gain_reduce_kernel, dim3(planes), dim3(LS_GAIN_RED_THREADS), 0, s, (const double*)a.gain_partial, (int)a.C,
-                     tiles, grad_loss, a.l1_scale, grad_gain);
-  lr_prof_end(LRK_LOSS_BWD, s);
-  return hipGetLastError();
-}
-
-// The MASKED instantiations (lograst_loss_*_masked): a.mask and / or a.fg set, a.gain selects GAIN.
-hipError_t lr_launch_loss_fwd_masked(const LossArgs& a, float wa, float wb, float* out3, hipStream_t s) {
-  const uint32_t blocks = (uint32_t)a.ntx * (uint32_t)a.nty * (uint32_t)a.B * (uint32_t)a.C;
-  lr_prof_begin(LRK_LOSS_FWD, s);
-  if (a.gain) hipLaunchKernelGGL((loss_fwd_kernel<true, true>), dim3(blocks), dim3(LS_THREADS), 0, s, a);
-  else hipLaunchKernelGGL((loss_fwd_kernel<false, true>), dim3(blocks), dim3(LS_THREADS), 0, s, a);
-  const double count = (double)a.B * a.C * (double)(a.H - LS_HALO) * (double)(a.W - LS_HALO);
-  const double count_l1 = (double)a.B * a.C * (double)a.H * (double)a.W;
-  hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(LS_RED_THREADS), 0, s, reinterpret_cast<const float2*>(a.partial), blocks, 1.0 / count,
-                     1.0 / count_l1, wa, wb, out3);
-  lr_prof_end(LRK_LOSS_FWD, s);
-  return hipGetLastError();
-}
-
-hipError_t lr_launch_loss_bwd_masked(const LossArgs& a, const float* grad_loss, float* g_render, float* g_render_l1, float* grad_gain,
-                                     hipStream_t s) {
-  const uint32_t tiles = (uint32_t)a.ntx * (uint32_t)a.nty, planes = (uint32_t)a.B * (uint32_t)a.C;
-  lr_prof_begin(LRK_LOSS_BWD, s);
-  if (a.gain) {
-    hipLaunchKernelGGL((loss_bwd_kernel<true, true>), dim3(tiles * planes), dim3(LS_THREADS), 0, s, a, grad_loss, g_render, (float*)nullptr);
+  auto kernel = a.gain ? (a.mask ? loss_bwd_kernel<true, true> : loss_bwd_kernel<true, false>)
+                       : (a.mask ? loss_bwd_kernel<false, true> : loss_bwd_kernel<false, false>);
+  hipLaunchKernelGGL(kernel, dim3(tiles * planes), dim3(LS_THREADS), 0, s, a, grad_loss, g_render, g_render_l1);
+  if (a.gain)
     hipLaunchKernelGGL(loss_gain_reduce_kernel, dim3(planes), dim3(LS_GAIN_RED_THREADS), 0, s, (const double*)a.gain_partial, (int)a.C,
                        tiles, grad_loss, a.l1_scale, grad_gain);
-  } else {
-    hipLaunchKernelGGL((loss_bwd_kernel<false, true>), dim3(tiles * planes), dim3(LS_THREADS), 0, s, a, grad_loss, g_render, g_render_l1);
-  }
   lr_prof_end(LRK_LOSS_BWD, s);
   return hipGetLastError();
 }
@@ -598,3 +570,14 @@ hipError_t lr_launch_mask_bounds(int B, int H, int W, const float* mask, const i
                      threshold, record);
   return hipGetLastError();
 }
+
+// Instantiated here, in the order the code object has had them since each was added: the device code then compares equal
+// byte for byte whatever the host code above does.
+template __global__ void loss_fwd_kernel<true, false>(LossArgs);
+template __global__ void loss_fwd_kernel<false, false>(LossArgs);
+template __global__ void loss_bwd_kernel<false, false>(LossArgs, const float*, float*, float*);
+template __global__ void loss_bwd_kernel<true, false>(LossArgs, const float*, float*, float*);
+template __global__ void loss_fwd_kernel<true, true>(LossArgs);
+template __global__ void loss_fwd_kernel<false, true>(LossArgs);
+template __global__ void loss_bwd_kernel<true, true>(LossArgs, const float*, float*, float*);
+template __global__ void loss_bwd_kernel<false, true>(LossArgs, const float*, float*, float*);

@@ -37,7 +37,8 @@ def window_taps():
 
 
 def _strides(t):
-    return (ctypes.c_int64 * 4)(*t.stride())
+    """The element strides of an image [B, C, H, W] or a mask [B, H, W] as the library reads them; None for no tensor."""
+    return None if t is None else (ctypes.c_int64 * t.dim())(*t.stride())
 
 
 def _require(render, gt, render_l1):
@@ -55,114 +56,145 @@ def _require(render, gt, render_l1):
     return _lib.lib()
 
 
+def _require_mask(module, name, t, render):
+    B, _, H, W = render.shape
+    if not torch.is_tensor(t) or t.device != render.device:
+        raise ValueError(f"{name}: expected a tensor on {render.device}")
+    if t.dtype != torch.float32 or tuple(t.shape) != (B, H, W):
+        raise ValueError(f"{name}: expected a float32 tensor [{B}, {H}, {W}], got {t.dtype} {tuple(t.shape)}")
+    if t.requires_grad:
+        raise _lib.LograstError(f"log_amd.{module}: {name} gets no gradient (detach it)")
+    return t.detach()
+
+
+def _require_gain(gain, B, C, device):
+    if not torch.is_tensor(gain) or gain.device != device or gain.dtype != torch.float32 or tuple(gain.shape) != (B, C):
+        raise ValueError(f"l1_gain: expected a float32 tensor [{B}, {C}] on {device}, got "
+                         f"{getattr(gain, 'dtype', type(gain))} {tuple(getattr(gain, 'shape', ()))}")
+    return gain.detach().contiguous()
+
+
+def _call_forward(L, dims, r, g, rl, k, m, f, bg, gt_out, weights, out, maps):
+    """The forward entry point the inputs ask for, on fresh scratch of its own sizing function: a mask or a foreground takes
+    the masked one, else a gain the gain one, else the plain one."""
+    if m is not None or f is not None:
+        size, entry = L.lograst_loss_masked_scratch_bytes, L.lograst_loss_forward_masked
+        own = (_ptr(rl), _strides(rl), _ptr(g), _strides(g), _ptr(k), _ptr(m), _strides(m), _ptr(f), _strides(f), _ptr(bg),
+               _ptr(gt_out))
+    elif k is not None:
+        size, entry = L.lograst_loss_gain_scratch_bytes, L.lograst_loss_forward_gain
+        own = (_ptr(g), _strides(g), _ptr(k))
+    else:
+        size, entry = L.lograst_loss_scratch_bytes, L.lograst_loss_forward
+        own = (_ptr(rl), _strides(rl), _ptr(g), _strides(g))
+    nbytes = size(*dims)
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=r.device)
+    with torch.cuda.device(r.device):
+        _lib.check(entry(*dims, _ptr(r), _strides(r), *own, *weights, _ptr(out), _ptr(maps), _ptr(scratch), nbytes,
+                         _stream_ptr(r.device)))
+
+
+def _call_backward(L, dims, l1_weight, r, g, rl, k, m, gl, maps, g_render, g_l1, g_gain):
+    """The backward entry point: an ignore mask takes the masked one, else a gain the gain one, else the plain one -- after a
+    foreground alone too, where ``g`` is the composited ground truth.  Scratch only with a gain."""
+    nbytes, scratch = 0, None
+    if k is not None:
+        nbytes = (L.lograst_loss_gain_scratch_bytes if m is None else L.lograst_loss_masked_scratch_bytes)(*dims)
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=r.device)
+    head = (*dims, _ptr(r), _strides(r))
+    grads = (l1_weight, _ptr(gl), _ptr(maps), _ptr(g_render))
+    with torch.cuda.device(r.device):
+        stream = _stream_ptr(r.device)
+        if m is not None:
+            rc = L.lograst_loss_backward_masked(*head, _ptr(rl), _strides(rl), _ptr(g), _strides(g), _ptr(k), _ptr(m), _strides(m),
+                                                *grads, _ptr(g_l1), _ptr(g_gain), _ptr(scratch), nbytes, stream)
+        elif k is not None:
+            rc = L.lograst_loss_backward_gain(*head, _ptr(g), _strides(g), _ptr(k), *grads, _ptr(g_gain), _ptr(scratch), nbytes,
+                                              stream)
+        else:
+            rc = L.lograst_loss_backward(*head, _ptr(rl), _strides(rl), _ptr(g), _strides(g), *grads, _ptr(g_l1), stream)
+        _lib.check(rc)
+
+
+# How a gt that wants a gradient is refused differs between the two modules, and callers may rely on either: log_amd.loss asks
+# autograd (ctx.needs_input_grad), log_amd.masked_loss the tensor (gt.requires_grad) -- torch does not promise that the two
+# agree in every grad mode -- and each message names its module.  So the caller hands in its name and its rule: (module, the
+# tensor is asked).
+FROM_LOSS, FROM_MASKED_LOSS = ("loss", False), ("masked_loss", True)
+
+
 class _L1SSIM(torch.autograd.Function):
+    """The loss in all its forms -- an ignore mask, a foreground composite over a background, render_l1 or a gain for the L1
+    term, each None where absent: gradients for render, render_l1 and the gain.  -> (loss, stats [l1, ssim], composited gt or
+    None)."""
+
     @staticmethod
-    def forward(ctx, render, gt, render_l1, ssim_weight, l1_weight):
+    def forward(ctx, render, gt, mask, foreground, background, render_l1, gain, ssim_weight, l1_weight, caller):
         L = _require(render, gt, render_l1)
-        if ctx.needs_input_grad[1]:
-            raise _lib.LograstError("log_amd.loss: gt gets no gradient (detach it)")
+        module, ask_tensor = caller
+        if gt.requires_grad if ask_tensor else ctx.needs_input_grad[1]:
+            raise _lib.LograstError(f"log_amd.{module}: gt gets no gradient (detach it)")
         device = render.device
-        B, C, H, W = (int(s) for s in render.shape)
+        dims = B, C, H, W = tuple(int(s) for s in render.shape)
+        m = None if mask is None else _require_mask(module, "mask", mask, render)
+        f = None if foreground is None else _require_mask(module, "foreground", foreground, render)
+        bg = None
+        if f is not None:
+            if (not torch.is_tensor(background) or background.device != device or background.dtype != torch.float32
+                    or tuple(background.shape) != (C,)):
+                raise ValueError(f"background: expected a float32 tensor [{C}] on {device} with a foreground mask")
+            if background.requires_grad:
+                raise _lib.LograstError(f"log_amd.{module}: background gets no gradient (detach it)")
+            bg = background.detach().contiguous()
+        k = None if gain is None else _require_gain(gain, B, C, device)
         r, g = render.detach(), gt.detach()
         rl = None
         if render_l1 is not None:
             rl = render_l1.detach()
             if rl.data_ptr() == r.data_ptr() and rl.stride() == r.stride():
                 rl = None
-        need_grad = any(ctx.needs_input_grad[i] for i in (0, 2))
+        need_grad = any(ctx.needs_input_grad[i] for i in (0, 5, 6))
         out = torch.empty(3, dtype=torch.float32, device=device)
         nmaps = 3 * B * C * max(H - WINDOW + 1, 0) * max(W - WINDOW + 1, 0)
         maps = torch.empty(nmaps, dtype=torch.float32, device=device) if need_grad else None
-        nbytes = L.lograst_loss_scratch_bytes(B, C, H, W)
-        scratch = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        with torch.cuda.device(device):
-            _lib.check(L.lograst_loss_forward(
-                B, C, H, W, _ptr(r), _strides(r), _ptr(rl), _strides(rl) if rl is not None else None, _ptr(g), _strides(g),
-                float(ssim_weight), float(l1_weight), _ptr(out), _ptr(maps), _ptr(scratch), nbytes, _stream_ptr(device)))
-        ctx.geom = (B, C, H, W, float(l1_weight))
-        ctx.tensors = (r, g, rl, maps)
+        gt_out = torch.empty(dims, dtype=torch.float32, device=device) if f is not None else None
+        _call_forward(L, dims, r, g, rl, k, m, f, bg, gt_out, (float(ssim_weight), float(l1_weight)), out, maps)
+        ctx.geom = (dims, float(l1_weight))
+        ctx.tensors = (r, gt_out if gt_out is not None else g, rl, k, m, maps)
         ctx.l1_is_input = render_l1 is not None
         loss, stats = out[0], out[1:3]
-        ctx.mark_non_differentiable(stats)
-        return loss, stats
+        if gt_out is None:
+            ctx.mark_non_differentiable(stats)
+        else:
+            ctx.mark_non_differentiable(stats, gt_out)
+        return loss, stats, gt_out
 
     @staticmethod
     @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_loss, _grad_stats):
-        B, C, H, W, l1_weight = ctx.geom
-        r, g, rl, maps = ctx.tensors
+    def backward(ctx, grad_loss, _grad_stats, _grad_gt):
+        dims, l1_weight = ctx.geom
+        r, g, rl, k, m, maps = ctx.tensors
         device = r.device
-        L = _lib.lib()
         gl = grad_loss.detach().to(device=device, dtype=torch.float32).reshape(1).contiguous()
-        g_render = torch.empty((B, C, H, W), dtype=torch.float32, device=device)
-        g_l1 = torch.empty((B, C, H, W), dtype=torch.float32, device=device) if rl is not None else None
-        with torch.cuda.device(device):
-            _lib.check(L.lograst_loss_backward(
-                B, C, H, W, _ptr(r), _strides(r), _ptr(rl), _strides(rl) if rl is not None else None, _ptr(g), _strides(g),
-                l1_weight, _ptr(gl), _ptr(maps), _ptr(g_render), _ptr(g_l1), _stream_ptr(device)))
+        g_render = torch.empty(dims, dtype=torch.float32, device=device)
+        g_l1 = torch.empty(dims, dtype=torch.float32, device=device) if rl is not None else None
+        g_gain = torch.zeros(dims[:2], dtype=torch.float32, device=device) if k is not None else None
+        _call_backward(_lib.lib(), dims, l1_weight, r, g, rl, k, m, gl, maps, g_render, g_l1, g_gain)
         if rl is None and ctx.l1_is_input:
             g_l1 = None          # render_l1 was render itself: its L1 term is already in g_render
-        return (g_render if ctx.needs_input_grad[0] else None, None,
-                g_l1 if ctx.l1_is_input and ctx.needs_input_grad[2] else None, None, None)
-
-
-class _L1SSIMGain(torch.autograd.Function):
-    """The loss with the L1 term on ``gain[b, c] * render``: gradients for render and for the gain."""
-
-    @staticmethod
-    def forward(ctx, render, gt, gain, ssim_weight, l1_weight):
-        L = _require(render, gt, None)
-        if ctx.needs_input_grad[1]:
-            raise _lib.LograstError("log_amd.loss: gt gets no gradient (detach it)")
-        device = render.device
-        B, C, H, W = (int(s) for s in render.shape)
-        if not torch.is_tensor(gain) or gain.device != device or gain.dtype != torch.float32 or tuple(gain.shape) != (B, C):
-            raise ValueError(f"l1_gain: expected a float32 tensor [{B}, {C}] on {device}, got "
-                             f"{getattr(gain, 'dtype', type(gain))} {tuple(getattr(gain, 'shape', ()))}")
-        r, g, k = render.detach(), gt.detach(), gain.detach().contiguous()
-        need_grad = any(ctx.needs_input_grad[i] for i in (0, 2))
-        out = torch.empty(3, dtype=torch.float32, device=device)
-        nmaps = 3 * B * C * max(H - WINDOW + 1, 0) * max(W - WINDOW + 1, 0)
-        maps = torch.empty(nmaps, dtype=torch.float32, device=device) if need_grad else None
-        nbytes = L.lograst_loss_gain_scratch_bytes(B, C, H, W)
-        scratch = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        with torch.cuda.device(device):
-            _lib.check(L.lograst_loss_forward_gain(
-                B, C, H, W, _ptr(r), _strides(r), _ptr(g), _strides(g), _ptr(k), float(ssim_weight), float(l1_weight),
-                _ptr(out), _ptr(maps), _ptr(scratch), nbytes, _stream_ptr(device)))
-        ctx.geom = (B, C, H, W, float(l1_weight))
-        ctx.tensors = (r, g, k, maps)
-        loss, stats = out[0], out[1:3]
-        ctx.mark_non_differentiable(stats)
-        return loss, stats
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_loss, _grad_stats):
-        B, C, H, W, l1_weight = ctx.geom
-        r, g, k, maps = ctx.tensors
-        device = r.device
-        L = _lib.lib()
-        gl = grad_loss.detach().to(device=device, dtype=torch.float32).reshape(1).contiguous()
-        g_render = torch.empty((B, C, H, W), dtype=torch.float32, device=device)
-        g_gain = torch.zeros((B, C), dtype=torch.float32, device=device)
-        nbytes = L.lograst_loss_gain_scratch_bytes(B, C, H, W)
-        scratch = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        with torch.cuda.device(device):
-            _lib.check(L.lograst_loss_backward_gain(
-                B, C, H, W, _ptr(r), _strides(r), _ptr(g), _strides(g), _ptr(k), l1_weight, _ptr(gl), _ptr(maps),
-                _ptr(g_render), _ptr(g_gain), _ptr(scratch), nbytes, _stream_ptr(device)))
-        return (g_render if ctx.needs_input_grad[0] else None, None, g_gain if ctx.needs_input_grad[2] else None, None, None)
+        return (g_render if ctx.needs_input_grad[0] else None, None, None, None, None,
+                g_l1 if ctx.l1_is_input and ctx.needs_input_grad[5] else None,
+                g_gain if k is not None and ctx.needs_input_grad[6] else None, None, None, None)
 
 
 def _fused_gain(render, gt, gain, ssim_weight, l1_weight):
-    return _L1SSIMGain.apply(render, gt, gain, ssim_weight, l1_weight)
+    return _L1SSIM.apply(render, gt, None, None, None, None, gain, ssim_weight, l1_weight, FROM_LOSS)[:2]
 
 
 def _fused(render, gt, render_l1, ssim_weight, l1_weight):
     if render_l1 is render:
         render_l1 = None
-    return _L1SSIM.apply(render, gt, render_l1, ssim_weight, l1_weight)
+    return _L1SSIM.apply(render, gt, None, None, None, render_l1, None, ssim_weight, l1_weight, FROM_LOSS)[:2]
 
 
 def l1_ssim_loss(render, gt, render_l1=None, ssim_weight=0.2, l1_weight=0.8, l1_gain=None):
@@ -209,6 +241,13 @@ def _modules_covered(self):
             and isinstance(getattr(self, "l1_loss", None), torch.nn.L1Loss) and self.l1_loss.reduction == "mean")
 
 
+def _publish(output, loss, stats):
+    """How every calculate_loss of this package ends: ONE read-back for loss_dict; the loss keeps its graph."""
+    l1_value, ssim_value = stats.tolist()
+    output["loss_dict"] = {"l1": l1_value, "ssim": ssim_value}
+    output["loss"] = loss
+
+
 _masked_branch = None     # log_amd.masked_loss.set_enabled(True) puts its mask_ignore branch here; None: the torch blend below
 
 
@@ -225,10 +264,7 @@ def _make_calculate_loss(original):
         render_l1 = output["render_correct"][:, :3] if "render_correct" in output.keys() else render
         if not (_fusable(render_l1) and render_l1.shape == render.shape):
             return original(self, gt_image, render, output, None)     # (the blend is already applied)
-        loss, stats = _fused(render, gt_image, render_l1, 0.2, 0.8)
-        l1_value, ssim_value = stats.tolist()
-        output["loss_dict"] = {"l1": l1_value, "ssim": ssim_value}
-        output["loss"] = loss
+        _publish(output, *_fused(render, gt_image, render_l1, 0.2, 0.8))
     calculate_loss._lograst_original = original
     return calculate_loss
 
@@ -259,3 +295,23 @@ def uninstall():
     rr = sys.modules.get("LoG.render.renderer")
     if rr is not None and hasattr(rr.NaiveRendererAndLoss.calculate_loss, "_lograst_original"):
         rr.NaiveRendererAndLoss.calculate_loss = rr.NaiveRendererAndLoss.calculate_loss._lograst_original
+
+
+class Underneath:
+    """For a module whose drop-ins stand on this one's calculate_loss (masked_loss, view_correction): its install() gets
+    install() here first, unless something of this package already stands as the renderer's calculate_loss, and its
+    uninstall() takes this module away again only where it was this object that put it there."""
+
+    def __init__(self):
+        self.installed = False
+
+    def install(self, renderer):
+        standing = renderer.calculate_loss
+        if not hasattr(standing, "_lograst_original") and not getattr(standing, "__module__", "").startswith("log_amd."):
+            install()
+            self.installed = True
+
+    def uninstall(self):
+        if self.installed:
+            uninstall()
+            self.installed = False

@@ -32,113 +32,6 @@ from .rasterizer import _ptr, _stream_ptr
 RECORD_INTS = 8      # int32 per image of the bounds record (launch.hpp: MB_RECORD_INTS)
 
 
-def _strides3(t):
-    return (ctypes.c_int64 * 3)(*t.stride())
-
-
-def _require_mask(name, t, render):
-    if t is None:
-        return None
-    B, _, H, W = render.shape
-    if not torch.is_tensor(t) or t.device != render.device:
-        raise ValueError(f"{name}: expected a tensor on {render.device}")
-    if t.dtype != torch.float32 or tuple(t.shape) != (B, H, W):
-        raise ValueError(f"{name}: expected a float32 tensor [{B}, {H}, {W}], got {t.dtype} {tuple(t.shape)}")
-    if t.requires_grad:
-        raise _lib.LograstError(f"log_amd.masked_loss: {name} gets no gradient (detach it)")
-    return t.detach()
-
-
-class _MaskedL1SSIM(torch.autograd.Function):
-    """The loss with an ignore mask and / or a foreground composite: gradients for render, render_l1 and the gain."""
-
-    @staticmethod
-    def forward(ctx, render, gt, mask, foreground, background, render_l1, gain, ssim_weight, l1_weight):
-        L = _loss._require(render, gt, render_l1)
-        if gt.requires_grad:
-            raise _lib.LograstError("log_amd.masked_loss: gt gets no gradient (detach it)")
-        device = render.device
-        B, C, H, W = (int(s) for s in render.shape)
-        m, f = _require_mask("mask", mask, render), _require_mask("foreground", foreground, render)
-        bg = None
-        if f is not None:
-            if (not torch.is_tensor(background) or background.device != device or background.dtype != torch.float32
-                    or tuple(background.shape) != (C,)):
-                raise ValueError(f"background: expected a float32 tensor [{C}] on {device} with a foreground mask")
-            if background.requires_grad:
-                raise _lib.LograstError("log_amd.masked_loss: background gets no gradient (detach it)")
-            bg = background.detach().contiguous()
-        k = None
-        if gain is not None:
-            if not torch.is_tensor(gain) or gain.device != device or gain.dtype != torch.float32 or tuple(gain.shape) != (B, C):
-                raise ValueError(f"l1_gain: expected a float32 tensor [{B}, {C}] on {device}, got "
-                                 f"{getattr(gain, 'dtype', type(gain))} {tuple(getattr(gain, 'shape', ()))}")
-            k = gain.detach().contiguous()
-        r, g = render.detach(), gt.detach()
-        rl = None
-        if render_l1 is not None:
-            rl = render_l1.detach()
-            if rl.data_ptr() == r.data_ptr() and rl.stride() == r.stride():
-                rl = None
-        need_grad = any(ctx.needs_input_grad[i] for i in (0, 5, 6))
-        out = torch.empty(3, dtype=torch.float32, device=device)
-        nmaps = 3 * B * C * max(H - _loss.WINDOW + 1, 0) * max(W - _loss.WINDOW + 1, 0)
-        maps = torch.empty(nmaps, dtype=torch.float32, device=device) if need_grad else None
-        gt_out = torch.empty((B, C, H, W), dtype=torch.float32, device=device) if f is not None else None
-        nbytes = L.lograst_loss_masked_scratch_bytes(B, C, H, W)
-        scratch = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        with torch.cuda.device(device):
-            _lib.check(L.lograst_loss_forward_masked(
-                B, C, H, W, _ptr(r), _loss._strides(r), _ptr(rl), _loss._strides(rl) if rl is not None else None,
-                _ptr(g), _loss._strides(g), _ptr(k), _ptr(m), _strides3(m) if m is not None else None,
-                _ptr(f), _strides3(f) if f is not None else None, _ptr(bg), _ptr(gt_out), float(ssim_weight), float(l1_weight),
-                _ptr(out), _ptr(maps), _ptr(scratch), nbytes, _stream_ptr(device)))
-        ctx.geom = (B, C, H, W, float(l1_weight))
-        ctx.tensors = (r, gt_out if gt_out is not None else g, rl, k, m, maps)
-        ctx.l1_is_input = render_l1 is not None
-        loss, stats = out[0], out[1:3]
-        if gt_out is None:
-            ctx.mark_non_differentiable(stats)
-            return loss, stats, None
-        ctx.mark_non_differentiable(stats, gt_out)
-        return loss, stats, gt_out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_loss, _grad_stats, _grad_gt):
-        B, C, H, W, l1_weight = ctx.geom
-        r, g, rl, k, m, maps = ctx.tensors
-        device = r.device
-        L = _lib.lib()
-        gl = grad_loss.detach().to(device=device, dtype=torch.float32).reshape(1).contiguous()
-        g_render = torch.empty((B, C, H, W), dtype=torch.float32, device=device)
-        g_l1 = torch.empty((B, C, H, W), dtype=torch.float32, device=device) if rl is not None else None
-        g_gain = torch.zeros((B, C), dtype=torch.float32, device=device) if k is not None else None
-        nbytes = L.lograst_loss_masked_scratch_bytes(B, C, H, W) if k is not None else 0
-        scratch = torch.empty(nbytes, dtype=torch.uint8, device=device) if k is not None else None
-        rls = _loss._strides(rl) if rl is not None else None
-        with torch.cuda.device(device):
-            stream = _stream_ptr(device)
-            if m is not None:
-                _lib.check(L.lograst_loss_backward_masked(
-                    B, C, H, W, _ptr(r), _loss._strides(r), _ptr(rl), rls, _ptr(g), _loss._strides(g), _ptr(k), _ptr(m),
-                    _strides3(m), l1_weight, _ptr(gl), _ptr(maps), _ptr(g_render), _ptr(g_l1), _ptr(g_gain), _ptr(scratch),
-                    nbytes, stream))
-            elif k is not None:      # a composite alone: the plain backward on the composited ground truth
-                _lib.check(L.lograst_loss_backward_gain(
-                    B, C, H, W, _ptr(r), _loss._strides(r), _ptr(g), _loss._strides(g), _ptr(k), l1_weight, _ptr(gl), _ptr(maps),
-                    _ptr(g_render), _ptr(g_gain), _ptr(scratch), nbytes, stream))
-            else:
-                _lib.check(L.lograst_loss_backward(
-                    B, C, H, W, _ptr(r), _loss._strides(r), _ptr(rl), rls, _ptr(g), _loss._strides(g), l1_weight, _ptr(gl),
-                    _ptr(maps), _ptr(g_render), _ptr(g_l1), stream))
-        if rl is None and ctx.l1_is_input:
-            g_l1 = None          # render_l1 was render itself: its L1 term is already in g_render
-        return (g_render if ctx.needs_input_grad[0] else None, None, None, None, None,
-                g_l1 if ctx.l1_is_input and ctx.needs_input_grad[5] else None,
-                g_gain if k is not None and ctx.needs_input_grad[6] else None, None, None)
-
-
 def _fused_masked(render, gt, mask, foreground, background, render_l1, l1_gain, ssim_weight, l1_weight):
     """-> (loss, stats [l1, ssim], gt_used)."""
     if mask is None and foreground is None:
@@ -149,7 +42,8 @@ def _fused_masked(render, gt, mask, foreground, background, render_l1, l1_gain, 
         raise ValueError("a foreground mask needs the background it composites the ground truth over")
     if render_l1 is render:
         render_l1 = None
-    loss, stats, gt_out = _MaskedL1SSIM.apply(render, gt, mask, foreground, background, render_l1, l1_gain, ssim_weight, l1_weight)
+    loss, stats, gt_out = _loss._L1SSIM.apply(render, gt, mask, foreground, background, render_l1, l1_gain, ssim_weight, l1_weight,
+                                              _loss.FROM_MASKED_LOSS)
     return loss, stats, gt if gt_out is None else gt_out
 
 
@@ -184,7 +78,7 @@ def mask_bounds(mask, threshold=0.5):
     B, H, W = (int(s) for s in m.shape)
     record = torch.empty((B, RECORD_INTS), dtype=torch.int32, device=m.device)
     with torch.cuda.device(m.device):
-        _lib.check(L.lograst_mask_bounds(B, H, W, _ptr(m), _strides3(m), float(threshold), _ptr(record),
+        _lib.check(L.lograst_mask_bounds(B, H, W, _ptr(m), _loss._strides(m), float(threshold), _ptr(record),
                                          record.numel() * 4, _stream_ptr(m.device)))
     return record
 
@@ -223,10 +117,7 @@ def _calculate_loss_branch(gt_image, render, output, mask_ignore):
     if render_l1 is not None and not (_loss._fusable(render_l1) and render_l1.shape == render.shape
                                       and render_l1.device == render.device):
         return False
-    loss, stats, _ = _fused_masked(render, gt_image, mask_ignore, None, None, render_l1, None, 0.2, 0.8)
-    l1_value, ssim_value = stats.tolist()
-    output["loss_dict"] = {"l1": l1_value, "ssim": ssim_value}
-    output["loss"] = loss
+    _loss._publish(output, *_fused_masked(render, gt_image, mask_ignore, None, None, render_l1, None, 0.2, 0.8)[:2])
     return True
 
 
@@ -331,10 +222,8 @@ def forward(self, batch, model):
     if mask_ignore is not None:
         mask_ignore = mask_ignore[:, t:b + 1, l:r + 1]
     loss, values, gt_used = _fused_masked(render, gt, mask_ignore, fg, rand_bkgd, None, None, 0.2, 0.8)
-    l1_value, ssim_value = values.tolist()
+    _loss._publish(output, loss, values)
     dropins.count("readbacks", "forward")
-    output["loss_dict"] = {"l1": l1_value, "ssim": ssim_value}
-    output["loss"] = loss
     if mask_ignore is not None:
         output["mask_ignore"] = mask_ignore
     output["gt"] = gt_used
@@ -344,37 +233,27 @@ def forward(self, batch, model):
 
 # ---- installation ----------------------------------------------------------------------------------------------------
 
-_installed_loss = False
+_underneath = _loss.Underneath()
 _was_enabled = None
 
 
 def install():
     """Patch the reference in place (needs LoG importable): log_amd.loss first (where nothing of this package is installed
     as calculate_loss yet), the switch on, then the two MaskForeground methods -> MaskForeground."""
-    global _installed_loss, _was_enabled
-    targets = _targets()
-    renderer = targets["forward"][0]
-    if not hasattr(renderer.calculate_loss, "_lograst_original") and not _is_ours(renderer.calculate_loss):
-        _loss.install()
-        _installed_loss = True
+    global _was_enabled
+    _underneath.install(_targets()["forward"][0])
     if _was_enabled is None:
         _was_enabled = enabled()
     set_enabled(True)
     return dropins.install()["forward"][0]
 
 
-def _is_ours(fn):
-    return getattr(fn, "__module__", "").startswith("log_amd.")
-
-
 def uninstall():
     """Put back what install() replaced, the switch as it was, and log_amd.loss where install() installed it."""
-    global _installed_loss, _was_enabled
+    global _was_enabled
     dropins.uninstall()
     dropins._saved.clear()
     if _was_enabled is not None:
         set_enabled(_was_enabled)
         _was_enabled = None
-    if _installed_loss:
-        _loss.uninstall()
-        _installed_loss = False
+    _underneath.uninstall()

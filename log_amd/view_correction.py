@@ -133,11 +133,8 @@ def _gain(self, gt_image, render, output, count, rows):
     """-> l1_gain [B, C] for the fused path, or raises Fallback."""
     if "render_correct" not in output.keys():
         raise Fallback("no render_correct in output")
-    ssim_mod = getattr(self, "ssim_loss", None)
     if not (_loss._fusable(gt_image, render) and gt_image.shape == render.shape and gt_image.device == render.device
-            and not gt_image.requires_grad and getattr(ssim_mod, "window_size", None) == _loss.WINDOW
-            and getattr(ssim_mod, "padding", 0) == 0 and isinstance(getattr(self, "l1_loss", None), torch.nn.L1Loss)
-            and self.l1_loss.reduction == "mean"):
+            and not gt_image.requires_grad and _loss._modules_covered(self)):
         raise Fallback("tensors or loss modules the kernels do not cover")
     B, C = int(render.shape[0]), int(render.shape[1])
     if count != B or len(rows) != B:
@@ -167,36 +164,26 @@ def calculate_loss(self, gt_image, render, output, mask_ignore=None):
         l1 = _loss._fused_gain(render, gt_image, gain, 0.0, 1.0)[0]
         loss = 0.2 * ssim + 0.8 * l1
         values = torch.stack([l1.detach(), ssim.detach()])
-    l1_value, ssim_value = values.tolist()
+    _loss._publish(output, loss, values)
     dropins.count("readbacks", "calculate_loss")
-    output["loss_dict"] = {"l1": l1_value, "ssim": ssim_value}
-    output["loss"] = loss
 
 
 # ---- installation ----------------------------------------------------------------------------------------------------
 
-_installed_loss = False
+_underneath = _loss.Underneath()
 
 
 def install():
     """Patch the reference classes in place (needs LoG importable): log_amd.loss first, then the three methods above, the
     loss wrapper around what is then installed as calculate_loss."""
-    global _installed_loss
-    targets = _targets()
-    renderer = targets["calculate_loss"][0]
-    if renderer.calculate_loss is not calculate_loss and not hasattr(renderer.calculate_loss, "_lograst_original"):
-        _loss.install()
-        _installed_loss = True
+    _underneath.install(_targets()["calculate_loss"][0])
     handed_out.take()
     return dropins.install()["step"][0]
 
 
 def uninstall():
     """Put back what install() replaced (log_amd.loss too where install() installed it)."""
-    global _installed_loss
     dropins.uninstall()
     dropins._saved.clear()             # the next install() wraps what is installed then
     handed_out.take()
-    if _installed_loss:
-        _loss.uninstall()
-        _installed_loss = False
+    _underneath.uninstall()

@@ -11,7 +11,8 @@
   gap32, this input's |fp32 - float64|), gradients |hip - ref64| <= min(1e-4 |ref64|, 8 |ref32 - ref64|); the gain's gradient
   per element within 8 * (|ref32 - ref64| + 2^-24 * S), S its condition scale (tests/view_correction_ref.within).
 * The bounds: exact integers against numpy.
-* The drop-in MaskForeground.forward on stand-in renderer and model classes (the reference is not needed on the device)."""
+* The drop-in MaskForeground.forward on stand-in renderer and model classes (the reference is not needed on the device).
+* Which of the six C entry points each kind of input calls, forward and backward, counted."""
 import glob
 import os
 import sys
@@ -534,3 +535,59 @@ def test_view_correction_calculate_loss_with_the_switch_on_takes_gain_and_mask_i
            param.grad[indices], None)
     _check_against_restatement("view_correction switch on", got, mref.masked_loss(render0, gt, mask, gain=gain),
                                mref.masked_loss(render0, gt, mask, gain=gain, dtype=torch.float32), render0)
+
+
+# ---- which entry point runs ------------------------------------------------------------------------------------------
+
+LOSS_ENTRY_POINTS = ("forward", "backward", "forward_gain", "backward_gain", "forward_masked", "backward_masked")
+# input kind -> (what it adds to (render, gt), the entry point of the forward, the entry point of the backward)
+DISPATCH = {
+    "plain": ((), "forward", "backward"),
+    "render_l1 of its own": (("render_l1",), "forward", "backward"),
+    "render_l1 is render": (("render_l1 is render",), "forward", "backward"),
+    "gain": (("gain",), "forward_gain", "backward_gain"),
+    "mask": (("mask",), "forward_masked", "backward_masked"),
+    "mask + gain": (("mask", "gain"), "forward_masked", "backward_masked"),
+    "mask + render_l1": (("mask", "render_l1"), "forward_masked", "backward_masked"),
+    "foreground": (("foreground",), "forward_masked", "backward"),
+    "foreground + gain": (("foreground", "gain"), "forward_masked", "backward_gain"),
+    "foreground + mask": (("foreground", "mask"), "forward_masked", "backward_masked"),
+}
+
+
+@pytest.mark.parametrize("H,W", [(11, 11), (43, 42)])
+def test_each_input_kind_calls_its_entry_points(monkeypatch, H, W):
+    """The six C functions behind counters: a mask or a foreground takes the masked forward, else a gain the gain forward, else
+    the plain one; an ignore mask takes the masked backward, else a gain the gain backward, else the plain backward (after a
+    foreground alone: on the composited ground truth).  One call each, no other."""
+    from log_amd import _lib
+    from log_amd.loss import l1_ssim_loss
+    from log_amd.masked_loss import masked_l1_ssim_loss
+    L = _lib.lib()
+    calls = []
+
+    def counted(name, fn):
+        def call(*args):
+            calls.append(name)
+            return fn(*args)
+        return call
+    for name in LOSS_ENTRY_POINTS:
+        monkeypatch.setattr(L, "lograst_loss_" + name, counted(name, getattr(L, "lograst_loss_" + name)))
+    render0, gt, render_l1, masks = _inputs(1, 3, H, W, 31 * H + W)
+    bg = torch.tensor([0.2, 0.5, 0.8], device=DEV)
+    gain = torch.tensor([[1.1, 0.93, 1.04]], device=DEV)
+    for kind, (adds, forward, backward) in DISPATCH.items():
+        r = _leaf(render0)
+        rl = r if "render_l1 is render" in adds else _leaf(render_l1) if "render_l1" in adds else None
+        k = _leaf(gain) if "gain" in adds else None
+        m = masks["random"] if "mask" in adds else None
+        f = masks["binary"] if "foreground" in adds else None
+        del calls[:]
+        if m is None and f is None:
+            loss = l1_ssim_loss(r, gt, rl, l1_gain=k)[0]
+        else:
+            loss = masked_l1_ssim_loss(r, gt, m, f, bg if f is not None else None, rl, k)[0]
+        assert calls == [forward], (kind, calls)
+        loss.backward()
+        assert calls == [forward, backward], (kind, calls)
+        assert r.grad is not None and (k is None or k.grad is not None) and (rl is None or rl.grad is not None), kind
