@@ -408,7 +408,9 @@ int lograst_project_backward(const lograst_view* view, int32_t n, const float* m
 /* ---- "next" row N1: simple_knn._C.distCUDA2 ----------------------------------------------------------
  * Replaces distCUDA2 (third-party simple-knn, un-vendored; called at /root/reference/LoG/utils/file.py:88-91 and
  * LoG/model/base_gaussian.py:39-42): out[i] = mean squared distance from point i to its 3 nearest other
- * points (exact, fp32).  scratch: lograst_knn_scratch_bytes(p) bytes of device memory. */
+ * points (exact, fp32).  scratch: lograst_knn_scratch_bytes(p) bytes of device memory.  Exactly p floats of `out` are
+ * written.  p < 4: a point has fewer than three other points and out[i] is unspecified (some non-NaN float; a caller that
+ * may see such a cloud chooses its own scale). */
 size_t lograst_knn_scratch_bytes(int32_t p);
 int lograst_knn_mean_dist2(int32_t p, const float* points, float* out, void* scratch, size_t scratch_bytes,
                            void* stream);
@@ -418,7 +420,10 @@ int lograst_knn_mean_dist2(int32_t p, const float* points, float* out, void* scr
  * [n, max_coeffs, 3]; clamped[n*3] (u8) records which channels hit the clamp.  Backward: dl_dshs[n,max_coeffs,3]
  * is overwritten (accumulate = 0) or added to (accumulate != 0: running sums over views), the direction gradient
  * is ADDED to dl_dmeans3d.  (Third-party package's computeColorFromSH;
- * LoG passes colors_precomp instead, LoG/render/renderer.py:144-145.) */
+ * LoG passes colors_precomp instead, LoG/render/renderer.py:144-145.)
+ * Alignment: every pointer needs the alignment of its element type only (4 bytes for the float arrays).  shs and dl_dshs
+ * move as 16-byte accesses when 3 * max_coeffs % 4 == 0 and the pointer is 16-byte aligned, one float at a time
+ * otherwise; both ways give the same bits. */
 int lograst_sh_forward(int32_t n, int32_t degree, int32_t max_coeffs, const float* means3d, const float* campos,
                        const float* shs, float* colors, uint8_t* clamped, void* stream);
 int lograst_sh_backward(int32_t n, int32_t degree, int32_t max_coeffs, const float* means3d, const float* campos,
@@ -582,7 +587,9 @@ int lograst_sparse_adam(int32_t m, int32_t num_points, const int64_t* index, con
  * passes through) and applied at once to model row index[r] and its moments as lograst_sparse_adam applies them -- the
  * gradients are never written.  keys[6] in the order xyz, scaling, opacity, rotation, colors, shs (widths 3, 3, 1, 4, 3,
  * 3 * sh_coeffs; `grad` is ignored, `param` = the gathered raw rows [n, width]; model_param == NULL: key not optimised).
- * Same op sequences as the two kernels: the model and the moments come out bit for bit the same. */
+ * Same op sequences as the two kernels: the model and the moments come out bit for bit the same.
+ * Alignment: raw_rotation and dl_dact_rotation must be 16-byte aligned (LOGRAST_ERR_ARG otherwise, before any device
+ * work); every other pointer, the keys' blocks included, needs the alignment of its element type only. */
 int lograst_activate_backward_adam(int32_t n, const float* raw_xyz, const float* raw_scaling, const float* raw_opacity,
                                    const float* raw_rotation, int32_t sh_coeffs, int32_t active_degree,
                                    const float* camera_center, const float* dl_dact_xyz, const float* dl_dact_scaling,
@@ -700,7 +707,11 @@ int lograst_densify_tree(int32_t p, int32_t num_nodes, int32_t children, int32_t
  * coefficients, K = 0 allowed with shs = NULL) is copied to the raw_* outputs [n, ...] (the step's parameters) and
  * activated: act_scaling = exp, act_opacity = sigmoid, act_rotation = q / max(|q|, 1e-12), act_colors =
  * 0.28209479 * colors + 0.5 (+ eval_sh_wobase(normalize(xyz - camera_center), shs, active_degree) when
- * active_degree > 0; degrees 1..3, camera_center = 3 floats on the device).  xyz is passed through (raw_xyz). */
+ * active_degree > 0; degrees 1..3, camera_center = 3 floats on the device).  xyz is passed through (raw_xyz).
+ * An index[r] below 0 or >= num_points reads row 0 of the model.
+ * Alignment: rotation, raw_rotation and act_rotation are read and written one quaternion (16 bytes) at a time and must be
+ * 16-byte aligned (LOGRAST_ERR_ARG otherwise, before any device work); every other pointer, shs and raw_shs included,
+ * needs 4 bytes (index: 8). */
 int lograst_gather_activate(int32_t n, int32_t num_points, const int64_t* index, const float* xyz,
                             const float* scaling, const float* opacity, const float* rotation, const float* colors,
                             const float* shs, int32_t sh_coeffs, int32_t active_degree, const float* camera_center,
@@ -709,7 +720,10 @@ int lograst_gather_activate(int32_t n, int32_t num_points, const int64_t* index,
                             float* act_rotation, float* act_colors, void* stream);
 /* Backward of the activations for the first n rows (the rows that are parameters): from dL/d(act_*) to
  * dL/d(raw_*).  dl_dshs (may be NULL) is [n, sh_coeffs, 3]; coefficients above active_degree get 0.  The direction
- * is detached in the reference (activation.py:30), so xyz receives no gradient from the colours. */
+ * is detached in the reference (activation.py:30), so xyz receives no gradient from the colours.
+ * Alignment: raw_rotation, dl_dact_rotation and dl_drotation must be 16-byte aligned (LOGRAST_ERR_ARG otherwise, before
+ * any device work).  dl_dshs needs 4 bytes: it is written 16 bytes at a time when 3 * sh_coeffs % 4 == 0 and it is 16-byte
+ * aligned, one float at a time otherwise, with the same bits.  Every other pointer: 4 bytes. */
 int lograst_activate_backward(int32_t n, const float* raw_xyz, const float* raw_scaling, const float* raw_opacity,
                               const float* raw_rotation, int32_t sh_coeffs, int32_t active_degree,
                               const float* camera_center, const float* dl_dact_scaling, const float* dl_dact_opacity,

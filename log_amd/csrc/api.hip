@@ -1682,6 +1682,9 @@ int lograst_gather_activate(int32_t n, int32_t num_points, const int64_t* index,
       !raw_rotation || !raw_colors || !act_scaling || !act_opacity || !act_rotation || !act_colors)
     return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
   if (sh_coeffs > 0 && (!shs || !raw_shs)) return lr_fail(LOGRAST_ERR_ARG, "NULL shs pointer");
+  if ((reinterpret_cast<uintptr_t>(rotation) | reinterpret_cast<uintptr_t>(raw_rotation) |
+       reinterpret_cast<uintptr_t>(act_rotation)) & 15u)
+    return lr_fail(LOGRAST_ERR_ARG, "rotation / raw_rotation / act_rotation must be 16-byte aligned");
   GatherArgs a;
   a.index = index; a.xyz = xyz; a.scaling = scaling; a.opacity = opacity; a.rotation = rotation; a.colors = colors;
   a.shs = shs; a.campos = camera_center;
@@ -1705,6 +1708,9 @@ int lograst_activate_backward(int32_t n, const float* raw_xyz, const float* raw_
   if (!raw_xyz || !raw_scaling || !raw_opacity || !raw_rotation || !dl_dact_scaling || !dl_dact_opacity ||
       !dl_dact_rotation || !dl_dact_colors || !dl_dscaling || !dl_dopacity || !dl_drotation || !dl_dcolors)
     return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
+  if ((reinterpret_cast<uintptr_t>(raw_rotation) | reinterpret_cast<uintptr_t>(dl_dact_rotation) |
+       reinterpret_cast<uintptr_t>(dl_drotation)) & 15u)
+    return lr_fail(LOGRAST_ERR_ARG, "raw_rotation / dl_dact_rotation / dl_drotation must be 16-byte aligned");
   ActBwdArgs a;
   a.r_xyz = raw_xyz; a.r_scaling = raw_scaling; a.r_opacity = raw_opacity; a.r_rotation = raw_rotation;
   a.campos = camera_center;

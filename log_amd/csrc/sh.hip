@@ -20,11 +20,14 @@ __constant__ float kC3[7] = {-0.5900435899266435f, 2.890611442640554f, -0.457045
 // LDS (row stride L+1 floats: odd, so the per-lane row walks are bank-conflict free).  Measured at 10 M Gaussians,
 // degree 3: forward 2.68 -> 0.6 ms, backward 4.51 -> 1.25 ms (3.1 TB/s).
 
-// wave-cooperative copy of `count` floats between global memory (contiguous) and the wave's LDS rows
+// wave-cooperative copy of `count` floats between global memory (contiguous) and the wave's LDS rows.  The float4 path
+// needs whole float4s per row (L % 4 == 0) and a 16-byte aligned global address; `glob` is base + 64 * wave * L floats, so
+// with L % 4 == 0 its alignment is the base pointer's: the test is wave-uniform.  Any other base (the C ABI asks for 4-byte
+// alignment of shs / dl_dshs only) takes the scalar path, which gives the same bits.
 template <bool TO_LDS, bool ADD = false>
 LR_DEV void lr_sh_wave_copy(float* __restrict__ lds, float* __restrict__ glob, int L, int count, int lane) {
   const uint32_t magic = 0xffffffffu / (uint32_t)L + 1u;  // e / L for e < 65536
-  if ((L & 3) == 0) {
+  if ((L & 3) == 0 && (reinterpret_cast<uintptr_t>(glob) & 15u) == 0) {
     for (int e = 4 * lane; e < count; e += 256) {  // count is a multiple of L, L of 4: float4s never straddle rows
       const int g = (int)__umulhi((uint32_t)e, magic), j = e - g * L;
       float* row = lds + g * (L + 1) + j;
@@ -36,6 +39,8 @@ LR_DEV void lr_sh_wave_copy(float* __restrict__ lds, float* __restrict__ glob, i
         if (ADD) {
           const float4 old = *reinterpret_cast<const float4*>(glob + e);
           o.x += old.x; o.y += old.y; o.z += old.z; o.w += old.w;
+        } else {  // as the scalar path's `+ 0.f`: a gradient that came out as -0.0 (negative basis x cut channel) leaves as +0.0
+          o.x += 0.f; o.y += 0.f; o.z += 0.f; o.w += 0.f;
         }
         *reinterpret_cast<float4*>(glob + e) = o;
       }

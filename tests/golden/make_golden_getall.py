@@ -3,7 +3,12 @@ container only): the gathers of LoG.get_all (LoG/model/level_of_gaussian.py:262-
 because the method needs a whole LoG object; the full method is exercised by tests/test_log_plumbing_cpu.py) and
 Activation.activate_root_return (LoG/model/activation.py:27-44, imported), with gradients from torch autograd.
 
-    python tests/golden/make_golden_getall.py
+    python tests/golden/make_golden_getall.py [name ...]     (no name: every file)
+
+The sched_* cases are the (active degree, stored K) pairs a LoG training run passes through before the active degree
+reaches the stored one (level_of_gaussian.py:21,35-36: active_sh_degree starts at 0 and is raised a step at a time, shs
+keeps (max + 1)^2 - 1 coefficients throughout), at row counts on the edges of the kernels' 64-row waves and 256-row
+workgroups.  Their names sort behind the five older files, which tests address by position.
 """
 import os
 import sys
@@ -55,7 +60,14 @@ def main():
                      ("deg1", dict(seed=2, P=2500, n_leaf=1000, n_node=130, K=3, degree=1)),
                      ("deg2", dict(seed=5, P=900, n_leaf=333, n_node=41, K=8, degree=2)),
                      ("deg3", dict(seed=3, P=1500, n_leaf=700, n_node=0, K=15, degree=3)),
-                     ("nosh", dict(seed=4, P=800, n_leaf=300, n_node=50, K=0, degree=0))):
+                     ("nosh", dict(seed=4, P=800, n_leaf=300, n_node=50, K=0, degree=0)),
+                     ("sched_d0k15", dict(seed=11, P=400, n_leaf=200, n_node=57, K=15, degree=0)),
+                     ("sched_d1k15", dict(seed=12, P=150, n_leaf=60, n_node=5, K=15, degree=1)),
+                     ("sched_d2k15", dict(seed=13, P=450, n_leaf=260, n_node=41, K=15, degree=2)),
+                     ("sched_d1k8", dict(seed=14, P=120, n_leaf=64, n_node=0, K=8, degree=1)),
+                     ("sched_d2k15_one", dict(seed=15, P=40, n_leaf=1, n_node=0, K=15, degree=2))):
+        if sys.argv[1:] and name not in sys.argv[1:]:
+            continue
         f = os.path.join(HERE, f"getall_{name}.npz")
         np.savez_compressed(f, **case(**kw))
         print(name, os.path.getsize(f) // 1024, "KiB")

@@ -260,3 +260,43 @@ def test_backward_form_is_the_written_out_table():
         assert L.lograst_backward_form(None, big) == -1 and b"view" in L.lograst_last_error()
     finally:
         assert L.lograst_reset_knobs() == 0
+
+
+def test_gather_and_activate_family_refuses_misaligned_quaternion_blocks():
+    """include/lograst.h: the rotation blocks of lograst_gather_activate, lograst_activate_backward and
+    lograst_activate_backward_adam move one quaternion (16 bytes) at a time and must be 16-byte aligned.  A pointer 4, 8 or
+    12 bytes past a boundary is refused with LOGRAST_ERR_ARG before any device work -- on a machine without a GPU, with
+    made-up addresses nobody dereferences.  Every other pointer of the calls below sits 4 bytes past a boundary and is not
+    what the refusal names."""
+    import torch  # noqa: F401
+    from log_amd import _lib
+    L = _lib.lib()
+    P = ctypes.c_void_p
+    A = 0x10000                                     # addresses are A * slot (+ offset): aligned unless made otherwise
+    keys = (_lib.LograstAdamKey * 6)()
+
+    def gather(rotation=3 * A, raw_rotation=13 * A, act_rotation=18 * A):
+        return L.lograst_gather_activate(8, 100, P(1 * A), P(2 * A + 4), P(4 * A + 4), P(5 * A + 4), P(rotation), P(6 * A + 4),
+                                         P(7 * A + 4), 15, 3, P(8 * A + 4), P(9 * A + 4), P(10 * A + 4), P(11 * A + 4),
+                                         P(raw_rotation), P(14 * A + 4), P(15 * A + 4), P(16 * A + 4), P(17 * A + 4),
+                                         P(act_rotation), P(19 * A + 4), None)
+
+    def backward(raw_rotation=4 * A, dl_dact_rotation=8 * A, dl_drotation=12 * A):
+        return L.lograst_activate_backward(8, P(1 * A + 4), P(2 * A + 4), P(3 * A + 4), P(raw_rotation), 15, 3, P(5 * A + 4),
+                                           P(6 * A + 4), P(7 * A + 4), P(dl_dact_rotation), P(9 * A + 4), P(10 * A + 4),
+                                           P(11 * A + 4), P(dl_drotation), P(13 * A + 4), P(14 * A + 4), None)
+
+    def fused(raw_rotation=4 * A, dl_dact_rotation=9 * A):
+        return L.lograst_activate_backward_adam(8, P(1 * A + 4), P(2 * A + 4), P(3 * A + 4), P(raw_rotation), 15, 3, P(5 * A + 4),
+                                                P(6 * A + 4), P(7 * A + 4), P(8 * A + 4), P(dl_dact_rotation), P(10 * A + 4),
+                                                100, P(11 * A), P(12 * A + 4), keys, 0.9, 0.999, 1.0, 1e-15, None)
+
+    for call, names in ((gather, ("rotation", "raw_rotation", "act_rotation")),
+                        (backward, ("raw_rotation", "dl_dact_rotation", "dl_drotation")),
+                        (fused, ("raw_rotation", "dl_dact_rotation"))):
+        for name in names:
+            for off in (4, 8, 12):
+                default = call.__defaults__[call.__code__.co_varnames.index(name)]
+                assert call(**{name: default + off}) == -1, (call.__name__, name, off)
+                msg = L.lograst_last_error()
+                assert b"16-byte aligned" in msg and name.encode() in msg, (call.__name__, name, off, msg)

@@ -83,3 +83,84 @@ def test_nothing_selected_on_the_device():
     sum(v.sum() for v in ret.values()).backward()
     params = model.gaussian.visibility_flag["params"]
     assert all(p.shape[0] == 0 for p in params.values())
+
+
+def _small_model(gen, P, K):
+    r = lambda *s: torch.randn(*s, device=DEV, generator=gen)
+    bufs = {"scaling": r(P, 3) - 3, "colors": r(P, 3), "xyz": torch.rand(P, 3, device=DEV, generator=gen) - 0.5,
+            "opacity": r(P, 1) * 2, "rotation": r(P, 4)}
+    if K:
+        bufs["shs"] = r(P, K, 3) * 0.3
+    return bufs
+
+
+@pytest.mark.parametrize("K,degrees", [(1, (0,)), (4, (0, 1)), (12, (0, 1, 2))], ids=["K1", "K4", "K12"])
+def test_row_lengths_no_reference_configuration_produces(K, degrees):
+    """lr_ga_check admits any K from 0 to 15.  K = 1 takes the gather loop's own branch (its multiply-high constant does not
+    fit 32 bits); K = 4 and 12 take the float4 path of the backward's wave copy (K = 8 is the only such K a fixture has).
+    Against float64 torch (getall_util.torch_get_all64) with the tolerances of getall_util.check: activations rtol 3e-6 /
+    atol 1e-6, gradients 2e-5 relative L2, raw copies and params exact.  Rows: one, a wave plus one, a workgroup plus one."""
+    from log_amd import get_all
+    worst = {}
+    for degree in degrees:
+        for n_leaf, n_node in ((1, 0), (60, 5), (200, 57)):
+            n = n_leaf + n_node
+            assert n in (1, 65, 257)
+            gen = torch.Generator(device=DEV).manual_seed(100 * K + 10 * degree + n)
+            P = 2 * n + 3
+            bufs = _small_model(gen, P, K)
+            perm = torch.randperm(P, device=DEV, generator=gen)
+            index, index_node = perm[:n_leaf], perm[n_leaf:n]
+            campos = torch.tensor([0.3, -2.5, 0.8], device=DEV)
+            model = U.stand_in(bufs, index, index_node, degree)
+            ret = get_all.get_all(model, {"camera_center": campos}, None)
+            params = model.gaussian.visibility_flag["params"]
+            p_ref, a_ref = U.torch_get_all64(bufs, index, index_node, campos, degree)
+            ups = {k: torch.randn(v.shape, device=DEV, generator=gen) for k, v in a_ref.items()}
+            sum((ret[k] * ups[k]).sum() for k in ups).backward()
+            sum((a_ref[k] * ups[k].double()).sum() for k in ups).backward()
+            for k in a_ref:
+                np.testing.assert_allclose(ret[k].detach().cpu().numpy(), a_ref[k].detach().cpu().numpy(), rtol=3e-6, atol=1e-6,
+                                           err_msg=str((k, K, degree, n)))
+            assert list(params) == list(bufs)
+            for k in bufs:
+                assert params[k].shape[0] == n_leaf
+                assert torch.equal(params[k].detach(), bufs[k][index]), (k, K, degree, n)        # raw copies: exact
+                if k == "shs" and degree == 0:
+                    assert params[k].grad is None and p_ref[k].grad is None
+                    continue
+                want = p_ref[k].grad
+                err = float((params[k].grad.double() - want).norm() / want.norm().clamp_min(1e-30))
+                worst[k] = max(worst.get(k, 0.0), err)
+                assert err < 2e-5, (k, K, degree, n, err)
+                if k == "shs":
+                    nk = (degree + 1) ** 2 - 1
+                    assert bool((params[k].grad[:, nk:] == 0).all()) and float(params[k].grad[:, :nk].abs().sum()) > 0
+    print("K = %d: largest relative L2 of a gradient %s" % (K, {k: "%.2e" % v for k, v in worst.items()}))
+
+
+@pytest.mark.parametrize("K,degree", [(0, 0), (1, 0), (8, 2), (15, 3)])
+def test_an_invalid_index_reads_row_zero(K, degree):
+    """include/lograst.h: an index below 0 or >= num_points reads row 0 of the model.  No fault, and the other rows come
+    out bit for bit as in a run in which those indices are written as 0 -- so do the invalid rows themselves."""
+    from log_amd import rasterizer as R
+    bits = lambda t: t.contiguous().view(torch.int32)
+    for n in (1, 65, 257):
+        gen = torch.Generator(device=DEV).manual_seed(31 * K + n)
+        P = n + 40
+        bufs = _small_model(gen, P, K)
+        index = torch.randperm(P, device=DEV, generator=gen)[:n]
+        bad = index.clone()
+        where = torch.tensor(sorted({0, n // 2, n - 1}), device=DEV)
+        bad[where] = torch.tensor([-1, P, 2 ** 40][:len(where)], device=DEV)
+        fixed = bad.clone()
+        fixed[where] = 0
+        campos = torch.tensor([0.3, -2.5, 0.8], device=DEV)
+        got = R._backend.gather_activate(bad, bufs, degree, campos if degree > 0 else None)
+        want = R._backend.gather_activate(fixed, bufs, degree, campos if degree > 0 else None)
+        torch.cuda.synchronize()
+        for g, w in zip(got, want):
+            assert set(g) == set(w)
+            for k in w:
+                assert torch.equal(bits(g[k]), bits(w[k])), (k, K, degree, n)
+        assert torch.equal(got[0]["xyz"][where], bufs["xyz"][:1].expand(len(where), 3))

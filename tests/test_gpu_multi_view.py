@@ -19,6 +19,7 @@ KEYS = ("xyz", "scaling", "opacity", "rotation", "colors", "shs")
 WIDTH = {"xyz": 3, "scaling": 3, "opacity": 1, "rotation": 4, "colors": 3}
 SHAPES = [(n, P) for n in (0, 1, 255, 256, 257, 3000) for P in (1, 257, 5000)]
 SH = [(0, 0), (3, 1), (15, 2), (15, 3)]
+SH_SCHEDULE = [(15, 0), (15, 1), (8, 1)]     # active degree below the stored one, as a training run starts (the sums only)
 B1, B2, EPS = 0.9, 0.999, 1e-15
 
 
@@ -81,7 +82,7 @@ def _parent_add(R, view, n, degree, want, seen):
 
 
 @pytest.mark.parametrize("row_major", [False, True], ids=["attribute_major", "row_major"])
-@pytest.mark.parametrize("K,degree", SH)
+@pytest.mark.parametrize("K,degree", SH + SH_SCHEDULE)
 def test_sums_equal_the_parents_backward_added_by_index(K, degree, row_major):
     from log_amd import multi_view as mv, rasterizer as R
     gen = torch.Generator(device=DEV).manual_seed(17 * K + degree + int(row_major))
