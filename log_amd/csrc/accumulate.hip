@@ -1,11 +1,14 @@
 // accumulate.hip -- steps over several views of the LoG model: every view's activation backward is ADDED into sums laid out
 // by model row, and one Adam step is taken over the rows some view saw.
-//   * lr_launch_activate_bwd_accumulate : ga_bwd_kernel's gradients (sh.hip; same op sequences, dL/dxyz passed through) of the
+// The arithmetic is not written here: the chain rule, the SH row fill, the map of a row's 14 small values and the halves of
+// the Adam update live in sh_basis.hpp (the element update itself, lr_adam_elem, in common.hpp), one definition each, called
+// by these kernels and by those of sh.hip and counter.hip.  This file holds the two kernels' memory access.
+//   * lr_launch_activate_bwd_accumulate : ga_bwd_kernel's gradients (sh.hip; the same functions, dL/dxyz passed through) of the
 //                                         rows with radii > 0, added into row index[r] of six strided targets; seen[index[r]]
 //                                         += 1.  Plain read-modify-writes: a view's index has no duplicates and the views follow
 //                                         each other on the stream, so the sums are taken in view order and the same views
 //                                         give the same bits.
-//   * lr_launch_accumulated_adam        : adam_kernel's update (counter.hip; same op sequence) of every row with seen > 0, from
+//   * lr_launch_accumulated_adam        : adam_kernel's update (counter.hip; the same function) of every row with seen > 0, from
 //                                         the accumulated gradient, which is zero-filled on the way, as seen is: what the step
 //                                         clears is what the views touched, not P x (14 + 3 K) floats.
 // Both are streaming kernels with a scattered (first) or a masked (second) row access: HBM-bound.
@@ -23,13 +26,12 @@ static __constant__ float kC2[5] = {1.0925484305920792f, -1.0925484305920792f, 0
 static __constant__ float kC3[7] = {-0.5900435899266435f, 2.890611442640554f, -0.4570457994644658f, 0.3731763325901154f,
                                     -0.4570457994644658f, 1.445305721320277f, -0.5900435899266435f};
 #define LR_SH_TABLES_DEFINED
-#include "sh_basis.hpp"   // lr_sh_basis (reads the two tables above), lr_sh_wave_sync, the Adam element halves
-
-#define ACC_SH_UNROLL 8
+#include "sh_basis.hpp"   // lr_sh_basis (reads the two tables above) and everything the row kernels of both files share
 
 // ---- one view's activation backward, added by model row ---------------------------------------------------------------
-// One lane per compact row, as ga_bwd_kernel: the 14 small values stay in the lane (all old sums requested, then all stores);
-// the 3 K SH gradients go through the wave's LDS rows so that the wave walks them contiguously.
+// One lane per compact row, as ga_bwd_kernel: the 14 small values (ga_act_grads) stay in the lane (all old sums requested,
+// then all stores); the 3 K SH gradients (ga_sh_grad_row) go through the wave's LDS rows so that the wave walks them
+// contiguously.  What is this kernel's own is where the values go: read-modify-writes of the strided targets.
 // key order: 0 xyz, 1 scaling, 2 opacity, 3 rotation, 4 colors, 5 shs (base == nullptr: not accumulated).
 __global__ void __launch_bounds__(256)
 acc_bwd_kernel(ActBwdArgs a, AccArgs t) {
@@ -51,39 +53,19 @@ acc_bwd_kernel(ActBwdArgs a, AccArgs t) {
     const size_t c = (size_t)i;
 #pragma unroll
     for (int k = 0; k < 3; k++) gc[k] = a.g_a_colors[3 * c + k];
-    // the row's 14 small values: xyz 0-2, scaling 3-5, colors 6-8, opacity 9, rotation 10-13 (keys 0, 1, 4, 2, 3)
+    // the row's 14 small values; a key without a target is not loaded
+    unsigned want = 0;
+#pragma unroll
+    for (int key = 0; key < 5; key++) want |= t.t[key].base ? GA_KEY(key) : 0u;
     float g[14], old[14];
     float* p[14];
 #pragma unroll
-    for (int k = 0; k < 3; k++) {
-      g[k] = t.t[0].base ? t.g_a_xyz[3 * c + k] : 0.f;
-      g[3 + k] = t.t[1].base ? a.g_a_scaling[3 * c + k] * expf(a.r_scaling[3 * c + k]) : 0.f;
-      g[6 + k] = gc[k] * SH_C0;
-    }
-    g[9] = 0.f;
-    if (t.t[2].base) {
-      const float sg = ga_sigmoid(a.r_opacity[c]);
-      g[9] = a.g_a_opacity[c] * (sg * (1.f - sg));
-    }
-    {
-      float4 q = {0.f, 0.f, 0.f, 1.f}, gy = {0.f, 0.f, 0.f, 0.f};
-      if (t.t[3].base) { q = reinterpret_cast<const float4*>(a.r_rotation)[c]; gy = reinterpret_cast<const float4*>(a.g_a_rotation)[c]; }
-      const float n2 = q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w, nrm = sqrtf(n2);
-      float4 gq;
-      if (nrm > 1e-12f) {   // y = q / |q|: dL/dq = (g - y (y . g)) / |q|; below eps the clamp makes y = q / eps
-        const float ix = 1.f / nrm, yx = q.x * ix, yy = q.y * ix, yz = q.z * ix, yw = q.w * ix;
-        const float dot = yx * gy.x + yy * gy.y + yz * gy.z + yw * gy.w;
-        gq = float4{(gy.x - yx * dot) * ix, (gy.y - yy * dot) * ix, (gy.z - yz * dot) * ix, (gy.w - yw * dot) * ix};
-      } else {
-        gq = float4{gy.x * 1e12f, gy.y * 1e12f, gy.z * 1e12f, gy.w * 1e12f};
-      }
-      g[10] = gq.x; g[11] = gq.y; g[12] = gq.z; g[13] = gq.w;
-    }
+    for (int k = 0; k < 3; k++) g[k] = (want & GA_KEY(0)) ? t.g_a_xyz[3 * c + k] : 0.f;
+    ga_act_grads(a, c, want, gc, g);
 #pragma unroll
     for (int k = 0; k < 14; k++) {
-      const int key = k < 3 ? 0 : (k < 6 ? 1 : (k < 9 ? 4 : (k < 10 ? 2 : 3)));
-      const int col = k < 3 ? k : (k < 6 ? k - 3 : (k < 9 ? k - 6 : (k < 10 ? 0 : k - 10)));
-      p[k] = t.t[key].base ? t.t[key].base + lr_acc_offset(row, t.t[key].stride, col) : nullptr;
+      const AccTarget& tk = t.t[ga_small(k).key];
+      p[k] = tk.base ? tk.base + lr_acc_offset(row, tk.stride, ga_small(k).col) : nullptr;
     }
     // all old sums requested, then all stores
 #pragma unroll
@@ -97,33 +79,17 @@ acc_bwd_kernel(ActBwdArgs a, AccArgs t) {
   if (L > 0 && t.t[5].base) {
     float* const wl = lr_sh_lds + wave * 64 * (L + 1);
     lr_rowidx[wave][lane] = row;
-    if (row >= 0) {
-      float b[16], bx[16], by[16], bz[16];
-#pragma unroll
-      for (int k = 0; k < 16; k++) b[k] = 0.f;
-      if (a.deg > 0) {
-        const float vx = a.r_xyz[3 * (size_t)i] - a.campos[0], vy = a.r_xyz[3 * (size_t)i + 1] - a.campos[1],
-                    vz = a.r_xyz[3 * (size_t)i + 2] - a.campos[2];
-        const float nrm = sqrtf(vx * vx + vy * vy + vz * vz);
-        lr_sh_basis(a.deg, vx / nrm, vy / nrm, vz / nrm, b, bx, by, bz);
-      }
-      const int nk = (a.deg + 1) * (a.deg + 1);
-      float* rowp = wl + lane * (L + 1);
-      for (int k = 0; k < a.K; k++) {
-        const float w = (k + 1 < nk && k + 1 < 16) ? b[k + 1] : 0.f;   // coefficients above the active degree: zero gradient
-        rowp[3 * k] = w * gc[0]; rowp[3 * k + 1] = w * gc[1]; rowp[3 * k + 2] = w * gc[2];
-      }
-    }
+    if (row >= 0) ga_sh_grad_row(a, i, gc, wl + lane * (L + 1));
     lr_sh_wave_sync();
     // the wave walks its rows' L gradients contiguously: element x = (row r, column c) of the wave's block; the model side
-    // is one contiguous 4 L-byte piece per visible row.  ACC_SH_UNROLL elements per lane in flight.
+    // is one contiguous 4 L-byte piece per visible row.  GA_SH_UNROLL elements per lane in flight.
     const uint32_t magic = 0xffffffffu / (uint32_t)L + 1u;    // x / L for x < 65536 (L >= 3)
     const int total = rows * L;
-    for (int x0 = lane; x0 < total; x0 += 64 * ACC_SH_UNROLL) {
-      float* p[ACC_SH_UNROLL];
-      float g[ACC_SH_UNROLL], old[ACC_SH_UNROLL];
+    for (int x0 = lane; x0 < total; x0 += 64 * GA_SH_UNROLL) {
+      float* p[GA_SH_UNROLL];
+      float g[GA_SH_UNROLL], old[GA_SH_UNROLL];
 #pragma unroll
-      for (int u = 0; u < ACC_SH_UNROLL; u++) {
+      for (int u = 0; u < GA_SH_UNROLL; u++) {
         const int x = x0 + 64 * u;
         p[u] = nullptr; g[u] = 0.f;
         if (x < total) {
@@ -133,9 +99,9 @@ acc_bwd_kernel(ActBwdArgs a, AccArgs t) {
         }
       }
 #pragma unroll
-      for (int u = 0; u < ACC_SH_UNROLL; u++) old[u] = p[u] ? *p[u] : 0.f;
+      for (int u = 0; u < GA_SH_UNROLL; u++) old[u] = p[u] ? *p[u] : 0.f;
 #pragma unroll
-      for (int u = 0; u < ACC_SH_UNROLL; u++)
+      for (int u = 0; u < GA_SH_UNROLL; u++)
         if (p[u]) *p[u] = old[u] + g[u];
     }
   }
@@ -143,14 +109,10 @@ acc_bwd_kernel(ActBwdArgs a, AccArgs t) {
 
 hipError_t lr_launch_activate_bwd_accumulate(const ActBwdArgs& a, const AccArgs& t, hipStream_t s) {
   if (a.n <= 0) return hipSuccess;
-  const size_t lds = sizeof(float) * 4 * 64 * (size_t)(3 * a.K + 1);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(acc_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-    attr_set = true;
-  }
+  lr_ga_lds_once<acc_bwd_kernel>();
   lr_prof_begin(LRK_GATHER_BWD, s);
-  hipLaunchKernelGGL(acc_bwd_kernel, dim3((a.n + 255) / 256), dim3(256), (a.K > 0 && t.t[5].base) ? lds : 0, s, a, t);
+  hipLaunchKernelGGL(acc_bwd_kernel, dim3((a.n + 255) / 256), dim3(256), (a.K > 0 && t.t[5].base) ? lr_ga_lds_bytes(a.K) : 0, s,
+                     a, t);
   lr_prof_end(LRK_GATHER_BWD, s);
   return hipGetLastError();
 }
@@ -176,13 +138,12 @@ acc_adam_kernel(AdamArgs f, AccStepArgs t) {
   const uint64_t mask = __ballot(live);
   if (!mask) return;
   if (live) {
-    // the row's 14 small values: xyz 0-2, scaling 3-5, colors 6-8, opacity 9, rotation 10-13 (keys 0, 1, 4, 2, 3)
+    // the row's 14 small values
     GaElem e[14];
     float* gp[14];
 #pragma unroll
     for (int k = 0; k < 14; k++) {
-      const int key = k < 3 ? 0 : (k < 6 ? 1 : (k < 9 ? 4 : (k < 10 ? 2 : 3)));
-      const int col = k < 3 ? k : (k < 6 ? k - 3 : (k < 9 ? k - 6 : (k < 10 ? 0 : k - 10)));
+      const int key = ga_small(k).key, col = ga_small(k).col;
       const AdamKey& key_k = f.key[key];
       e[k].on = key_k.model != nullptr;
       e[k].o = lr_acc_offset(p, key_k.width, col);
@@ -191,10 +152,10 @@ acc_adam_kernel(AdamArgs f, AccStepArgs t) {
       e[k].g = e[k].on ? *gp[k] : 0.f;
     }
 #pragma unroll
-    for (int k = 0; k < 14; k++) ga_adam_load(f.key[k < 3 ? 0 : (k < 6 ? 1 : (k < 9 ? 4 : (k < 10 ? 2 : 3)))], e[k]);
+    for (int k = 0; k < 14; k++) ga_adam_load(f.key[ga_small(k).key], e[k]);
 #pragma unroll
     for (int k = 0; k < 14; k++) {
-      ga_adam_store(f.key[k < 3 ? 0 : (k < 6 ? 1 : (k < 9 ? 4 : (k < 10 ? 2 : 3)))], f, e[k]);
+      ga_adam_store(f.key[ga_small(k).key], f, e[k]);
       if (gp[k]) *gp[k] = 0.f;
     }
   }
@@ -205,11 +166,11 @@ acc_adam_kernel(AdamArgs f, AccStepArgs t) {
     const int rows = left < 64 ? (int)left : 64;
     const uint32_t magic = 0xffffffffu / (uint32_t)L + 1u;    // x / L for x < 65536 (L >= 3)
     const int total = rows * L;
-    for (int x0 = lane; x0 < total; x0 += 64 * ACC_SH_UNROLL) {
-      GaElem e[ACC_SH_UNROLL];
-      float* gp[ACC_SH_UNROLL];
+    for (int x0 = lane; x0 < total; x0 += 64 * GA_SH_UNROLL) {
+      GaElem e[GA_SH_UNROLL];
+      float* gp[GA_SH_UNROLL];
 #pragma unroll
-      for (int u = 0; u < ACC_SH_UNROLL; u++) {
+      for (int u = 0; u < GA_SH_UNROLL; u++) {
         const int x = x0 + 64 * u;
         e[u].on = false; e[u].o = 0; e[u].p0 = 0.f; e[u].g = 0.f; gp[u] = nullptr;
         if (x < total) {
@@ -224,9 +185,9 @@ acc_adam_kernel(AdamArgs f, AccStepArgs t) {
         }
       }
 #pragma unroll
-      for (int u = 0; u < ACC_SH_UNROLL; u++) ga_adam_load(sh, e[u]);
+      for (int u = 0; u < GA_SH_UNROLL; u++) ga_adam_load(sh, e[u]);
 #pragma unroll
-      for (int u = 0; u < ACC_SH_UNROLL; u++) {
+      for (int u = 0; u < GA_SH_UNROLL; u++) {
         ga_adam_store(sh, f, e[u]);
         if (gp[u]) *gp[u] = 0.f;
       }

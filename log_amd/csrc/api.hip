@@ -1429,6 +1429,29 @@ int lograst_eval_read(const void* record, double* out16, void* stream) {
   return LOGRAST_OK;
 }
 
+// ---- the Adam steps over model rows: lograst_sparse_adam, lograst_activate_backward_adam, lograst_accumulated_adam ------
+// One key of a step.  Which of `param` (the gathered rows the step starts from) and `grad` the caller's kernel reads differs:
+// the fused step has the gradient in registers, the accumulated one reads the model row itself; what is not read is not
+// required and not passed on.
+static int lr_adam_key(AdamKey& d, const lograst_adam_key& k, bool reads_param, bool reads_grad) {
+  if (!k.model_param || (reads_param && !k.param) || (reads_grad && !k.grad) || !k.exp_avg || !k.exp_avg_sq)
+    return lr_fail(LOGRAST_ERR_ARG, "NULL pointer in key");
+  d.model = (float*)k.model_param;
+  d.param = reads_param ? (const float*)k.param : nullptr;
+  d.grad = reads_grad ? (const float*)k.grad : nullptr;
+  d.exp_avg = (float*)k.exp_avg; d.exp_avg_sq = (float*)k.exp_avg_sq; d.max_exp_avg_sq = (float*)k.max_exp_avg_sq;
+  d.width = k.width; d.neg_step_size = -k.step_size;
+  return LOGRAST_OK;
+}
+// the reference's Python scalars are doubles that torch narrows to fp32 when they meet an fp32 tensor
+static void lr_adam_scalars(AdamArgs& a, double beta1, double beta2, double bias_correction2_sqrt, double eps) {
+  a.beta1 = (float)beta1; a.beta2 = (float)beta2; a.omb1 = (float)(1.0 - beta1); a.omb2 = (float)(1.0 - beta2);
+  a.bc2_sqrt = (float)bias_correction2_sqrt; a.eps = (float)eps;
+}
+// widths of the keys of a LoG row in the order of every key list: xyz, scaling, opacity, rotation, colors; shs: 3 * sh_coeffs
+static const int kStepKeyWidths[6] = {3, 3, 1, 4, 3, 0};
+static int lr_step_key_width(int i, int32_t sh_coeffs) { return i == 5 ? 3 * sh_coeffs : kStepKeyWidths[i]; }
+
 int lograst_sparse_adam(int32_t m, int32_t num_points, const int64_t* index, const uint8_t* flag_vis,
                         int32_t num_keys, const lograst_adam_key* keys, double beta1, double beta2,
                         double bias_correction2_sqrt, double eps, void* stream) {
@@ -1439,18 +1462,12 @@ int lograst_sparse_adam(int32_t m, int32_t num_points, const int64_t* index, con
   AdamArgs a;
   memset(&a, 0, sizeof(a));
   for (int i = 0; i < num_keys; i++) {
-    const lograst_adam_key& k = keys[i];
-    if (!k.model_param || !k.param || !k.grad || !k.exp_avg || !k.exp_avg_sq) return lr_fail(LOGRAST_ERR_ARG, "NULL pointer in key");
-    if (k.width < 1) return lr_fail(LOGRAST_ERR_ARG, "key width must be >= 1");
-    a.key[i].model = (float*)k.model_param; a.key[i].param = (const float*)k.param; a.key[i].grad = (const float*)k.grad;
-    a.key[i].exp_avg = (float*)k.exp_avg; a.key[i].exp_avg_sq = (float*)k.exp_avg_sq;
-    a.key[i].max_exp_avg_sq = (float*)k.max_exp_avg_sq;
-    a.key[i].width = k.width; a.key[i].neg_step_size = -k.step_size;
+    int rc = lr_adam_key(a.key[i], keys[i], true, true);
+    if (rc) return rc;
+    if (keys[i].width < 1) return lr_fail(LOGRAST_ERR_ARG, "key width must be >= 1");
   }
   a.index = index; a.flag_vis = flag_vis; a.m = m; a.num_points = num_points;
-  // the reference's Python scalars are doubles that torch narrows to fp32 when they meet an fp32 tensor
-  a.beta1 = (float)beta1; a.beta2 = (float)beta2; a.omb1 = (float)(1.0 - beta1); a.omb2 = (float)(1.0 - beta2);
-  a.bc2_sqrt = (float)bias_correction2_sqrt; a.eps = (float)eps;
+  lr_adam_scalars(a, beta1, beta2, bias_correction2_sqrt, eps);
   g_prof_call++;
   LR_HIP(lr_launch_sparse_adam(a, num_keys, (hipStream_t)stream));
   return LOGRAST_OK;
@@ -1667,6 +1684,35 @@ static int lr_ga_check(int32_t n, int32_t sh_coeffs, int32_t active_degree, cons
   if (active_degree > 0 && !camera_center) return lr_fail(LOGRAST_ERR_ARG, "camera_center is NULL");
   return LOGRAST_OK;
 }
+// the quaternion blocks are read and written as float4 (the third pointer may be absent)
+static bool lr_aligned16(const void* a, const void* b, const void* c = nullptr) {
+  return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & 15u) == 0;
+}
+// The front of the three lograst_activate_backward*: lr_ga_check, then -- unless n == 0, which the caller returns as OK -- the
+// model's size where the call has one (`num_points`; the plain backward passes 1), the NULL check of the common pointers
+// together with the caller's own (`others`: all of them non-NULL), the alignment of the quaternion blocks (`rotation_out`
+// is the plain backward's third) under the caller's message, and the inputs of ActBwdArgs; the outputs stay NULL.
+static int lr_act_bwd_args(ActBwdArgs& a, int32_t n, const float* raw_xyz, const float* raw_scaling, const float* raw_opacity,
+                           const float* raw_rotation, int32_t sh_coeffs, int32_t active_degree, const float* camera_center,
+                           const float* dl_dact_scaling, const float* dl_dact_opacity, const float* dl_dact_rotation,
+                           const float* dl_dact_colors, int32_t num_points, bool others, const float* rotation_out,
+                           const char* alignment) {
+  int rc = lr_ga_check(n, sh_coeffs, active_degree, camera_center);
+  if (rc || n == 0) return rc;
+  if (num_points <= 0) return lr_fail(LOGRAST_ERR_ARG, "rows of an empty model");
+  if (!raw_xyz || !raw_scaling || !raw_opacity || !raw_rotation || !dl_dact_scaling || !dl_dact_opacity || !dl_dact_rotation ||
+      !dl_dact_colors || !others)
+    return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
+  if (!lr_aligned16(raw_rotation, dl_dact_rotation, rotation_out)) return lr_fail(LOGRAST_ERR_ARG, alignment);
+  memset(&a, 0, sizeof(a));
+  a.r_xyz = raw_xyz; a.r_scaling = raw_scaling; a.r_opacity = raw_opacity; a.r_rotation = raw_rotation;
+  a.campos = camera_center;
+  a.g_a_scaling = dl_dact_scaling; a.g_a_opacity = dl_dact_opacity; a.g_a_rotation = dl_dact_rotation;
+  a.g_a_colors = dl_dact_colors;
+  a.n = n; a.K = sh_coeffs; a.deg = active_degree;
+  return LOGRAST_OK;
+}
+static const char kAlignStep[] = "raw_rotation / dl_dact_rotation must be 16-byte aligned";
 
 int lograst_gather_activate(int32_t n, int32_t num_points, const int64_t* index, const float* xyz,
                             const float* scaling, const float* opacity, const float* rotation, const float* colors,
@@ -1682,8 +1728,7 @@ int lograst_gather_activate(int32_t n, int32_t num_points, const int64_t* index,
       !raw_rotation || !raw_colors || !act_scaling || !act_opacity || !act_rotation || !act_colors)
     return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
   if (sh_coeffs > 0 && (!shs || !raw_shs)) return lr_fail(LOGRAST_ERR_ARG, "NULL shs pointer");
-  if ((reinterpret_cast<uintptr_t>(rotation) | reinterpret_cast<uintptr_t>(raw_rotation) |
-       reinterpret_cast<uintptr_t>(act_rotation)) & 15u)
+  if (!lr_aligned16(rotation, raw_rotation, act_rotation))
     return lr_fail(LOGRAST_ERR_ARG, "rotation / raw_rotation / act_rotation must be 16-byte aligned");
   GatherArgs a;
   a.index = index; a.xyz = xyz; a.scaling = scaling; a.opacity = opacity; a.rotation = rotation; a.colors = colors;
@@ -1702,23 +1747,14 @@ int lograst_activate_backward(int32_t n, const float* raw_xyz, const float* raw_
                               const float* camera_center, const float* dl_dact_scaling, const float* dl_dact_opacity,
                               const float* dl_dact_rotation, const float* dl_dact_colors, float* dl_dscaling,
                               float* dl_dopacity, float* dl_drotation, float* dl_dcolors, float* dl_dshs, void* stream) {
-  int rc = lr_ga_check(n, sh_coeffs, active_degree, camera_center);
-  if (rc) return rc;
-  if (n == 0) return LOGRAST_OK;
-  if (!raw_xyz || !raw_scaling || !raw_opacity || !raw_rotation || !dl_dact_scaling || !dl_dact_opacity ||
-      !dl_dact_rotation || !dl_dact_colors || !dl_dscaling || !dl_dopacity || !dl_drotation || !dl_dcolors)
-    return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
-  if ((reinterpret_cast<uintptr_t>(raw_rotation) | reinterpret_cast<uintptr_t>(dl_dact_rotation) |
-       reinterpret_cast<uintptr_t>(dl_drotation)) & 15u)
-    return lr_fail(LOGRAST_ERR_ARG, "raw_rotation / dl_dact_rotation / dl_drotation must be 16-byte aligned");
   ActBwdArgs a;
-  a.r_xyz = raw_xyz; a.r_scaling = raw_scaling; a.r_opacity = raw_opacity; a.r_rotation = raw_rotation;
-  a.campos = camera_center;
-  a.g_a_scaling = dl_dact_scaling; a.g_a_opacity = dl_dact_opacity; a.g_a_rotation = dl_dact_rotation;
-  a.g_a_colors = dl_dact_colors;
+  int rc = lr_act_bwd_args(a, n, raw_xyz, raw_scaling, raw_opacity, raw_rotation, sh_coeffs, active_degree, camera_center,
+                           dl_dact_scaling, dl_dact_opacity, dl_dact_rotation, dl_dact_colors, 1,
+                           dl_dscaling && dl_dopacity && dl_drotation && dl_dcolors, dl_drotation,
+                           "raw_rotation / dl_dact_rotation / dl_drotation must be 16-byte aligned");
+  if (rc || n == 0) return rc;
   a.g_scaling = dl_dscaling; a.g_opacity = dl_dopacity; a.g_rotation = dl_drotation; a.g_colors = dl_dcolors;
   a.g_shs = dl_dshs;
-  a.n = n; a.K = sh_coeffs; a.deg = active_degree;
   g_prof_call++;
   LR_HIP(lr_launch_activate_bwd(a, (hipStream_t)stream));
   return LOGRAST_OK;
@@ -1731,41 +1767,22 @@ int lograst_activate_backward_adam(int32_t n, const float* raw_xyz, const float*
                                    int32_t num_points, const int64_t* index, const int32_t* radii,
                                    const lograst_adam_key* keys, double beta1, double beta2, double bias_correction2_sqrt,
                                    double eps, void* stream) {
-  int rc = lr_ga_check(n, sh_coeffs, active_degree, camera_center);
-  if (rc) return rc;
-  if (n == 0) return LOGRAST_OK;
-  if (num_points <= 0) return lr_fail(LOGRAST_ERR_ARG, "rows of an empty model");
-  if (!raw_xyz || !raw_scaling || !raw_opacity || !raw_rotation || !dl_dact_xyz || !dl_dact_scaling || !dl_dact_opacity ||
-      !dl_dact_rotation || !dl_dact_colors || !index || !radii || !keys)
-    return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
-  static const int widths[6] = {3, 3, 1, 4, 3, 0};
   ActBwdArgs a;
-  memset(&a, 0, sizeof(a));
-  a.r_xyz = raw_xyz; a.r_scaling = raw_scaling; a.r_opacity = raw_opacity; a.r_rotation = raw_rotation;
-  a.campos = camera_center;
-  a.g_a_scaling = dl_dact_scaling; a.g_a_opacity = dl_dact_opacity; a.g_a_rotation = dl_dact_rotation;
-  a.g_a_colors = dl_dact_colors;
-  a.n = n; a.K = sh_coeffs; a.deg = active_degree;
+  int rc = lr_act_bwd_args(a, n, raw_xyz, raw_scaling, raw_opacity, raw_rotation, sh_coeffs, active_degree, camera_center,
+                           dl_dact_scaling, dl_dact_opacity, dl_dact_rotation, dl_dact_colors, num_points,
+                           dl_dact_xyz && index && radii && keys, nullptr, kAlignStep);
+  if (rc || n == 0) return rc;
   AdamArgs f;
   memset(&f, 0, sizeof(f));
   for (int i = 0; i < 6; i++) {
     const lograst_adam_key& k = keys[i];
     if (!k.model_param) continue;                            // key not optimised in this step
-    const int w = i == 5 ? 3 * sh_coeffs : widths[i];
-    if (k.width != w) return lr_fail(LOGRAST_ERR_ARG, "lograst_activate_backward_adam: key widths are 3, 3, 1, 4, 3, 3 * sh_coeffs (xyz, scaling, opacity, rotation, colors, shs)");
+    if (k.width != lr_step_key_width(i, sh_coeffs)) return lr_fail(LOGRAST_ERR_ARG, "lograst_activate_backward_adam: key widths are 3, 3, 1, 4, 3, 3 * sh_coeffs (xyz, scaling, opacity, rotation, colors, shs)");
     if (i == 5 && (sh_coeffs == 0 || active_degree == 0)) return lr_fail(LOGRAST_ERR_ARG, "shs key without active SH coefficients");
-    if (!k.param || !k.exp_avg || !k.exp_avg_sq) return lr_fail(LOGRAST_ERR_ARG, "NULL pointer in key");
-    a.g_shs = nullptr;
-    f.key[i].model = (float*)k.model_param; f.key[i].param = (const float*)k.param; f.key[i].grad = nullptr;
-    f.key[i].exp_avg = (float*)k.exp_avg; f.key[i].exp_avg_sq = (float*)k.exp_avg_sq;
-    f.key[i].max_exp_avg_sq = (float*)k.max_exp_avg_sq;
-    f.key[i].width = k.width; f.key[i].neg_step_size = -k.step_size;
+    if ((rc = lr_adam_key(f.key[i], k, true, false))) return rc;
   }
-  if ((reinterpret_cast<uintptr_t>(raw_rotation) | reinterpret_cast<uintptr_t>(dl_dact_rotation)) & 15u)
-    return lr_fail(LOGRAST_ERR_ARG, "raw_rotation / dl_dact_rotation must be 16-byte aligned");
   f.index = index; f.flag_vis = nullptr; f.m = n; f.num_points = num_points;
-  f.beta1 = (float)beta1; f.beta2 = (float)beta2; f.omb1 = (float)(1.0 - beta1); f.omb2 = (float)(1.0 - beta2);
-  f.bc2_sqrt = (float)bias_correction2_sqrt; f.eps = (float)eps;
+  lr_adam_scalars(f, beta1, beta2, bias_correction2_sqrt, eps);
   g_prof_call++;
   LR_HIP(lr_launch_activate_bwd_adam(a, f, dl_dact_xyz, radii, (hipStream_t)stream));
   return LOGRAST_OK;
@@ -1777,8 +1794,6 @@ size_t lograst_accumulate_target_floats(int32_t num_points, int32_t row_stride_f
   return lr_acc_offset((int64_t)num_points - 1, row_stride_floats, width);
 }
 
-static const int kAccWidths[6] = {3, 3, 1, 4, 3, 0};   // xyz, scaling, opacity, rotation, colors; shs: 3 * sh_coeffs
-
 int lograst_activate_backward_accumulate(int32_t n, const float* raw_xyz, const float* raw_scaling, const float* raw_opacity,
                                          const float* raw_rotation, int32_t sh_coeffs, int32_t active_degree,
                                          const float* camera_center, const float* dl_dact_xyz, const float* dl_dact_scaling,
@@ -1786,29 +1801,17 @@ int lograst_activate_backward_accumulate(int32_t n, const float* raw_xyz, const 
                                          const float* dl_dact_colors, int32_t num_points, const int64_t* index,
                                          const int32_t* radii, const lograst_acc_target* targets, int32_t* seen,
                                          void* stream) {
-  int rc = lr_ga_check(n, sh_coeffs, active_degree, camera_center);
-  if (rc) return rc;
-  if (n == 0) return LOGRAST_OK;
-  if (num_points <= 0) return lr_fail(LOGRAST_ERR_ARG, "rows of an empty model");
-  if (!raw_xyz || !raw_scaling || !raw_opacity || !raw_rotation || !dl_dact_xyz || !dl_dact_scaling || !dl_dact_opacity ||
-      !dl_dact_rotation || !dl_dact_colors || !index || !radii || !targets || !seen)
-    return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
-  if ((reinterpret_cast<uintptr_t>(raw_rotation) | reinterpret_cast<uintptr_t>(dl_dact_rotation)) & 15u)
-    return lr_fail(LOGRAST_ERR_ARG, "raw_rotation / dl_dact_rotation must be 16-byte aligned");
   ActBwdArgs a;
-  memset(&a, 0, sizeof(a));
-  a.r_xyz = raw_xyz; a.r_scaling = raw_scaling; a.r_opacity = raw_opacity; a.r_rotation = raw_rotation;
-  a.campos = camera_center;
-  a.g_a_scaling = dl_dact_scaling; a.g_a_opacity = dl_dact_opacity; a.g_a_rotation = dl_dact_rotation;
-  a.g_a_colors = dl_dact_colors;
-  a.n = n; a.K = sh_coeffs; a.deg = active_degree;
+  int rc = lr_act_bwd_args(a, n, raw_xyz, raw_scaling, raw_opacity, raw_rotation, sh_coeffs, active_degree, camera_center,
+                           dl_dact_scaling, dl_dact_opacity, dl_dact_rotation, dl_dact_colors, num_points,
+                           dl_dact_xyz && index && radii && targets && seen, nullptr, kAlignStep);
+  if (rc || n == 0) return rc;
   AccArgs t;
   memset(&t, 0, sizeof(t));
   for (int i = 0; i < ACC_KEYS; i++) {
     if (!targets[i].base) continue;
-    const int w = i == 5 ? 3 * sh_coeffs : kAccWidths[i];
     if (i == 5 && sh_coeffs == 0) return lr_fail(LOGRAST_ERR_ARG, "shs target without SH coefficients");
-    if (targets[i].row_stride_floats < w)
+    if (targets[i].row_stride_floats < lr_step_key_width(i, sh_coeffs))
       return lr_fail(LOGRAST_ERR_ARG, "lograst_activate_backward_accumulate: a target's row stride is smaller than its key's width (3, 3, 1, 4, 3, 3 * sh_coeffs)");
     t.t[i].base = targets[i].base; t.t[i].stride = targets[i].row_stride_floats;
   }
@@ -1831,20 +1834,16 @@ int lograst_accumulated_adam(int32_t num_points, int32_t* seen, const lograst_ad
   for (int i = 0; i < ACC_KEYS; i++) {
     const lograst_adam_key& k = keys[i];
     if (!k.model_param) continue;                            // key not optimised
-    if (i == 5 ? (k.width < 3 || k.width > 45 || k.width % 3) : k.width != kAccWidths[i])
+    // (no sh_coeffs in this call: the shs key is as wide as some count of 1..15 coefficients makes it)
+    if (i == 5 ? (k.width < 3 || k.width > 45 || k.width % 3) : k.width != lr_step_key_width(i, 0))
       return lr_fail(LOGRAST_ERR_ARG, "lograst_accumulated_adam: key widths are 3, 3, 1, 4, 3, 3 * sh_coeffs (xyz, scaling, opacity, rotation, colors, shs)");
-    if (!k.grad || !k.exp_avg || !k.exp_avg_sq) return lr_fail(LOGRAST_ERR_ARG, "NULL pointer in key");
+    int rc = lr_adam_key(f.key[i], k, false, true);
+    if (rc) return rc;
     if (grad_row_stride_floats[i] < k.width) return lr_fail(LOGRAST_ERR_ARG, "lograst_accumulated_adam: a gradient row stride is smaller than its key's width");
-    f.key[i].model = (float*)k.model_param; f.key[i].param = nullptr; f.key[i].grad = (const float*)k.grad;
-    f.key[i].exp_avg = (float*)k.exp_avg; f.key[i].exp_avg_sq = (float*)k.exp_avg_sq;
-    f.key[i].max_exp_avg_sq = (float*)k.max_exp_avg_sq;
-    f.key[i].width = k.width; f.key[i].neg_step_size = -k.step_size;
     t.gstride[i] = grad_row_stride_floats[i];
   }
   f.num_points = num_points;
-  // the reference's Python scalars are doubles that torch narrows to fp32 when they meet an fp32 tensor
-  f.beta1 = (float)beta1; f.beta2 = (float)beta2; f.omb1 = (float)(1.0 - beta1); f.omb2 = (float)(1.0 - beta2);
-  f.bc2_sqrt = (float)bias_correction2_sqrt; f.eps = (float)eps;
+  lr_adam_scalars(f, beta1, beta2, bias_correction2_sqrt, eps);
   t.seen = seen; t.moved = moved_out;
   g_prof_call++;
   LR_HIP(lr_launch_accumulated_adam(f, t, (hipStream_t)stream));

@@ -127,6 +127,18 @@ LR_DEV float lr_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c);
 // max(a, b) that hands a NaN on, like torch.maximum (fmaxf returns the other operand): the amsgrad maximum of a row whose
 // gradient is NaN becomes NaN with its moments, as in the reference's _single_tensor_adam
 LR_DEV float lr_max_nan(float a, float b) { return (b >= a || b != b) ? b : a; }
+// One element's Adam update, the op sequence of _single_tensor_adam in fp32 -- THE definition: adam_kernel and
+// corrector_step_kernel (counter.hip) and ga_adam_store (sh_basis.hpp: the fused and the accumulated step) all call it, which
+// is what makes them agree bit for bit.  vd is the second moment the step divides by: max(vm, v) with amsgrad, else v.
+struct LrAdamElem { float m, v, vd, p; };
+LR_DEV LrAdamElem lr_adam_elem(float g, float m0, float v0, float vm, bool has_max, float beta1, float beta2, float omb1,
+                               float omb2, float bc2_sqrt, float eps, float neg_step_size, float p0) {
+  const float m = lr_fma(g, omb1, m0 * beta1);
+  const float v = lr_fma(omb2 * g, g, v0 * beta2);
+  const float vd = has_max ? lr_max_nan(vm, v) : v;
+  const float denom = sqrtf(vd) / bc2_sqrt + eps;
+  return LrAdamElem{m, v, vd, p0 + neg_step_size * (m / denom)};
+}
 LR_DEV float lr_dot3p(float a0, float a1, float a2, float b0, float b1, float b2, float c) {
   return lr_fma(a0, b0, lr_fma(a1, b1, lr_fma(a2, b2, c)));
 }

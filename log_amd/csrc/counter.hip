@@ -246,17 +246,12 @@ adam_kernel(AdamArgs a) {
 #pragma unroll
     for (int u = 0; u < ADAM_UNROLL; u++) {
       if (!ok[u]) continue;
-      const float m = lr_fma(g[u], a.omb1, m0[u] * a.beta1);
-      const float v = lr_fma(a.omb2 * g[u], g[u], v0[u] * a.beta2);
-      k.exp_avg[o[u]] = m;
-      k.exp_avg_sq[o[u]] = v;
-      float vd = v;
-      if (k.max_exp_avg_sq) {
-        vd = lr_max_nan(vm[u], v);
-        k.max_exp_avg_sq[o[u]] = vd;
-      }
-      const float denom = sqrtf(vd) / a.bc2_sqrt + a.eps;
-      k.model[o[u]] = p0[u] + k.neg_step_size * (m / denom);
+      const LrAdamElem r = lr_adam_elem(g[u], m0[u], v0[u], vm[u], k.max_exp_avg_sq != nullptr, a.beta1, a.beta2, a.omb1, a.omb2,
+                                        a.bc2_sqrt, a.eps, k.neg_step_size, p0[u]);
+      k.exp_avg[o[u]] = r.m;
+      k.exp_avg_sq[o[u]] = r.v;
+      if (k.max_exp_avg_sq) k.max_exp_avg_sq[o[u]] = r.vd;
+      k.model[o[u]] = r.p;
     }
   }
 }
@@ -298,15 +293,12 @@ corrector_step_kernel(CorrectorArgs a) {
   const float step_size = (1.f / bc1) * lr;
   const float bc2_sqrt = sqrtf(bc2);
   const size_t o = (size_t)a.index * (size_t)a.width + (size_t)c;
-  const float g = a.grad[o];
-  const float m = lr_fma(g, a.omb1, a.exp_avg[o] * a.beta1);
-  const float v = lr_fma(a.omb2 * g, g, a.exp_avg_sq[o] * a.beta2);
-  const float vd = lr_max_nan(a.max_exp_avg_sq[o], v);
-  const float denom = sqrtf(vd) / bc2_sqrt + a.eps;
-  a.exp_avg[o] = m;
-  a.exp_avg_sq[o] = v;
-  a.max_exp_avg_sq[o] = vd;
-  a.param[o] = a.param[o] + (-step_size) * (m / denom);
+  const LrAdamElem r = lr_adam_elem(a.grad[o], a.exp_avg[o], a.exp_avg_sq[o], a.max_exp_avg_sq[o], true, a.beta1, a.beta2, a.omb1,
+                                    a.omb2, bc2_sqrt, a.eps, -step_size, a.param[o]);
+  a.exp_avg[o] = r.m;
+  a.exp_avg_sq[o] = r.v;
+  a.max_exp_avg_sq[o] = r.vd;
+  a.param[o] = r.p;
   a.grad[o] = 0.f;
 }
 

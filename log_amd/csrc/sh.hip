@@ -12,7 +12,7 @@ __constant__ float kC2[5] = {1.0925484305920792f, -1.0925484305920792f, 0.315391
 __constant__ float kC3[7] = {-0.5900435899266435f, 2.890611442640554f, -0.4570457994644658f, 0.3731763325901154f,
                              -0.4570457994644658f, 1.445305721320277f, -0.5900435899266435f};
 #define LR_SH_TABLES_DEFINED
-#include "sh_basis.hpp"   // lr_sh_basis (reads the two tables above), lr_sh_wave_sync, the Adam element halves
+#include "sh_basis.hpp"   // lr_sh_basis (reads the two tables above) and everything the row kernels of both files share
 
 // Memory layout is [Gaussian][coefficient][channel] (L = 3*M floats per Gaussian): a lane walking its own
 // coefficients reads 4 bytes out of every 192 (M = 16), one cache line per instruction per lane.  Instead every wave
@@ -249,45 +249,19 @@ ga_bwd_kernel(ActBwdArgs a) {
   const bool ok = i < a.n;
   float gc[3] = {0.f, 0.f, 0.f};
   if (ok) {
+    const size_t c = (size_t)i;
 #pragma unroll
-    for (int k = 0; k < 3; k++) {
-      gc[k] = a.g_a_colors[3 * (size_t)i + k];
-      a.g_colors[3 * (size_t)i + k] = gc[k] * SH_C0;
-      a.g_scaling[3 * (size_t)i + k] = a.g_a_scaling[3 * (size_t)i + k] * expf(a.r_scaling[3 * (size_t)i + k]);
-    }
-    const float sg = ga_sigmoid(a.r_opacity[i]);
-    a.g_opacity[i] = a.g_a_opacity[i] * (sg * (1.f - sg));
-    const float4 q = reinterpret_cast<const float4*>(a.r_rotation)[i], gy = reinterpret_cast<const float4*>(a.g_a_rotation)[i];
-    const float n2 = q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w, nrm = sqrtf(n2);
-    float4 gq = float4{0.f, 0.f, 0.f, 0.f};
-    if (nrm > 1e-12f) {   // y = q / |q|: dL/dq = (g - y (y . g)) / |q|; below eps the clamp makes y = q / eps
-      const float ix = 1.f / nrm, yx = q.x * ix, yy = q.y * ix, yz = q.z * ix, yw = q.w * ix;
-      const float dot = yx * gy.x + yy * gy.y + yz * gy.z + yw * gy.w;
-      gq = float4{(gy.x - yx * dot) * ix, (gy.y - yy * dot) * ix, (gy.z - yz * dot) * ix, (gy.w - yw * dot) * ix};
-    } else {
-      gq = float4{gy.x * 1e12f, gy.y * 1e12f, gy.z * 1e12f, gy.w * 1e12f};
-    }
-    reinterpret_cast<float4*>(a.g_rotation)[i] = gq;
+    for (int k = 0; k < 3; k++) gc[k] = a.g_a_colors[3 * c + k];
+    float g[14];                                            // (g[0..2], dL/dxyz, is not this kernel's: autograd passes it on)
+    ga_act_grads(a, c, GA_ALL_KEYS, gc, g);
+#pragma unroll
+    for (int k = 0; k < 3; k++) { a.g_colors[3 * c + k] = g[6 + k]; a.g_scaling[3 * c + k] = g[3 + k]; }
+    a.g_opacity[c] = g[9];
+    reinterpret_cast<float4*>(a.g_rotation)[c] = float4{g[10], g[11], g[12], g[13]};
   }
   if (L > 0 && a.g_shs) {
     float* const wl = lr_sh_lds + wave * 64 * (L + 1);
-    if (ok) {
-      float b[16], bx[16], by[16], bz[16];
-#pragma unroll
-      for (int k = 0; k < 16; k++) b[k] = 0.f;
-      if (a.deg > 0) {
-        const float vx = a.r_xyz[3 * (size_t)i] - a.campos[0], vy = a.r_xyz[3 * (size_t)i + 1] - a.campos[1],
-                    vz = a.r_xyz[3 * (size_t)i + 2] - a.campos[2];
-        const float nrm = sqrtf(vx * vx + vy * vy + vz * vz);
-        lr_sh_basis(a.deg, vx / nrm, vy / nrm, vz / nrm, b, bx, by, bz);
-      }
-      const int nk = (a.deg + 1) * (a.deg + 1);
-      float* rowp = wl + lane * (L + 1);
-      for (int k = 0; k < a.K; k++) {
-        const float w = (k + 1 < nk && k + 1 < 16) ? b[k + 1] : 0.f;   // coefficients above the active degree: zero gradient
-        rowp[3 * k] = w * gc[0]; rowp[3 * k + 1] = w * gc[1]; rowp[3 * k + 2] = w * gc[2];
-      }
-    }
+    if (ok) ga_sh_grad_row(a, i, gc, wl + lane * (L + 1));
     lr_sh_wave_sync();
     lr_sh_wave_copy<false, false>(wl, a.g_shs + (size_t)i0 * L, L, rows * L, lane);
   }
@@ -298,11 +272,11 @@ ga_bwd_kernel(ActBwdArgs a) {
 // written compact) and, one launch later, SparseOptimizer.step (sparse_optimizer.py:41-78,163-196), which reads those
 // gradients back together with the gathered parameters and both moments.  Fused, a raw gradient never leaves the registers /
 // the wave's LDS rows: per element the kernel reads the gathered parameter (compact) and both moments (model rows) and
-// writes both moments and the model row -- 24 bytes instead of 32 (+ the launch).  Same op sequences as ga_bwd_kernel and
-// adam_kernel (counter.hip), so the model and the moments come out bit for bit as from the two kernels.
+// writes both moments and the model row -- 24 bytes instead of 32 (+ the launch).  The chain rule is ga_bwd_kernel's and the
+// update adam_kernel's (counter.hip) -- the same functions of sh_basis.hpp and common.hpp -- so the model and the moments come
+// out bit for bit as from the two kernels.
 // key order: 0 xyz, 1 scaling, 2 opacity, 3 rotation, 4 colors, 5 shs (model == nullptr: key not optimised).
 
-#define GA_SH_UNROLL 8
 __global__ void __launch_bounds__(256)
 ga_bwd_adam_kernel(ActBwdArgs a, AdamArgs f, const float* __restrict__ g_a_xyz, const int32_t* __restrict__ radii) {
   extern __shared__ float lr_sh_lds[];
@@ -324,75 +298,34 @@ ga_bwd_adam_kernel(ActBwdArgs a, AdamArgs f, const float* __restrict__ g_a_xyz, 
     for (int k = 0; k < 3; k++) gc[k] = a.g_a_colors[3 * (size_t)i + k];
   }
   {
-    // the row's 14 small values: xyz 0-2, scaling 3-5, colors 6-8, opacity 9, rotation 10-13 (keys 0, 1, 4, 2, 3)
+    // the row's 14 small values; a row that is not visible wants no key: nothing of it is loaded
     const bool vis = row >= 0;
     const size_t r = vis ? (size_t)row : 0, c = ok ? (size_t)i : 0;
+    unsigned want = 0;
+#pragma unroll
+    for (int key = 0; key < 5; key++) want |= (vis && f.key[key].model) ? GA_KEY(key) : 0u;
+    float g[14];
+#pragma unroll
+    for (int k = 0; k < 3; k++) g[k] = (want & GA_KEY(0)) ? g_a_xyz[3 * c + k] : 0.f;
+    ga_act_grads(a, c, want, gc, g);
     GaElem e[14];
-    float4 q = {0.f, 0.f, 0.f, 1.f}, gy = {0.f, 0.f, 0.f, 0.f};
-    if (vis && f.key[3].model) { q = reinterpret_cast<const float4*>(a.r_rotation)[c]; gy = reinterpret_cast<const float4*>(a.g_a_rotation)[c]; }
 #pragma unroll
-    for (int k = 0; k < 3; k++) {
-      e[k].on = vis && f.key[0].model; e[k].o = 3 * r + k;
-      e[k].p0 = e[k].on ? f.key[0].param[3 * c + k] : 0.f;
-      e[k].g = e[k].on ? g_a_xyz[3 * c + k] : 0.f;
-      e[3 + k].on = vis && f.key[1].model; e[3 + k].o = 3 * r + k;
-      e[3 + k].p0 = e[3 + k].on ? f.key[1].param[3 * c + k] : 0.f;
-      e[3 + k].g = e[3 + k].on ? a.g_a_scaling[3 * c + k] * expf(a.r_scaling[3 * c + k]) : 0.f;
-      e[6 + k].on = vis && f.key[4].model; e[6 + k].o = 3 * r + k;
-      e[6 + k].p0 = e[6 + k].on ? f.key[4].param[3 * c + k] : 0.f;
-      e[6 + k].g = gc[k] * SH_C0;
-    }
-    e[9].on = vis && f.key[2].model; e[9].o = r;
-    e[9].p0 = e[9].on ? f.key[2].param[c] : 0.f;
-    e[9].g = 0.f;
-    if (e[9].on) {
-      const float sg = ga_sigmoid(a.r_opacity[c]);
-      e[9].g = a.g_a_opacity[c] * (sg * (1.f - sg));
-    }
-    {
-      const float n2 = q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w, nrm = sqrtf(n2);
-      float4 gq;
-      if (nrm > 1e-12f) {   // y = q / |q|: dL/dq = (g - y (y . g)) / |q|; below eps the clamp makes y = q / eps
-        const float ix = 1.f / nrm, yx = q.x * ix, yy = q.y * ix, yz = q.z * ix, yw = q.w * ix;
-        const float dot = yx * gy.x + yy * gy.y + yz * gy.z + yw * gy.w;
-        gq = float4{(gy.x - yx * dot) * ix, (gy.y - yy * dot) * ix, (gy.z - yz * dot) * ix, (gy.w - yw * dot) * ix};
-      } else {
-        gq = float4{gy.x * 1e12f, gy.y * 1e12f, gy.z * 1e12f, gy.w * 1e12f};
-      }
-      const float gqa[4] = {gq.x, gq.y, gq.z, gq.w};
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-        e[10 + k].on = vis && f.key[3].model; e[10 + k].o = 4 * r + k;
-        e[10 + k].p0 = e[10 + k].on ? f.key[3].param[4 * c + k] : 0.f;
-        e[10 + k].g = gqa[k];
-      }
+    for (int k = 0; k < 14; k++) {
+      const GaSmall s = ga_small(k);
+      e[k].on = (want & GA_KEY(s.key)) != 0; e[k].o = s.width * r + s.col;
+      e[k].p0 = e[k].on ? f.key[s.key].param[s.width * c + s.col] : 0.f;
+      e[k].g = g[k];
     }
     // all moments requested, then all updates
 #pragma unroll
-    for (int k = 0; k < 14; k++) ga_adam_load(f.key[k < 3 ? 0 : (k < 6 ? 1 : (k < 9 ? 4 : (k < 10 ? 2 : 3)))], e[k]);
+    for (int k = 0; k < 14; k++) ga_adam_load(f.key[ga_small(k).key], e[k]);
 #pragma unroll
-    for (int k = 0; k < 14; k++) ga_adam_store(f.key[k < 3 ? 0 : (k < 6 ? 1 : (k < 9 ? 4 : (k < 10 ? 2 : 3)))], f, e[k]);
+    for (int k = 0; k < 14; k++) ga_adam_store(f.key[ga_small(k).key], f, e[k]);
   }
   if (L > 0 && f.key[5].model) {
     float* const wl = lr_sh_lds + wave * 64 * (L + 1);
     lr_rowidx[wave][lane] = row;
-    if (ok) {
-      float b[16], bx[16], by[16], bz[16];
-#pragma unroll
-      for (int k = 0; k < 16; k++) b[k] = 0.f;
-      if (a.deg > 0) {
-        const float vx = a.r_xyz[3 * (size_t)i] - a.campos[0], vy = a.r_xyz[3 * (size_t)i + 1] - a.campos[1],
-                    vz = a.r_xyz[3 * (size_t)i + 2] - a.campos[2];
-        const float nrm = sqrtf(vx * vx + vy * vy + vz * vz);
-        lr_sh_basis(a.deg, vx / nrm, vy / nrm, vz / nrm, b, bx, by, bz);
-      }
-      const int nk = (a.deg + 1) * (a.deg + 1);
-      float* rowp = wl + lane * (L + 1);
-      for (int k = 0; k < a.K; k++) {
-        const float w = (k + 1 < nk && k + 1 < 16) ? b[k + 1] : 0.f;   // coefficients above the active degree: zero gradient
-        rowp[3 * k] = w * gc[0]; rowp[3 * k + 1] = w * gc[1]; rowp[3 * k + 2] = w * gc[2];
-      }
-    }
+    if (ok) ga_sh_grad_row(a, i, gc, wl + lane * (L + 1));
     lr_sh_wave_sync();
     // the wave walks its rows' L coefficients contiguously: element e = (row r, column c) of the compact block; the model
     // side is one contiguous 4 L-byte piece per visible row.  GA_SH_UNROLL elements per lane in flight.
@@ -421,43 +354,28 @@ ga_bwd_adam_kernel(ActBwdArgs a, AdamArgs f, const float* __restrict__ g_a_xyz, 
 hipError_t lr_launch_activate_bwd_adam(const ActBwdArgs& a, const AdamArgs& f, const float* g_a_xyz, const int32_t* radii,
                                        hipStream_t s) {
   if (a.n <= 0) return hipSuccess;
-  const size_t lds = sizeof(float) * 4 * 64 * (size_t)(3 * a.K + 1);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(ga_bwd_adam_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-    attr_set = true;
-  }
+  lr_ga_lds_once<ga_bwd_adam_kernel>();
   lr_prof_begin(LRK_ADAM, s);
-  hipLaunchKernelGGL(ga_bwd_adam_kernel, dim3((a.n + 255) / 256), dim3(256), (a.K > 0 && f.key[5].model) ? lds : 0, s, a, f,
-                     g_a_xyz, radii);
+  hipLaunchKernelGGL(ga_bwd_adam_kernel, dim3((a.n + 255) / 256), dim3(256),
+                     (a.K > 0 && f.key[5].model) ? lr_ga_lds_bytes(a.K) : 0, s, a, f, g_a_xyz, radii);
   lr_prof_end(LRK_ADAM, s);
   return hipGetLastError();
 }
 
 hipError_t lr_launch_gather_activate(const GatherArgs& a, hipStream_t s) {
   if (a.n <= 0) return hipSuccess;
-  const size_t lds = sizeof(float) * 4 * 64 * (size_t)(3 * a.K + 1);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(ga_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(ga_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-    attr_set = true;
-  }
+  lr_ga_lds_once<ga_fwd_kernel>();
+  lr_ga_lds_once<ga_bwd_kernel>();   // (with the forward, as it always was: the backward's first launch finds it done)
   lr_prof_begin(LRK_GATHER, s);
-  hipLaunchKernelGGL(ga_fwd_kernel, dim3((a.n + 255) / 256), dim3(256), a.K > 0 ? lds : 0, s, a);
+  hipLaunchKernelGGL(ga_fwd_kernel, dim3((a.n + 255) / 256), dim3(256), a.K > 0 ? lr_ga_lds_bytes(a.K) : 0, s, a);
   lr_prof_end(LRK_GATHER, s);
   return hipGetLastError();
 }
 hipError_t lr_launch_activate_bwd(const ActBwdArgs& a, hipStream_t s) {
   if (a.n <= 0) return hipSuccess;
-  const size_t lds = sizeof(float) * 4 * 64 * (size_t)(3 * a.K + 1);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(ga_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-    attr_set = true;
-  }
+  lr_ga_lds_once<ga_bwd_kernel>();
   lr_prof_begin(LRK_GATHER_BWD, s);
-  hipLaunchKernelGGL(ga_bwd_kernel, dim3((a.n + 255) / 256), dim3(256), (a.K > 0 && a.g_shs) ? lds : 0, s, a);
+  hipLaunchKernelGGL(ga_bwd_kernel, dim3((a.n + 255) / 256), dim3(256), (a.K > 0 && a.g_shs) ? lr_ga_lds_bytes(a.K) : 0, s, a);
   lr_prof_end(LRK_GATHER_BWD, s);
   return hipGetLastError();
 }

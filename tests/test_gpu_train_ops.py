@@ -221,13 +221,15 @@ _FUSED_SCHEDULE = [(0, 15), (1, 15), (2, 15)]
 _FUSED_SIZES = [(1, 1), (65, 63), (257, 256), (321, 300)]
 
 
-@pytest.mark.parametrize("degree,amsgrad,K,sizes",
-                         [pytest.param(3, False, None, None, id="3-False"), pytest.param(1, True, None, None, id="1-True"),
-                          pytest.param(0, False, None, None, id="0-False")] +
-                         [pytest.param(d, d == 1, k, None, id="deg%d-K%d" % (d, k)) for d, k in _FUSED_SCHEDULE] +
-                         [pytest.param(d, d == 2, k, sz, id="deg%d-K%d-%dof%d" % (d, k, sz[1], sz[0]))
-                          for d, k in _FUSED_SCHEDULE + [(3, 15)] for sz in _FUSED_SIZES])
-def test_fused_step_kernel_equals_activation_backward_plus_sparse_adam(degree, amsgrad, K, sizes):
+@pytest.mark.parametrize("degree,amsgrad,K,sizes,left_out",
+                         [pytest.param(3, False, None, None, (), id="3-False"), pytest.param(1, True, None, None, (), id="1-True"),
+                          pytest.param(0, False, None, None, (), id="0-False")] +
+                         [pytest.param(d, d == 1, k, None, (), id="deg%d-K%d" % (d, k)) for d, k in _FUSED_SCHEDULE] +
+                         [pytest.param(d, d == 2, k, sz, (), id="deg%d-K%d-%dof%d" % (d, k, sz[1], sz[0]))
+                          for d, k in _FUSED_SCHEDULE + [(3, 15)] for sz in _FUSED_SIZES] +
+                         # keys that are not optimised: their inputs are not loaded, their rows and moments stay
+                         [pytest.param(2, True, 15, (65, 63), ("rotation", "scaling"), id="deg2-K15-63of65-no_rotation_no_scaling")])
+def test_fused_step_kernel_equals_activation_backward_plus_sparse_adam(degree, amsgrad, K, sizes, left_out):
     """Round 6 (round-5 verdict, next #6): lograst_activate_backward_adam -- the activation backward applying the reference's
     sparse Adam itself, the compact raw gradients never written -- against the two kernels it replaces, on IDENTICAL inputs
     (the same gathered rows, the same dL/d(activated), the same visibility): same op sequences, so the model, both moments
@@ -255,7 +257,7 @@ def test_fused_step_kernel_equals_activation_backward_plus_sparse_adam(degree, a
     radii = (torch.rand(n_all, device=dev, generator=gen) < 0.6).to(torch.int32) * 7
     if sizes is not None:
         radii[0] = 7                                          # a handful of rows: at least one of them is visible
-    keys = [k for k in bufs if k != "shs" or degree > 0]
+    keys = [k for k in bufs if (k != "shs" or degree > 0) and k not in left_out]
     lr = {"xyz": 1.6e-4, "scaling": 5e-3, "opacity": 0.05, "rotation": 1e-3, "colors": 2.5e-3, "shs": 1.25e-4}
     m1_0 = {k: rnd(*v.shape) * 1e-3 for k, v in bufs.items()}
     m2_0 = {k: (rnd(*v.shape) * 1e-3) ** 2 for k, v in bufs.items()}
@@ -287,6 +289,9 @@ def test_fused_step_kernel_equals_activation_backward_plus_sparse_adam(degree, a
         if amsgrad:
             assert torch.equal(ax[k], bx[k]), k
         touched += int((mb[k] != bufs[k]).sum())
+    for k in left_out:                                        # the fused kernel left the key's model rows and moments alone
+        assert torch.equal(mb[k], bufs[k]) and torch.equal(b1[k], m1_0[k]) and torch.equal(b2[k], m2_0[k]), k
+        assert not amsgrad or torch.equal(bx[k], mx_0[k]), k
     # a visible row moves in all of its 14 + 3 K values and both moments move with it; counted on the model alone, and with
     # the 100 000 of the full size (17 003 rows, about 10 200 visible: 9.8 per visible row) scaled to the rows of this case
     n_vis = int((radii[:n] > 0).sum())
