@@ -38,11 +38,14 @@ extern "C" {
  * version change (new entry points only): lograst_pack_rows_hinted, lograst_add_visible, lograst_add_visible_n.
  * 2: lograst_view gained cov3d_precomp / dl_dcov3d; 3: the backward accumulates into 64-byte rows (bwd_rows); lograst_view gained walk_form.  Added since without a version change (new entry points only): lograst_sparse_segment_floats / lograst_pack_rows / lograst_unpack_rows / lograst_ordered_lengths / lograst_finish_lists.
  * lograst_recomposite / lograst_record_bytes and the profiling slot "recolor" (LOGRAST_NUM_KERNELS 22 -> 23, appended) are
- * additions within version 4, as is lograst_backward_form: no existing entry point, layout or default changed. */
+ * additions within version 4, as is lograst_backward_form: no existing entry point, layout or default changed.  So are the
+ * aux-channel entry points lograst_forward_aux / lograst_forward_render_aux / lograst_forward_speculative_aux /
+ * lograst_backward_aux (new entry points only; lograst_view is untouched; bwd_rows slots 9-11 and, in that call, 12-14 are theirs). */
 #define LOGRAST_TILE 16        /* pixels per tile side (tile rects are part of the integer contract) */
 #define LOGRAST_REC_FLOATS 16  /* floats per projected-Gaussian record (64 B): see log_amd/csrc/project.hip */
 /* The reverse walk's accumulators: ONE 64-byte row per Gaussian -- slots 0-1 dL/d(ndc mean x, y), 2-4 dL/d(conic A, B, C),
- * 5 dL/dopacity, 6-8 dL/dcolour r g b, 9-11 unused, 12-15 scratch of the chain rule (band views keep the compact list of
+ * 5 dL/dopacity, 6-8 dL/dcolour r g b, 9-11 unused (lograst_backward_aux: dL/daux colour r g b; it also keeps the aux
+ * image's dL/d(conic A, B, C) in 12-14), 12-15 scratch of the chain rule (band views keep the compact list of
  * the live rows there: row 0 its length, rows 1.. four indices each; whatever the caller finds in bwd_rows after
  * lograst_backward is unspecified).  A memory-side atomic costs one operation per 64-byte line whatever the number of lanes
  * in it (tools/micro/atomic_lines.hip), so a (wave, Gaussian) visit commits all nine sums as one. */
@@ -270,6 +273,37 @@ int lograst_forward_speculative(const lograst_view* view, int32_t n, const float
                                 float* bwd_scratch, int32_t bwd_scratch_floats, uint32_t* status,
                                 uint32_t* num_instances_host, uint32_t* max_tile_len_host, void* stream);
 
+/* Aux channels: a second colour triple per Gaussian, aux_colors [n, 3] fp32, composited into aux_image [3, H, W] by the SAME
+ * walk that produces `image` -- one list fetch, one record gather, one support decision, one alpha evaluation, one T and
+ * stop test per visit, three more fused multiply-adds per contributing pixel.  The three sums are accumulated with the same
+ * weights, in the same list order, with the same fma as the RGB sums, and the image is written as fma(T, bg[c], sum) with
+ * the view's own bg: aux_image has the bits of `image` from a second forward whose colors are aux_colors (LoG's depth pass:
+ * [view z, world z, 1], LoG/render/renderer.py:186-201).  Every other output (radii, final_t, n_contrib, the fork's maps,
+ * point_weight, hit masks, bwd_scratch) is what the entry point without _aux leaves.  The three calls below are
+ * lograst_forward / lograst_forward_render / lograst_forward_speculative with (aux_colors, aux_image) behind `status`.
+ * Quadrant form only: the compositing kernel is the quadrant one whatever view->walk_form or LOGRAST_FWD_ROWS say, and the
+ * hit masks it leaves are quadrant masks (pass hit_mask_form = LOGRAST_FORM_QUADRANT to the backward).  LOGRAST_ERR_ARG
+ * before any launch: aux_colors or aux_image NULL with n > 0; a band view (tile_row_begin / tile_row_end); cov3d_precomp. */
+int lograst_forward_aux(const lograst_view* view, int32_t n, const float* means3d, const float* scales,
+                        const float* rotations, const float* opacities, const float* colors, int32_t* radii, void* geom,
+                        void* tile_state, uint64_t* keys, uint32_t* point_list, uint32_t capacity, uint32_t max_tile_len,
+                        float* image, float* final_t, int32_t* n_contrib, int32_t* point_id_pixel,
+                        float* point_weight_pixel, float* point_weight, float* bwd_scratch, int32_t bwd_scratch_floats,
+                        uint32_t* status, const float* aux_colors, float* aux_image, void* stream);
+int lograst_forward_render_aux(const lograst_view* view, int32_t n, const void* geom, void* tile_state,
+                               uint64_t* keys, uint32_t* point_list, uint32_t capacity, uint32_t max_tile_len,
+                               float* image, float* final_t, int32_t* n_contrib, int32_t* point_id_pixel,
+                               float* point_weight_pixel, float* point_weight, float* bwd_scratch,
+                               int32_t bwd_scratch_floats, uint32_t* status, const float* aux_colors, float* aux_image,
+                               void* stream);
+int lograst_forward_speculative_aux(const lograst_view* view, int32_t n, const float* means3d, const float* scales,
+                                    const float* rotations, const float* opacities, const float* colors, int32_t* radii,
+                                    void* geom, void* tile_state, uint64_t* keys, uint32_t* point_list, uint32_t capacity,
+                                    uint32_t max_tile_len, float* image, float* final_t, int32_t* n_contrib,
+                                    int32_t* point_id_pixel, float* point_weight_pixel, float* point_weight,
+                                    float* bwd_scratch, int32_t bwd_scratch_floats, uint32_t* status, const float* aux_colors,
+                                    float* aux_image, uint32_t* num_instances_host, uint32_t* max_tile_len_host, void* stream);
+
 /* Image split into bands of tile rows (new design, SURVEY 8e / BASELINE configs[4]; view->tile_row_begin/end): the
  * tile-row range every Gaussian's rect covers on the WHOLE image, rows_out[i] = y0 | y1 << 16 (rows [y0, y1); 0 = the
  * projection drops this Gaussian), computed by the projection's own code: the Gaussians lograst_forward keeps for a band
@@ -395,6 +429,25 @@ int lograst_backward(const lograst_view* view, int32_t n, const float* means3d, 
                      const float* dl_dimage, float* dl_dmeans2d, float* bwd_rows, float* dl_dopacities,
                      float* dl_dcolors, float* dl_dmeans3d, float* dl_dscales, float* dl_drotations,
                      const float* point_weight, int32_t flags, void* stream);
+
+/* The backward of a lograst_forward*_aux call: ONE reverse walk and ONE chain-rule launch for both images.  dl_dimage and
+ * dl_daux_image are the gradients of `image` and `aux_image` ([3, H, W] each); either may be NULL = zeros, not both.
+ * dL/dalpha is evaluated per image; fifteen per-Gaussian sums leave in four atomic instructions on the Gaussian's one 64-byte
+ * row of bwd_rows (bwd_row_floats must be LOGRAST_BWD_ROW_FLOATS: slots 9-11 take dL/daux colour, slots 12-14 the aux
+ * image's dL/dconic, kept apart from the image's in 2-4), and the chain rule writes dl_daux_colors [n, 3] next to dl_dcolors
+ * (zeros for Gaussians that composited nowhere).  dl_dmeans2d and the geometry gradients are the sums over both images; the
+ * conic part of the chain rule -- ill-conditioned in fp32 for needle-shaped Gaussians -- runs once per image inside the one
+ * launch and the results are added, which is the arithmetic of two lograst_backward calls.  Fresh gradients only: flags may hold
+ * LOGRAST_BWD_SCRATCH_ZEROED and LOGRAST_BWD_CONIC_TOUCHED_ONLY.  Quadrant form only (view->hit_masks are read when
+ * hit_mask_form = LOGRAST_FORM_QUADRANT).  LOGRAST_ERR_ARG before any launch: a band view; cov3d_precomp; aux_colors or
+ * dl_daux_colors NULL; both image gradients NULL; bwd_row_floats != 16; LOGRAST_BWD_ACCUMULATE / _ACCUMULATE_ROWS. */
+int lograst_backward_aux(const lograst_view* view, int32_t n, const float* means3d, const float* scales,
+                         const float* rotations, const int32_t* radii, const void* geom, const void* tile_state,
+                         const uint32_t* point_list, const float* final_t, const int32_t* n_contrib,
+                         const float* aux_colors, const float* dl_dimage, const float* dl_daux_image, float* dl_dmeans2d,
+                         float* bwd_rows, int32_t bwd_row_floats, float* dl_dopacities, float* dl_dcolors,
+                         float* dl_daux_colors, float* dl_dmeans3d, float* dl_dscales, float* dl_drotations,
+                         const float* point_weight, int32_t flags, void* stream);
 
 /* Stage A6b alone: the per-Gaussian chain rule, given dL/d(ndc mean) [n,3] and dL/d(conic) [n,4] (as left
  * by the reverse walk).  Writes dl_dmeans3d/dl_dscales/dl_drotations.  lograst_backward = reverse walk +

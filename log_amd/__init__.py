@@ -18,7 +18,7 @@ def install_compute_radius():
 
 def install_all(fused_step=False, fused_loss=False, reuse_geometry=False, fused_depth_loss=False, device_densify=False,
                 device_prepare=False, device_decide=False, device_view_correction=False, device_evaluate=False, device_init=False,
-                views_per_step=None, masked_loss=False):
+                views_per_step=None, masked_loss=False, fused_depth_pass=False):
     """Everything a LoG process needs, in one call: the LoG.cuda.compute_radius module, then every
     drop-in method assigned onto LoG's own classes (needs LoG importable): LoG.get_all, TensorTree.traverse,
     Counter.update_by_output, SparseOptimizer.step.
@@ -62,7 +62,12 @@ def install_all(fused_step=False, fused_loss=False, reuse_geometry=False, fused_
     masked_loss (opt-in): a mask_ignore in calculate_loss is blended inside the loss kernels, and MaskForeground.forward /
     bound_from_mask take the mask's bounding box from one kernel, crop by views and composite the ground truth inside the
     same loss call (log_amd.masked_loss.install, which installs log_amd.loss as well: two read-backs per foreground step,
-    the bounds and loss_dict); without it masks stay torch code around the loss."""
+    the bounds and loss_dict); without it masks stay torch code around the loss.
+    fused_depth_pass (opt-in): NaiveRendererAndLoss.render hands the reference's own render a proxy around the rasterizer, so
+    that a render_depth: True view composites [view z, world z, 1] in the walk of its colour call and its second rasterizer
+    call launches nothing (log_amd.depth_pass.install: same depth / height / accmap bits, one reverse walk and one chain rule
+    for both images; quadrant kernels only -- see INTEGRATION 3b for where that is slower); reuse_geometry then has nothing
+    left to reuse on such a view."""
     install_compute_radius()
     from . import rasterizer
     rasterizer.set_geometry_reuse(bool(reuse_geometry))
@@ -99,4 +104,7 @@ def install_all(fused_step=False, fused_loss=False, reuse_geometry=False, fused_
     if device_init:
         from . import init_pass
         installed.append(init_pass.install())
+    if fused_depth_pass:
+        from . import depth_pass
+        installed.append(depth_pass.install())
     return installed

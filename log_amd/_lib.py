@@ -124,6 +124,16 @@ _SIGNATURES = {
     "lograst_forward_speculative": (ctypes.c_int, [ctypes.POINTER(LograstView), c_int32] + [c_void_p] * 10
                                     + [c_uint32, c_uint32] + [c_void_p] * 7 + [c_int32, c_void_p]
                                     + [ctypes.POINTER(c_uint32), ctypes.POINTER(c_uint32), c_void_p]),
+    # aux channels: the three forwards with (aux_colors, aux_image) behind `status`
+    "lograst_forward_aux": (ctypes.c_int, [ctypes.POINTER(LograstView), c_int32] + [c_void_p] * 10 + [c_uint32, c_uint32]
+                            + [c_void_p] * 7 + [c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "lograst_forward_render_aux": (ctypes.c_int, [ctypes.POINTER(LograstView), c_int32, c_void_p, c_void_p, c_void_p,
+                                                  c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                  c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
+                                                  c_void_p]),
+    "lograst_forward_speculative_aux": (ctypes.c_int, [ctypes.POINTER(LograstView), c_int32] + [c_void_p] * 10
+                                        + [c_uint32, c_uint32] + [c_void_p] * 7 + [c_int32, c_void_p, c_void_p, c_void_p]
+                                        + [ctypes.POINTER(c_uint32), ctypes.POINTER(c_uint32), c_void_p]),
     "lograst_tile_rows": (ctypes.c_int, [ctypes.POINTER(LograstView), c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                                          c_void_p]),
     "lograst_stream_copy": (ctypes.c_int, [c_void_p, c_void_p, c_size_t, c_int32, c_void_p]),
@@ -146,6 +156,8 @@ _SIGNATURES = {
     "lograst_get_knob": (ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(c_int32)]),
     "lograst_reset_knobs": (ctypes.c_int, []),
     "lograst_backward": (ctypes.c_int, [ctypes.POINTER(LograstView), c_int32] + [c_void_p] * 18 + [c_int32, c_void_p]),
+    "lograst_backward_aux": (ctypes.c_int, [ctypes.POINTER(LograstView), c_int32] + [c_void_p] * 14 + [c_int32]
+                             + [c_void_p] * 7 + [c_int32, c_void_p]),
     "lograst_project_backward": (ctypes.c_int, [ctypes.POINTER(LograstView), c_int32] + [c_void_p] * 10),
     "lograst_sh_forward": (ctypes.c_int, [c_int32, c_int32, c_int32] + [c_void_p] * 6),
     "lograst_sh_backward": (ctypes.c_int, [c_int32, c_int32, c_int32] + [c_void_p] * 7 + [c_int32, c_void_p]),

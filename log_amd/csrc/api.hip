@@ -365,6 +365,8 @@ struct LrForwardArgs {
   void* stream;
   int speculative;              // stage 2 is enqueued before the host knows whether `capacity` suffices
   hipEvent_t after_stage1;      // recorded between the stages (or nullptr)
+  int aux;                      // the *_aux entry points: aux_colors [n, 3] are composited into aux_image [3, H, W] by the same walk
+  const float* aux_colors; float* aux_image;
 };
 
 // stage 1 launches: memset of header + counters, projection (+ counting / ranking), tile scan
@@ -425,12 +427,12 @@ static void lr_composite(const LrView& v, const LrPlan& p, const LrForwardArgs& 
                          uint32_t* st, bool sort_rest, hipStream_t s) {
   float* const zrows = c.touched_only ? a.bwd_scratch : nullptr;
   lr_launch_blend_fwd(v, geom, st, p.tiles, a.point_list, a.capacity, a.image, a.final_t, a.n_contrib, a.point_id_pixel,
-                      a.point_weight_pixel, a.point_weight, zrows, p.big_input ? 1 : 0, c.lazy, v.masks, s);
+                      a.point_weight_pixel, a.point_weight, zrows, p.big_input ? 1 : 0, c.lazy, v.masks, s, a.aux_colors, a.aux_image);
   if (c.lazy) {
     lr_prof_begin(LRK_LAZY_TAIL, s);
     if (sort_rest) lr_launch_sort_rest(st, p.tiles, a.keys, a.point_list, a.capacity, a.max_tile_len, 2, s);
     lr_launch_blend_fwd(v, geom, st, p.tiles, a.point_list, a.capacity, a.image, a.final_t, a.n_contrib, a.point_id_pixel,
-                        a.point_weight_pixel, a.point_weight, zrows, p.big_input ? 1 : 0, 2, v.masks, s);
+                        a.point_weight_pixel, a.point_weight, zrows, p.big_input ? 1 : 0, 2, v.masks, s, a.aux_colors, a.aux_image);
     lr_prof_end(LRK_LAZY_TAIL, s);
   }
 }
@@ -496,7 +498,19 @@ static int lr_check_stage2_args(const LrView& v, const LrForwardArgs& a, bool so
   return LOGRAST_OK;
 }
 
-// The one forward body behind the four entry points, in two halves (lograst_forward_speculative has checks of its own
+// What the *_aux entry points ask on top (forward: aux_colors / aux_image; backward: its own list): whole images, scales and
+// rotations.  The aux walk exists in the quadrant form only, and the chain rule's aux output not next to cov3d_precomp.
+static int lr_check_aux_view(const LrView& v) {
+  if (v.ty0 != 0 || v.ty1 != v.gy) return lr_fail(LOGRAST_ERR_ARG, "aux channels render whole images only (tile_row_begin / tile_row_end)");
+  if (v.cov3d) return lr_fail(LOGRAST_ERR_ARG, "aux channels have no cov3d_precomp form");
+  return LOGRAST_OK;
+}
+static int lr_check_aux_args(const LrView& v, const LrForwardArgs& a) {
+  if (a.n > 0 && (!a.aux_colors || !a.aux_image)) return lr_fail(LOGRAST_ERR_ARG, "aux_colors / aux_image are NULL");
+  return lr_check_aux_view(v);
+}
+
+// The one forward body behind the four entry points and their _aux forms, in two halves (lograst_forward_speculative has checks of its own
 // between them): the view and the argument checks of the stages asked for, stage 1's first; then plan and launches.
 static int lr_forward_check(const LrForwardArgs& a, bool stage1, bool stage2, LrView* v) {
   g_prof_call++;
@@ -504,6 +518,7 @@ static int lr_forward_check(const LrForwardArgs& a, bool stage1, bool stage2, Lr
   if (rc) return rc;
   if (stage1 && (rc = lr_check_stage1_args(*v, a))) return rc;
   if (stage2 && (rc = lr_check_stage2_args(*v, a))) return rc;
+  if (a.aux && (rc = lr_check_aux_args(*v, a))) return rc;
   return LOGRAST_OK;
 }
 static int lr_forward_launch(const LrView& v, const LrForwardArgs& a, bool stage1, bool stage2) {
@@ -565,6 +580,34 @@ int lograst_forward(const lograst_view* view, int32_t n, const float* means3d, c
   return lr_forward(a, true, true);
 }
 
+// ---- aux channels: the forward entry points once more, with a second colour triple per Gaussian ----------------------
+static LrForwardArgs lr_with_aux(LrForwardArgs a, const float* aux_colors, float* aux_image) {
+  a.aux = 1; a.aux_colors = aux_colors; a.aux_image = aux_image;
+  return a;
+}
+int lograst_forward_aux(const lograst_view* view, int32_t n, const float* means3d, const float* scales,
+                        const float* rotations, const float* opacities, const float* colors, int32_t* radii, void* geom,
+                        void* tile_state, uint64_t* keys, uint32_t* point_list, uint32_t capacity, uint32_t max_tile_len,
+                        float* image, float* final_t, int32_t* n_contrib, int32_t* point_id_pixel,
+                        float* point_weight_pixel, float* point_weight, float* bwd_scratch, int32_t bwd_scratch_floats,
+                        uint32_t* status, const float* aux_colors, float* aux_image, void* stream) {
+  const LrForwardArgs a = {view, n, means3d, scales, rotations, opacities, colors, radii, geom, tile_state,
+                           keys, point_list, capacity, max_tile_len, image, final_t, n_contrib, point_id_pixel,
+                           point_weight_pixel, point_weight, bwd_scratch, bwd_scratch_floats, status, stream};
+  return lr_forward(lr_with_aux(a, aux_colors, aux_image), true, true);
+}
+int lograst_forward_render_aux(const lograst_view* view, int32_t n, const void* geom, void* tile_state,
+                               uint64_t* keys, uint32_t* point_list, uint32_t capacity, uint32_t max_tile_len,
+                               float* image, float* final_t, int32_t* n_contrib, int32_t* point_id_pixel,
+                               float* point_weight_pixel, float* point_weight, float* bwd_scratch,
+                               int32_t bwd_scratch_floats, uint32_t* status, const float* aux_colors, float* aux_image,
+                               void* stream) {
+  const LrForwardArgs a = {view, n, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, const_cast<void*>(geom), tile_state,
+                           keys, point_list, capacity, max_tile_len, image, final_t, n_contrib, point_id_pixel,
+                           point_weight_pixel, point_weight, bwd_scratch, bwd_scratch_floats, status, stream};
+  return lr_forward(lr_with_aux(a, aux_colors, aux_image), false, true);
+}
+
 // The stage-2 outputs of a forward once more, for other colours, from the lists of a forward that ran: no fill, no sort.
 int lograst_recomposite(const lograst_view* view, int32_t n, const int32_t* radii, const void* geom, const void* tile_state,
                         const uint32_t* point_list, uint32_t capacity, uint32_t max_tile_len, const float* colors,
@@ -615,16 +658,8 @@ static int lr_spec_get(LrSpec** out) {
   return LOGRAST_OK;
 }
 
-int lograst_forward_speculative(const lograst_view* view, int32_t n, const float* means3d, const float* scales,
-                                const float* rotations, const float* opacities, const float* colors, int32_t* radii,
-                                void* geom, void* tile_state, uint64_t* keys, uint32_t* point_list, uint32_t capacity,
-                                uint32_t max_tile_len, float* image, float* final_t, int32_t* n_contrib,
-                                int32_t* point_id_pixel, float* point_weight_pixel, float* point_weight,
-                                float* bwd_scratch, int32_t bwd_scratch_floats, uint32_t* status,
-                                uint32_t* num_instances_host, uint32_t* max_tile_len_host, void* stream) {
-  LrForwardArgs a = {view, n, means3d, scales, rotations, opacities, colors, radii, geom, tile_state,
-                     keys, point_list, capacity, max_tile_len, image, final_t, n_contrib, point_id_pixel,
-                     point_weight_pixel, point_weight, bwd_scratch, bwd_scratch_floats, status, stream};
+static int lr_forward_speculative(LrForwardArgs a, uint32_t* num_instances_host, uint32_t* max_tile_len_host) {
+  void* const tile_state = a.tile_state;
   LrView v;
   int rc = lr_forward_check(a, true, true, &v);
   if (rc) return rc;
@@ -645,6 +680,30 @@ int lograst_forward_speculative(const lograst_view* view, int32_t n, const float
   *num_instances_host = sp->pinned[LR_HDR_NUM];
   *max_tile_len_host = sp->pinned[LR_HDR_MAXLEN];
   return LOGRAST_OK;
+}
+int lograst_forward_speculative(const lograst_view* view, int32_t n, const float* means3d, const float* scales,
+                                const float* rotations, const float* opacities, const float* colors, int32_t* radii,
+                                void* geom, void* tile_state, uint64_t* keys, uint32_t* point_list, uint32_t capacity,
+                                uint32_t max_tile_len, float* image, float* final_t, int32_t* n_contrib,
+                                int32_t* point_id_pixel, float* point_weight_pixel, float* point_weight,
+                                float* bwd_scratch, int32_t bwd_scratch_floats, uint32_t* status,
+                                uint32_t* num_instances_host, uint32_t* max_tile_len_host, void* stream) {
+  const LrForwardArgs a = {view, n, means3d, scales, rotations, opacities, colors, radii, geom, tile_state,
+                           keys, point_list, capacity, max_tile_len, image, final_t, n_contrib, point_id_pixel,
+                           point_weight_pixel, point_weight, bwd_scratch, bwd_scratch_floats, status, stream};
+  return lr_forward_speculative(a, num_instances_host, max_tile_len_host);
+}
+int lograst_forward_speculative_aux(const lograst_view* view, int32_t n, const float* means3d, const float* scales,
+                                    const float* rotations, const float* opacities, const float* colors, int32_t* radii,
+                                    void* geom, void* tile_state, uint64_t* keys, uint32_t* point_list, uint32_t capacity,
+                                    uint32_t max_tile_len, float* image, float* final_t, int32_t* n_contrib,
+                                    int32_t* point_id_pixel, float* point_weight_pixel, float* point_weight,
+                                    float* bwd_scratch, int32_t bwd_scratch_floats, uint32_t* status, const float* aux_colors,
+                                    float* aux_image, uint32_t* num_instances_host, uint32_t* max_tile_len_host, void* stream) {
+  const LrForwardArgs a = {view, n, means3d, scales, rotations, opacities, colors, radii, geom, tile_state,
+                           keys, point_list, capacity, max_tile_len, image, final_t, n_contrib, point_id_pixel,
+                           point_weight_pixel, point_weight, bwd_scratch, bwd_scratch_floats, status, stream};
+  return lr_forward_speculative(lr_with_aux(a, aux_colors, aux_image), num_instances_host, max_tile_len_host);
 }
 
 int lograst_tile_rows(const lograst_view* view, int32_t n, const float* means3d, const float* scales,
@@ -797,12 +856,15 @@ int lograst_read_state(const void* tile_state, uint32_t* num_instances_host, uin
   return LOGRAST_OK;
 }
 
-int lograst_backward(const lograst_view* view, int32_t n, const float* means3d, const float* scales,
-                     const float* rotations, const int32_t* radii, const void* geom, const void* tile_state,
-                     const uint32_t* point_list, const float* final_t, const int32_t* n_contrib,
-                     const float* dl_dimage, float* dl_dmeans2d, float* bwd_rows, float* dl_dopacities,
-                     float* dl_dcolors, float* dl_dmeans3d, float* dl_dscales, float* dl_drotations,
-                     const float* point_weight, int32_t flags, void* stream) {
+// What lograst_backward_aux has on top of lograst_backward (aux.on = 0: the plain backward).
+struct LrBackwardAux { int on; const float* aux_colors; const float* dl_daux_image; int32_t bwd_row_floats; float* dl_daux_colors; };
+// The one backward body behind lograst_backward and lograst_backward_aux.
+static int lr_backward(const lograst_view* view, int32_t n, const float* means3d, const float* scales,
+                       const float* rotations, const int32_t* radii, const void* geom, const void* tile_state,
+                       const uint32_t* point_list, const float* final_t, const int32_t* n_contrib,
+                       const float* dl_dimage, float* dl_dmeans2d, float* bwd_rows, float* dl_dopacities,
+                       float* dl_dcolors, float* dl_dmeans3d, float* dl_dscales, float* dl_drotations,
+                       const float* point_weight, int32_t flags, void* stream, const LrBackwardAux& aux) {
   float* const dl_dconic = bwd_rows;   // (the fourth gradient argument: since version 3 the n x 16 accumulator rows)
   g_prof_call++;
   LrView v;
@@ -811,7 +873,16 @@ int lograst_backward(const lograst_view* view, int32_t n, const float* means3d, 
   if (n < 0) return lr_fail(LOGRAST_ERR_ARG, "negative Gaussian count");
   if (n == 0) return LOGRAST_OK;
   const bool sink_rows = (flags & LOGRAST_BWD_ACCUMULATE_ROWS) != 0;
-  if (!means3d || !radii || !geom || !tile_state || !final_t || !n_contrib || !dl_dimage ||
+  if (aux.on) {   // (before anything else of the call: the aux form's own argument errors)
+    if ((rc = lr_check_aux_view(v))) return rc;
+    if (!aux.aux_colors || !aux.dl_daux_colors) return lr_fail(LOGRAST_ERR_ARG, "aux_colors / dl_daux_colors are NULL");
+    if (!dl_dimage && !aux.dl_daux_image) return lr_fail(LOGRAST_ERR_ARG, "dl_dimage and dl_daux_image are both NULL");
+    if (aux.bwd_row_floats != LOGRAST_BWD_ROW_FLOATS)
+      return lr_fail(LOGRAST_ERR_ARG, "bwd_rows must hold LOGRAST_BWD_ROW_FLOATS (16) floats per Gaussian (dL/daux_colors: slots 9..11)");
+    if (flags & (LOGRAST_BWD_ACCUMULATE | LOGRAST_BWD_ACCUMULATE_ROWS))
+      return lr_fail(LOGRAST_ERR_ARG, "lograst_backward_aux writes fresh gradients (no LOGRAST_BWD_ACCUMULATE / _ROWS form)");
+  }
+  if (!means3d || !radii || !geom || !tile_state || !final_t || !n_contrib || (!aux.on && !dl_dimage) ||
       !dl_dmeans2d || !dl_dconic || !dl_dmeans3d || (!sink_rows && (!dl_dopacities || !dl_dcolors)))
     return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
   if (sink_rows) {   // dl_dmeans3d = the caller's [n][LOGRAST_GRAD_ROW_FLOATS] running sums; the other four are not used
@@ -845,13 +916,35 @@ int lograst_backward(const lograst_view* view, int32_t n, const float* means3d, 
     LR_HIP(hipMemsetAsync(dl_dconic, 0, sizeof(float) * LOGRAST_BWD_ROW_FLOATS * (size_t)n, s));
   // capacity check is a forward concern: a list that rendered is by construction within capacity
   lr_launch_blend_bwd(v, geom, st, tiles, point_list, 0xffffffffu, final_t, n_contrib, dl_dimage, dl_dconic,
-                      big_input ? 1 : 0, v.masks, s);
+                      big_input ? 1 : 0, v.masks, s, aux.on ? aux.aux_colors : nullptr, aux.on ? aux.dl_daux_image : nullptr);
   // the chain rule reads every live Gaussian's accumulator row and hands out the separate outputs: dL/dmeans2D (written
   // for all rows), dL/dopacities and dL/dcolors (written, or added to the caller's running sums)
   lr_launch_project_bwd(v, n, means3d, scales, rotations, radii, nullptr, nullptr, dl_dconic, dl_dmeans2d, dl_dopacities,
-                        dl_dcolors, point_weight, dl_dmeans3d, dl_dscales, dl_drotations, accumulate, sink_rows, big_input, s);
+                        dl_dcolors, point_weight, dl_dmeans3d, dl_dscales, dl_drotations, accumulate, sink_rows, big_input, s,
+                        aux.on ? aux.dl_daux_colors : nullptr);
   LR_HIP(hipGetLastError());
   return LOGRAST_OK;
+}
+int lograst_backward(const lograst_view* view, int32_t n, const float* means3d, const float* scales,
+                     const float* rotations, const int32_t* radii, const void* geom, const void* tile_state,
+                     const uint32_t* point_list, const float* final_t, const int32_t* n_contrib,
+                     const float* dl_dimage, float* dl_dmeans2d, float* bwd_rows, float* dl_dopacities,
+                     float* dl_dcolors, float* dl_dmeans3d, float* dl_dscales, float* dl_drotations,
+                     const float* point_weight, int32_t flags, void* stream) {
+  return lr_backward(view, n, means3d, scales, rotations, radii, geom, tile_state, point_list, final_t, n_contrib, dl_dimage,
+                     dl_dmeans2d, bwd_rows, dl_dopacities, dl_dcolors, dl_dmeans3d, dl_dscales, dl_drotations, point_weight,
+                     flags, stream, LrBackwardAux{0, nullptr, nullptr, 0, nullptr});
+}
+int lograst_backward_aux(const lograst_view* view, int32_t n, const float* means3d, const float* scales,
+                         const float* rotations, const int32_t* radii, const void* geom, const void* tile_state,
+                         const uint32_t* point_list, const float* final_t, const int32_t* n_contrib,
+                         const float* aux_colors, const float* dl_dimage, const float* dl_daux_image, float* dl_dmeans2d,
+                         float* bwd_rows, int32_t bwd_row_floats, float* dl_dopacities, float* dl_dcolors,
+                         float* dl_daux_colors, float* dl_dmeans3d, float* dl_dscales, float* dl_drotations,
+                         const float* point_weight, int32_t flags, void* stream) {
+  return lr_backward(view, n, means3d, scales, rotations, radii, geom, tile_state, point_list, final_t, n_contrib, dl_dimage,
+                     dl_dmeans2d, bwd_rows, dl_dopacities, dl_dcolors, dl_dmeans3d, dl_dscales, dl_drotations, point_weight,
+                     flags, stream, LrBackwardAux{1, aux_colors, dl_daux_image, bwd_row_floats, dl_daux_colors});
 }
 
 int lograst_project_backward(const lograst_view* view, int32_t n, const float* means3d, const float* scales,

@@ -135,6 +135,15 @@ LR_DEV void lr_lazy_park(const LrView& v, size_t pix, bool done, float T, float 
   image[pix] = C0; image[plane + pix] = C1; image[2 * plane + pix] = C2;
   if (EXTRAS) { pid[pix] = wid; pwp[pix] = wmax; }
 }
+// (aux channels: the three aux sums between the two passes, in the aux image's planes as the RGB sums are in the image's)
+LR_DEV void lr_lazy_park_aux(const LrView& v, size_t pix, float D0, float D1, float D2, float* aux_image) {
+  const size_t plane = (size_t)v.W * v.H;
+  aux_image[pix] = D0; aux_image[plane + pix] = D1; aux_image[2 * plane + pix] = D2;
+}
+LR_DEV void lr_lazy_resume_aux(const LrView& v, size_t pix, float& D0, float& D1, float& D2, const float* aux_image) {
+  const size_t plane = (size_t)v.W * v.H;
+  D0 = aux_image[pix]; D1 = aux_image[plane + pix]; D2 = aux_image[2 * plane + pix];
+}
 template <bool EXTRAS>
 LR_DEV void lr_lazy_resume(const LrView& v, size_t pix, bool& done, float& T, float& C0, float& C1, float& C2, int& last,
                            int& wid, float& wmax, const float* image, const float* final_T, const int* n_contrib,
@@ -224,14 +233,20 @@ LR_DEV void lr_fwd_commit_chunk(uint32_t* wmx, int lane, uint32_t id_prev, float
   __builtin_amdgcn_wave_barrier();
 }
 
-template <bool EXTRAS>
+// AUX (lograst_forward_aux): a second colour triple per Gaussian, aux_colors [N, 3], composited into aux_image [3, H, W] by
+// the same walk -- three more sums per pixel, accumulated with the same w, in the same list order, with the same lr_fma as
+// C0..C2, so aux_image has the bits of a second forward over aux_colors.  The triple is read straight from the caller's
+// [N, 3] array through the scalar cache, in the record's batch of scalar loads (12 bytes of one more line per visited
+// entry; the 64-byte records are not touched: the reverse walk and a recomposite read them).
+template <bool EXTRAS, bool AUX = false>
 __global__ void __launch_bounds__(256)
 lr_blend_fwd_kernel(LrView v, const float4* __restrict__ geom, const uint32_t* __restrict__ state,
                     uint32_t tiles, const uint32_t* __restrict__ plist, uint32_t capacity,
                     float* __restrict__ image, float* __restrict__ final_T, int* __restrict__ n_contrib,
                     int* __restrict__ pid, float* __restrict__ pwp, float* __restrict__ pw,
                     float4* __restrict__ zero_conic, int xcd_mode, int cull, uint32_t* __restrict__ lazy_state, int lazy,
-                    uint64_t* __restrict__ masks, uint32_t* __restrict__ hdr_w) {
+                    uint64_t* __restrict__ masks, uint32_t* __restrict__ hdr_w,
+                    const float* __restrict__ aux_colors = nullptr, float* __restrict__ aux_image = nullptr) {
   if (lr_bail(state, capacity)) return;
   if (lazy == 2 && !lazy_state[LR_HDR_OPEN]) return;         // nobody parked (lazy_state: the tile state again, through the pointer these kernels WRITE sorted[] / open[] / the flag with)
   if (masks && blockIdx.x == 0 && threadIdx.x == 0) hdr_w[LR_HDR_MASKS] = LR_MASK_FORM_QUAD;
@@ -257,9 +272,11 @@ lr_blend_fwd_kernel(LrView v, const float4* __restrict__ geom, const uint32_t* _
   const size_t pix = inside ? (size_t)py * v.W + px : 0;
   bool done = !inside;
   float T = 1.f, C0 = 0.f, C1 = 0.f, C2 = 0.f, wmax = 0.f;
+  float D0 = 0.f, D1 = 0.f, D2 = 0.f;                         // (AUX: the aux image's sums)
   int wid = -1, last = 0;
   if (lazy == 2) {                                           // second pass: this wave parked at list position `first`
     if (inside) lr_lazy_resume<EXTRAS>(v, pix, done, T, C0, C1, C2, last, wid, wmax, image, final_T, n_contrib, pid, pwp);
+    if (AUX && inside) lr_lazy_resume_aux(v, pix, D0, D1, D2, aux_image);
     beg += first;
   }
 
@@ -309,7 +326,18 @@ lr_blend_fwd_kernel(LrView v, const float4* __restrict__ geom, const uint32_t* _
       const float cbl0 = reinterpret_cast<const float*>(r0)[8], cbl1 = reinterpret_cast<const float*>(r1)[8];
       // keep the colour loads in this one batch of scalar loads (left alone the compiler sinks them below the hit test:
       // a second, exposed scalar-cache round trip in every contributing iteration)
-      asm volatile("" : : "s"(q01.z), "s"(q01.w), "s"(cbl0), "s"(q11.z), "s"(q11.w), "s"(cbl1));
+      // (AUX: the aux triples are issued in front of that fence and named by it too -- their addresses need gid0 / gid1 only,
+      // and nothing has brought their lines in before, as the next chunk's vector prefetch has the records')
+      float ax0 = 0.f, ay0 = 0.f, az0 = 0.f, ax1 = 0.f, ay1 = 0.f, az1 = 0.f;
+      if (AUX) {
+        const float* __restrict__ a0 = aux_colors + 3 * (size_t)(uint32_t)gid0;
+        const float* __restrict__ a1 = aux_colors + 3 * (size_t)(uint32_t)gid1;
+        ax0 = a0[0]; ay0 = a0[1]; az0 = a0[2]; ax1 = a1[0]; ay1 = a1[1]; az1 = a1[2];
+        asm volatile("" : : "s"(q01.z), "s"(q01.w), "s"(cbl0), "s"(q11.z), "s"(q11.w), "s"(cbl1),
+                     "s"(ax0), "s"(ay0), "s"(az0), "s"(ax1), "s"(ay1), "s"(az1));
+      } else {
+        asm volatile("" : : "s"(q01.z), "s"(q01.w), "s"(cbl0), "s"(q11.z), "s"(q11.w), "s"(cbl1));
+      }
       const float op0 = q01.y, op1 = q11.y;
       const lr_f2 dx2 = lr_f2{q00.x, q10.x} - pxf, dy2 = lr_f2{q00.y, q10.y} - pyf;
       const lr_f2 hdx2 = dx2 * -0.5f, hdy2 = dy2 * -0.5f;
@@ -344,6 +372,7 @@ lr_blend_fwd_kernel(LrView v, const float4* __restrict__ geom, const uint32_t* _
         const float cr = q01.z, cg = q01.w, cbl = cbl0;
         const int gid = gid0;
         if (acc0) { C0 = lr_fma(cr, w0, C0); C1 = lr_fma(cg, w0, C1); C2 = lr_fma(cbl, w0, C2); }
+        if (AUX && acc0) { D0 = lr_fma(ax0, w0, D0); D1 = lr_fma(ay0, w0, D1); D2 = lr_fma(az0, w0, D2); }
         if (EXTRAS) {
           if (w0 > wmax) { wmax = w0; wid = gid; }
           const uint32_t m = lr_wave_umax_to63(__float_as_uint(w0));  // w >= 0: unsigned order == float order
@@ -354,6 +383,7 @@ lr_blend_fwd_kernel(LrView v, const float4* __restrict__ geom, const uint32_t* _
         const float cr = q11.z, cg = q11.w, cbl = cbl1;
         const int gid = gid1;
         if (acc1) { C0 = lr_fma(cr, w1, C0); C1 = lr_fma(cg, w1, C1); C2 = lr_fma(cbl, w1, C2); }
+        if (AUX && acc1) { D0 = lr_fma(ax1, w1, D0); D1 = lr_fma(ay1, w1, D1); D2 = lr_fma(az1, w1, D2); }
         if (EXTRAS) {
           if (w1 > wmax) { wmax = w1; wid = gid; }
           const uint32_t m = lr_wave_umax_to63(__float_as_uint(w1));
@@ -367,6 +397,7 @@ lr_blend_fwd_kernel(LrView v, const float4* __restrict__ geom, const uint32_t* _
   if (clamped && !__all(done)) {                             // out of ordered entries with a pixel open: to be continued
     if (lane == 0) { atomicOr(lazy_state + lr_sorted_off(tiles) + tiles + tile, 1u << quad); atomicOr(lazy_state + LR_HDR_OPEN, 1u); }   // open[tile], header
     if (inside) lr_lazy_park<EXTRAS>(v, pix, done, T, C0, C1, C2, last, wid, wmax, image, final_T, n_contrib, pid, pwp);
+    if (AUX && inside) lr_lazy_park_aux(v, pix, D0, D1, D2, aux_image);
     return;
   }
 
@@ -377,6 +408,11 @@ lr_blend_fwd_kernel(LrView v, const float4* __restrict__ geom, const uint32_t* _
     image[pix] = lr_fma(T, v.bg[0], C0);
     image[plane + pix] = lr_fma(T, v.bg[1], C1);
     image[2 * plane + pix] = lr_fma(T, v.bg[2], C2);
+    if (AUX) {                                                // (the view's own bg: LoG's depth image carries T * bg too)
+      aux_image[pix] = lr_fma(T, v.bg[0], D0);
+      aux_image[plane + pix] = lr_fma(T, v.bg[1], D1);
+      aux_image[2 * plane + pix] = lr_fma(T, v.bg[2], D2);
+    }
     if (EXTRAS) { pid[pix] = wid; pwp[pix] = wmax; }
   }
 }
@@ -416,13 +452,34 @@ LR_DEV void lr_reduce9(const float v[9], float& r0, float& r1, float& r2) {
   r2 = lr_row_sum(lr_swap_add16(s8, s8));
 }
 
-template <bool MASKS>
+// AUX (lograst_backward_aux): four full quads.  The rows of r2 / r3 are the sums of (v8, v10, v9, v11) / (v12, v14, v13, v15).
+LR_DEV void lr_reduce16(const float v[16], float& r0, float& r1, float& r2, float& r3) {
+  const float p0 = lr_swap_add32(v[0], v[1]), p1 = lr_swap_add32(v[2], v[3]);
+  const float p2 = lr_swap_add32(v[4], v[5]), p3 = lr_swap_add32(v[6], v[7]);
+  const float p4 = lr_swap_add32(v[8], v[9]), p5 = lr_swap_add32(v[10], v[11]);
+  const float p6 = lr_swap_add32(v[12], v[13]), p7 = lr_swap_add32(v[14], v[15]);
+  r0 = lr_row_sum(lr_swap_add16(p0, p1));
+  r1 = lr_row_sum(lr_swap_add16(p2, p3));
+  r2 = lr_row_sum(lr_swap_add16(p4, p5));
+  r3 = lr_row_sum(lr_swap_add16(p6, p7));
+}
+
+// AUX: the reverse walk of a forward that composited aux_colors into a second image (lr_blend_fwd_kernel<., true>).  The
+// colour behind the current entry is kept for both triples and dL/dalpha is evaluated once per image, each with the op
+// sequence of a walk over that image alone.  dL/dmean and dL/dopacity are committed as the sums over both images; dL/dconic
+// is committed PER IMAGE (slots 2-4: `image`, slots 12-14: the aux image): the chain rule behind it is ill-conditioned in
+// fp32 for needle-shaped Gaussians, and evaluated once on the sum it lands as far from two evaluations added -- what two
+// rasterizer calls compute -- as either lies from the exact value (measured: profiles/aux_channels.md).  Fifteen sums leave
+// in four atomic instructions on the Gaussian's one 64-byte row; the third carries conic C (slot 4) and dL/daux_colors
+// (slots 9..11), the fourth the aux image's conic.  dL_dimage / dL_daux: NULL = zeros.
+template <bool MASKS, bool AUX = false>
 __global__ void __launch_bounds__(256)
 lr_blend_bwd_kernel(LrView v, const float4* __restrict__ geom, const uint32_t* __restrict__ state,
                     uint32_t tiles, const uint32_t* __restrict__ plist, uint32_t capacity,
                     const float* __restrict__ final_T, const int* __restrict__ n_contrib,
                     const float* __restrict__ dL_dimage, float* __restrict__ acc_rows,
-                    int xcd_mode, const uint64_t* __restrict__ masks) {
+                    int xcd_mode, const uint64_t* __restrict__ masks,
+                    const float* __restrict__ aux_colors = nullptr, const float* __restrict__ dL_daux = nullptr) {
   if (lr_bail(state, capacity)) return;
   const uint32_t tile = lr_tile_of_block(blockIdx.x, tiles, v.gx, v.gy, xcd_mode, state);
   if (tile >= tiles) return;
@@ -442,11 +499,18 @@ lr_blend_bwd_kernel(LrView v, const float4* __restrict__ geom, const uint32_t* _
   const float sx = 0.5f * (float)v.W, sy = 0.5f * (float)v.H;
   const float Tf = in ? final_T[pix] : 0.f;
   const int lastc = in ? n_contrib[pix] : 0;
-  const float dp0 = in ? dL_dimage[pix] : 0.f;
-  const float dp1 = in ? dL_dimage[plane + pix] : 0.f;
-  const float dp2 = in ? dL_dimage[2 * plane + pix] : 0.f;
+  const bool in_c = AUX ? (in && dL_dimage != nullptr) : in;   // (AUX: either image gradient may be absent = zeros)
+  const float dp0 = in_c ? dL_dimage[pix] : 0.f;
+  const float dp1 = in_c ? dL_dimage[plane + pix] : 0.f;
+  const float dp2 = in_c ? dL_dimage[2 * plane + pix] : 0.f;
+  const bool in_a = AUX && in && dL_daux != nullptr;
+  const float da0 = in_a ? dL_daux[pix] : 0.f;
+  const float da1 = in_a ? dL_daux[plane + pix] : 0.f;
+  const float da2 = in_a ? dL_daux[2 * plane + pix] : 0.f;
   const float bgdot = lr_fma(v.bg[0], dp0, lr_fma(v.bg[1], dp1, v.bg[2] * dp2));
+  const float bgdot_a = lr_fma(v.bg[0], da0, lr_fma(v.bg[1], da1, v.bg[2] * da2));   // (AUX: the same term of the aux image)
   float T = Tf, acc0 = 0.f, acc1 = 0.f, acc2 = 0.f;  // acc = colour composited behind the current entry
+  float acd0 = 0.f, acd1 = 0.f, acd2 = 0.f;          // (AUX: the aux colour behind it)
   int maxc = lastc;
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) maxc = max(maxc, __shfl_xor(maxc, off));
@@ -461,6 +525,10 @@ lr_blend_bwd_kernel(LrView v, const float4* __restrict__ geom, const uint32_t* _
   const int row = lane >> 4;
   float* const base0 = acc_rows + ((row < 3) ? 6 + row : 5);
   float* const base1 = acc_rows + ((lane == 1) ? 4 : row);
+  //   AUX, atomic #3, rows 0..3: conic C (slot 4) and the aux colour r, g, b (slots 9..11); lane 1 then carries nothing in #2
+  //   AUX, atomic #4, rows 0..2: the aux image's conic A, B, C (slots 12..14)
+  float* const base2 = acc_rows + ((row == 0) ? 4 : 8 + row);
+  float* const base3 = acc_rows + 12 + row;
   const bool lead = (lane & 15) == 0;
 
   // Reverse walk in 64-entry chunks from the deepest contributor; lane l of chunk ch holds list position
@@ -520,7 +588,18 @@ lr_blend_bwd_kernel(LrView v, const float4* __restrict__ geom, const uint32_t* _
       const float cbl0 = reinterpret_cast<const float*>(rr0)[8], cbl1 = reinterpret_cast<const float*>(rr1)[8];
       // keep the colour loads in this first batch of scalar loads: left alone the compiler sinks them below the hit
       // test, i.e. a second, fully exposed scalar-cache round trip in every contributing iteration
-      asm volatile("" : : "s"(q01.z), "s"(q01.w), "s"(cbl0), "s"(q11.z), "s"(q11.w), "s"(cbl1));
+      // (AUX: the aux triples are issued in front of that fence and named by it too -- their addresses need gid0 / gid1 only,
+      // and nothing has brought their lines in before, as the next chunk's vector prefetch has the records')
+      float ax0 = 0.f, ay0 = 0.f, az0 = 0.f, ax1 = 0.f, ay1 = 0.f, az1 = 0.f;
+      if (AUX) {
+        const float* __restrict__ a0 = aux_colors + 3 * (size_t)(uint32_t)gid0;
+        const float* __restrict__ a1 = aux_colors + 3 * (size_t)(uint32_t)gid1;
+        ax0 = a0[0]; ay0 = a0[1]; az0 = a0[2]; ax1 = a1[0]; ay1 = a1[1]; az1 = a1[2];
+        asm volatile("" : : "s"(q01.z), "s"(q01.w), "s"(cbl0), "s"(q11.z), "s"(q11.w), "s"(cbl1),
+                     "s"(ax0), "s"(ay0), "s"(az0), "s"(ax1), "s"(ay1), "s"(az1));
+      } else {
+        asm volatile("" : : "s"(q01.z), "s"(q01.w), "s"(cbl0), "s"(q11.z), "s"(q11.w), "s"(cbl1));
+      }
       const float op0 = q01.y, op1 = q11.y;
       const lr_f2 dx2 = lr_f2{q00.x, q10.x} - pxf, dy2 = lr_f2{q00.y, q10.y} - pyf;
       const lr_f2 hdx2 = dx2 * -0.5f, hdy2 = dy2 * -0.5f;
@@ -555,6 +634,18 @@ lr_blend_bwd_kernel(LrView v, const float4* __restrict__ geom, const uint32_t* _
                   a0b = lr_fma(alpha.x, cbl.x, om.x * acc2);   // colour behind entry 1
       lr_f2 dL_dalpha = lr_fma2(cr - lr_f2{acc0, a0r}, lr_f2{dp0, dp0},
                                 lr_fma2(cg - lr_f2{acc1, a0g}, lr_f2{dp1, dp1}, (cbl - lr_f2{acc2, a0b}) * dp2));
+      lr_f2 dL_dalpha_a = {0.f, 0.f};
+      if (AUX) {                                                // the same sum over the aux image's three channels
+        const lr_f2 ax = {ax0, ax1}, ay = {ay0, ay1}, az = {az0, az1};
+        const float d0x = lr_fma(alpha.x, ax.x, om.x * acd0), d0y = lr_fma(alpha.x, ay.x, om.x * acd1),
+                    d0z = lr_fma(alpha.x, az.x, om.x * acd2);  // aux colour behind entry 1
+        dL_dalpha_a = lr_fma2(ax - lr_f2{acd0, d0x}, lr_f2{da0, da0},
+                              lr_fma2(ay - lr_f2{acd1, d0y}, lr_f2{da1, da1}, (az - lr_f2{acd2, d0z}) * da2));
+        dL_dalpha_a = lr_fma2(dL_dalpha_a, T2, -(Tf * rc) * bgdot_a);
+        acd0 = lr_fma(alpha.y, ax.y, om.y * d0x);
+        acd1 = lr_fma(alpha.y, ay.y, om.y * d0y);
+        acd2 = lr_fma(alpha.y, az.y, om.y * d0z);
+      }
       dL_dalpha = lr_fma2(dL_dalpha, T2, -(Tf * rc) * bgdot);
       acc0 = lr_fma(alpha.y, cr.y, om.y * a0r);
       acc1 = lr_fma(alpha.y, cg.y, om.y * a0g);
@@ -566,22 +657,41 @@ lr_blend_bwd_kernel(LrView v, const float4* __restrict__ geom, const uint32_t* _
       const lr_f2 dG_ddy = lr_fma2(-Cr, gdy, -(Br * gdx));     // -gdy*C - gdx*B
       // slot order chosen so that lr_reduce9's rows land on contiguous destinations:
       //   r0 rows = (s0,s2,s1,s3) = (col r, col g, col b, opacity); r1 rows = (s4,s6,s5,s7) = (mean x, mean y, conic A, conic B); r2 = conic C
-      lr_f2 s2[9];
+      constexpr int NS = AUX ? 16 : 9;
+      lr_f2 s2[NS];
       s2[0] = w * dp0; s2[2] = w * dp1; s2[1] = w * dp2; s2[3] = G * dL_dalpha;
       s2[4] = dL_dG * dG_ddx * sx; s2[6] = dL_dG * dG_ddy * sy;
       s2[5] = -0.5f * gdx * dx2 * dL_dG; s2[7] = -gdx * dy2 * dL_dG;
       s2[8] = -0.5f * gdy * dy2 * dL_dG;
+      if (AUX) {
+        // r2 rows = (s8,s10,s9,s11) = (conic C, aux r, aux g, aux b); r3 rows = (s12,s14,s13,s15) = (aux conic A, B, C, -)
+        const lr_f2 dL_dG_a = lr_f2{op0, op1} * dL_dalpha_a;
+        s2[10] = w * da0; s2[9] = w * da1; s2[11] = w * da2;
+        s2[3] = s2[3] + G * dL_dalpha_a;
+        s2[4] = s2[4] + dL_dG_a * dG_ddx * sx; s2[6] = s2[6] + dL_dG_a * dG_ddy * sy;
+        s2[12] = -0.5f * gdx * dx2 * dL_dG_a; s2[14] = -gdx * dy2 * dL_dG_a;
+        s2[13] = -0.5f * gdy * dy2 * dL_dG_a; s2[15] = lr_f2{0.f, 0.f};
+      }
 #pragma unroll
       for (int e = 0; e < 2; e++) {
         if (!(e ? any1 : any0)) continue;                       // wave-uniform: nothing to commit for this entry
         const int gid = e ? gid1 : gid0;
-        float sv[9];
+        float sv[NS];
 #pragma unroll
-        for (int m = 0; m < 9; m++) sv[m] = e ? s2[m].y : s2[m].x;
+        for (int m = 0; m < NS; m++) sv[m] = e ? s2[m].y : s2[m].x;
         float r0, r1, r2;
-        lr_reduce9(sv, r0, r1, r2);
-        if (lead) atomicAdd(base0 + (size_t)gid * LOGRAST_BWD_ROW_FLOATS, r0);
-        if (lead || lane == 1) atomicAdd(base1 + (size_t)gid * LOGRAST_BWD_ROW_FLOATS, lane == 1 ? r2 : r1);
+        if (AUX) {
+          float r3;
+          lr_reduce16(sv, r0, r1, r2, r3);
+          if (lead) atomicAdd(base0 + (size_t)gid * LOGRAST_BWD_ROW_FLOATS, r0);
+          if (lead) atomicAdd(base1 + (size_t)gid * LOGRAST_BWD_ROW_FLOATS, r1);
+          if (lead) atomicAdd(base2 + (size_t)gid * LOGRAST_BWD_ROW_FLOATS, r2);
+          if (lead && row < 3) atomicAdd(base3 + (size_t)gid * LOGRAST_BWD_ROW_FLOATS, r3);
+        } else {
+          lr_reduce9(sv, r0, r1, r2);
+          if (lead) atomicAdd(base0 + (size_t)gid * LOGRAST_BWD_ROW_FLOATS, r0);
+          if (lead || lane == 1) atomicAdd(base1 + (size_t)gid * LOGRAST_BWD_ROW_FLOATS, lane == 1 ? r2 : r1);
+        }
       }
     }
   }
@@ -1155,14 +1265,14 @@ int lr_blend_bwd_form(const LrView& v, int big_input) {
 void lr_launch_blend_fwd(const LrView& v, const void* geom, const uint32_t* state, uint32_t tiles,
                          const uint32_t* plist, uint32_t capacity, float* image, float* final_T, int* n_contrib,
                          int* pid, float* pwp, float* pw, float* zero_conic, int big_input, int lazy, uint64_t* masks,
-                         hipStream_t s) {
+                         hipStream_t s, const float* aux_colors, float* aux_image) {
   uint32_t* const hdr_w = const_cast<uint32_t*>(state);     // (header word LR_HDR_MASKS: which form left hit masks)
   uint32_t* const lazy_state = lazy ? const_cast<uint32_t*>(state) : nullptr;   // (the tile state once more, writable: open[] and header word LR_HDR_OPEN are all a compositing kernel writes there)
   int xcd_mode = lr_knob(LRKNOB_XCD_MODE);
   // LOGRAST_FWD_ROWS: 1 = row-split form (lr_blend_fwd_rows_kernel), 0 = one quadrant per wave, 2 (default) = the caller's
   // hint (lograst_view.walk_form), quadrant without one.  Measured, MI355X: 30 M tiny splats 706 -> 658 us (random
   // opacities 1267 -> 1188); C2's 1 M 174 -> 193; a tree-ordered heavy-tailed view 278 -> 347.
-  const int rows = lr_blend_fwd_form(v) == (int)LR_MASK_FORM_ROWS;
+  const int rows = !aux_image && lr_blend_fwd_form(v) == (int)LR_MASK_FORM_ROWS;   // (aux channels: quadrant kernels only)
   const int fwd_block_test = lr_knob(LRKNOB_FWD_BLOCK_TEST);
   const int exact_masks = lr_knob(LRKNOB_HIT_MASKS) != 2;   // row-split form: hit masks = contributions (2: support ballots)
   // Both forward kernels still take `cull` (always 1: the support tests run) as a run-time argument.  With the tests
@@ -1176,7 +1286,14 @@ void lr_launch_blend_fwd(const LrView& v, const void* geom, const uint32_t* stat
   const float4* g4 = reinterpret_cast<const float4*>(geom);
   float4* z4 = reinterpret_cast<float4*>(zero_conic);
   if (lazy != 2) lr_prof_begin(LRK_BLEND_FWD, s);           // (the second pass is timed by its caller, with the sort of the tails)
-  if (rows) {
+  if (aux_image) {
+    if (v.extras)
+      hipLaunchKernelGGL((lr_blend_fwd_kernel<true, true>), dim3(grid), dim3(256), 0, s, v, g4, state, tiles, plist, capacity,
+                         image, final_T, n_contrib, pid, pwp, pw, z4, xcd_mode, 1, lazy_state, lazy, masks, hdr_w, aux_colors, aux_image);
+    else
+      hipLaunchKernelGGL((lr_blend_fwd_kernel<false, true>), dim3(grid), dim3(256), 0, s, v, g4, state, tiles, plist, capacity,
+                         image, final_T, n_contrib, pid, pwp, pw, z4, xcd_mode, 1, lazy_state, lazy, masks, hdr_w, aux_colors, aux_image);
+  } else if (rows) {
     if (v.extras)
       hipLaunchKernelGGL(lr_blend_fwd_rows_kernel<true>, dim3(grid), dim3(256), 0, s, v, g4, state, tiles, plist, capacity,
                          image, final_T, n_contrib, pid, pwp, pw, z4, xcd_mode, 1, lazy_state, lazy, masks, hdr_w, fwd_block_test, exact_masks);
@@ -1186,30 +1303,37 @@ void lr_launch_blend_fwd(const LrView& v, const void* geom, const uint32_t* stat
   } else {
     if (v.extras)
       hipLaunchKernelGGL(lr_blend_fwd_kernel<true>, dim3(grid), dim3(256), 0, s, v, g4, state, tiles, plist, capacity,
-                         image, final_T, n_contrib, pid, pwp, pw, z4, xcd_mode, 1, lazy_state, lazy, masks, hdr_w);
+                         image, final_T, n_contrib, pid, pwp, pw, z4, xcd_mode, 1, lazy_state, lazy, masks, hdr_w, nullptr, nullptr);
     else
       hipLaunchKernelGGL(lr_blend_fwd_kernel<false>, dim3(grid), dim3(256), 0, s, v, g4, state, tiles, plist, capacity,
-                         image, final_T, n_contrib, pid, pwp, pw, z4, xcd_mode, 1, lazy_state, lazy, masks, hdr_w);
+                         image, final_T, n_contrib, pid, pwp, pw, z4, xcd_mode, 1, lazy_state, lazy, masks, hdr_w, nullptr, nullptr);
   }
   if (lazy != 2) lr_prof_end(LRK_BLEND_FWD, s);
 }
 
 void lr_launch_blend_bwd(const LrView& v, const void* geom, const uint32_t* state, uint32_t tiles,
                          const uint32_t* plist, uint32_t capacity, const float* final_T, const int* n_contrib,
-                         const float* dL_dimage, float* acc_rows, int big_input, const uint64_t* masks, hipStream_t s) {
+                         const float* dL_dimage, float* acc_rows, int big_input, const uint64_t* masks, hipStream_t s,
+                         const float* aux_colors, const float* dL_daux) {
   const int xcd_mode = lr_knob(LRKNOB_XCD_MODE);
   uint32_t grid = lr_blend_grid(tiles, v.gx, v.gy, xcd_mode);
   // LOGRAST_BWD_ROWS=1: the row-split form (the four 16-lane rows of a wave walk their own 4x4 blocks); 0: one
   // (Gaussian, quadrant) pair per visit; 2 (default): the caller's hint (lograst_view.walk_form: row-split for views of
   // tiny splats, few tile instances per Gaussian), else row-split on large inputs.  Measured, MI355X: 30 M tiny splats
   // 949 -> 700 us, with random opacities 1768 -> 1259; C2's 1 M 292 -> 307; a tree-ordered heavy-tailed view 448 -> 579.
-  const int rows = lr_blend_bwd_form(v, big_input) == (int)LR_MASK_FORM_ROWS;
+  const int rows = !aux_colors && lr_blend_bwd_form(v, big_input) == (int)LR_MASK_FORM_ROWS;   // (aux channels: quadrant kernels only)
   const int block_test = lr_knob(LRKNOB_BWD_BLOCK_TEST);
   lr_prof_begin(LRK_BLEND_BWD, s);
   // the forward's hit masks serve a reverse walk of the SAME form only (v.mask_form: what the caller says its forward launched)
   const bool use_masks = masks != nullptr && v.mask_form == (rows ? (int)LR_MASK_FORM_ROWS : (int)LR_MASK_FORM_QUAD);
   const float4* g4 = reinterpret_cast<const float4*>(geom);
-  if (rows && use_masks)
+  if (aux_colors && use_masks)
+    hipLaunchKernelGGL((lr_blend_bwd_kernel<true, true>), dim3(grid), dim3(256), 0, s, v, g4, state, tiles, plist, capacity,
+                       final_T, n_contrib, dL_dimage, acc_rows, xcd_mode, masks, aux_colors, dL_daux);
+  else if (aux_colors)
+    hipLaunchKernelGGL((lr_blend_bwd_kernel<false, true>), dim3(grid), dim3(256), 0, s, v, g4, state, tiles, plist, capacity,
+                       final_T, n_contrib, dL_dimage, acc_rows, xcd_mode, masks, aux_colors, dL_daux);
+  else if (rows && use_masks)
     hipLaunchKernelGGL(lr_blend_bwd_rows_kernel<true>, dim3(grid), dim3(256), 0, s, v, g4, state, tiles, plist, capacity,
                        final_T, n_contrib, dL_dimage, acc_rows, xcd_mode, block_test, masks);
   else if (rows)
@@ -1217,9 +1341,9 @@ void lr_launch_blend_bwd(const LrView& v, const void* geom, const uint32_t* stat
                        final_T, n_contrib, dL_dimage, acc_rows, xcd_mode, block_test, masks);
   else if (use_masks)
     hipLaunchKernelGGL(lr_blend_bwd_kernel<true>, dim3(grid), dim3(256), 0, s, v, g4, state, tiles, plist, capacity,
-                       final_T, n_contrib, dL_dimage, acc_rows, xcd_mode, masks);
+                       final_T, n_contrib, dL_dimage, acc_rows, xcd_mode, masks, nullptr, nullptr);
   else
     hipLaunchKernelGGL(lr_blend_bwd_kernel<false>, dim3(grid), dim3(256), 0, s, v, g4, state, tiles, plist, capacity,
-                       final_T, n_contrib, dL_dimage, acc_rows, xcd_mode, masks);
+                       final_T, n_contrib, dL_dimage, acc_rows, xcd_mode, masks, nullptr, nullptr);
   lr_prof_end(LRK_BLEND_BWD, s);
 }

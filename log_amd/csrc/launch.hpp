@@ -39,12 +39,13 @@ void lr_launch_ordered_lengths(const uint32_t* state, uint32_t tiles, uint32_t* 
 void lr_launch_blend_fwd(const LrView& v, const void* geom, const uint32_t* state, uint32_t tiles,
                          const uint32_t* plist, uint32_t capacity, float* image, float* final_T, int* n_contrib,
                          int* pid, float* pwp, float* pw, float* zero_conic, int big_input, int lazy, uint64_t* masks,
-                         hipStream_t s);
+                         hipStream_t s, const float* aux_colors = nullptr, float* aux_image = nullptr);   // aux: quadrant form, whatever the view says
 int lr_blend_fwd_form(const LrView& v);
 int lr_blend_bwd_form(const LrView& v, int big_input);
 void lr_launch_blend_bwd(const LrView& v, const void* geom, const uint32_t* state, uint32_t tiles,
                          const uint32_t* plist, uint32_t capacity, const float* final_T, const int* n_contrib,
-                         const float* dL_dimage, float* acc_rows, int big_input, const uint64_t* masks, hipStream_t s);
+                         const float* dL_dimage, float* acc_rows, int big_input, const uint64_t* masks, hipStream_t s,
+                         const float* aux_colors = nullptr, const float* dL_daux = nullptr);   // aux: quadrant form; either gradient may be NULL
 
 // project_bwd.hip
 // rows != NULL: the 64-byte accumulator rows of lograst_backward (+ its three separate outputs); NULL: g_mean2d / g_conic.
@@ -53,7 +54,7 @@ void lr_launch_project_bwd(const LrView& v, int N, const float* means, const flo
                            const int* radii, const float* g_mean2d, const float* g_conic, const float* rows,
                            float* o_mean2d, float* o_opac, float* o_col, const float* pw,
                            float* g_means3d, float* g_scales, float* g_rots, bool accumulate, bool sink_rows,
-                           bool big_input, hipStream_t s);
+                           bool big_input, hipStream_t s, float* o_aux = nullptr);   // o_aux: dL/daux_colors [N, 3] out of the rows' slots 9..11 (fresh gradients, no cov3d)
 
 // exchange.hip
 void lx_launch_pack_rows(float* rows, int groups, long long rows_per_group, int kmax, float* packed,

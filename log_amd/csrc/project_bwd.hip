@@ -124,16 +124,17 @@ LR_DEV void lr_project_bwd_row(const LrView& v, int i, const float* __restrict__
 
 // The chain rule of ONE live Gaussian i: reads its accumulator row (AOS) or its (dL/dmean2D, dL/dconic) pair, hands out
 // the per-view outputs and writes / adds the gradients (see lr_project_bwd_kernel for the template flags).
-template <bool ACCUMULATE, bool COV, bool AOS, bool SINKROWS>
+template <bool ACCUMULATE, bool COV, bool AOS, bool SINKROWS, bool AUXO = false>
 // (No __restrict__ here: the kernels' own parameters carry it.  Repeated on this inlined function it gave the scheduler
 // licence to hoist every load of the row above the chain rule -- 136 -> 170 VGPRs, three waves per SIMD -> two, the
 // 30 M-row launch 402 -> 477 us.)
 LR_DEV void lr_pbwd_live_row(const LrView& v, int i, const float* means, const float* scales, const float* rots,
                              const float* g_mean2d, const float* g_conic, const float4* rows, float* o_mean2d,
                              float* o_opac, float* o_col, float* g_means3d, float* g_scales, float* g_rots,
-                             float* m2d_slice = nullptr, int slice_base = 0, bool staged = false) {
+                             float* m2d_slice = nullptr, int slice_base = 0, bool staged = false, float* o_aux = nullptr) {
     float gm[3], gs[3] = {0.f, 0.f, 0.f}, gq[4] = {0.f, 0.f, 0.f, 0.f};
     float gnx, gny, gA, gB, gC;
+    float gA2 = 0.f, gB2 = 0.f, gC2 = 0.f;   // (AUXO)
     // running sums (ACCUMULATE): every old value is requested up front, next to the row's inputs -- the row is a chain of
     // ~20 scattered accesses, and the read-modify-writes behind the chain rule's ~600 instructions were fully exposed
     float old_m[3] = {0.f, 0.f, 0.f}, old_s[3] = {0.f, 0.f, 0.f}, old_c[3] = {0.f, 0.f, 0.f}, old_o = 0.f;
@@ -159,6 +160,12 @@ LR_DEV void lr_pbwd_live_row(const LrView& v, int i, const float* means, const f
     if (AOS) {
       const float4 a0 = rows[4 * (size_t)i], a1 = rows[4 * (size_t)i + 1];
       const float cb = reinterpret_cast<const float*>(rows + 4 * (size_t)i + 2)[0];
+      if (AUXO) {   // slots 9..11: dL/daux_colors of a reverse walk with aux channels (fresh gradients only)
+        const float* const ar = reinterpret_cast<const float*>(rows + 4 * (size_t)i + 2);
+        o_aux[3 * (size_t)i + 0] = ar[1]; o_aux[3 * (size_t)i + 1] = ar[2]; o_aux[3 * (size_t)i + 2] = ar[3];
+        const float4 a3 = rows[4 * (size_t)i + 3];   // slots 12..14: the aux image's dL/dconic (below)
+        gA2 = a3.x; gB2 = a3.y; gC2 = a3.z;
+      }
       gnx = a0.x; gny = a0.y; gA = a0.z; gB = a0.w; gC = a1.x;
       if (staged) {   // the workgroup's slice of dL/dmeans2D sits in LDS and leaves as whole lines (lr_project_bwd_kernel)
         float* const o = m2d_slice + 3 * (i - slice_base);
@@ -178,6 +185,18 @@ LR_DEV void lr_pbwd_live_row(const LrView& v, int i, const float* means, const f
       gA = gc4.x; gB = gc4.y; gC = gc4.z;
     }
     lr_project_bwd_row<ACCUMULATE, COV>(v, i, means, scales, rots, gnx, gny, gA, gB, gC, gm, gs, gq);
+    if (AUXO) {
+      // The aux image's dL/dconic goes through the chain rule on its own and the results are added -- the arithmetic of two
+      // rasterizer calls.  (The conic part is ill-conditioned in fp32 for needle-shaped Gaussians: one evaluation on the
+      // summed dL/dconic differs from two evaluations added by as much as either differs from the exact value.  The centre
+      // part, dL/dmean, is not: it arrives as one sum.)
+      float gm2[3], gs2[3] = {0.f, 0.f, 0.f}, gq2[4] = {0.f, 0.f, 0.f, 0.f};
+      lr_project_bwd_row<ACCUMULATE, COV>(v, i, means, scales, rots, 0.f, 0.f, gA2, gB2, gC2, gm2, gs2, gq2);
+#pragma unroll
+      for (int k = 0; k < 3; k++) { gm[k] += gm2[k]; gs[k] += gs2[k]; }
+#pragma unroll
+      for (int k = 0; k < 4; k++) gq[k] += gq2[k];
+    }
     if (SINKROWS) {    // running sums over views, one row per Gaussian
       sr0.x += gm[0]; sr0.y += gm[1]; sr0.z += gm[2]; sr0.w += gs[0];
       sr1.x += gs[1]; sr1.y += gs[2]; sr1.z += gq[0]; sr1.w += gq[1];
@@ -217,13 +236,16 @@ LR_DEV void lr_pbwd_live_row(const LrView& v, int i, const float* means, const f
 // dL/drotations, 10 dL/dopacity, 11-13 dL/dcolour, 14-15 untouched) -- a live Gaussian then costs one read-modify-write of
 // one line instead of five in five arrays (the live rows are scattered: at 30 M Gaussians 7 % of them, each piece of 4-16
 // bytes pulling its own 64-byte line through the memory system in both directions).
+// AUXO (lograst_backward_aux; AOS, fresh gradients, not COV): the rows' slots 9..11 leave as dL/daux_colors [N, 3] -- a
+// live row's values, zeros for the others, exactly as dL/dcolour -- and slots 12..14 hold the aux image's dL/dconic, which
+// takes its own pass through the chain rule inside the same launch (lr_pbwd_live_row).
 // WAVES: waves per SIMD the register allocator aims for (1 = its own choice: ~130 VGPRs, three waves).  Measured, 30 M
 // Gaussians, running sums / fresh gradients: default 374 / 736 us, 4 waves (128 VGPRs, no scratch) 391 / 865, 5 (spills)
 // 473 / 877, 6: 518 / 918 -- more resident workgroups make the scattered rows' traffic worse, not better.  A band view
 // (nearly all flag pass: a fraction of a percent of 100 M rows is live) gains from four: 738 -> 638 us -- the row-major
 // sink's kernel exists in both forms and band views launch the second (unless they take the compact-list form below, the
 // default; the current compiler spills 10 VGPRs in it, 22 before the staged slice: profiles/chain_rule_dmeans2d_lines.md).
-template <bool ACCUMULATE, bool TOUCHED, bool COV, bool AOS, bool SINKROWS = false, int WAVES = 1>
+template <bool ACCUMULATE, bool TOUCHED, bool COV, bool AOS, bool SINKROWS = false, int WAVES = 1, bool AUXO = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES)))
 lr_project_bwd_kernel(LrView v, int N, const float* __restrict__ means, const float* __restrict__ scales,
                       const float* __restrict__ rots, const int* __restrict__ radii,
@@ -231,7 +253,8 @@ lr_project_bwd_kernel(LrView v, int N, const float* __restrict__ means, const fl
                       const float4* __restrict__ rows, float* __restrict__ o_mean2d, float* __restrict__ o_opac,
                       float* __restrict__ o_col,
                       const float* __restrict__ pw, float* __restrict__ g_means3d, float* __restrict__ g_scales,
-                      float* __restrict__ g_rots, int clear_inside) {
+                      float* __restrict__ g_rots, int clear_inside, float* __restrict__ o_aux = nullptr) {
+  static_assert(!AUXO || (AOS && !ACCUMULATE && !COV && !SINKROWS), "dL/daux_colors: fresh gradients from the accumulator rows only");
   __shared__ uint32_t live_list[LR_PBWD_ROWS];
   __shared__ uint32_t live_count;
   // STAGE (the instantiations the large-input running-sum route launches; taken when clear_inside == 0): the workgroup's
@@ -291,6 +314,7 @@ lr_project_bwd_kernel(LrView v, int N, const float* __restrict__ means, const fl
         // whole slice of each array with full-width stores here, instead of 12-byte pieces per dead row from the flag
         // pass below (three store instructions covering a third of every line each)
         clear(o_opac + (size_t)base, rows_here); clear(o_col + 3 * (size_t)base, 3 * rows_here);
+        if (AUXO) clear(o_aux + 3 * (size_t)base, 3 * rows_here);
         clear(g_means3d + 3 * (size_t)base, 3 * rows_here);
         if (COV) {
           clear(v.g_cov3d + 6 * (size_t)base, 6 * rows_here);
@@ -327,9 +351,9 @@ lr_project_bwd_kernel(LrView v, int N, const float* __restrict__ means, const fl
   __syncthreads();
   const uint32_t n = live_count;
   for (uint32_t j = (uint32_t)tid; j < n; j += 256u)
-    lr_pbwd_live_row<ACCUMULATE, COV, AOS, SINKROWS>(v, (int)live_list[j], means, scales, rots, g_mean2d, g_conic, rows,
-                                                     o_mean2d, o_opac, o_col, g_means3d, g_scales, g_rots,
-                                                     STAGE ? m2d_slice : nullptr, base, staged);
+    lr_pbwd_live_row<ACCUMULATE, COV, AOS, SINKROWS, AUXO>(v, (int)live_list[j], means, scales, rots, g_mean2d, g_conic, rows,
+                                                           o_mean2d, o_opac, o_col, g_means3d, g_scales, g_rots,
+                                                           STAGE ? m2d_slice : nullptr, base, staged, o_aux);
   if (staged) {
     // the slice leaves: every row of the block is defined here (zero unless live), 16 bytes per lane and 1 KB per wave and
     // store instruction -- whole lines (three instructions for a full block); non-temporal like the zero pass it replaces
@@ -437,11 +461,21 @@ void lr_launch_project_bwd(const LrView& v, int N, const float* means, const flo
                            const int* radii, const float* g_mean2d, const float* g_conic, const float* rows,
                            float* o_mean2d, float* o_opac, float* o_col, const float* pw,
                            float* g_means3d, float* g_scales, float* g_rots, bool accumulate, bool sink_rows,
-                           bool big_input, hipStream_t s) {
+                           bool big_input, hipStream_t s, float* o_aux) {
   if (N <= 0) return;
   lr_prof_begin(LRK_PROJECT_BWD, s);
   const dim3 grid((N + LR_PBWD_ROWS - 1) / LR_PBWD_ROWS), block(256);
   const float4* rows4 = reinterpret_cast<const float4*>(rows);
+  if (o_aux) {   // (lograst_backward_aux checked: rows, fresh gradients, no cov3d_precomp; every output cleared inside)
+    if (pw)
+      hipLaunchKernelGGL((lr_project_bwd_kernel<false, true, false, true, false, 1, true>), grid, block, 0, s, v, N, means, scales,
+                         rots, radii, g_mean2d, g_conic, rows4, o_mean2d, o_opac, o_col, pw, g_means3d, g_scales, g_rots, 1, o_aux);
+    else
+      hipLaunchKernelGGL((lr_project_bwd_kernel<false, false, false, true, false, 1, true>), grid, block, 0, s, v, N, means, scales,
+                         rots, radii, g_mean2d, g_conic, rows4, o_mean2d, o_opac, o_col, pw, g_means3d, g_scales, g_rots, 1, o_aux);
+    lr_prof_end(LRK_PROJECT_BWD, s);
+    return;
+  }
   // dL/dmeans2D is a per-view output, defined for every row.  When the other gradients are running sums (nothing else is
   // written for a dead row) and the input is large (clear_inside == 0), the kernel's workgroups neither clear their slice
   // between their flag reads and their barrier nor overwrite live rows with 12-byte stores: the slice is staged in LDS and
@@ -478,19 +512,19 @@ void lr_launch_project_bwd(const LrView& v, int N, const float* means, const flo
     const bool band = v.ty0 > 0 || v.ty1 < v.gy;
     if (pw && band)
       hipLaunchKernelGGL((lr_project_bwd_kernel<true, true, false, true, true, 4>), grid, block, 0, s, v, N, means, scales, rots,
-                         radii, g_mean2d, g_conic, rows4, o_mean2d, o_opac, o_col, pw, g_means3d, g_scales, g_rots, clear_inside);
+                         radii, g_mean2d, g_conic, rows4, o_mean2d, o_opac, o_col, pw, g_means3d, g_scales, g_rots, clear_inside, nullptr);
     else if (pw)
       hipLaunchKernelGGL((lr_project_bwd_kernel<true, true, false, true, true>), grid, block, 0, s, v, N, means, scales, rots,
-                         radii, g_mean2d, g_conic, rows4, o_mean2d, o_opac, o_col, pw, g_means3d, g_scales, g_rots, clear_inside);
+                         radii, g_mean2d, g_conic, rows4, o_mean2d, o_opac, o_col, pw, g_means3d, g_scales, g_rots, clear_inside, nullptr);
     else
       hipLaunchKernelGGL((lr_project_bwd_kernel<true, false, false, true, true>), grid, block, 0, s, v, N, means, scales, rots,
-                         radii, g_mean2d, g_conic, rows4, o_mean2d, o_opac, o_col, pw, g_means3d, g_scales, g_rots, clear_inside);
+                         radii, g_mean2d, g_conic, rows4, o_mean2d, o_opac, o_col, pw, g_means3d, g_scales, g_rots, clear_inside, nullptr);
     lr_prof_end(LRK_PROJECT_BWD, s);
     return;
   }
 #define LR_PBWD2(A, T, C, O) hipLaunchKernelGGL((lr_project_bwd_kernel<A, T, C, O>), grid, block, 0, s, v, N, means, scales, \
                                                 rots, radii, g_mean2d, g_conic, rows4, o_mean2d, o_opac, o_col, pw,       \
-                                                g_means3d, g_scales, g_rots, clear_inside)
+                                                g_means3d, g_scales, g_rots, clear_inside, nullptr)
 #define LR_PBWD(A, T, C) do { if (rows) LR_PBWD2(A, T, C, true); else LR_PBWD2(A, T, C, false); } while (0)
 #define LR_PBWD_C(A, T) do { if (v.cov3d) LR_PBWD(A, T, true); else LR_PBWD(A, T, false); } while (0)
   if (accumulate) { if (pw) LR_PBWD_C(true, true); else LR_PBWD_C(true, false); }

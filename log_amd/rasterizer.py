@@ -573,19 +573,22 @@ class HipBackend:
         arena = torch.empty(max(total, 1), dtype=torch.uint8, device=device)
         return {name: arena[off:off + n].view(dt).view(shape) for (name, dt, shape), (off, n) in zip(parts, spans)}
 
-    def _begin(self, L, view, flavour, device, N, own, scratch_floats):
+    def _begin(self, L, view, flavour, device, N, own, scratch_floats, aux=False):
         """What forward() and recomposite() share once view.walk_form is set: -> (o, kept, scratch_floats, masks_for,
         mask_form): the outputs, the _carve parts that outlive the call (`own`: the caller's, in front), the normalised
-        scratch_floats, the hit-mask buffer for a capacity, and the form those masks are written in (0: no masks)."""
+        scratch_floats, the hit-mask buffer for a capacity, and the form those masks are written in (0: no masks).
+        aux: a forward with aux channels -- one more output image, and the quadrant kernels whatever the view asks for."""
         H, W = view.height, view.width
         i32, f32 = torch.int32, torch.float32
-        fwd_form = int(L.lograst_forward_form(ctypes.byref(view)))   # 1 = row-split, 2 = quadrant
+        fwd_form = _lib.FORM_QUADRANT if aux else int(L.lograst_forward_form(ctypes.byref(view)))   # 1 = row-split, 2 = quadrant
         self._note_form("fwd", fwd_form == 1)
         # what the caller gets (image, radii, the fork's maps) / what backward needs / what dies with this call
         # (every output is an allocation of its own, like the third-party packages': views of one arena would share a
         # version counter -- an in-place op on `radii` would invalidate `image` for autograd -- and any one of them kept
         # alive would pin all the others' memory)
         o = {"image": torch.empty(3, H, W, dtype=f32, device=device), "radii": torch.empty(N, dtype=i32, device=device)}
+        if aux:
+            o["aux_image"] = torch.empty(3, H, W, dtype=f32, device=device)
         if flavour.extras:
             o.update(pid=torch.empty(H, W, dtype=i32, device=device), pwp=torch.empty(H, W, dtype=f32, device=device),
                      pw=torch.empty(N, dtype=f32, device=device))
@@ -618,17 +621,36 @@ class HipBackend:
                      bwd_scratch=k.get("bwd_scratch"),
                      # what this stage 2 ran with (a recomposite walks the lists under the same decisions)
                      capacity=int(capacity), max_len=int(max_len), fwd_walk_form=int(view.walk_form),
-                     keys=keys)   # keep_keys(True) only: the (depth, id) key buffer, for finish_lists
+                     keys=keys,   # keep_keys(True) only: the (depth, id) key buffer, for finish_lists
+                     aux_colors=None)   # forward_aux: the second colour triples its walk composited (backward_aux reads them)
         return o["image"], o["radii"], o.get("pid"), o.get("pwp"), o.get("pw"), saved
 
+    def forward_aux(self, rs, flavour, use_filter, means3D, scales, rotations, opacities, colors, aux_colors,
+                    scratch_floats=0):
+        """forward() with a second colour triple per Gaussian (aux_colors [N, 3] fp32) composited by the same walk
+        (lograst_forward*_aux): -> (image, radii, pid, pwp, pw, aux_image, saved).  Whole images, scales / rotations form,
+        quadrant kernels (saved["hit_mask_form"] and last_forms say so); every capacity mode of forward()."""
+        if _tile_rows.get() != (0, 0):
+            raise ValueError("aux_colors: a tile_rows band is not supported (whole images only)")
+        if aux_colors.shape != (means3D.shape[0], 3) or aux_colors.dtype != torch.float32 or not aux_colors.is_contiguous():
+            raise ValueError("aux_colors must be a contiguous float32 [N, 3] tensor")
+        image, radii, pid, pwp, pw, saved = self.forward(rs, flavour, use_filter, means3D, scales, rotations, opacities, colors,
+                                                         scratch_floats=scratch_floats, _aux=aux_colors)
+        return image, radii, pid, pwp, pw, saved.pop("aux_image"), saved
+
     def forward(self, rs, flavour, use_filter, means3D, scales, rotations, opacities, colors, scratch_floats=0,
-                cov3D=None):
+                cov3D=None, _aux=None):
         """scratch_floats: non-zero = allocate the backward's accumulator rows (16 fp32 = 64 B per Gaussian,
         include/lograst.h: LOGRAST_BWD_ROW_FLOATS) and have the forward clear them: saved as `bwd_scratch` and consumed by
         the first backward.
-        cov3D: the rasterizer's cov3D_precomp ([N, 6] fp32) instead of scales / rotations (both None then)."""
+        cov3D: the rasterizer's cov3D_precomp ([N, 6] fp32) instead of scales / rotations (both None then).
+        _aux: forward_aux's aux_colors (the body is this one: the *_aux entry points take two more pointers)."""
         device = means3D.device
         L = self.require(device)
+        aux = _aux is not None
+        fwd_one, fwd_spec, fwd_project, fwd_render = (
+            (L.lograst_forward_aux, L.lograst_forward_speculative_aux, L.lograst_forward_project, L.lograst_forward_render_aux)
+            if aux else (L.lograst_forward, L.lograst_forward_speculative, L.lograst_forward_project, L.lograst_forward_render))
         N = means3D.shape[0]
         H, W = int(rs.image_height), int(rs.image_width)
         view, keep = self.make_view(rs, flavour, use_filter, device, cov3D=cov3D)
@@ -642,7 +664,8 @@ class HipBackend:
         view.walk_form = pin or self.walk_form(_capacity_hint if _capacity_hint is not None else _cap_model.ratio(ckey) * N, N)
         o, kept, scratch_floats, masks_for, mask_form = self._begin(
             L, view, flavour, device, N,
-            [("geom", u8, (L.lograst_geom_bytes(N),)), ("state", u8, (L.lograst_tile_state_bytes(W, H, N),))], scratch_floats)
+            [("geom", u8, (L.lograst_geom_bytes(N),)), ("state", u8, (L.lograst_tile_state_bytes(W, H, N),))], scratch_floats,
+            aux=aux)
         instances = None
 
         def lists_for(cap, plist=None):
@@ -659,36 +682,39 @@ class HipBackend:
         def stage2_args(k, keys, plist, capacity, max_len):
             return (_ptr(keys), _ptr(plist), capacity, max_len, _ptr(o["image"]), _ptr(k["final_T"]), _ptr(k["n_contrib"]),
                     _ptr(o.get("pid")), _ptr(o.get("pwp")), _ptr(o.get("pw")), _ptr(k.get("bwd_scratch")), scratch_floats,
-                    _ptr(status), stream)
+                    _ptr(status)) + ((_ptr(_aux), _ptr(o["aux_image"])) if aux else ()) + (stream,)
         n_host, m_host = ctypes.c_uint32(0), ctypes.c_uint32(0)
         with torch.cuda.device(device):
             if _capacity_hint is not None:   # sync-free: the caller's capacity, one call
                 capacity, max_len = _capacity_hint, _max_len_hint
                 k = self._carve(device, kept + [("plist", i32, (capacity,))])
                 plist, keys, masks = lists_for(capacity, plist=k["plist"])
-                _lib.check(L.lograst_forward(*stage1_args(k), *stage2_args(k, keys, plist, capacity, max_len)))
+                _lib.check(fwd_one(*stage1_args(k), *stage2_args(k, keys, plist, capacity, max_len)))
             else:
                 k = self._carve(device, kept)
                 retry = True
                 if _speculative and N > 0:   # both stages with a guessed capacity; the host reads the real one afterwards
                     capacity, max_len = _cap_model.guess(ckey, N, _tiles(W, H))
                     plist, keys, masks = lists_for(capacity)
-                    _lib.check(L.lograst_forward_speculative(*stage1_args(k), *stage2_args(k, keys, plist, capacity, max_len)[:-1],
-                                                             ctypes.byref(n_host), ctypes.byref(m_host), stream))
+                    _lib.check(fwd_spec(*stage1_args(k), *stage2_args(k, keys, plist, capacity, max_len)[:-1],
+                                        ctypes.byref(n_host), ctypes.byref(m_host), stream))
                     instances = int(n_host.value)
                     retry = instances > capacity or (max_len != 0 and int(m_host.value) > max_len)
                     _cap_model.update(ckey, N, instances, int(m_host.value), retry)
                 else:                        # exact: stage 1, read the header, stage 2
-                    _lib.check(L.lograst_forward_project(*stage1_args(k), ctypes.byref(n_host), ctypes.byref(m_host), stream))
+                    _lib.check(fwd_project(*stage1_args(k), ctypes.byref(n_host), ctypes.byref(m_host), stream))
                 if retry:   # (a speculative stage 2 that did not fit rendered nothing: once more with exact buffers)
                     capacity, max_len = int(n_host.value), max(int(m_host.value), 1)
                     plist, keys, masks = lists_for(capacity)
-                    _lib.check(L.lograst_forward_render(ctypes.byref(view), N, _ptr(k["geom"]), _ptr(k["state"]),
-                                                        *stage2_args(k, keys, plist, capacity, max_len)))
+                    _lib.check(fwd_render(ctypes.byref(view), N, _ptr(k["geom"]), _ptr(k["state"]),
+                                          *stage2_args(k, keys, plist, capacity, max_len)))
         if instances is None:
             instances = capacity          # exact mode: the real count; sync-free: the caller's (tight) upper bound
-        return self._finish(view, o, k, k["state"].view(i32), plist, (view.tile_row_begin, view.tile_row_end), instances, pin,
-                            capacity, max_len, masks, mask_form, keys if _keep_keys else None)
+        out = self._finish(view, o, k, k["state"].view(i32), plist, (view.tile_row_begin, view.tile_row_end), instances, pin,
+                           capacity, max_len, masks, mask_form, keys if _keep_keys else None)
+        if aux:   # (forward_aux takes the image out again)
+            out[-1].update(aux_colors=_aux, aux_image=o["aux_image"])
+        return out
 
     def recomposite(self, rs, flavour, use_filter, saved, colors, scratch_floats=0):
         """The forward of the same Gaussians with other colours, from the `saved` dict of a forward that ran (full image,
@@ -716,13 +742,30 @@ class HipBackend:
         return self._finish(view, o, k, saved["state"], saved["plist"], saved["tile_rows"], saved["instances"],
                             saved["walk_form_pin"], capacity, max_len, masks, mask_form, None)
 
-    def backward(self, rs, flavour, use_filter, means3D, scales, rotations, saved, grad_image, sink=None, cov3D=None):
+    def backward_aux(self, rs, flavour, use_filter, means3D, scales, rotations, saved, grad_image, grad_aux):
+        """The backward of forward_aux: one reverse walk and one chain-rule launch for both images (lograst_backward_aux).
+        grad_image / grad_aux: dL/dimage, dL/daux_image; either may be None (= zeros), not both.
+        -> (dL/dmeans3D, dL/dmeans2D, dL/dcolors, dL/dopacities, dL/dscales, dL/drotations, dL/daux_colors)."""
+        if saved.get("aux_colors") is None:
+            raise _lib.LograstError("backward_aux needs the saved record of a forward_aux call")
+        if grad_image is None and grad_aux is None:
+            raise ValueError("backward_aux: both image gradients are None")
+        return self.backward(rs, flavour, use_filter, means3D, scales, rotations, saved, grad_image, _aux=(grad_aux,))
+
+    def backward(self, rs, flavour, use_filter, means3D, scales, rotations, saved, grad_image, sink=None, cov3D=None,
+                 _aux=None):
         """sink: optional dict of running-sum tensors (means3D, scales, rotations, opacities, colors) that this call
         adds into (LOGRAST_BWD_ACCUMULATE); the corresponding returned gradients are then None.
-        cov3D (the forward's cov3D_precomp; no sink): the last two results are (dL/dcov3D [N, 6], None)."""
+        cov3D (the forward's cov3D_precomp; no sink): the last two results are (dL/dcov3D [N, 6], None).
+        _aux: backward_aux's (dL/daux_image,) (the body is this one; fresh gradients only)."""
         device = means3D.device
         L = self.require(device)
         N = means3D.shape[0]
+        aux = _aux is not None
+        if aux and (sink is not None or cov3D is not None):
+            raise ValueError("backward_aux writes fresh gradients: no gradient sink, no cov3D_precomp")
+        if not aux and saved.get("aux_colors") is not None:
+            raise _lib.LograstError("this forward composited aux channels: its backward is backward_aux")
         g_cov = None
         if cov3D is not None:
             if sink is not None:
@@ -731,7 +774,8 @@ class HipBackend:
         view, keep = self.make_view(rs, flavour, use_filter, device, cov3D=cov3D, g_cov3D=g_cov)
         view.tile_row_begin, view.tile_row_end = saved["tile_rows"]   # the band the forward rendered
         f32 = dict(dtype=torch.float32, device=device)
-        grad_image = grad_image.to(torch.float32).contiguous()
+        grad_image = grad_image.to(torch.float32).contiguous() if grad_image is not None else None
+        grad_aux = _aux[0].to(torch.float32).contiguous() if aux and _aux[0] is not None else None
         need = _lib.BWD_ROW_FLOATS
         # The reverse walk adds into ONE 64-byte accumulator row per Gaussian (mean x y, conic A B C, opacity, colour):
         # the block the forward already cleared for this purpose (first backward of this forward), else a fresh
@@ -747,7 +791,7 @@ class HipBackend:
             flags |= 4
         # tiny splats -> the row-split reverse walk; a form pinned for the forward holds for its backward
         view.walk_form = saved["walk_form_pin"] or self.walk_form(saved["instances"], N)
-        self._note_form("bwd", L.lograst_backward_form(ctypes.byref(view), N) == 1)
+        self._note_form("bwd", not aux and L.lograst_backward_form(ctypes.byref(view), N) == 1)   # (aux: quadrant kernels only)
         hm = saved["hit_masks"]      # the forward's support ballots (lograst_view.hit_masks): the reverse walk reads them
         if hm is not None:
             view.hit_masks, view.hit_mask_words = hm.data_ptr(), hm.numel()
@@ -757,7 +801,7 @@ class HipBackend:
         if sink is None:
             g = self._carve(device, [("rot", torch.float32, (N, 4)), ("means3D", torch.float32, (N, 3)),
                                      ("scales", torch.float32, (N, 3)), ("colors", torch.float32, (N, 3)),
-                                     ("opac", torch.float32, (N,))])
+                                     ("opac", torch.float32, (N,))] + ([("aux", torch.float32, (N, 3))] if aux else []))
             g_means3D, g_scales, g_rot, g_colors, g_opac = g["means3D"], g["scales"], g["rot"], g["colors"], g["opac"]
         elif "rows" in sink:   # one 64-byte row of running sums per Gaussian (LOGRAST_BWD_ACCUMULATE_ROWS)
             g_means3D, g_scales, g_rot, g_opac, g_colors = sink["rows"], None, None, None, None
@@ -766,6 +810,18 @@ class HipBackend:
             g_opac, g_colors = sink["opacities"], sink["colors"]
             g_means3D, g_scales, g_rot = sink["means3D"], sink["scales"], sink["rotations"]
             flags |= 2
+        if aux:
+            with torch.cuda.device(device):
+                _lib.check(L.lograst_backward_aux(ctypes.byref(view), N, _ptr(means3D), _ptr(scales), _ptr(rotations),
+                                                  _ptr(saved["radii"]), _ptr(saved["geom"]), _ptr(saved["state"]),
+                                                  _ptr(saved["plist"]), _ptr(saved["final_T"]), _ptr(saved["n_contrib"]),
+                                                  _ptr(saved["aux_colors"]), _ptr(grad_image), _ptr(grad_aux), _ptr(g_means2D),
+                                                  _ptr(g_conic), need, _ptr(g_opac), _ptr(g_colors), _ptr(g["aux"]),
+                                                  _ptr(g_means3D), _ptr(g_scales), _ptr(g_rot), _ptr(pw), flags,
+                                                  _stream_ptr(device)))
+            del keep
+            self.last_conic_grad = None
+            return g_means3D, g_means2D, g_colors, g_opac, g_scales, g_rot, g["aux"]
         with torch.cuda.device(device):
             _lib.check(L.lograst_backward(ctypes.byref(view), N, _ptr(means3D), _ptr(scales), _ptr(rotations),
                                           _ptr(saved["radii"]), _ptr(saved["geom"]), _ptr(saved["state"]),
@@ -1229,9 +1285,24 @@ def _leaf_grad_sink(leaves, device):
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, colors, shs, opacities, scales, rotations, rs, flavour, use_filter, cov3D=None,
-                reuse=None):
-        """reuse: the calling rasterizer object's _ReuseSlot while geometry reuse is on (set_geometry_reuse), else None."""
+                reuse=None, aux_colors=None):
+        """reuse: the calling rasterizer object's _ReuseSlot while geometry reuse is on (set_geometry_reuse), else None.
+        aux_colors: a second colour triple per Gaussian [N, 3], composited into one more output image (the last one) by the
+        same walk and differentiated by the same reverse walk (HipBackend.forward_aux / backward_aux)."""
         m = means3D.detach().to(torch.float32).contiguous()
+        ax = None
+        if aux_colors is not None:
+            if cov3D is not None:
+                raise ValueError("aux_colors cannot be combined with cov3D_precomp (pass scales / rotations)")
+            if _tile_rows.get() != (0, 0):
+                raise ValueError("aux_colors cannot be combined with a tile_rows band (whole images only)")
+            if _grad_sink is not None:
+                raise ValueError("aux_colors cannot be combined with accumulate_grads_into (its backward returns fresh gradients)")
+            if not (hasattr(_backend, "forward_aux") and hasattr(_backend, "backward_aux")):
+                raise _lib.LograstError("this backend has no forward_aux / backward_aux: aux_colors is not available")
+            ax = aux_colors.detach().to(torch.float32).contiguous()
+            if ax.shape != (m.shape[0], 3):
+                raise ValueError("aux_colors must be [N, 3]")
         cov = None
         if cov3D is not None:   # the packages' cov3D_precomp input (not LoG's path): scales / rotations are absent
             cov = cov3D.detach().to(torch.float32).contiguous()
@@ -1258,13 +1329,20 @@ class _RasterizeGaussians(torch.autograd.Function):
             raise ValueError("rasterizer inputs must be means3D[N,3], scales[N,3], rotations[N,4], "
                              "colors_precomp[N,3], opacities[N,1]")
         wants_grad = any(ctx.needs_input_grad[:7])   # all False under torch.no_grad()
-        wants_grad = wants_grad or (cov is not None and ctx.needs_input_grad[10])
+        wants_grad = wants_grad or (cov is not None and ctx.needs_input_grad[10]) or (ax is not None and ctx.needs_input_grad[12])
         scratch_floats = _lib.BWD_ROW_FLOATS if wants_grad else 0
         first = None
-        if reuse is not None:   # the same Gaussians as this object's last forward: composite its lists again
+        aux_image = None
+        if reuse is not None and ax is None:   # the same Gaussians as this object's last forward: composite its lists again
             first, why = reuse.match(_backend, rs, flavour, use_filter, m.device, (m, s, r, o), cov)
             _count_reuse(why)
-        if first is not None:
+        if ax is not None:      # one walk for both images; never remembered as a reusable forward
+            if reuse is not None:
+                reuse.forget()
+                _count_reuse("aux")
+            image, radii, pid, pwp, pw, aux_image, saved = _backend.forward_aux(rs, flavour, use_filter, m, s, r, o, c, ax,
+                                                                                scratch_floats=scratch_floats)
+        elif first is not None:
             image, radii, pid, pwp, pw, saved = _backend.recomposite(rs, flavour, use_filter, first, c,
                                                                      scratch_floats=scratch_floats)
         else:
@@ -1282,22 +1360,28 @@ class _RasterizeGaussians(torch.autograd.Function):
         # the backward trusts the forward's point_weight (which Gaussians it may skip, which dL/dconic rows are cleared):
         # an in-place change of that output between forward and backward is refused, like autograd does for saved tensors
         ctx.radii, ctx.pw, ctx.pw_version = radii, pw, pw._version if pw is not None else None
-        ctx.leaves = (means3D, colors, opacities, scales, rotations) if (sh is None and cov is None) else None
+        ctx.leaves = (means3D, colors, opacities, scales, rotations) if (sh is None and cov is None and ax is None) else None
         ctx.sh = (sh, clamped)
+        ctx.aux = ax is not None
+        # the reverse walk reads aux_colors again (the RGB colours sit in the records, a copy): an in-place change of the
+        # caller's tensor between forward and backward is refused, as autograd refuses it for saved tensors
+        ctx.aux_colors, ctx.aux_version = ax, ax._version if ax is not None else None
         ctx.shapes = (means2D.shape, opacities.shape)
         ctx.save_for_backward(m, s, r)
+        tail = (aux_image,) if ax is not None else ()
         if flavour.extras:
             ctx.mark_non_differentiable(radii, pid, pwp, pw)
-            return image, radii, pid, pwp, pw
+            return (image, radii, pid, pwp, pw) + tail
         ctx.mark_non_differentiable(radii)
-        return image, radii
+        return (image, radii) + tail
 
     @staticmethod
     def backward(ctx, grad_image, *unused):
         m, s, r = ctx.saved_tensors
-        if grad_image is None:   # no gradient reached the image: nothing flows on, and no visibility is published
+        grad_aux = unused[-1] if ctx.aux else None   # (the aux image is the last output)
+        if grad_image is None and grad_aux is None:   # no gradient reached an image: nothing flows on, and no visibility is published
             _backward_view.cur = None
-            return (None,) * 12
+            return (None,) * 13
         # which view's backward is running: nodes further down the same graph (log_amd.get_all's fused step) take the
         # visibility of THIS render from here (the rasterizer's node runs before the nodes that produced its inputs)
         _publish_backward_view(ctx.radii, m)
@@ -1306,10 +1390,15 @@ class _RasterizeGaussians(torch.autograd.Function):
         if ctx.pw is not None and ctx.pw._version != ctx.pw_version:
             raise RuntimeError("the rasterizer's point_weight output was modified in place between forward and backward; "
                                "the backward uses it to skip Gaussians that contributed to no pixel -- clone it first")
+        if ctx.aux and ctx.aux_colors._version != ctx.aux_version:
+            raise RuntimeError("the rasterizer's aux_colors input was modified in place between forward and backward; the "
+                               "backward composites it again -- clone it first")
         # where the gradients go: back to autograd (sink None), or added into running sums -- one row per Gaussian, or one
         # tensor per input (with native SH: the colour gradient into a scratch, from there into the running dL/dshs)
         n = m.shape[0]
         sink = _grad_sink if ctx.cov is None else None
+        if ctx.aux and sink is not None:
+            raise ValueError("aux_colors cannot be combined with accumulate_grads_into (its backward returns fresh gradients)")
         if sink is None and ctx.leaves is not None and (   # (leaves: None under cov3D_precomp or native SH)
                 _inplace_leaf_grads or all(getattr(t, _INPLACE_TAG, False) for t in ctx.leaves if t is not None)):
             sink = _leaf_grad_sink(ctx.leaves, m.device)
@@ -1331,9 +1420,14 @@ class _RasterizeGaussians(torch.autograd.Function):
                 sink = dict(sink, colors=torch.zeros(n, 3, dtype=torch.float32, device=m.device))
         else:
             sink = None   # (a sink without an "shs" entry under native SH: the gradients go back to autograd)
-        g_m3, g_m2, g_c, g_o, g_s, g_r = _backend.backward(ctx.rs, ctx.flavour, ctx.use_filter, m,
-                                                           *((s, r) if ctx.cov is None else (None, None)), ctx.saved,
-                                                           grad_image, sink=sink, cov3D=ctx.cov)
+        g_aux = None
+        if ctx.aux:   # both images through one reverse walk and one chain rule: means2D gets the one summed gradient
+            g_m3, g_m2, g_c, g_o, g_s, g_r, g_aux = _backend.backward_aux(ctx.rs, ctx.flavour, ctx.use_filter, m, s, r, ctx.saved,
+                                                                          grad_image, grad_aux)
+        else:
+            g_m3, g_m2, g_c, g_o, g_s, g_r = _backend.backward(ctx.rs, ctx.flavour, ctx.use_filter, m,
+                                                               *((s, r) if ctx.cov is None else (None, None)), ctx.saved,
+                                                               grad_image, sink=sink, cov3D=ctx.cov)
         g_sh = g_cov = None
         if ctx.cov is not None:   # (the backend's last two results are then (dL/dcov3D, None))
             g_cov, g_s = g_s, None
@@ -1344,7 +1438,7 @@ class _RasterizeGaussians(torch.autograd.Function):
             _backend.sh_backward(m, ctx.rs.campos, sh, int(ctx.rs.sh_degree), clamped, sink["colors"], sink["means3D"],
                                  into=sink["shs"])
         return (g_m3, g_m2.reshape(m2_shape), g_c, g_sh, g_o.reshape(o_shape) if g_o is not None else None, g_s, g_r,
-                None, None, None, g_cov, None)
+                None, None, None, g_cov, None, g_aux)
 
 
 class GaussianRasterizer(nn.Module):
@@ -1382,7 +1476,12 @@ class GaussianRasterizer(nn.Module):
             return _backend.tile_rows(self.raster_settings, self.FLAVOUR, use_filter, xyz, scaling, rotation)
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None, **kwargs):
+                cov3D_precomp=None, aux_colors=None, **kwargs):
+        """aux_colors (extension; the third-party packages have no such argument): a second colour triple per Gaussian,
+        [N, 3].  The call then returns its usual tuple plus ``aux_image`` [3, H, W] as the last element: the image a second
+        call with ``colors_precomp=aux_colors`` would return, bit for bit, from the same compositing walk; one autograd node
+        whose backward takes either or both image gradients.  Not with cov3D_precomp, a ``tile_rows`` band or
+        ``accumulate_grads_into``."""
         flavour = self.FLAVOUR
         use_filter = True
         if "use_filter" in kwargs:
@@ -1408,7 +1507,7 @@ class GaussianRasterizer(nn.Module):
             del self.__dict__["_reuse_slot"]    # switched off: nothing stays pinned
         with walk_form(self.walk_form) if self.walk_form not in (None, "auto") else contextlib.nullcontext():
             ret = _RasterizeGaussians.apply(means3D, means2D, colors_precomp, shs, opacities, scales, rotations,
-                                            self.raster_settings, flavour, use_filter, cov3D_precomp, slot)
+                                            self.raster_settings, flavour, use_filter, cov3D_precomp, slot, aux_colors)
         if flavour.extras:
             # how many Gaussians the ids of point_id_pixel index: lets log_amd.counter's stand-in for the
             # torch.unique call at LoG/render/renderer.py:156 recognise the map and take the histogram kernel
