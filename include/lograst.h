@@ -458,6 +458,37 @@ int lograst_project_backward(const lograst_view* view, int32_t n, const float* m
                              const float* dl_dconic, float* dl_dmeans3d, float* dl_dscales,
                              float* dl_drotations, void* stream);
 
+/* Camera gradients: lograst_backward / lograst_project_backward once more, with dL/dviewmatrix and dL/dprojmatrix as two
+ * further outputs ([4, 4] fp32 each, row-major, the layout of view->viewmatrix / view->projmatrix; written whole, never
+ * added to).  The chain-rule launch sums them over the Gaussians it differentiates, the terms evaluated in double (the fp32
+ * chain is ill-conditioned on needle-shaped Gaussians, and these sums are much smaller than their terms):
+ * with t = [p 1] V the view-space centre, T = J V[:3,:3]^T the EWA factor and hom = [p 1] P,
+ *   dL/dV[j][k] = sum dL/dT-terms + p_j dL/dt_k,  dL/dV[3][k] = sum dL/dt_k   (k = 0..2; dL/dt behind the 1.3 tan(fov) clamps),
+ *   dL/dP[j][c] = sum p_j dL/dhom_c,              dL/dP[3][c] = sum dL/dhom_c (c = 0, 1, 3).
+ * Column 3 of dL/dviewmatrix and column 2 of dL/dprojmatrix are exactly 0: no output depends on them.  Each workgroup stores
+ * its 24 partial sums to camera_scratch (lograst_camera_scratch_bytes(n) bytes of device memory, 8-byte aligned; its content
+ * afterwards is unspecified) and a finishing kernel (two above 2 M Gaussians) adds them in workgroup order in double: no float atomics, and identical
+ * inputs give identical bits.  Every other output is what the entry point without _camera writes (the per-Gaussian results
+ * of lograst_project_backward_camera bit for bit).  n == 0, or no live Gaussian: zeros.  view->campos does not exist in
+ * this ABI; a native-SH colour's dependence on the camera position is outside these gradients.
+ * Fresh gradients only, scales / rotations form, whole images.  LOGRAST_ERR_ARG before any launch: LOGRAST_BWD_ACCUMULATE or
+ * LOGRAST_BWD_ACCUMULATE_ROWS in flags; view->cov3d_precomp; a band view (tile_row_begin / tile_row_end); a NULL gradient
+ * matrix; a scratch that is NULL or too small.  There is no camera form of lograst_backward_aux.  (Additions within
+ * version 4: new entry points only, lograst_view untouched.) */
+size_t lograst_camera_scratch_bytes(int32_t n);
+int lograst_backward_camera(const lograst_view* view, int32_t n, const float* means3d, const float* scales,
+                            const float* rotations, const int32_t* radii, const void* geom, const void* tile_state,
+                            const uint32_t* point_list, const float* final_t, const int32_t* n_contrib,
+                            const float* dl_dimage, float* dl_dmeans2d, float* bwd_rows, float* dl_dopacities,
+                            float* dl_dcolors, float* dl_dmeans3d, float* dl_dscales, float* dl_drotations,
+                            const float* point_weight, int32_t flags, float* dl_dviewmatrix, float* dl_dprojmatrix,
+                            void* camera_scratch, size_t camera_scratch_bytes, void* stream);
+int lograst_project_backward_camera(const lograst_view* view, int32_t n, const float* means3d, const float* scales,
+                                    const float* rotations, const int32_t* radii, const float* dl_dmeans2d,
+                                    const float* dl_dconic, float* dl_dmeans3d, float* dl_dscales, float* dl_drotations,
+                                    float* dl_dviewmatrix, float* dl_dprojmatrix, void* camera_scratch,
+                                    size_t camera_scratch_bytes, void* stream);
+
 /* ---- "next" row N1: simple_knn._C.distCUDA2 ----------------------------------------------------------
  * Replaces distCUDA2 (third-party simple-knn, un-vendored; called at /root/reference/LoG/utils/file.py:88-91 and
  * LoG/model/base_gaussian.py:39-42): out[i] = mean squared distance from point i to its 3 nearest other
@@ -877,6 +908,23 @@ int lograst_mask_bounds_read(const void* record, int32_t batch, int32_t* host_ou
 int lograst_corrector_step(int32_t views, int32_t width, int32_t index, int32_t start_step, double lr_init, double lr_final,
                            int32_t* steps, float* param, float* grad, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq,
                            void* stream);
+
+/* ---- a per-view pose table (log_amd/pose.py) ---------------------------------------------------------------------------
+ * table f32[views, 6], contiguous: row i = (omega[3], upsilon[3]), the camera-frame perturbation p_cam' = R(omega) p_cam +
+ * upsilon of view i, R by Rodrigues' formula (its series below |omega|^2 = 1e-2).  viewmatrix / projmatrix: [4, 4] fp32
+ * device arrays in the rasterizer's row-vector convention.  With E = [[R^T - I, 0], [upsilon, 0]] and W = viewmatrix E:
+ *   viewmatrix_out = viewmatrix + W,  projmatrix_out = projmatrix + W (viewmatrix^-1 projmatrix),
+ *   campos_out [3] = row 3 of viewmatrix_out^-1,
+ * both inverses by the rigid closed form, everything in double and rounded once: a zero row returns the inputs' bits.
+ * lograst_pose_backward ADDS dL/d(row index) into table_grad f32[views, 6] from dL/dviewmatrix_out, dL/dprojmatrix_out and
+ * dL/dcampos_out (each may be NULL = zeros; all NULL: nothing is launched); viewmatrix and projmatrix are constants.
+ * One launch of one wave each, nothing comes back to the host; index is a host integer.  The table steps with
+ * lograst_corrector_step at width 6. */
+int lograst_pose_apply(int32_t views, int32_t index, const float* table, const float* viewmatrix, const float* projmatrix,
+                       float* viewmatrix_out, float* projmatrix_out, float* campos_out, void* stream);
+int lograst_pose_backward(int32_t views, int32_t index, const float* table, const float* viewmatrix, const float* projmatrix,
+                          const float* dl_dviewmatrix, const float* dl_dprojmatrix, const float* dl_dcampos, float* table_grad,
+                          void* stream);
 
 /* ---- the depth term of depth-supervised training (LoG/render/renderer.py:268-292 append_depth_loss with
  * LoG/render/loss.py:47-117 ScaleAndShiftInvariantLoss, one gradient scale) --------------------------------------------

@@ -159,6 +159,14 @@ _SIGNATURES = {
     "lograst_backward_aux": (ctypes.c_int, [ctypes.POINTER(LograstView), c_int32] + [c_void_p] * 14 + [c_int32]
                              + [c_void_p] * 7 + [c_int32, c_void_p]),
     "lograst_project_backward": (ctypes.c_int, [ctypes.POINTER(LograstView), c_int32] + [c_void_p] * 10),
+    # camera gradients: the two backwards with (dl_dviewmatrix, dl_dprojmatrix, scratch, scratch_bytes) in front of `stream`
+    "lograst_camera_scratch_bytes": (c_size_t, [c_int32]),
+    "lograst_backward_camera": (ctypes.c_int, [ctypes.POINTER(LograstView), c_int32] + [c_void_p] * 18 + [c_int32]
+                                + [c_void_p] * 3 + [c_size_t, c_void_p]),
+    "lograst_project_backward_camera": (ctypes.c_int, [ctypes.POINTER(LograstView), c_int32] + [c_void_p] * 12
+                                        + [c_size_t, c_void_p]),
+    "lograst_pose_apply": (ctypes.c_int, [c_int32, c_int32] + [c_void_p] * 7),
+    "lograst_pose_backward": (ctypes.c_int, [c_int32, c_int32] + [c_void_p] * 8),
     "lograst_sh_forward": (ctypes.c_int, [c_int32, c_int32, c_int32] + [c_void_p] * 6),
     "lograst_sh_backward": (ctypes.c_int, [c_int32, c_int32, c_int32] + [c_void_p] * 7 + [c_int32, c_void_p]),
     "lograst_knn_scratch_bytes": (c_size_t, [c_int32]),

@@ -858,18 +858,46 @@ int lograst_read_state(const void* tile_state, uint32_t* num_instances_host, uin
 
 // What lograst_backward_aux has on top of lograst_backward (aux.on = 0: the plain backward).
 struct LrBackwardAux { int on; const float* aux_colors; const float* dl_daux_image; int32_t bwd_row_floats; float* dl_daux_colors; };
-// The one backward body behind lograst_backward and lograst_backward_aux.
+// What the *_camera entry points have on top: dL/dviewmatrix and dL/dprojmatrix [4, 4] and the chain rule's partials scratch.
+struct LrBackwardCam { int on; float* dl_dview; float* dl_dproj; void* scratch; size_t scratch_bytes; };
+// Their own argument errors, before any launch; *done: n == 0, the two gradients are zeros and nothing else is to do.
+static int lr_check_camera(const LrView& v, int32_t n, int32_t flags, const LrBackwardCam& cam, hipStream_t s, bool* done) {
+  *done = false;
+  if (!cam.dl_dview || !cam.dl_dproj) return lr_fail(LOGRAST_ERR_ARG, "dl_dviewmatrix / dl_dprojmatrix are NULL");
+  if (flags & (LOGRAST_BWD_ACCUMULATE | LOGRAST_BWD_ACCUMULATE_ROWS))
+    return lr_fail(LOGRAST_ERR_ARG, "camera gradients come with fresh gradients only (no LOGRAST_BWD_ACCUMULATE / _ROWS form)");
+  if (v.cov3d) return lr_fail(LOGRAST_ERR_ARG, "camera gradients have no cov3d_precomp form");
+  if (v.ty0 != 0 || v.ty1 != v.gy)
+    return lr_fail(LOGRAST_ERR_ARG, "camera gradients are summed over whole images only (tile_row_begin / tile_row_end)");
+  if (n < 0) return lr_fail(LOGRAST_ERR_ARG, "negative Gaussian count");
+  if (n == 0) {
+    LR_HIP(hipMemsetAsync(cam.dl_dview, 0, 16 * sizeof(float), s));
+    LR_HIP(hipMemsetAsync(cam.dl_dproj, 0, 16 * sizeof(float), s));
+    *done = true;
+    return LOGRAST_OK;
+  }
+  if (!cam.scratch || cam.scratch_bytes < lr_camera_scratch_bytes(n))
+    return lr_fail(LOGRAST_ERR_ARG, "camera scratch is NULL or smaller than lograst_camera_scratch_bytes(n)");
+  if (reinterpret_cast<uintptr_t>(cam.scratch) & 7u) return lr_fail(LOGRAST_ERR_ARG, "camera scratch must be 8-byte aligned");
+  return LOGRAST_OK;
+}
+// The one backward body behind lograst_backward, lograst_backward_aux and lograst_backward_camera.
 static int lr_backward(const lograst_view* view, int32_t n, const float* means3d, const float* scales,
                        const float* rotations, const int32_t* radii, const void* geom, const void* tile_state,
                        const uint32_t* point_list, const float* final_t, const int32_t* n_contrib,
                        const float* dl_dimage, float* dl_dmeans2d, float* bwd_rows, float* dl_dopacities,
                        float* dl_dcolors, float* dl_dmeans3d, float* dl_dscales, float* dl_drotations,
-                       const float* point_weight, int32_t flags, void* stream, const LrBackwardAux& aux) {
+                       const float* point_weight, int32_t flags, void* stream, const LrBackwardAux& aux,
+                       const LrBackwardCam& cam = LrBackwardCam{0, nullptr, nullptr, nullptr, 0}) {
   float* const dl_dconic = bwd_rows;   // (the fourth gradient argument: since version 3 the n x 16 accumulator rows)
   g_prof_call++;
   LrView v;
   int rc = lr_make_view(view, &v);
   if (rc) return rc;
+  if (cam.on) {
+    bool done;
+    if ((rc = lr_check_camera(v, n, flags, cam, (hipStream_t)stream, &done)) || done) return rc;
+  }
   if (n < 0) return lr_fail(LOGRAST_ERR_ARG, "negative Gaussian count");
   if (n == 0) return LOGRAST_OK;
   const bool sink_rows = (flags & LOGRAST_BWD_ACCUMULATE_ROWS) != 0;
@@ -921,7 +949,8 @@ static int lr_backward(const lograst_view* view, int32_t n, const float* means3d
   // for all rows), dL/dopacities and dL/dcolors (written, or added to the caller's running sums)
   lr_launch_project_bwd(v, n, means3d, scales, rotations, radii, nullptr, nullptr, dl_dconic, dl_dmeans2d, dl_dopacities,
                         dl_dcolors, point_weight, dl_dmeans3d, dl_dscales, dl_drotations, accumulate, sink_rows, big_input, s,
-                        aux.on ? aux.dl_daux_colors : nullptr);
+                        aux.on ? aux.dl_daux_colors : nullptr, cam.on ? static_cast<float*>(cam.scratch) : nullptr, cam.dl_dview,
+                        cam.dl_dproj);
   LR_HIP(hipGetLastError());
   return LOGRAST_OK;
 }
@@ -947,14 +976,33 @@ int lograst_backward_aux(const lograst_view* view, int32_t n, const float* means
                      flags, stream, LrBackwardAux{1, aux_colors, dl_daux_image, bwd_row_floats, dl_daux_colors});
 }
 
-int lograst_project_backward(const lograst_view* view, int32_t n, const float* means3d, const float* scales,
-                             const float* rotations, const int32_t* radii, const float* dl_dmeans2d,
-                             const float* dl_dconic, float* dl_dmeans3d, float* dl_dscales,
-                             float* dl_drotations, void* stream) {
+int lograst_backward_camera(const lograst_view* view, int32_t n, const float* means3d, const float* scales,
+                            const float* rotations, const int32_t* radii, const void* geom, const void* tile_state,
+                            const uint32_t* point_list, const float* final_t, const int32_t* n_contrib,
+                            const float* dl_dimage, float* dl_dmeans2d, float* bwd_rows, float* dl_dopacities,
+                            float* dl_dcolors, float* dl_dmeans3d, float* dl_dscales, float* dl_drotations,
+                            const float* point_weight, int32_t flags, float* dl_dviewmatrix, float* dl_dprojmatrix,
+                            void* camera_scratch, size_t camera_scratch_bytes, void* stream) {
+  return lr_backward(view, n, means3d, scales, rotations, radii, geom, tile_state, point_list, final_t, n_contrib, dl_dimage,
+                     dl_dmeans2d, bwd_rows, dl_dopacities, dl_dcolors, dl_dmeans3d, dl_dscales, dl_drotations, point_weight,
+                     flags, stream, LrBackwardAux{0, nullptr, nullptr, 0, nullptr},
+                     LrBackwardCam{1, dl_dviewmatrix, dl_dprojmatrix, camera_scratch, camera_scratch_bytes});
+}
+size_t lograst_camera_scratch_bytes(int32_t n) { return lr_camera_scratch_bytes(n); }
+
+// The one body behind lograst_project_backward and lograst_project_backward_camera.
+static int lr_project_backward(const lograst_view* view, int32_t n, const float* means3d, const float* scales,
+                               const float* rotations, const int32_t* radii, const float* dl_dmeans2d,
+                               const float* dl_dconic, float* dl_dmeans3d, float* dl_dscales,
+                               float* dl_drotations, void* stream, const LrBackwardCam& cam) {
   g_prof_call++;
   LrView v;
   int rc = lr_make_view(view, &v);
   if (rc) return rc;
+  if (cam.on) {
+    bool done;
+    if ((rc = lr_check_camera(v, n, 0, cam, (hipStream_t)stream, &done)) || done) return rc;
+  }
   if (n < 0) return lr_fail(LOGRAST_ERR_ARG, "negative Gaussian count");
   if (n == 0) return LOGRAST_OK;
   if (!means3d || !radii || !dl_dmeans2d || !dl_dconic || !dl_dmeans3d)
@@ -965,9 +1013,25 @@ int lograst_project_backward(const lograst_view* view, int32_t n, const float* m
        reinterpret_cast<uintptr_t>(dl_drotations)) & 15u)
     return lr_fail(LOGRAST_ERR_ARG, "rotations / dl_dconic / dl_drotations must be 16-byte aligned");
   lr_launch_project_bwd(v, n, means3d, scales, rotations, radii, dl_dmeans2d, dl_dconic, nullptr, nullptr, nullptr,
-                        nullptr, nullptr, dl_dmeans3d, dl_dscales, dl_drotations, false, false, false, (hipStream_t)stream);
+                        nullptr, nullptr, dl_dmeans3d, dl_dscales, dl_drotations, false, false, false, (hipStream_t)stream,
+                        nullptr, cam.on ? static_cast<float*>(cam.scratch) : nullptr, cam.dl_dview, cam.dl_dproj);
   LR_HIP(hipGetLastError());
   return LOGRAST_OK;
+}
+int lograst_project_backward(const lograst_view* view, int32_t n, const float* means3d, const float* scales,
+                             const float* rotations, const int32_t* radii, const float* dl_dmeans2d,
+                             const float* dl_dconic, float* dl_dmeans3d, float* dl_dscales,
+                             float* dl_drotations, void* stream) {
+  return lr_project_backward(view, n, means3d, scales, rotations, radii, dl_dmeans2d, dl_dconic, dl_dmeans3d, dl_dscales,
+                             dl_drotations, stream, LrBackwardCam{0, nullptr, nullptr, nullptr, 0});
+}
+int lograst_project_backward_camera(const lograst_view* view, int32_t n, const float* means3d, const float* scales,
+                                    const float* rotations, const int32_t* radii, const float* dl_dmeans2d,
+                                    const float* dl_dconic, float* dl_dmeans3d, float* dl_dscales, float* dl_drotations,
+                                    float* dl_dviewmatrix, float* dl_dprojmatrix, void* camera_scratch,
+                                    size_t camera_scratch_bytes, void* stream) {
+  return lr_project_backward(view, n, means3d, scales, rotations, radii, dl_dmeans2d, dl_dconic, dl_dmeans3d, dl_dscales,
+                             dl_drotations, stream, LrBackwardCam{1, dl_dviewmatrix, dl_dprojmatrix, camera_scratch, camera_scratch_bytes});
 }
 
 size_t lograst_knn_scratch_bytes(int32_t p) { return lr_knn_scratch_bytes(p); }
@@ -1583,6 +1647,33 @@ int lograst_corrector_step(int32_t views, int32_t width, int32_t index, int32_t 
   a.beta1 = (float)0.9; a.beta2 = (float)0.999; a.omb1 = (float)(1.0 - 0.9); a.omb2 = (float)(1.0 - 0.999); a.eps = (float)1e-15;
   g_prof_call++;
   LR_HIP(lr_launch_corrector_step(a, (hipStream_t)stream));
+  return LOGRAST_OK;
+}
+
+// ---- per-view pose table (pose.hip) --------------------------------------------------------------------------
+static int lr_pose_args(int32_t views, int32_t index, const float* table, const float* viewmatrix, const float* projmatrix) {
+  if (views < 1) return lr_fail(LOGRAST_ERR_ARG, "views must be >= 1");
+  if (index < 0 || index >= views) return lr_fail(LOGRAST_ERR_ARG, "index outside [0, views)");
+  if (!table || !viewmatrix || !projmatrix) return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
+  return LOGRAST_OK;
+}
+int lograst_pose_apply(int32_t views, int32_t index, const float* table, const float* viewmatrix, const float* projmatrix,
+                       float* viewmatrix_out, float* projmatrix_out, float* campos_out, void* stream) {
+  if (lr_pose_args(views, index, table, viewmatrix, projmatrix)) return LOGRAST_ERR_ARG;
+  if (!viewmatrix_out || !projmatrix_out || !campos_out) return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
+  g_prof_call++;
+  LR_HIP(lr_launch_pose_apply(table, index, viewmatrix, projmatrix, viewmatrix_out, projmatrix_out, campos_out, (hipStream_t)stream));
+  return LOGRAST_OK;
+}
+int lograst_pose_backward(int32_t views, int32_t index, const float* table, const float* viewmatrix, const float* projmatrix,
+                          const float* dl_dviewmatrix, const float* dl_dprojmatrix, const float* dl_dcampos, float* table_grad,
+                          void* stream) {
+  if (lr_pose_args(views, index, table, viewmatrix, projmatrix)) return LOGRAST_ERR_ARG;
+  if (!table_grad) return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
+  if (!dl_dviewmatrix && !dl_dprojmatrix && !dl_dcampos) return LOGRAST_OK;   // no gradient arrived: nothing to add
+  g_prof_call++;
+  LR_HIP(lr_launch_pose_backward(table, index, viewmatrix, projmatrix, dl_dviewmatrix, dl_dprojmatrix, dl_dcampos, table_grad,
+                                 (hipStream_t)stream));
   return LOGRAST_OK;
 }
 

@@ -54,7 +54,12 @@ void lr_launch_project_bwd(const LrView& v, int N, const float* means, const flo
                            const int* radii, const float* g_mean2d, const float* g_conic, const float* rows,
                            float* o_mean2d, float* o_opac, float* o_col, const float* pw,
                            float* g_means3d, float* g_scales, float* g_rots, bool accumulate, bool sink_rows,
-                           bool big_input, hipStream_t s, float* o_aux = nullptr);   // o_aux: dL/daux_colors [N, 3] out of the rows' slots 9..11 (fresh gradients, no cov3d)
+                           bool big_input, hipStream_t s, float* o_aux = nullptr,
+                           float* cam_partials = nullptr, float* cam_dv = nullptr, float* cam_dp = nullptr);   // o_aux: dL/daux_colors [N, 3] out of the rows' slots 9..11 (fresh gradients, no cov3d)
+
+// cam_partials (+ cam_dv, cam_dp [4, 4]): the camera sums -- one row of 24 partials per workgroup of the chain rule, then
+// dL/dviewmatrix / dL/dprojmatrix by a finishing kernel; lr_camera_scratch_bytes(N) bytes (fresh gradients, no cov3d, no o_aux)
+size_t lr_camera_scratch_bytes(int N);
 
 // exchange.hip
 void lx_launch_pack_rows(float* rows, int groups, long long rows_per_group, int kmax, float* packed,
@@ -126,6 +131,12 @@ hipError_t lr_launch_id_histogram(int n, const int32_t* pid, int npix, int32_t* 
 hipError_t lr_launch_counter(const CounterArgs& a, hipStream_t s);
 hipError_t lr_launch_sparse_adam(const AdamArgs& a, int num_keys, hipStream_t s);
 hipError_t lr_launch_corrector_step(const CorrectorArgs& a, hipStream_t s);
+
+// pose.hip: one row of a [views, 6] pose table applied to a camera, and dL/d(row) added into the table's gradient
+hipError_t lr_launch_pose_apply(const float* table, int index, const float* view, const float* proj, float* view_out,
+                                float* proj_out, float* campos_out, hipStream_t s);
+hipError_t lr_launch_pose_backward(const float* table, int index, const float* view, const float* proj, const float* g_view,
+                                   const float* g_proj, const float* g_campos, float* grad, hipStream_t s);
 
 // loss.hip
 size_t lr_loss_scratch_bytes(int B, int C, int H, int W);

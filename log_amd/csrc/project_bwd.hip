@@ -13,6 +13,112 @@
 // write of the running sums: in an opaque scene most Gaussians are hidden (30 M random Gaussians at opacity 0.999:
 // the kernel went from 0.83 ms, at the copy rate, to the touched rows' share).
 // The chain rule of ONE Gaussian the forward composited (gm, gs, gq, and dL/dcov3D written / added in place when COV).
+#define LR_CAM_SUMS 24
+// CAM: the row's terms of dL/dviewmatrix and dL/dprojmatrix, added into cam[LR_CAM_SUMS] (layout: lr_camera_finish_kernel).
+// The chain rule once more, in DOUBLE, as far as the camera needs it (no dL/dSigma -> scales / rotations part).  The fp32
+// chain above is ill-conditioned for needle-shaped Gaussians (det = a c - b^2 and the quadratic forms in dL/dconic cancel): a
+// Gaussian's own gradients carry that error to its own row, but the camera sums add the rows of ALL Gaussians into 24 numbers
+// that are ~10x smaller than the sum of the terms' magnitudes, and the rows' fp32 errors do not cancel with them -- on a
+// 1024-Gaussian test scene the fp32 terms put dL/dviewmatrix 3e-4 from the float64 reference, these 1e-5 (what the fp32
+// forward's decisions leave).  The reverse walk's fp32 sums are not the problem: they enter linearly.  The per-Gaussian
+// outputs keep the fp32 chain and its bits.  V and P are row-major in the row-vector convention: t_k = sum_j p_j V[j][k] +
+// V[3][k], T0[j] = J00 V[j][0] + J02 V[j][2], T1[j] = J11 V[j][1] + J12 V[j][2], hom_c = sum_j p_j P[j][c] + P[3][c]; dL/dt is
+// taken behind the clamp branches (a clamped axis has J02 = -fx ux / tz: no t.x in it), so the J terms are the direct partials
+// in V.  Column 3 of V and column 2 of P reach no output: structural zeros, not summed.
+LR_DEV void lr_camera_row(const LrView& v, const float pf[3], const float sf[3], const float qf[4], float gnx, float gny,
+                          float gA, float gB, float gC, float* cam) {
+  const float* __restrict__ Vf = v.view;
+  const float* __restrict__ Pf = v.proj;
+  double V[12];   // rows 0..3, columns 0..2
+#pragma unroll
+  for (int j = 0; j < 4; j++)
+#pragma unroll
+    for (int k = 0; k < 3; k++) V[3 * j + k] = (double)Vf[4 * j + k];
+  const double p[3] = {(double)pf[0], (double)pf[1], (double)pf[2]};
+  const double r = qf[0], x = qf[1], y = qf[2], z = qf[3];
+  const double R[9] = {1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - r * z), 2.0 * (x * z + r * y),
+                       2.0 * (x * y + r * z), 1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z - r * x),
+                       2.0 * (x * z - r * y), 2.0 * (y * z + r * x), 1.0 - 2.0 * (x * x + y * y)};
+  double M[9];
+#pragma unroll
+  for (int i = 0; i < 3; i++)
+#pragma unroll
+    for (int k = 0; k < 3; k++) M[3 * i + k] = R[3 * i + k] * (double)sf[k];
+  double S3[9];
+#pragma unroll
+  for (int i = 0; i < 3; i++)
+#pragma unroll
+    for (int k = 0; k < 3; k++) S3[3 * i + k] = M[3 * i] * M[3 * k] + M[3 * i + 1] * M[3 * k + 1] + M[3 * i + 2] * M[3 * k + 2];
+  double t[3];
+#pragma unroll
+  for (int k = 0; k < 3; k++) t[k] = p[0] * V[k] + p[1] * V[3 + k] + p[2] * V[6 + k] + V[9 + k];
+  const double fx = v.fx, fy = v.fy, tz = t[2], tz2 = tz * tz, tz3 = tz2 * tz;
+  const double limx = 1.3 * (double)v.tanfovx, limy = 1.3 * (double)v.tanfovy;
+  const double txtz = t[0] / tz, tytz = t[1] / tz;
+  const bool cx = (txtz < -limx) || (txtz > limx), cy = (tytz < -limy) || (tytz > limy);
+  const double ux = fmin(limx, fmax(-limx, txtz)), uy = fmin(limy, fmax(-limy, tytz));
+  const double txc = ux * tz, tyc = uy * tz;
+  const double j00 = fx / tz, j02 = -(fx * txc) / tz2, j11 = fy / tz, j12 = -(fy * tyc) / tz2;
+  double T0[3], T1[3], ts0[3], ts1[3];
+#pragma unroll
+  for (int j = 0; j < 3; j++) {
+    T0[j] = j00 * V[3 * j] + j02 * V[3 * j + 2];
+    T1[j] = j11 * V[3 * j + 1] + j12 * V[3 * j + 2];
+  }
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    ts0[k] = T0[0] * S3[k] + T0[1] * S3[3 + k] + T0[2] * S3[6 + k];
+    ts1[k] = T1[0] * S3[k] + T1[1] * S3[3 + k] + T1[2] * S3[6 + k];
+  }
+  const double a_raw = ts0[0] * T0[0] + ts0[1] * T0[1] + ts0[2] * T0[2];
+  const double b = ts0[0] * T1[0] + ts0[1] * T1[1] + ts0[2] * T1[2];
+  const double c_raw = ts1[0] * T1[0] + ts1[1] * T1[1] + ts1[2] * T1[2];
+  double a = a_raw, c = c_raw;
+  if (v.filter_mode == LOGRAST_FILTER_DILATE) { a += (double)0.3f; c += (double)0.3f; }   // (the forward's fp32 constant)
+  else if (v.filter_mode == LOGRAST_FILTER_CLAMP) { a = fmax(a, (double)0.3f); c = fmax(c, (double)0.3f); }
+  const double det = a * c - b * b, di2 = 1.0 / (det * det);
+  const double dA = gA, dB = gB, dC = gC;
+  double ga = di2 * (-c * c * dA + b * c * dB - b * b * dC);
+  const double gb = di2 * (2.0 * b * c * dA - (det + 2.0 * b * b) * dB + 2.0 * a * b * dC);
+  double gc = di2 * (-b * b * dA + a * b * dB - a * a * dC);
+  if (v.filter_mode == LOGRAST_FILTER_CLAMP) {
+    if (!(a_raw >= (double)0.3f)) ga = 0.0;
+    if (!(c_raw >= (double)0.3f)) gc = 0.0;
+  }
+  const double hb = 0.5 * gb;
+  double gT0[3], gT1[3];
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    gT0[k] = 2.0 * (ga * ts0[k] + hb * ts1[k]);
+    gT1[k] = 2.0 * (hb * ts0[k] + gc * ts1[k]);
+  }
+  double gj00 = 0.0, gj02 = 0.0, gj11 = 0.0, gj12 = 0.0;
+#pragma unroll
+  for (int j = 0; j < 3; j++) {
+    gj00 += gT0[j] * V[3 * j]; gj02 += gT0[j] * V[3 * j + 2];
+    gj11 += gT1[j] * V[3 * j + 1]; gj12 += gT1[j] * V[3 * j + 2];
+  }
+  const double g_txc = -fx / tz2 * gj02, g_tyc = -fy / tz2 * gj12;
+  double g_tz = -fx / tz2 * gj00 - fy / tz2 * gj11 + 2.0 * fx * txc / tz3 * gj02 + 2.0 * fy * tyc / tz3 * gj12;
+  double g_tx, g_ty;
+  if (cx) { g_tx = 0.0; g_tz += ux * g_txc; } else { g_tx = g_txc; }
+  if (cy) { g_ty = 0.0; g_tz += uy * g_tyc; } else { g_ty = g_tyc; }
+  // centre path: ndc = h.xy / (h.w + eps)
+  const double hx = p[0] * (double)Pf[0] + p[1] * (double)Pf[4] + p[2] * (double)Pf[8] + (double)Pf[12];
+  const double hy = p[0] * (double)Pf[1] + p[1] * (double)Pf[5] + p[2] * (double)Pf[9] + (double)Pf[13];
+  const double hw = p[0] * (double)Pf[3] + p[1] * (double)Pf[7] + p[2] * (double)Pf[11] + (double)Pf[15];
+  const double pw = 1.0 / (hw + 0.0000001);
+  const double ghx = (double)gnx * pw, ghy = (double)gny * pw, ghw = -((double)gnx * hx + (double)gny * hy) * pw * pw;
+#pragma unroll
+  for (int j = 0; j < 3; j++) {
+    cam[3 * j + 0] += (float)(j00 * gT0[j] + p[j] * g_tx);
+    cam[3 * j + 1] += (float)(j11 * gT1[j] + p[j] * g_ty);
+    cam[3 * j + 2] += (float)(j02 * gT0[j] + j12 * gT1[j] + p[j] * g_tz);
+    cam[12 + 3 * j + 0] += (float)(p[j] * ghx); cam[12 + 3 * j + 1] += (float)(p[j] * ghy); cam[12 + 3 * j + 2] += (float)(p[j] * ghw);
+  }
+  cam[9] += (float)g_tx; cam[10] += (float)g_ty; cam[11] += (float)g_tz;
+  cam[21] += (float)ghx; cam[22] += (float)ghy; cam[23] += (float)ghw;
+}
 template <bool ACCUMULATE, bool COV>
 LR_DEV void lr_project_bwd_row(const LrView& v, int i, const float* __restrict__ means, const float* __restrict__ scales,
                                const float* __restrict__ rots, float gnx, float gny, float gA, float gB, float gC,
@@ -124,14 +230,15 @@ LR_DEV void lr_project_bwd_row(const LrView& v, int i, const float* __restrict__
 
 // The chain rule of ONE live Gaussian i: reads its accumulator row (AOS) or its (dL/dmean2D, dL/dconic) pair, hands out
 // the per-view outputs and writes / adds the gradients (see lr_project_bwd_kernel for the template flags).
-template <bool ACCUMULATE, bool COV, bool AOS, bool SINKROWS, bool AUXO = false>
+template <bool ACCUMULATE, bool COV, bool AOS, bool SINKROWS, bool AUXO = false, bool CAM = false>
 // (No __restrict__ here: the kernels' own parameters carry it.  Repeated on this inlined function it gave the scheduler
 // licence to hoist every load of the row above the chain rule -- 136 -> 170 VGPRs, three waves per SIMD -> two, the
 // 30 M-row launch 402 -> 477 us.)
 LR_DEV void lr_pbwd_live_row(const LrView& v, int i, const float* means, const float* scales, const float* rots,
                              const float* g_mean2d, const float* g_conic, const float4* rows, float* o_mean2d,
                              float* o_opac, float* o_col, float* g_means3d, float* g_scales, float* g_rots,
-                             float* m2d_slice = nullptr, int slice_base = 0, bool staged = false, float* o_aux = nullptr) {
+                             float* m2d_slice = nullptr, int slice_base = 0, bool staged = false, float* o_aux = nullptr,
+                             float* cam = nullptr) {
     float gm[3], gs[3] = {0.f, 0.f, 0.f}, gq[4] = {0.f, 0.f, 0.f, 0.f};
     float gnx, gny, gA, gB, gC;
     float gA2 = 0.f, gB2 = 0.f, gC2 = 0.f;   // (AUXO)
@@ -217,6 +324,16 @@ LR_DEV void lr_pbwd_live_row(const LrView& v, int i, const float* means, const f
         reinterpret_cast<float4*>(g_rots)[i] = float4{gq[0], gq[1], gq[2], gq[3]};
       }
     }
+    if (CAM) {
+      // behind the row's stores and behind a scheduling fence: interleaved with the fp32 chain the double chain took every
+      // register a wave can have (256 VGPRs + AGPRs, one wave per SIMD); the row's 40 input bytes are read again (cache hits)
+      __builtin_amdgcn_sched_barrier(0);
+      const float pf[3] = {means[3 * i], means[3 * i + 1], means[3 * i + 2]};
+      const float sf[3] = {scales[3 * i] * v.scale_modifier, scales[3 * i + 1] * v.scale_modifier, scales[3 * i + 2] * v.scale_modifier};
+      const float4 q4 = reinterpret_cast<const float4*>(rots)[i];
+      const float qf[4] = {q4.x, q4.y, q4.z, q4.w};
+      lr_camera_row(v, pf, sf, qf, gnx, gny, gA, gB, gC, cam);
+    }
 }
 
 // One workgroup owns LR_PBWD_ROWS consecutive Gaussians.  Their live flags are read coalesced; the live rows are
@@ -239,13 +356,20 @@ LR_DEV void lr_pbwd_live_row(const LrView& v, int i, const float* means, const f
 // AUXO (lograst_backward_aux; AOS, fresh gradients, not COV): the rows' slots 9..11 leave as dL/daux_colors [N, 3] -- a
 // live row's values, zeros for the others, exactly as dL/dcolour -- and slots 12..14 hold the aux image's dL/dconic, which
 // takes its own pass through the chain rule inside the same launch (lr_pbwd_live_row).
+// CAM (lograst_backward_camera / lograst_project_backward_camera; fresh gradients, not COV, not AUXO): every live row's
+// terms of dL/dviewmatrix and dL/dprojmatrix -- LR_CAM_SUMS sums, the terms from a second, double pass over the row
+// (lr_camera_row) -- are added up per lane, per wave (shuffles), per workgroup (LDS, wave order), and the workgroup STORES its partials to row
+// blockIdx.x of cam_out [workgroups, LR_CAM_SUMS]: a workgroup without a live row stores zeros, lanes without a row add
+// zeros.  No atomics: every workgroup adding into the same two lines is the worst shape for a float atomic, and the order of
+// the additions would change from run to run.  lr_camera_finish_kernel adds the rows up in workgroup order.
 // WAVES: waves per SIMD the register allocator aims for (1 = its own choice: ~130 VGPRs, three waves).  Measured, 30 M
 // Gaussians, running sums / fresh gradients: default 374 / 736 us, 4 waves (128 VGPRs, no scratch) 391 / 865, 5 (spills)
 // 473 / 877, 6: 518 / 918 -- more resident workgroups make the scattered rows' traffic worse, not better.  A band view
 // (nearly all flag pass: a fraction of a percent of 100 M rows is live) gains from four: 738 -> 638 us -- the row-major
 // sink's kernel exists in both forms and band views launch the second (unless they take the compact-list form below, the
 // default; the current compiler spills 10 VGPRs in it, 22 before the staged slice: profiles/chain_rule_dmeans2d_lines.md).
-template <bool ACCUMULATE, bool TOUCHED, bool COV, bool AOS, bool SINKROWS = false, int WAVES = 1, bool AUXO = false>
+template <bool ACCUMULATE, bool TOUCHED, bool COV, bool AOS, bool SINKROWS = false, int WAVES = 1, bool AUXO = false,
+          bool CAM = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES)))
 lr_project_bwd_kernel(LrView v, int N, const float* __restrict__ means, const float* __restrict__ scales,
                       const float* __restrict__ rots, const int* __restrict__ radii,
@@ -253,10 +377,13 @@ lr_project_bwd_kernel(LrView v, int N, const float* __restrict__ means, const fl
                       const float4* __restrict__ rows, float* __restrict__ o_mean2d, float* __restrict__ o_opac,
                       float* __restrict__ o_col,
                       const float* __restrict__ pw, float* __restrict__ g_means3d, float* __restrict__ g_scales,
-                      float* __restrict__ g_rots, int clear_inside, float* __restrict__ o_aux = nullptr) {
+                      float* __restrict__ g_rots, int clear_inside, float* __restrict__ o_aux = nullptr,
+                      float* __restrict__ cam_out = nullptr) {
+  static_assert(!CAM || (!ACCUMULATE && !COV && !SINKROWS && !AUXO), "camera sums: fresh gradients, scales / rotations, no aux");
   static_assert(!AUXO || (AOS && !ACCUMULATE && !COV && !SINKROWS), "dL/daux_colors: fresh gradients from the accumulator rows only");
   __shared__ uint32_t live_list[LR_PBWD_ROWS];
   __shared__ uint32_t live_count;
+  __shared__ uint32_t cam_count[CAM ? LR_PBWD_ROWS / 64 : 1];   // (CAM: live rows per (round, wave) slice of the block)
   // STAGE (the instantiations the large-input running-sum route launches; taken when clear_inside == 0): the workgroup's
   // slice of dL/dmeans2D -- 1024 rows x 12 bytes = 12 288 contiguous bytes, a multiple of 64 -- is built in LDS (zeros,
   // then the live rows' values) and leaves with 16-byte stores that cover whole 64-byte lines.  The memory side charges
@@ -341,7 +468,9 @@ lr_project_bwd_kernel(LrView v, int N, const float* __restrict__ means, const fl
       }
     }
     const uint64_t m = __ballot(live);
-    if (m) {
+    if (CAM) {   // (the list is built below, in row order)
+      if ((tid & 63) == 0) cam_count[k * 4 + (tid >> 6)] = (uint32_t)__popcll(m);
+    } else if (m) {
       uint32_t first = 0;
       if ((tid & 63) == 0) first = atomicAdd(&live_count, (uint32_t)__popcll(m));
       first = (uint32_t)__shfl((int)first, 0);
@@ -349,11 +478,56 @@ lr_project_bwd_kernel(LrView v, int N, const float* __restrict__ means, const fl
     }
   }
   __syncthreads();
+  if (CAM) {
+    // The order in which the waves' atomics reserve their slots changes from run to run, and with it which lane adds which
+    // row's terms: the camera sums would differ in their last bits.  Here every (round, wave) slice of the list starts
+    // behind the slices in front of it: the list is in row order, and identical inputs give identical sums.
+#pragma unroll
+    for (int k = 0; k < LR_PBWD_ROWS / 256; k++) {
+      const int i = base + k * 256 + tid;
+      const bool live = i < N && rad_k[k] > 0 && (!TOUCHED || pw_k[k] > 0.f);
+      const uint64_t m = __ballot(live);
+      uint32_t first = 0;
+      for (int w = 0; w < k * 4 + (tid >> 6); w++) first += cam_count[w];
+      if (live) live_list[first + (uint32_t)__popcll(m & ((1ull << (tid & 63)) - 1ull))] = (uint32_t)i;
+    }
+    if (tid == 0) {
+      uint32_t total = 0;
+      for (int w = 0; w < LR_PBWD_ROWS / 64; w++) total += cam_count[w];
+      live_count = total;
+    }
+    __syncthreads();
+  }
   const uint32_t n = live_count;
+  float cam[CAM ? LR_CAM_SUMS : 1];
+  if (CAM) {
+#pragma unroll
+    for (int c = 0; c < LR_CAM_SUMS; c++) cam[c] = 0.f;
+  }
   for (uint32_t j = (uint32_t)tid; j < n; j += 256u)
-    lr_pbwd_live_row<ACCUMULATE, COV, AOS, SINKROWS, AUXO>(v, (int)live_list[j], means, scales, rots, g_mean2d, g_conic, rows,
-                                                           o_mean2d, o_opac, o_col, g_means3d, g_scales, g_rots,
-                                                           STAGE ? m2d_slice : nullptr, base, staged, o_aux);
+    lr_pbwd_live_row<ACCUMULATE, COV, AOS, SINKROWS, AUXO, CAM>(v, (int)live_list[j], means, scales, rots, g_mean2d, g_conic, rows,
+                                                                o_mean2d, o_opac, o_col, g_means3d, g_scales, g_rots,
+                                                                STAGE ? m2d_slice : nullptr, base, staged, o_aux, cam);
+  if (CAM && n == 0u) {   // (most workgroups of a large view: no live row, nothing to reduce)
+    if (tid < LR_CAM_SUMS) cam_out[(size_t)blockIdx.x * LR_CAM_SUMS + tid] = 0.f;
+  } else if (CAM) {
+    // lane -> wave (a butterfly: every lane ends with the wave's sum, in an order fixed by the lane numbers) -> workgroup
+    __shared__ float cam_wave[256 / 64][LR_CAM_SUMS];
+#pragma unroll
+    for (int c = 0; c < LR_CAM_SUMS; c++) {
+      float x = cam[c];
+#pragma unroll
+      for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d);
+      cam[c] = x;
+    }
+    if ((tid & 63) == 0) {
+#pragma unroll
+      for (int c = 0; c < LR_CAM_SUMS; c++) cam_wave[tid >> 6][c] = cam[c];
+    }
+    __syncthreads();
+    if (tid < LR_CAM_SUMS)
+      cam_out[(size_t)blockIdx.x * LR_CAM_SUMS + tid] = ((cam_wave[0][tid] + cam_wave[1][tid]) + cam_wave[2][tid]) + cam_wave[3][tid];
+  }
   if (staged) {
     // the slice leaves: every row of the block is defined here (zero unless live), 16 bytes per lane and 1 KB per wave and
     // store instruction -- whole lines (three instructions for a full block); non-temporal like the zero pass it replaces
@@ -457,15 +631,96 @@ lr_pbwd_list_kernel(LrView v, int N, const float* __restrict__ means, const floa
   }
 }
 
+// ---- camera gradients: the workgroups' partial sums -> dL/dviewmatrix, dL/dprojmatrix ----------------------------------
+// partials [G, LR_CAM_SUMS] as lr_project_bwd_kernel<CAM> stored them: slots 3 r + k (r = 0..3, k = 0..2) dL/dV[r][k], slots
+// 12 + 3 r + c' dL/dP[r][c] with c' = 0, 1, 2 for the columns c = 0, 1, 3.  Everything is added in workgroup order, in double,
+// with a bracketing that depends on G alone -- identical inputs give identical bits -- and rounded to fp32 once: block b of
+// B takes the rows [b chunk, (b + 1) chunk); in it LR_CAM_GROUPS lane groups of LR_CAM_SUMS lanes take consecutive sub-ranges,
+// and their sums are added in group order.  B = 1 (G <= LR_CAM_ONE_BLOCK rows, views of up to 2 M Gaussians): that block
+// writes dV [4, 4] and dP [4, 4] itself -- whole, column 3 of dV and column 2 of dP are 0.  Otherwise the blocks leave their
+// sums as doubles in `stage` [B, LR_CAM_SUMS] and lr_camera_total_kernel adds those in block order.  (One block for the 29 297
+// rows of a 30 M-Gaussian view took 0.22 ms, as much as the camera sums cost the chain-rule launch itself.)
+#define LR_CAM_GROUPS 42        // 42 x 24 = 1008 of 1024 lanes
+#define LR_CAM_ONE_BLOCK 2048
+#define LR_CAM_BLOCKS 64
+LR_DEV void lr_camera_write(const double* sums, int tid, float* __restrict__ dV, float* __restrict__ dP) {   // tid < 32
+  const int mat = tid >> 4, r = (tid >> 2) & 3, col = tid & 3;
+  const bool zero = mat ? col == 2 : col == 3;
+  const int slot = mat ? 12 + 3 * r + (col == 3 ? 2 : col) : 3 * r + col;
+  (mat ? dP : dV)[4 * r + col] = zero ? 0.f : (float)sums[slot];
+}
+__global__ void __launch_bounds__(1024)
+lr_camera_finish_kernel(const float* __restrict__ partials, int G, double* __restrict__ stage, float* __restrict__ dV,
+                        float* __restrict__ dP) {
+  __shared__ double part[LR_CAM_GROUPS][LR_CAM_SUMS];
+  __shared__ double sums[LR_CAM_SUMS];
+  const int tid = threadIdx.x, g = tid / LR_CAM_SUMS, c = tid - g * LR_CAM_SUMS;
+  const int chunk = (G + (int)gridDim.x - 1) / (int)gridDim.x;
+  const int r0 = min(G, (int)blockIdx.x * chunk), r1 = min(G, r0 + chunk);
+  if (g < LR_CAM_GROUPS) {
+    const int sub = (r1 - r0 + LR_CAM_GROUPS - 1) / LR_CAM_GROUPS;
+    const int w0 = min(r1, r0 + g * sub), w1 = min(r1, w0 + sub);
+    double acc = 0.0;
+#pragma unroll 8
+    for (int w = w0; w < w1; w++) acc += (double)partials[(size_t)w * LR_CAM_SUMS + c];
+    part[g][c] = acc;
+  }
+  __syncthreads();
+  if (tid < LR_CAM_SUMS) {
+    double acc = 0.0;
+    for (int k = 0; k < LR_CAM_GROUPS; k++) acc += part[k][tid];
+    if (gridDim.x == 1) sums[tid] = acc; else stage[(size_t)blockIdx.x * LR_CAM_SUMS + tid] = acc;
+  }
+  if (gridDim.x == 1) {
+    __syncthreads();
+    if (tid < 32) lr_camera_write(sums, tid, dV, dP);
+  }
+}
+__global__ void __launch_bounds__(64)
+lr_camera_total_kernel(const double* __restrict__ stage, int B, float* __restrict__ dV, float* __restrict__ dP) {
+  __shared__ double sums[LR_CAM_SUMS];
+  const int tid = threadIdx.x;
+  if (tid < LR_CAM_SUMS) {
+    double acc = 0.0;
+    for (int b = 0; b < B; b++) acc += stage[(size_t)b * LR_CAM_SUMS + tid];
+    sums[tid] = acc;
+  }
+  __syncthreads();
+  if (tid < 32) lr_camera_write(sums, tid, dV, dP);
+}
+// the partials' rows, then (8-byte aligned: a row is 96 bytes) the blocks' double sums
+static size_t lr_camera_rows(int N) { return (size_t)(N > 0 ? (N + LR_PBWD_ROWS - 1) / LR_PBWD_ROWS : 1); }
+size_t lr_camera_scratch_bytes(int N) {
+  return sizeof(float) * LR_CAM_SUMS * lr_camera_rows(N) + sizeof(double) * LR_CAM_SUMS * LR_CAM_BLOCKS;
+}
+static void lr_launch_camera_finish(float* partials, int N, float* dV, float* dP, hipStream_t s) {
+  const int G = (int)lr_camera_rows(N);
+  double* stage = reinterpret_cast<double*>(partials + (size_t)G * LR_CAM_SUMS);
+  const int B = G <= LR_CAM_ONE_BLOCK ? 1 : LR_CAM_BLOCKS;
+  hipLaunchKernelGGL(lr_camera_finish_kernel, dim3(B), dim3(1024), 0, s, partials, G, stage, dV, dP);
+  if (B > 1) hipLaunchKernelGGL(lr_camera_total_kernel, dim3(1), dim3(64), 0, s, stage, B, dV, dP);
+}
+
 void lr_launch_project_bwd(const LrView& v, int N, const float* means, const float* scales, const float* rots,
                            const int* radii, const float* g_mean2d, const float* g_conic, const float* rows,
                            float* o_mean2d, float* o_opac, float* o_col, const float* pw,
                            float* g_means3d, float* g_scales, float* g_rots, bool accumulate, bool sink_rows,
-                           bool big_input, hipStream_t s, float* o_aux) {
+                           bool big_input, hipStream_t s, float* o_aux, float* cam_partials, float* cam_dv, float* cam_dp) {
   if (N <= 0) return;
   lr_prof_begin(LRK_PROJECT_BWD, s);
   const dim3 grid((N + LR_PBWD_ROWS - 1) / LR_PBWD_ROWS), block(256);
   const float4* rows4 = reinterpret_cast<const float4*>(rows);
+  if (cam_partials) {   // (the *_camera entry points checked: fresh gradients, no cov3d_precomp, whole image, no aux; cleared inside)
+#define LR_PBWD_CAM(T, O) hipLaunchKernelGGL((lr_project_bwd_kernel<false, T, false, O, false, 3, false, true>), grid, block, 0, s, \
+                                             v, N, means, scales, rots, radii, g_mean2d, g_conic, rows4, o_mean2d, o_opac,      \
+                                             o_col, pw, g_means3d, g_scales, g_rots, 1, nullptr, cam_partials)
+    if (rows) { if (pw) LR_PBWD_CAM(true, true); else LR_PBWD_CAM(false, true); }
+    else { if (pw) LR_PBWD_CAM(true, false); else LR_PBWD_CAM(false, false); }
+#undef LR_PBWD_CAM
+    lr_launch_camera_finish(cam_partials, N, cam_dv, cam_dp, s);
+    lr_prof_end(LRK_PROJECT_BWD, s);
+    return;
+  }
   if (o_aux) {   // (lograst_backward_aux checked: rows, fresh gradients, no cov3d_precomp; every output cleared inside)
     if (pw)
       hipLaunchKernelGGL((lr_project_bwd_kernel<false, true, false, true, false, 1, true>), grid, block, 0, s, v, N, means, scales,

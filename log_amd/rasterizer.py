@@ -509,6 +509,19 @@ class tile_rows:
         return False
 
 
+def _refuse_camera_with(sink=False, cov3D=False, band=False, aux=False):
+    """The one list of what camera gradients (dL/dviewmatrix, dL/dprojmatrix) cannot be combined with: each is a follow-up,
+    not a silent zero."""
+    if sink:
+        raise ValueError("camera gradients cannot be combined with accumulate_grads_into (they come with fresh gradients)")
+    if cov3D:
+        raise ValueError("camera gradients cannot be combined with cov3D_precomp (pass scales / rotations)")
+    if band:
+        raise ValueError("camera gradients cannot be combined with a tile_rows band (whole images only)")
+    if aux:
+        raise ValueError("camera gradients cannot be combined with aux_colors (no camera form of the aux backward)")
+
+
 class HipBackend:
     """Drives the kernels.  All buffers come from torch's caching allocator."""
 
@@ -752,16 +765,25 @@ class HipBackend:
             raise ValueError("backward_aux: both image gradients are None")
         return self.backward(rs, flavour, use_filter, means3D, scales, rotations, saved, grad_image, _aux=(grad_aux,))
 
+    def backward_camera(self, rs, flavour, use_filter, means3D, scales, rotations, saved, grad_image):
+        """backward() with the camera sums: -> its six fresh gradients, then dL/dviewmatrix and dL/dprojmatrix ([4, 4] fp32).
+        (The method autograd looks for: a backend without it has no camera gradients.)"""
+        return self.backward(rs, flavour, use_filter, means3D, scales, rotations, saved, grad_image, camera=True)
+
     def backward(self, rs, flavour, use_filter, means3D, scales, rotations, saved, grad_image, sink=None, cov3D=None,
-                 _aux=None):
+                 _aux=None, camera=False):
         """sink: optional dict of running-sum tensors (means3D, scales, rotations, opacities, colors) that this call
         adds into (LOGRAST_BWD_ACCUMULATE); the corresponding returned gradients are then None.
         cov3D (the forward's cov3D_precomp; no sink): the last two results are (dL/dcov3D [N, 6], None).
-        _aux: backward_aux's (dL/daux_image,) (the body is this one; fresh gradients only)."""
+        _aux: backward_aux's (dL/daux_image,) (the body is this one; fresh gradients only).
+        camera: two more results behind the six, dL/dviewmatrix and dL/dprojmatrix (fresh fp32 [4, 4] each, summed inside the
+        chain-rule launch: lograst_backward_camera).  Fresh gradients, scales / rotations, whole images, no aux channels."""
         device = means3D.device
         L = self.require(device)
         N = means3D.shape[0]
         aux = _aux is not None
+        if camera:
+            _refuse_camera_with(sink=sink is not None, cov3D=cov3D is not None, band=tuple(saved["tile_rows"]) != (0, 0), aux=aux)
         if aux and (sink is not None or cov3D is not None):
             raise ValueError("backward_aux writes fresh gradients: no gradient sink, no cov3D_precomp")
         if not aux and saved.get("aux_colors") is not None:
@@ -822,13 +844,18 @@ class HipBackend:
             del keep
             self.last_conic_grad = None
             return g_means3D, g_means2D, g_colors, g_opac, g_scales, g_rot, g["aux"]
+        args = (ctypes.byref(view), N, _ptr(means3D), _ptr(scales), _ptr(rotations), _ptr(saved["radii"]), _ptr(saved["geom"]),
+                _ptr(saved["state"]), _ptr(saved["plist"]), _ptr(saved["final_T"]), _ptr(saved["n_contrib"]), _ptr(grad_image),
+                _ptr(g_means2D), _ptr(g_conic), _ptr(g_opac), _ptr(g_colors), _ptr(g_means3D), _ptr(g_scales), _ptr(g_rot),
+                _ptr(pw), flags)
+        g_cam = ()
         with torch.cuda.device(device):
-            _lib.check(L.lograst_backward(ctypes.byref(view), N, _ptr(means3D), _ptr(scales), _ptr(rotations),
-                                          _ptr(saved["radii"]), _ptr(saved["geom"]), _ptr(saved["state"]),
-                                          _ptr(saved["plist"]), _ptr(saved["final_T"]), _ptr(saved["n_contrib"]),
-                                          _ptr(grad_image), _ptr(g_means2D), _ptr(g_conic), _ptr(g_opac),
-                                          _ptr(g_colors), _ptr(g_means3D), _ptr(g_scales), _ptr(g_rot), _ptr(pw),
-                                          flags, _stream_ptr(device)))
+            if camera:
+                g_cam, scratch = self._camera_outputs(L, N, device)
+                _lib.check(L.lograst_backward_camera(*args, _ptr(g_cam[0]), _ptr(g_cam[1]), _ptr(scratch), 4 * scratch.numel(),
+                                                     _stream_ptr(device)))
+            else:
+                _lib.check(L.lograst_backward(*args, _stream_ptr(device)))
         del keep
         # test introspection only: dL/dconic [N, 4] (A, B, C, 0) out of the accumulator rows
         self.last_conic_grad = (torch.cat([acc.view(N, need)[:, 2:5], acc.new_zeros(N, 1)], dim=1)
@@ -837,7 +864,14 @@ class HipBackend:
             return None, g_means2D, None, None, None, None
         if cov3D is not None:
             return g_means3D, g_means2D, g_colors, g_opac, g_cov, None
-        return g_means3D, g_means2D, g_colors, g_opac, g_scales, g_rot
+        return (g_means3D, g_means2D, g_colors, g_opac, g_scales, g_rot) + g_cam
+
+    @staticmethod
+    def _camera_outputs(L, N, device):
+        """((dL/dviewmatrix, dL/dprojmatrix), the chain rule's partials scratch) for a *_camera call."""
+        g = torch.empty(2, 4, 4, dtype=torch.float32, device=device)
+        scratch = torch.empty(int(L.lograst_camera_scratch_bytes(N)) // 4, dtype=torch.float32, device=device)
+        return (g[0], g[1]), scratch
 
     def sh_forward(self, means3D, campos, shs, degree):
         """Native `shs=` path (lograst_sh_forward): colours[N,3] and the clamp mask u8[N,3]."""
@@ -867,24 +901,32 @@ class HipBackend:
         return g_shs if into is None else None
 
     def project_backward(self, rs, flavour, use_filter, means3D, scales, rotations, radii, g_means2D, g_conic,
-                         cov3D=None):
+                         cov3D=None, camera=False):
         """Stage A6b alone (lograst_project_backward): used by the parity tests.  With cov3D: -> (dL/dmeans3D,
-        dL/dcov3D, None)."""
+        dL/dcov3D, None).  camera: (dL/dviewmatrix, dL/dprojmatrix) behind the three (lograst_project_backward_camera)."""
         device = means3D.device
         L = self.require(device)
         N = means3D.shape[0]
+        if camera:
+            _refuse_camera_with(cov3D=cov3D is not None, band=_tile_rows.get() != (0, 0))
         g_cov = torch.empty(N, 6, dtype=torch.float32, device=device) if cov3D is not None else None
         view, keep = self.make_view(rs, flavour, use_filter, device, cov3D=cov3D, g_cov3D=g_cov)
         f32 = dict(dtype=torch.float32, device=device)
         g_means3D, g_scales, g_rot = torch.empty(N, 3, **f32), torch.empty(N, 3, **f32), torch.empty(N, 4, **f32)
+        args = (ctypes.byref(view), N, _ptr(means3D), _ptr(scales), _ptr(rotations), _ptr(radii), _ptr(g_means2D), _ptr(g_conic),
+                _ptr(g_means3D), _ptr(g_scales), _ptr(g_rot))
+        g_cam = ()
         with torch.cuda.device(device):
-            _lib.check(L.lograst_project_backward(ctypes.byref(view), N, _ptr(means3D), _ptr(scales), _ptr(rotations),
-                                                  _ptr(radii), _ptr(g_means2D), _ptr(g_conic), _ptr(g_means3D),
-                                                  _ptr(g_scales), _ptr(g_rot), _stream_ptr(device)))
+            if camera:
+                g_cam, scratch = self._camera_outputs(L, N, device)
+                _lib.check(L.lograst_project_backward_camera(*args, _ptr(g_cam[0]), _ptr(g_cam[1]), _ptr(scratch),
+                                                             4 * scratch.numel(), _stream_ptr(device)))
+            else:
+                _lib.check(L.lograst_project_backward(*args, _stream_ptr(device)))
         del keep
         if cov3D is not None:
             return g_means3D, g_cov, None
-        return g_means3D, g_scales, g_rot
+        return (g_means3D, g_scales, g_rot) + g_cam
 
     def tile_rows(self, rs, flavour, use_filter, means3D, scales, rotations):
         """-> (y0, y1) int32[N]: the tile rows [y0, y1) each Gaussian's rect covers on the whole image (y0 = y1 = 0 when
@@ -1285,10 +1327,28 @@ def _leaf_grad_sink(leaves, device):
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, colors, shs, opacities, scales, rotations, rs, flavour, use_filter, cov3D=None,
-                reuse=None, aux_colors=None):
+                reuse=None, aux_colors=None, *camera):
         """reuse: the calling rasterizer object's _ReuseSlot while geometry reuse is on (set_geometry_reuse), else None.
         aux_colors: a second colour triple per Gaussian [N, 3], composited into one more output image (the last one) by the
-        same walk and differentiated by the same reverse walk (HipBackend.forward_aux / backward_aux)."""
+        same walk and differentiated by the same reverse walk (HipBackend.forward_aux / backward_aux).
+        camera: absent, or (rs.viewmatrix, rs.projmatrix) when one of them requires grad (GaussianRasterizer.forward passes
+        them then, so that autograd sees them as inputs): the backward returns dL/dviewmatrix / dL/dprojmatrix for those that do
+        (HipBackend.backward_camera).  The values the kernels read are rs's, as always."""
+        ctx.camera = len(camera) == 2
+        if ctx.camera:
+            _refuse_camera_with(sink=_grad_sink is not None, cov3D=cov3D is not None, band=_tile_rows.get() != (0, 0),
+                                aux=aux_colors is not None)
+            if not hasattr(_backend, "backward_camera"):
+                raise _lib.LograstError("this backend has no backward_camera: camera gradients (viewmatrix / projmatrix with "
+                                        "requires_grad) are not available")
+            if any(t.numel() != 16 for t in camera):
+                raise ValueError("viewmatrix/projmatrix must be 4x4 and bg must have 3 entries")
+            ctx.camera_like = tuple((t.shape, t.device) for t in camera)   # (a matrix kept on the host gets its gradient there)
+            if reuse is not None:   # never a recomposited forward, never remembered as one
+                reuse.forget()
+                reuse = None
+        elif camera:
+            raise TypeError("viewmatrix and projmatrix go together")
         m = means3D.detach().to(torch.float32).contiguous()
         ax = None
         if aux_colors is not None:
@@ -1330,6 +1390,7 @@ class _RasterizeGaussians(torch.autograd.Function):
                              "colors_precomp[N,3], opacities[N,1]")
         wants_grad = any(ctx.needs_input_grad[:7])   # all False under torch.no_grad()
         wants_grad = wants_grad or (cov is not None and ctx.needs_input_grad[10]) or (ax is not None and ctx.needs_input_grad[12])
+        wants_grad = wants_grad or (ctx.camera and any(ctx.needs_input_grad[13:15]))
         scratch_floats = _lib.BWD_ROW_FLOATS if wants_grad else 0
         first = None
         aux_image = None
@@ -1360,7 +1421,8 @@ class _RasterizeGaussians(torch.autograd.Function):
         # the backward trusts the forward's point_weight (which Gaussians it may skip, which dL/dconic rows are cleared):
         # an in-place change of that output between forward and backward is refused, like autograd does for saved tensors
         ctx.radii, ctx.pw, ctx.pw_version = radii, pw, pw._version if pw is not None else None
-        ctx.leaves = (means3D, colors, opacities, scales, rotations) if (sh is None and cov is None and ax is None) else None
+        ctx.leaves = ((means3D, colors, opacities, scales, rotations)
+                      if (sh is None and cov is None and ax is None and not ctx.camera) else None)
         ctx.sh = (sh, clamped)
         ctx.aux = ax is not None
         # the reverse walk reads aux_colors again (the RGB colours sit in the records, a copy): an in-place change of the
@@ -1381,7 +1443,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         grad_aux = unused[-1] if ctx.aux else None   # (the aux image is the last output)
         if grad_image is None and grad_aux is None:   # no gradient reached an image: nothing flows on, and no visibility is published
             _backward_view.cur = None
-            return (None,) * 13
+            return (None,) * (15 if ctx.camera else 13)
         # which view's backward is running: nodes further down the same graph (log_amd.get_all's fused step) take the
         # visibility of THIS render from here (the rasterizer's node runs before the nodes that produced its inputs)
         _publish_backward_view(ctx.radii, m)
@@ -1397,6 +1459,8 @@ class _RasterizeGaussians(torch.autograd.Function):
         # tensor per input (with native SH: the colour gradient into a scratch, from there into the running dL/dshs)
         n = m.shape[0]
         sink = _grad_sink if ctx.cov is None else None
+        if ctx.camera:
+            _refuse_camera_with(sink=sink is not None)
         if ctx.aux and sink is not None:
             raise ValueError("aux_colors cannot be combined with accumulate_grads_into (its backward returns fresh gradients)")
         if sink is None and ctx.leaves is not None and (   # (leaves: None under cov3D_precomp or native SH)
@@ -1421,7 +1485,13 @@ class _RasterizeGaussians(torch.autograd.Function):
         else:
             sink = None   # (a sink without an "shs" entry under native SH: the gradients go back to autograd)
         g_aux = None
-        if ctx.aux:   # both images through one reverse walk and one chain rule: means2D gets the one summed gradient
+        g_cam = ()
+        if ctx.camera:   # the chain-rule launch sums the camera terms too; one that does not require grad gets None
+            g_m3, g_m2, g_c, g_o, g_s, g_r, g_v, g_p = _backend.backward_camera(ctx.rs, ctx.flavour, ctx.use_filter, m, s, r,
+                                                                                ctx.saved, grad_image)
+            g_cam = tuple(g.reshape(shape).to(dev) if need else None
+                          for g, need, (shape, dev) in zip((g_v, g_p), ctx.needs_input_grad[13:15], ctx.camera_like))
+        elif ctx.aux:   # both images through one reverse walk and one chain rule: means2D gets the one summed gradient
             g_m3, g_m2, g_c, g_o, g_s, g_r, g_aux = _backend.backward_aux(ctx.rs, ctx.flavour, ctx.use_filter, m, s, r, ctx.saved,
                                                                           grad_image, grad_aux)
         else:
@@ -1438,7 +1508,7 @@ class _RasterizeGaussians(torch.autograd.Function):
             _backend.sh_backward(m, ctx.rs.campos, sh, int(ctx.rs.sh_degree), clamped, sink["colors"], sink["means3D"],
                                  into=sink["shs"])
         return (g_m3, g_m2.reshape(m2_shape), g_c, g_sh, g_o.reshape(o_shape) if g_o is not None else None, g_s, g_r,
-                None, None, None, g_cov, None, g_aux)
+                None, None, None, g_cov, None, g_aux) + g_cam
 
 
 class GaussianRasterizer(nn.Module):
@@ -1481,7 +1551,13 @@ class GaussianRasterizer(nn.Module):
         [N, 3].  The call then returns its usual tuple plus ``aux_image`` [3, H, W] as the last element: the image a second
         call with ``colors_precomp=aux_colors`` would return, bit for bit, from the same compositing walk; one autograd node
         whose backward takes either or both image gradients.  Not with cov3D_precomp, a ``tile_rows`` band or
-        ``accumulate_grads_into``."""
+        ``accumulate_grads_into``.
+
+        Camera gradients (extension): when ``raster_settings.viewmatrix`` or ``.projmatrix`` requires grad, the backward
+        fills its ``.grad`` (or hands the gradient on, if it is no leaf): a fresh fp32 [4, 4], zeros when nothing is visible.
+        Column 3 of dL/dviewmatrix and column 2 of dL/dprojmatrix are exactly zero.  Not with cov3D_precomp, a ``tile_rows``
+        band, ``accumulate_grads_into`` or ``aux_colors``.  ``raster_settings.campos`` gets no gradient (it matters only
+        under native ``shs=``)."""
         flavour = self.FLAVOUR
         use_filter = True
         if "use_filter" in kwargs:
@@ -1506,8 +1582,14 @@ class GaussianRasterizer(nn.Module):
         elif "_reuse_slot" in self.__dict__:
             del self.__dict__["_reuse_slot"]    # switched off: nothing stays pinned
         with walk_form(self.walk_form) if self.walk_form not in (None, "auto") else contextlib.nullcontext():
+            rs = self.raster_settings
+            camera = tuple(t for t in (rs.viewmatrix, rs.projmatrix) if torch.is_tensor(t) and t.requires_grad)
+            if camera and torch.is_grad_enabled():
+                camera = (rs.viewmatrix, rs.projmatrix)
+            else:
+                camera = ()
             ret = _RasterizeGaussians.apply(means3D, means2D, colors_precomp, shs, opacities, scales, rotations,
-                                            self.raster_settings, flavour, use_filter, cov3D_precomp, slot, aux_colors)
+                                            rs, flavour, use_filter, cov3D_precomp, slot, aux_colors, *camera)
         if flavour.extras:
             # how many Gaussians the ids of point_id_pixel index: lets log_amd.counter's stand-in for the
             # torch.unique call at LoG/render/renderer.py:156 recognise the map and take the histogram kernel
