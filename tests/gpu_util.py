@@ -22,8 +22,9 @@ def settings(cam, bg, dev, scale_modifier=1.0):
 
 
 def hip_forward(cam, sc, bg, flavour=R.WODILATE, use_filter=True, dev="cuda:0", scale_modifier=1.0, scratch_floats=0,
-                fwd_form=None, hit_masks=None):
+                fwd_form=None, hit_masks=None, cov3d=None):
     """Raw backend call (keeps the intermediates).  Returns dict of numpy arrays + the torch `saved`.
+    cov3d: [N, 6] covariances handed over as cov3D_precomp instead of the scene's scales / rotations.
     scratch_floats=16: have the forward prepare the backward's accumulator rows, as the autograd path does.
     fwd_form: "rows" / "quadrant" forces the compositing kernel's form (knob LOGRAST_FWD_ROWS) for this call; None = what
     the package would pick (the resolution's history).  out["fwd_form"] says which one ran.
@@ -33,14 +34,14 @@ def hip_forward(cam, sc, bg, flavour=R.WODILATE, use_filter=True, dev="cuda:0", 
     if hit_masks is not None:
         prev = R.set_hit_masks(bool(hit_masks))
         try:
-            return hip_forward(cam, sc, bg, flavour, use_filter, dev, scale_modifier, scratch_floats, fwd_form)
+            return hip_forward(cam, sc, bg, flavour, use_filter, dev, scale_modifier, scratch_floats, fwd_form, cov3d=cov3d)
         finally:
             R.set_hit_masks(prev)
     if fwd_form is not None:
         prev = tune.get_knob("LOGRAST_FWD_ROWS")
         tune.set_knob("LOGRAST_FWD_ROWS", {"rows": 1, "quadrant": 0}[fwd_form])
         try:
-            out = hip_forward(cam, sc, bg, flavour, use_filter, dev, scale_modifier, scratch_floats)
+            out = hip_forward(cam, sc, bg, flavour, use_filter, dev, scale_modifier, scratch_floats, cov3d=cov3d)
         finally:
             tune.set_knob("LOGRAST_FWD_ROWS", prev)
         assert out["fwd_form"] == fwd_form
@@ -49,10 +50,13 @@ def hip_forward(cam, sc, bg, flavour=R.WODILATE, use_filter=True, dev="cuda:0", 
     rs = settings(cam, bg, dev, scale_modifier)
     t = lambda a: torch.tensor(np.ascontiguousarray(a, np.float32), device=dev)
     m, s, r, o, c = t(sc["xyz"]), t(sc["scaling"]), t(sc["rotation"]), t(sc["opacity"]).reshape(-1), t(sc["colors"])
+    cov = None
+    if cov3d is not None:
+        s, r, cov = None, None, t(cov3d)
     prev_keep = R.keep_keys(True)
     try:
         image, radii, pid, pwp, pw, saved = R._backend.forward(rs, flavour, use_filter, m, s, r, o, c,
-                                                               scratch_floats=scratch_floats)
+                                                               scratch_floats=scratch_floats, cov3D=cov)
     finally:
         R.keep_keys(prev_keep)
     torch.cuda.synchronize()
@@ -133,6 +137,115 @@ def visits(hf):
     pos = np.arange(hf["I"]) - offs[tile]
     slot = (offs[tile] >> 6) + tile + (pos >> 6)
     return ((words[slot] >> (pos & 63).astype(np.uint64)[:, None]) & np.uint64(1)).astype(bool)
+
+
+# ---- the binning stage's own record of a forward (log_amd/csrc/project.hip, common.hpp) ---------------------------------
+# ONE mirror of the layouts, in 32-bit words unless it says bytes:
+#   tile_state  header (16 words: LR_HDR_*) | ranked[tiles * 16] | big[tiles * 16] | offsets[tpad] | cursor[tiles * 16] |
+#               order[tpad] | basetab[batches][tiles] | hugemask[batches][4] (padded to 16 words) | survcount[batches]
+#               (tpad = tiles + 1 rounded up to 16: lr_tpad)
+#   geom        records, 64 B each | fill records, 16 B each | band views: the Gaussian index of every fill-record slot, 4 B
+#               each | (rounded up to 64 B: lr_midrank_off_bytes) rank rows of 16 uint16, lr_mid_cap(B) = B / 4 per batch
+#   fill record x = depth bits; y = x0 | y0 << 13 | (w - 1) << 26 | (h - 1) << 28 | big << 30 | ranked-mid << 31, all ones =
+#               no rect; up to 4 tiles: z, w = four 16-bit ranks inside the (batch, tile) run, 0xffff = dropped by the support
+#               cull; big: z = x1 | y1 << 16, and with bit 31: w = the rect's rank row inside its batch
+HDR_SPARSE, HDR_BATCH, HDR_HUGE, HDR_SPAN = 3, 6, 7, 8            # LR_HDR_SPARSE / _BATCH / _HUGE / _SPAN
+CTR_STRIDE, HDR_WORDS, HUGE_WORDS, MID_ROW = 16, 16, 4, 16        # LR_CTR_STRIDE, LR_HDR_WORDS, LR_HUGE_WORDS, LR_MID_ROW
+
+
+def state_offsets(tiles, batches):
+    """Word offsets into tile_state (common.hpp: lr_*_off)."""
+    tpad = (tiles + 1 + 15) & ~15
+    o = dict(ranked=HDR_WORDS)
+    o["big"] = o["ranked"] + tiles * CTR_STRIDE
+    o["offsets"] = o["big"] + tiles * CTR_STRIDE
+    o["cursor"] = o["offsets"] + tpad
+    o["order"] = o["cursor"] + tiles * CTR_STRIDE
+    o["basetab"] = o["order"] + tpad
+    o["hugemask"] = o["basetab"] + batches * tiles
+    o["survcount"] = o["hugemask"] + ((HUGE_WORDS * batches + 15) & ~15)
+    return o
+
+
+def midrank_off_bytes(n):
+    """lr_midrank_off_bytes: where the rank rows start inside geom."""
+    return ((64 + 16 + 4) * n + 63) & ~63
+
+
+def binning_record(hf):
+    """What the projection left behind for the fill and for lr_count_huge_kernel, decoded from saved["geom"] / saved["state"]
+    of a batched forward -> dict:
+    batch, huge, sparse, span   the header words
+    fill        uint32 [N, 4]: the fill records (band form: by SLOT; `survivor` maps slots to Gaussians)
+    has_rect, big, ranked_mid, x0, y0, w, h   per fill record (w = h = 0 without a rect)
+    rows        uint16 [batches * (batch / 4), 16]: the rank rows
+    flagged     {(batch, chunk)}: the bits of hugemask
+    survcount   uint32 [workgroups] (band form: survivors per projection workgroup), survivor uint32 [N]."""
+    rs, flavour, use_filter, m, s, r, saved = hf["_torch"]
+    N = int(m.shape[0])
+    W, H = int(rs.image_width), int(rs.image_height)
+    tiles = ((W + 15) // 16) * ((H + 15) // 16)
+    st = saved["state"]
+    hdr = st[:HDR_WORDS].cpu().numpy().view(np.uint32)
+    B = int(hdr[HDR_BATCH])
+    assert B > 0, "unbatched projection: no fill records"
+    batches = (N + B - 1) // B
+    off = state_offsets(tiles, batches)
+    assert off["offsets"] == (R.tile_offsets_of(saved, W, H).data_ptr() - st.data_ptr()) // 4
+    geom = saved["geom"]                                            # float32 view of the byte buffer
+    fill = geom[16 * N:20 * N].cpu().numpy().view(np.uint32).reshape(N, 4)
+    survivor = geom[20 * N:21 * N].cpu().numpy().view(np.uint32)
+    cap = B // 4
+    r0 = midrank_off_bytes(N) // 4
+    rows = geom[r0:r0 + batches * cap * MID_ROW // 2].cpu().numpy().view(np.uint16).reshape(batches * cap, MID_ROW)
+    mask = st[off["hugemask"]:off["hugemask"] + HUGE_WORDS * batches].cpu().numpy().view(np.uint32).reshape(batches, HUGE_WORDS)
+    flagged = {(b, 32 * wd + bit) for b in range(batches) for wd in range(HUGE_WORDS) for bit in range(32)
+               if (int(mask[b, wd]) >> bit) & 1}
+    survcount = st[off["survcount"]:off["survcount"] + batches].cpu().numpy().view(np.uint32)
+    y, z = fill[:, 1], fill[:, 2]
+    has = y != 0xffffffff
+    if hdr[HDR_SPARSE]:                                             # band form: only the first survcount[w] slots of a span are written
+        slot = np.arange(N, dtype=np.int64)
+        span = int(hdr[HDR_SPAN])
+        has &= slot % span < survcount[np.minimum(slot // span, batches - 1)]
+    big = has & ((y >> 30) & 1).astype(bool)
+    x0, y0 = np.where(has, y & 0x1fff, 0).astype(np.int64), np.where(has, (y >> 13) & 0x1fff, 0).astype(np.int64)
+    w = np.where(big, (z & 0xffff).astype(np.int64) - x0, np.where(has, ((y >> 26) & 3).astype(np.int64) + 1, 0))
+    h = np.where(big, (z >> 16).astype(np.int64) - y0, np.where(has, ((y >> 28) & 3).astype(np.int64) + 1, 0))
+    return dict(N=N, tiles=tiles, gx=(W + 15) // 16, batch=B, batches=batches, huge=int(hdr[HDR_HUGE]), sparse=int(hdr[HDR_SPARSE]),
+                span=int(hdr[HDR_SPAN]), fill=fill, has_rect=has, big=big, ranked_mid=big & (y >> 31).astype(bool), x0=x0, y0=y0,
+                w=w, h=h, rows=rows, flagged=flagged, survcount=survcount, survivor=survivor)
+
+
+def ranked_instances(rec, owner=None):
+    """Every RANKED tile instance of the record -> (batch, tile, rank, gaussian) int64 arrays, ranks of 0xffff (dropped by
+    the support cull) included: the rects of up to four tiles (tile k of the rect: one row, one column or 2x2, as
+    lr_project_one orders them) and the ranked 5..16-tile rects (tile t = (y - y0) w + (x - x0) of the rank row fill.w).
+    owner: the Gaussian of every fill record (band form: rec["survivor"]); default: its own index."""
+    fill, gx, B = rec["fill"], rec["gx"], rec["batch"]
+    gid = np.arange(rec["N"], dtype=np.int64) if owner is None else np.asarray(owner, np.int64)
+    out = []
+    small = np.nonzero(rec["has_rect"] & ~rec["big"])[0]
+    for i in small:
+        w, h, x0, y0 = int(rec["w"][i]), int(rec["h"][i]), int(rec["x0"][i]), int(rec["y0"][i])
+        nt = w * h
+        halves = [int(fill[i, 2]) & 0xffff, int(fill[i, 2]) >> 16, int(fill[i, 3]) & 0xffff, int(fill[i, 3]) >> 16]
+        for k in range(4):
+            if k < nt:
+                ty = k if w == 1 else ((k >> 1) if (w == 2 and nt == 4) else 0)
+                tx = k - ty * w
+                out.append((gid[i] // B, (y0 + ty) * gx + x0 + tx, halves[k], gid[i]))
+            else:
+                assert halves[k] == 0, (i, k, halves)               # the unused ranks of a fill record are zero
+    cap = B // 4
+    for i in np.nonzero(rec["ranked_mid"])[0]:
+        w, h, x0, y0 = int(rec["w"][i]), int(rec["h"][i]), int(rec["x0"][i]), int(rec["y0"][i])
+        b = gid[i] // B
+        row = rec["rows"][b * cap + int(fill[i, 3])]
+        for t in range(w * h):
+            out.append((b, (y0 + t // w) * gx + x0 + t % w, int(row[t]), gid[i]))
+    a = np.array(out, np.int64).reshape(-1, 4)
+    return a[:, 0], a[:, 1], a[:, 2], a[:, 3]
 
 
 class Grads(dict):
