@@ -28,16 +28,18 @@ def _rot(q):
     return R.reshape(-1, 3, 3)
 
 
-def render(width, height, tanfovx, tanfovy, viewmatrix, projmatrix, bg, means3D, means2D, scales,
-           rotations, opacities, colors, scale_modifier=1.0, filter_mode=FILTER_CLAMP, ndc_cull=True, cov3D_precomp=None):
-    """Returns (image[3,H,W], radii[N] int, aux dict).  All tensor inputs float64 (cast inside).
-    cov3D_precomp ([N, 6]: xx, xy, xz, yy, yz, zz) replaces scales / rotations when given (both then unused)."""
+def project(width, height, tanfovx, tanfovy, viewmatrix, projmatrix, means3D, means2D, scales, rotations,
+            scale_modifier=1.0, filter_mode=FILTER_CLAMP, ndc_cull=True, cov3D_precomp=None, decisions=None):
+    """The projection of render() on its own: -> dict(ndc [N, 2], conic (A, B, C), cov (a, b, c), vis, radius, tz), float64,
+    differentiable in every tensor input.  render() is this followed by the binning and the compositing.
+    decisions: None = every branch is decided here, in float64 (what render() does).  Otherwise a dict of bool tensors
+    taken from another evaluation of the same inputs (the fp32 forward's): cx / cy = the row is in the x / y clamp branch of
+    the EWA Jacobian, lowa / lowc = the CLAMP low-pass clamps that diagonal, and limx / limy = the clamp limits that
+    evaluation used.  The values are then this function's, the branches the other evaluation's."""
     dt = torch.float64
     V = viewmatrix.to(dt)
     P = projmatrix.to(dt)
-    bg = bg.to(dt)
     p = means3D.to(dt)
-    N = p.shape[0]
     W, H = int(width), int(height)
     fx = W / (2.0 * tanfovx)
     fy = H / (2.0 * tanfovy)
@@ -61,8 +63,14 @@ def render(width, height, tanfovx, tanfovy, viewmatrix, projmatrix, bg, means3D,
         Sigma = M @ M.transpose(1, 2)
     limx, limy = 1.3 * tanfovx, 1.3 * tanfovy
     tzs = torch.where(vis, tz, torch.ones_like(tz))  # keep culled rows finite
-    ux = torch.clamp(t[:, 0] / tzs, -limx, limx)
-    uy = torch.clamp(t[:, 1] / tzs, -limy, limy)
+    if decisions is None:
+        ux = torch.clamp(t[:, 0] / tzs, -limx, limx)
+        uy = torch.clamp(t[:, 1] / tzs, -limy, limy)
+    else:
+        limx, limy = float(decisions.get("limx", limx)), float(decisions.get("limy", limy))
+        rx, ry = t[:, 0] / tzs, t[:, 1] / tzs
+        ux = torch.where(decisions["cx"], torch.sign(rx.detach()) * limx, rx)
+        uy = torch.where(decisions["cy"], torch.sign(ry.detach()) * limy, ry)
     txc, tyc = ux * tzs, uy * tzs
     zero = torch.zeros_like(tzs)
     J = torch.stack([fx / tzs, zero, -(fx * txc) / (tzs * tzs),
@@ -74,7 +82,11 @@ def render(width, height, tanfovx, tanfovy, viewmatrix, projmatrix, bg, means3D,
     if filter_mode == FILTER_DILATE:
         a, c = a + 0.3, c + 0.3
     elif filter_mode == FILTER_CLAMP:
-        a, c = torch.clamp_min(a, 0.3), torch.clamp_min(c, 0.3)
+        if decisions is None:
+            a, c = torch.clamp_min(a, 0.3), torch.clamp_min(c, 0.3)
+        else:
+            a = torch.where(decisions["lowa"], torch.full_like(a, 0.3), a)
+            c = torch.where(decisions["lowc"], torch.full_like(c, 0.3), c)
     det = a * c - b * b
     vis = vis & (det.detach() != 0)
     dets = torch.where(vis, det, torch.ones_like(det))
@@ -82,6 +94,20 @@ def render(width, height, tanfovx, tanfovy, viewmatrix, projmatrix, bg, means3D,
     mid = 0.5 * (a + c)
     lam = mid + torch.sqrt(torch.clamp_min(mid * mid - det, 0.1))
     radius = torch.ceil(3.0 * torch.sqrt(lam)).detach()
+    return dict(ndc=ndc, conic=(cA, cB, cC), cov=(a, b, c), vis=vis, radius=radius, tz=tz)
+
+
+def render(width, height, tanfovx, tanfovy, viewmatrix, projmatrix, bg, means3D, means2D, scales,
+           rotations, opacities, colors, scale_modifier=1.0, filter_mode=FILTER_CLAMP, ndc_cull=True, cov3D_precomp=None):
+    """Returns (image[3,H,W], radii[N] int, aux dict).  All tensor inputs float64 (cast inside).
+    cov3D_precomp ([N, 6]: xx, xy, xz, yy, yz, zz) replaces scales / rotations when given (both then unused)."""
+    dt = torch.float64
+    bg = bg.to(dt)
+    N = means3D.shape[0]
+    W, H = int(width), int(height)
+    pr = project(width, height, tanfovx, tanfovy, viewmatrix, projmatrix, means3D, means2D, scales, rotations,
+                 scale_modifier=scale_modifier, filter_mode=filter_mode, ndc_cull=ndc_cull, cov3D_precomp=cov3D_precomp)
+    ndc, (cA, cB, cC), vis, radius, tz = pr["ndc"], pr["conic"], pr["vis"], pr["radius"], pr["tz"]
     mx = ((ndc[:, 0] + 1.0) * W - 1.0) * 0.5
     my = ((ndc[:, 1] + 1.0) * H - 1.0) * 0.5
     gx, gy = (W + 15) // 16, (H + 15) // 16
