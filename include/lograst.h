@@ -489,6 +489,27 @@ int lograst_project_backward_camera(const lograst_view* view, int32_t n, const f
                                     float* dl_dviewmatrix, float* dl_dprojmatrix, void* camera_scratch,
                                     size_t camera_scratch_bytes, void* stream);
 
+/* Absolute screen-space gradients (the AbsGS densification statistic; gsplat: `absgrad`): lograst_backward once more, with
+ * one further output dl_dmeans2d_abs [n, 3] (fp32, overwritten):
+ *   dl_dmeans2d_abs[g, 0] = sum over pixels | dL/dG dG/ddx 0.5 W |,  [g, 1] = sum over pixels | dL/dG dG/ddy 0.5 H |,  [g, 2] = 0
+ * -- the absolute values of the very fp32 per-pixel terms whose signed sums are dl_dmeans2d[g, 0..1], taken per pixel and
+ * per component in front of any reduction; units and scaling are dl_dmeans2d's.  The signed terms are odd around the splat
+ * centre and cancel for a large splat inside the image; these do not.  A Gaussian that contributed to no pixel gets exact
+ * zeros.  The reverse walk sums them into slots 9 and 10 of the Gaussian's accumulator row (the row-split form: eleven lanes
+ * of the one atomic instruction of a row visit; the quadrant form: two more lanes of its second atomic instruction), the
+ * chain rule hands them out.  Every other output is what lograst_backward writes (sums up to the order of the float atomics).
+ * The walk form follows lograst_backward_form as lograst_backward's does; view->hit_masks are read in either form.
+ * Fresh gradients only, scales / rotations form, whole images: flags may hold LOGRAST_BWD_SCRATCH_ZEROED and
+ * LOGRAST_BWD_CONIC_TOUCHED_ONLY.  LOGRAST_ERR_ARG before any launch: a band view (tile_row_begin / tile_row_end);
+ * view->cov3d_precomp; LOGRAST_BWD_ACCUMULATE / LOGRAST_BWD_ACCUMULATE_ROWS; dl_dmeans2d_abs NULL.  There is no abs form of
+ * lograst_backward_aux or lograst_backward_camera.  (An addition within version 4: a new entry point only.) */
+int lograst_backward_abs(const lograst_view* view, int32_t n, const float* means3d, const float* scales,
+                         const float* rotations, const int32_t* radii, const void* geom, const void* tile_state,
+                         const uint32_t* point_list, const float* final_t, const int32_t* n_contrib,
+                         const float* dl_dimage, float* dl_dmeans2d, float* bwd_rows, float* dl_dopacities,
+                         float* dl_dcolors, float* dl_dmeans3d, float* dl_dscales, float* dl_drotations,
+                         const float* point_weight, int32_t flags, float* dl_dmeans2d_abs, void* stream);
+
 /* ---- "next" row N1: simple_knn._C.distCUDA2 ----------------------------------------------------------
  * Replaces distCUDA2 (third-party simple-knn, un-vendored; called at /root/reference/LoG/utils/file.py:88-91 and
  * LoG/model/base_gaussian.py:39-42): out[i] = mean squared distance from point i to its 3 nearest other

@@ -16,9 +16,16 @@ def install_compute_radius():
     return shim
 
 
+def uninstall_abs_grad():
+    """What install_all(abs_grad=True) switched on, off again: the rasterizer's switch and the counter's."""
+    from . import counter, rasterizer
+    rasterizer.set_abs_grad(False)
+    counter.set_abs_grad(False)
+
+
 def install_all(fused_step=False, fused_loss=False, reuse_geometry=False, fused_depth_loss=False, device_densify=False,
                 device_prepare=False, device_decide=False, device_view_correction=False, device_evaluate=False, device_init=False,
-                views_per_step=None, masked_loss=False, fused_depth_pass=False):
+                views_per_step=None, masked_loss=False, fused_depth_pass=False, abs_grad=False):
     """Everything a LoG process needs, in one call: the LoG.cuda.compute_radius module, then every
     drop-in method assigned onto LoG's own classes (needs LoG importable): LoG.get_all, TensorTree.traverse,
     Counter.update_by_output, SparseOptimizer.step.
@@ -67,11 +74,20 @@ def install_all(fused_step=False, fused_loss=False, reuse_geometry=False, fused_
     that a render_depth: True view composites [view z, world z, 1] in the walk of its colour call and its second rasterizer
     call launches nothing (log_amd.depth_pass.install: same depth / height / accmap bits, one reverse walk and one chain rule
     for both images; quadrant kernels only -- see INTEGRATION 3b for where that is slower); reuse_geometry then has nothing
-    left to reuse on such a view."""
+    left to reuse on such a view.
+    abs_grad (opt-in): every rasterizer backward also sums the ABSOLUTE per-pixel terms of dL/dmeans2D
+    (log_amd.rasterizer.set_abs_grad: ``means2D.absgrad``), and Counter.update_by_output accumulates their norm into grad_sum
+    where the signed gradient's went (log_amd.counter.set_abs_grad) -- the AbsGS statistic under LoG's split decision.
+    split_grad_thres was tuned for the signed statistic and the absolute one is larger: nothing is retuned here (INTEGRATION
+    3b).  A render_depth: True view then takes two real rasterizer calls (fused_depth_pass falls back, reason abs_grad).
+    ``uninstall_abs_grad()`` switches both off again."""
     install_compute_radius()
     from . import rasterizer
     rasterizer.set_geometry_reuse(bool(reuse_geometry))
     from . import counter, get_all, lod, sparse_optimizer
+    if abs_grad:
+        rasterizer.set_abs_grad(True)
+        counter.set_abs_grad(True)
     get_all.set_fused_step(bool(fused_step))
     installed = [m.install() for m in (get_all, lod, counter, sparse_optimizer)]
     if fused_loss:

@@ -165,6 +165,8 @@ _SIGNATURES = {
                                 + [c_void_p] * 3 + [c_size_t, c_void_p]),
     "lograst_project_backward_camera": (ctypes.c_int, [ctypes.POINTER(LograstView), c_int32] + [c_void_p] * 12
                                         + [c_size_t, c_void_p]),
+    # absolute screen-space gradients: the backward with dl_dmeans2d_abs in front of `stream`
+    "lograst_backward_abs": (ctypes.c_int, [ctypes.POINTER(LograstView), c_int32] + [c_void_p] * 18 + [c_int32, c_void_p, c_void_p]),
     "lograst_pose_apply": (ctypes.c_int, [c_int32, c_int32] + [c_void_p] * 7),
     "lograst_pose_backward": (ctypes.c_int, [c_int32, c_int32] + [c_void_p] * 8),
     "lograst_sh_forward": (ctypes.c_int, [c_int32, c_int32, c_int32] + [c_void_p] * 6),

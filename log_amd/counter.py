@@ -29,6 +29,48 @@ def unique_ids(point_id_pixel, num_gaussians):
         return _r._backend.id_histogram(point_id_pixel, int(num_gaussians))
 
 
+# ---- abs-grad (opt-in): grad_sum from the absolute screen-space sums ----------------------------------------------------
+# With the switch on, the view's ``viewspace_points[i].absgrad`` (log_amd.rasterizer.set_abs_grad: the sums over pixels of the
+# ABSOLUTE per-pixel terms of dL/dmeans2D, same [N, 3] layout) goes to the counter kernel where ``.grad`` goes today, so
+# ``grad_sum`` becomes the per-view sum of the norm of absolute gradients -- the AbsGS statistic -- with no kernel change.
+# ``split_grad_thres`` was tuned for the signed statistic and the absolute one is larger: no threshold is retuned here.
+_abs_grad = False
+_abs_grad_missing = 0
+
+
+def set_abs_grad(enabled):
+    """True: update_by_output reads ``viewspace_points[i].absgrad`` instead of ``.grad`` (a tensor without one -- rendered
+    with the rasterizer's switch off -- falls back to ``.grad``; counted, logged once).  -> the previous setting."""
+    global _abs_grad
+    prev, _abs_grad = _abs_grad, bool(enabled)
+    return prev
+
+
+def abs_grad_stats(reset=False):
+    """{'enabled': the switch, 'missing': views since the last reset whose tensor had no ``absgrad`` (``.grad`` was used)}."""
+    global _abs_grad_missing
+    out = dict(enabled=_abs_grad, missing=_abs_grad_missing)
+    if reset:
+        _abs_grad_missing = 0
+    return out
+
+
+def _view_grad(points):
+    """What the counter reads for one view: ``.grad``, or with abs-grad on ``.absgrad`` where the tensor has one."""
+    global _abs_grad_missing
+    if not _abs_grad:
+        return points.grad
+    g = getattr(points, "absgrad", None)
+    if g is not None:
+        return g
+    if _abs_grad_missing == 0:
+        logging.getLogger("log_amd").warning(
+            "log_amd.counter: abs-grad is on but a view's viewspace_points has no .absgrad (rendered with "
+            "log_amd.rasterizer.set_abs_grad off?): using .grad for it; logged once, counted in abs_grad_stats()")
+    _abs_grad_missing += 1
+    return points.grad
+
+
 def update_by_output(self, output, fix_parent=False):
     """Same signature and side effects as Counter.update_by_output: the eight counter buffers are updated in place
     and ``flag_vis`` / ``index_vis`` are stored in ``output['visibility_flag'][i]`` (counter.py:48-51)."""
@@ -40,7 +82,7 @@ def update_by_output(self, output, fix_parent=False):
             if "index_node" in vf:
                 visible_index = torch.cat([visible_index, vf["index_node"]])
             flag_vis = _r._backend.counter_update(
-                buffers, visible_index, output["viewspace_points"][i].grad, output["radii"][i],
+                buffers, visible_index, _view_grad(output["viewspace_points"][i]), output["radii"][i],
                 output["point_weight"][i].data, output["point_id"][i], output["point_count"][i])
             vf["flag_vis"] = flag_vis
             vf["index_vis"] = torch.where(flag_vis)[0]

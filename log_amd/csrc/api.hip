@@ -860,6 +860,8 @@ int lograst_read_state(const void* tile_state, uint32_t* num_instances_host, uin
 struct LrBackwardAux { int on; const float* aux_colors; const float* dl_daux_image; int32_t bwd_row_floats; float* dl_daux_colors; };
 // What the *_camera entry points have on top: dL/dviewmatrix and dL/dprojmatrix [4, 4] and the chain rule's partials scratch.
 struct LrBackwardCam { int on; float* dl_dview; float* dl_dproj; void* scratch; size_t scratch_bytes; };
+// What lograst_backward_abs has on top: dl_dmeans2d_abs [n, 3].
+struct LrBackwardAbs { int on; float* dl_dmeans2d_abs; };
 // Their own argument errors, before any launch; *done: n == 0, the two gradients are zeros and nothing else is to do.
 static int lr_check_camera(const LrView& v, int32_t n, int32_t flags, const LrBackwardCam& cam, hipStream_t s, bool* done) {
   *done = false;
@@ -881,14 +883,15 @@ static int lr_check_camera(const LrView& v, int32_t n, int32_t flags, const LrBa
   if (reinterpret_cast<uintptr_t>(cam.scratch) & 7u) return lr_fail(LOGRAST_ERR_ARG, "camera scratch must be 8-byte aligned");
   return LOGRAST_OK;
 }
-// The one backward body behind lograst_backward, lograst_backward_aux and lograst_backward_camera.
+// The one backward body behind lograst_backward, lograst_backward_aux, lograst_backward_camera and lograst_backward_abs.
 static int lr_backward(const lograst_view* view, int32_t n, const float* means3d, const float* scales,
                        const float* rotations, const int32_t* radii, const void* geom, const void* tile_state,
                        const uint32_t* point_list, const float* final_t, const int32_t* n_contrib,
                        const float* dl_dimage, float* dl_dmeans2d, float* bwd_rows, float* dl_dopacities,
                        float* dl_dcolors, float* dl_dmeans3d, float* dl_dscales, float* dl_drotations,
                        const float* point_weight, int32_t flags, void* stream, const LrBackwardAux& aux,
-                       const LrBackwardCam& cam = LrBackwardCam{0, nullptr, nullptr, nullptr, 0}) {
+                       const LrBackwardCam& cam = LrBackwardCam{0, nullptr, nullptr, nullptr, 0},
+                       const LrBackwardAbs& ab = LrBackwardAbs{0, nullptr}) {
   float* const dl_dconic = bwd_rows;   // (the fourth gradient argument: since version 3 the n x 16 accumulator rows)
   g_prof_call++;
   LrView v;
@@ -897,6 +900,14 @@ static int lr_backward(const lograst_view* view, int32_t n, const float* means3d
   if (cam.on) {
     bool done;
     if ((rc = lr_check_camera(v, n, flags, cam, (hipStream_t)stream, &done)) || done) return rc;
+  }
+  if (ab.on) {   // (the abs form's own argument errors: before anything else of the call, n == 0 included)
+    if (!ab.dl_dmeans2d_abs) return lr_fail(LOGRAST_ERR_ARG, "dl_dmeans2d_abs is NULL");
+    if (flags & (LOGRAST_BWD_ACCUMULATE | LOGRAST_BWD_ACCUMULATE_ROWS))
+      return lr_fail(LOGRAST_ERR_ARG, "lograst_backward_abs writes fresh gradients (no LOGRAST_BWD_ACCUMULATE / _ROWS form)");
+    if (v.cov3d) return lr_fail(LOGRAST_ERR_ARG, "lograst_backward_abs has no cov3d_precomp form");
+    if (v.ty0 != 0 || v.ty1 != v.gy)
+      return lr_fail(LOGRAST_ERR_ARG, "lograst_backward_abs: whole images only (tile_row_begin / tile_row_end)");
   }
   if (n < 0) return lr_fail(LOGRAST_ERR_ARG, "negative Gaussian count");
   if (n == 0) return LOGRAST_OK;
@@ -944,13 +955,14 @@ static int lr_backward(const lograst_view* view, int32_t n, const float* means3d
     LR_HIP(hipMemsetAsync(dl_dconic, 0, sizeof(float) * LOGRAST_BWD_ROW_FLOATS * (size_t)n, s));
   // capacity check is a forward concern: a list that rendered is by construction within capacity
   lr_launch_blend_bwd(v, geom, st, tiles, point_list, 0xffffffffu, final_t, n_contrib, dl_dimage, dl_dconic,
-                      big_input ? 1 : 0, v.masks, s, aux.on ? aux.aux_colors : nullptr, aux.on ? aux.dl_daux_image : nullptr);
+                      big_input ? 1 : 0, v.masks, s, aux.on ? aux.aux_colors : nullptr, aux.on ? aux.dl_daux_image : nullptr,
+                      ab.on != 0);
   // the chain rule reads every live Gaussian's accumulator row and hands out the separate outputs: dL/dmeans2D (written
   // for all rows), dL/dopacities and dL/dcolors (written, or added to the caller's running sums)
   lr_launch_project_bwd(v, n, means3d, scales, rotations, radii, nullptr, nullptr, dl_dconic, dl_dmeans2d, dl_dopacities,
                         dl_dcolors, point_weight, dl_dmeans3d, dl_dscales, dl_drotations, accumulate, sink_rows, big_input, s,
                         aux.on ? aux.dl_daux_colors : nullptr, cam.on ? static_cast<float*>(cam.scratch) : nullptr, cam.dl_dview,
-                        cam.dl_dproj);
+                        cam.dl_dproj, ab.on ? ab.dl_dmeans2d_abs : nullptr);
   LR_HIP(hipGetLastError());
   return LOGRAST_OK;
 }
@@ -989,6 +1001,18 @@ int lograst_backward_camera(const lograst_view* view, int32_t n, const float* me
                      LrBackwardCam{1, dl_dviewmatrix, dl_dprojmatrix, camera_scratch, camera_scratch_bytes});
 }
 size_t lograst_camera_scratch_bytes(int32_t n) { return lr_camera_scratch_bytes(n); }
+
+int lograst_backward_abs(const lograst_view* view, int32_t n, const float* means3d, const float* scales,
+                         const float* rotations, const int32_t* radii, const void* geom, const void* tile_state,
+                         const uint32_t* point_list, const float* final_t, const int32_t* n_contrib,
+                         const float* dl_dimage, float* dl_dmeans2d, float* bwd_rows, float* dl_dopacities,
+                         float* dl_dcolors, float* dl_dmeans3d, float* dl_dscales, float* dl_drotations,
+                         const float* point_weight, int32_t flags, float* dl_dmeans2d_abs, void* stream) {
+  return lr_backward(view, n, means3d, scales, rotations, radii, geom, tile_state, point_list, final_t, n_contrib, dl_dimage,
+                     dl_dmeans2d, bwd_rows, dl_dopacities, dl_dcolors, dl_dmeans3d, dl_dscales, dl_drotations, point_weight,
+                     flags, stream, LrBackwardAux{0, nullptr, nullptr, 0, nullptr}, LrBackwardCam{0, nullptr, nullptr, nullptr, 0},
+                     LrBackwardAbs{1, dl_dmeans2d_abs});
+}
 
 // The one body behind lograst_project_backward and lograst_project_backward_camera.
 static int lr_project_backward(const lograst_view* view, int32_t n, const float* means3d, const float* scales,

@@ -464,6 +464,17 @@ LR_DEV void lr_reduce16(const float v[16], float& r0, float& r1, float& r2, floa
   r3 = lr_row_sum(lr_swap_add16(p6, p7));
 }
 
+// ABS (lograst_backward_abs): eleven sums.  The rows of r2 are the sums of (v8, v10, v9, 0): a third quad-packed reduction
+// with one operand missing, where lr_reduce9's r2 held v8 in every row.
+LR_DEV void lr_reduce11(const float v[11], float& r0, float& r1, float& r2) {
+  const float p0 = lr_swap_add32(v[0], v[1]), p1 = lr_swap_add32(v[2], v[3]);
+  const float p2 = lr_swap_add32(v[4], v[5]), p3 = lr_swap_add32(v[6], v[7]);
+  const float p4 = lr_swap_add32(v[8], v[9]), p5 = lr_swap_add32(v[10], 0.f);
+  r0 = lr_row_sum(lr_swap_add16(p0, p1));
+  r1 = lr_row_sum(lr_swap_add16(p2, p3));
+  r2 = lr_row_sum(lr_swap_add16(p4, p5));
+}
+
 // AUX: the reverse walk of a forward that composited aux_colors into a second image (lr_blend_fwd_kernel<., true>).  The
 // colour behind the current entry is kept for both triples and dL/dalpha is evaluated once per image, each with the op
 // sequence of a walk over that image alone.  dL/dmean and dL/dopacity are committed as the sums over both images; dL/dconic
@@ -472,7 +483,12 @@ LR_DEV void lr_reduce16(const float v[16], float& r0, float& r1, float& r2, floa
 // rasterizer calls compute -- as either lies from the exact value (measured: profiles/aux_channels.md).  Fifteen sums leave
 // in four atomic instructions on the Gaussian's one 64-byte row; the third carries conic C (slot 4) and dL/daux_colors
 // (slots 9..11), the fourth the aux image's conic.  dL_dimage / dL_daux: NULL = zeros.
-template <bool MASKS, bool AUX = false>
+// ABS (lograst_backward_abs; not with AUX): two more sums per Gaussian, the ABSOLUTE values of the per-pixel terms of dL/dmean
+// x and y -- |s2[4]| and |s2[6]|, the fp32 numbers the signed sums add, taken per pixel in front of any reduction -- into
+// slots 9 and 10 of the accumulator row (free in a call with fresh gradients on a whole image; whole rows are cleared by the
+// forward's touched-row clear and by the zero-fills).  The AbsGS densification statistic: the signed terms are odd around
+// the splat centre and cancel for a large splat inside the image, these do not.
+template <bool MASKS, bool AUX = false, bool ABS = false>
 __global__ void __launch_bounds__(256)
 lr_blend_bwd_kernel(LrView v, const float4* __restrict__ geom, const uint32_t* __restrict__ state,
                     uint32_t tiles, const uint32_t* __restrict__ plist, uint32_t capacity,
@@ -480,6 +496,7 @@ lr_blend_bwd_kernel(LrView v, const float4* __restrict__ geom, const uint32_t* _
                     const float* __restrict__ dL_dimage, float* __restrict__ acc_rows,
                     int xcd_mode, const uint64_t* __restrict__ masks,
                     const float* __restrict__ aux_colors = nullptr, const float* __restrict__ dL_daux = nullptr) {
+  static_assert(!(AUX && ABS), "absolute sums: no aux form (slots 9..11 are the aux colour's there)");
   if (lr_bail(state, capacity)) return;
   const uint32_t tile = lr_tile_of_block(blockIdx.x, tiles, v.gx, v.gy, xcd_mode, state);
   if (tile >= tiles) return;
@@ -524,7 +541,10 @@ lr_blend_bwd_kernel(LrView v, const float4* __restrict__ geom, const uint32_t* _
   //   atomic #2, rows 0..3: mean x,y (slots 0-1), conic A,B (slots 2-3); lane 1 additionally carries conic C (slot 4)
   const int row = lane >> 4;
   float* const base0 = acc_rows + ((row < 3) ? 6 + row : 5);
-  float* const base1 = acc_rows + ((lane == 1) ? 4 : row);
+  //   ABS, atomic #2: lanes 1 / 17 / 33 carry conic C (slot 4), |mean x| (slot 9), |mean y| (slot 10) -- the rows of the third
+  //   reduction (lr_reduce11) in spare lanes of the same instruction on the same line.  A third instruction as the aux form
+  //   has (rows 0..2 -> slots 4, 9, 10) was built and timed too: no faster on C2 (profiles/abs_grad.md), one instruction more.
+  float* const base1 = acc_rows + (ABS ? ((lane & 15) == 1 ? (row == 0 ? 4 : 8 + row) : row) : ((lane == 1) ? 4 : row));
   //   AUX, atomic #3, rows 0..3: conic C (slot 4) and the aux colour r, g, b (slots 9..11); lane 1 then carries nothing in #2
   //   AUX, atomic #4, rows 0..2: the aux image's conic A, B, C (slots 12..14)
   float* const base2 = acc_rows + ((row == 0) ? 4 : 8 + row);
@@ -657,12 +677,15 @@ lr_blend_bwd_kernel(LrView v, const float4* __restrict__ geom, const uint32_t* _
       const lr_f2 dG_ddy = lr_fma2(-Cr, gdy, -(Br * gdx));     // -gdy*C - gdx*B
       // slot order chosen so that lr_reduce9's rows land on contiguous destinations:
       //   r0 rows = (s0,s2,s1,s3) = (col r, col g, col b, opacity); r1 rows = (s4,s6,s5,s7) = (mean x, mean y, conic A, conic B); r2 = conic C
-      constexpr int NS = AUX ? 16 : 9;
+      constexpr int NS = AUX ? 16 : (ABS ? 11 : 9);
       lr_f2 s2[NS];
       s2[0] = w * dp0; s2[2] = w * dp1; s2[1] = w * dp2; s2[3] = G * dL_dalpha;
       s2[4] = dL_dG * dG_ddx * sx; s2[6] = dL_dG * dG_ddy * sy;
       s2[5] = -0.5f * gdx * dx2 * dL_dG; s2[7] = -gdx * dy2 * dL_dG;
       s2[8] = -0.5f * gdy * dy2 * dL_dG;
+      if (ABS) {   // r2 rows = (s8, s10, s9, 0) = (conic C, |mean x|, |mean y|, -)
+        s2[10] = lr_f2{fabsf(s2[4].x), fabsf(s2[4].y)}; s2[9] = lr_f2{fabsf(s2[6].x), fabsf(s2[6].y)};
+      }
       if (AUX) {
         // r2 rows = (s8,s10,s9,s11) = (conic C, aux r, aux g, aux b); r3 rows = (s12,s14,s13,s15) = (aux conic A, B, C, -)
         const lr_f2 dL_dG_a = lr_f2{op0, op1} * dL_dalpha_a;
@@ -687,6 +710,11 @@ lr_blend_bwd_kernel(LrView v, const float4* __restrict__ geom, const uint32_t* _
           if (lead) atomicAdd(base1 + (size_t)gid * LOGRAST_BWD_ROW_FLOATS, r1);
           if (lead) atomicAdd(base2 + (size_t)gid * LOGRAST_BWD_ROW_FLOATS, r2);
           if (lead && row < 3) atomicAdd(base3 + (size_t)gid * LOGRAST_BWD_ROW_FLOATS, r3);
+        } else if (ABS) {
+          lr_reduce11(sv, r0, r1, r2);
+          if (lead) atomicAdd(base0 + (size_t)gid * LOGRAST_BWD_ROW_FLOATS, r0);
+          const bool second = (lane & 15) == 1 && row < 3;
+          if (lead || second) atomicAdd(base1 + (size_t)gid * LOGRAST_BWD_ROW_FLOATS, second ? r2 : r1);
         } else {
           lr_reduce9(sv, r0, r1, r2);
           if (lead) atomicAdd(base0 + (size_t)gid * LOGRAST_BWD_ROW_FLOATS, r0);
@@ -764,7 +792,9 @@ LR_DEV uint64_t lr_row_mask(int row, uint64_t m0, uint64_t m1, uint64_t m2, uint
   return row == 0 ? m0 : (row == 1 ? m1 : (row == 2 ? m2 : m3));
 }
 
-template <bool MASKS>
+// ABS (lograst_backward_abs): as in lr_blend_bwd_kernel -- |mxs| and |mys| per pixel, summed into slots 9 and 10.  A row
+// visit stays ONE atomic instruction on one line: eleven lanes of the row carry the entry's eleven sums.
+template <bool MASKS, bool ABS = false>
 __global__ void __launch_bounds__(256)
 lr_blend_bwd_rows_kernel(LrView v, const float4* __restrict__ geom, const uint32_t* __restrict__ state,
                          uint32_t tiles, const uint32_t* __restrict__ plist, uint32_t capacity,
@@ -823,8 +853,10 @@ lr_blend_bwd_rows_kernel(LrView v, const float4* __restrict__ geom, const uint32
   // A B C, 5 opacity, 6-8 colour r g b).
   const int qd = li >> 2, sel = li & 3;
   const int slot = sel == 0 ? (qd == 0 ? 6 : (qd == 1 ? 8 : (qd == 2 ? 7 : 5)))
-                            : (sel == 1 ? (qd == 0 ? 0 : (qd == 1 ? 2 : (qd == 2 ? 1 : 3))) : 4);
-  const bool on_a = sel < 2 || li == 2, on_b = sel < 2 || li == 10;
+                            : (sel == 1 ? (qd == 0 ? 0 : (qd == 1 ? 2 : (qd == 2 ? 1 : 3))) : ((ABS && qd != 0) ? 8 + qd : 4));
+  // ABS: S3 is quad-packed per entry -- quads (conic C, |mean x|, |mean y|, -) -- and lanes 2, 6, 10 take it to slots 4, 9, 10
+  const bool on_a = ABS ? (sel < 2 || (sel == 2 && qd < 3)) : (sel < 2 || li == 2);
+  const bool on_b = ABS ? on_a : (sel < 2 || li == 10);
   float* const dst = acc_rows + slot;
 
   // the four blocks of this quadrant (wave-uniform), for the support tests
@@ -1001,11 +1033,19 @@ lr_blend_bwd_rows_kernel(LrView v, const float4* __restrict__ geom, const uint32
       const float s1b = lr_quad_total(lr_row_pair4(lr_row_pair8(c0.y, c1.y), lr_row_pair8(c2.y, go.y)));
       const float s2a = lr_quad_total(lr_row_pair4(lr_row_pair8(mxs.x, mys.x), lr_row_pair8(kA.x, kB.x)));
       const float s2b = lr_quad_total(lr_row_pair4(lr_row_pair8(mxs.y, mys.y), lr_row_pair8(kA.y, kB.y)));
-      float s3 = lr_row_pair8(kC.x, kC.y);                      // lanes 0-7: entry 0's conic C, lanes 8-15: entry 1's
-      s3 = lr_quad_total(s3 + lr_dpp_perm<0x141>(s3));
-      // one instruction per entry: nine lanes of every row, one 64-byte line per row
+      float s3, s3b;
+      if (ABS) {   // the third packed reduction per entry: quads (conic C, |mean x|, |mean y|, 0)
+        const lr_f2 ax = {fabsf(mxs.x), fabsf(mxs.y)}, ay = {fabsf(mys.x), fabsf(mys.y)};
+        s3 = lr_quad_total(lr_row_pair4(lr_row_pair8(kC.x, ay.x), lr_row_pair8(ax.x, 0.f)));
+        s3b = lr_quad_total(lr_row_pair4(lr_row_pair8(kC.y, ay.y), lr_row_pair8(ax.y, 0.f)));
+      } else {
+        s3 = lr_row_pair8(kC.x, kC.y);                          // lanes 0-7: entry 0's conic C, lanes 8-15: entry 1's
+        s3 = lr_quad_total(s3 + lr_dpp_perm<0x141>(s3));
+        s3b = s3;
+      }
+      // one instruction per entry: nine lanes of every row (ABS: eleven), one 64-byte line per row
       const float xa = sel == 0 ? s1a : (sel == 1 ? s2a : s3);
-      const float xb = sel == 0 ? s1b : (sel == 1 ? s2b : s3);
+      const float xb = sel == 0 ? s1b : (sel == 1 ? s2b : s3b);
       if (on_a && gida != 0xffffffffu) lr_atomic_add_noret(dst + (size_t)gida * LOGRAST_BWD_ROW_FLOATS, xa);
       if (on_b && gidb != 0xffffffffu) lr_atomic_add_noret(dst + (size_t)gidb * LOGRAST_BWD_ROW_FLOATS, xb);
     }
@@ -1314,7 +1354,7 @@ void lr_launch_blend_fwd(const LrView& v, const void* geom, const uint32_t* stat
 void lr_launch_blend_bwd(const LrView& v, const void* geom, const uint32_t* state, uint32_t tiles,
                          const uint32_t* plist, uint32_t capacity, const float* final_T, const int* n_contrib,
                          const float* dL_dimage, float* acc_rows, int big_input, const uint64_t* masks, hipStream_t s,
-                         const float* aux_colors, const float* dL_daux) {
+                         const float* aux_colors, const float* dL_daux, bool abs_sums) {
   const int xcd_mode = lr_knob(LRKNOB_XCD_MODE);
   uint32_t grid = lr_blend_grid(tiles, v.gx, v.gy, xcd_mode);
   // LOGRAST_BWD_ROWS=1: the row-split form (the four 16-lane rows of a wave walk their own 4x4 blocks); 0: one
@@ -1333,6 +1373,18 @@ void lr_launch_blend_bwd(const LrView& v, const void* geom, const uint32_t* stat
   else if (aux_colors)
     hipLaunchKernelGGL((lr_blend_bwd_kernel<false, true>), dim3(grid), dim3(256), 0, s, v, g4, state, tiles, plist, capacity,
                        final_T, n_contrib, dL_dimage, acc_rows, xcd_mode, masks, aux_colors, dL_daux);
+  else if (abs_sums && rows && use_masks)   // (lograst_backward_abs: the same four choices, slots 9 and 10 summed too)
+    hipLaunchKernelGGL((lr_blend_bwd_rows_kernel<true, true>), dim3(grid), dim3(256), 0, s, v, g4, state, tiles, plist, capacity,
+                       final_T, n_contrib, dL_dimage, acc_rows, xcd_mode, block_test, masks);
+  else if (abs_sums && rows)
+    hipLaunchKernelGGL((lr_blend_bwd_rows_kernel<false, true>), dim3(grid), dim3(256), 0, s, v, g4, state, tiles, plist, capacity,
+                       final_T, n_contrib, dL_dimage, acc_rows, xcd_mode, block_test, masks);
+  else if (abs_sums && use_masks)
+    hipLaunchKernelGGL((lr_blend_bwd_kernel<true, false, true>), dim3(grid), dim3(256), 0, s, v, g4, state, tiles, plist, capacity,
+                       final_T, n_contrib, dL_dimage, acc_rows, xcd_mode, masks, nullptr, nullptr);
+  else if (abs_sums)
+    hipLaunchKernelGGL((lr_blend_bwd_kernel<false, false, true>), dim3(grid), dim3(256), 0, s, v, g4, state, tiles, plist, capacity,
+                       final_T, n_contrib, dL_dimage, acc_rows, xcd_mode, masks, nullptr, nullptr);
   else if (rows && use_masks)
     hipLaunchKernelGGL(lr_blend_bwd_rows_kernel<true>, dim3(grid), dim3(256), 0, s, v, g4, state, tiles, plist, capacity,
                        final_T, n_contrib, dL_dimage, acc_rows, xcd_mode, block_test, masks);

@@ -45,7 +45,8 @@ int lr_blend_bwd_form(const LrView& v, int big_input);
 void lr_launch_blend_bwd(const LrView& v, const void* geom, const uint32_t* state, uint32_t tiles,
                          const uint32_t* plist, uint32_t capacity, const float* final_T, const int* n_contrib,
                          const float* dL_dimage, float* acc_rows, int big_input, const uint64_t* masks, hipStream_t s,
-                         const float* aux_colors = nullptr, const float* dL_daux = nullptr);   // aux: quadrant form; either gradient may be NULL
+                         const float* aux_colors = nullptr, const float* dL_daux = nullptr,   // aux: quadrant form; either gradient may be NULL
+                         bool abs_sums = false);   // abs_sums (no aux): |per-pixel terms of dL/dmean x, y| summed into the rows' slots 9, 10
 
 // project_bwd.hip
 // rows != NULL: the 64-byte accumulator rows of lograst_backward (+ its three separate outputs); NULL: g_mean2d / g_conic.
@@ -55,7 +56,8 @@ void lr_launch_project_bwd(const LrView& v, int N, const float* means, const flo
                            float* o_mean2d, float* o_opac, float* o_col, const float* pw,
                            float* g_means3d, float* g_scales, float* g_rots, bool accumulate, bool sink_rows,
                            bool big_input, hipStream_t s, float* o_aux = nullptr,
-                           float* cam_partials = nullptr, float* cam_dv = nullptr, float* cam_dp = nullptr);   // o_aux: dL/daux_colors [N, 3] out of the rows' slots 9..11 (fresh gradients, no cov3d)
+                           float* cam_partials = nullptr, float* cam_dv = nullptr, float* cam_dp = nullptr,   // o_aux: dL/daux_colors [N, 3] out of the rows' slots 9..11 (fresh gradients, no cov3d)
+                           float* o_abs = nullptr);   // o_abs: dl_dmeans2d_abs [N, 3] out of the rows' slots 9, 10 (fresh gradients, no cov3d, no o_aux, no camera sums)
 
 // cam_partials (+ cam_dv, cam_dp [4, 4]): the camera sums -- one row of 24 partials per workgroup of the chain rule, then
 // dL/dviewmatrix / dL/dprojmatrix by a finishing kernel; lr_camera_scratch_bytes(N) bytes (fresh gradients, no cov3d, no o_aux)

@@ -230,7 +230,7 @@ LR_DEV void lr_project_bwd_row(const LrView& v, int i, const float* __restrict__
 
 // The chain rule of ONE live Gaussian i: reads its accumulator row (AOS) or its (dL/dmean2D, dL/dconic) pair, hands out
 // the per-view outputs and writes / adds the gradients (see lr_project_bwd_kernel for the template flags).
-template <bool ACCUMULATE, bool COV, bool AOS, bool SINKROWS, bool AUXO = false, bool CAM = false>
+template <bool ACCUMULATE, bool COV, bool AOS, bool SINKROWS, bool AUXO = false, bool CAM = false, bool ABSO = false>
 // (No __restrict__ here: the kernels' own parameters carry it.  Repeated on this inlined function it gave the scheduler
 // licence to hoist every load of the row above the chain rule -- 136 -> 170 VGPRs, three waves per SIMD -> two, the
 // 30 M-row launch 402 -> 477 us.)
@@ -238,7 +238,7 @@ LR_DEV void lr_pbwd_live_row(const LrView& v, int i, const float* means, const f
                              const float* g_mean2d, const float* g_conic, const float4* rows, float* o_mean2d,
                              float* o_opac, float* o_col, float* g_means3d, float* g_scales, float* g_rots,
                              float* m2d_slice = nullptr, int slice_base = 0, bool staged = false, float* o_aux = nullptr,
-                             float* cam = nullptr) {
+                             float* cam = nullptr, float* o_abs = nullptr) {
     float gm[3], gs[3] = {0.f, 0.f, 0.f}, gq[4] = {0.f, 0.f, 0.f, 0.f};
     float gnx, gny, gA, gB, gC;
     float gA2 = 0.f, gB2 = 0.f, gC2 = 0.f;   // (AUXO)
@@ -272,6 +272,10 @@ LR_DEV void lr_pbwd_live_row(const LrView& v, int i, const float* means, const f
         o_aux[3 * (size_t)i + 0] = ar[1]; o_aux[3 * (size_t)i + 1] = ar[2]; o_aux[3 * (size_t)i + 2] = ar[3];
         const float4 a3 = rows[4 * (size_t)i + 3];   // slots 12..14: the aux image's dL/dconic (below)
         gA2 = a3.x; gB2 = a3.y; gC2 = a3.z;
+      }
+      if (ABSO) {   // slots 9, 10: the absolute sums of a reverse walk with ABS (fresh gradients only); column 2 as dL/dmeans2D's
+        const float* const ar = reinterpret_cast<const float*>(rows + 4 * (size_t)i + 2);
+        o_abs[3 * (size_t)i + 0] = ar[1]; o_abs[3 * (size_t)i + 1] = ar[2]; o_abs[3 * (size_t)i + 2] = 0.f;
       }
       gnx = a0.x; gny = a0.y; gA = a0.z; gB = a0.w; gC = a1.x;
       if (staged) {   // the workgroup's slice of dL/dmeans2D sits in LDS and leaves as whole lines (lr_project_bwd_kernel)
@@ -362,6 +366,10 @@ LR_DEV void lr_pbwd_live_row(const LrView& v, int i, const float* means, const f
 // blockIdx.x of cam_out [workgroups, LR_CAM_SUMS]: a workgroup without a live row stores zeros, lanes without a row add
 // zeros.  No atomics: every workgroup adding into the same two lines is the worst shape for a float atomic, and the order of
 // the additions would change from run to run.  lr_camera_finish_kernel adds the rows up in workgroup order.
+// ABSO (lograst_backward_abs; AOS, fresh gradients, not COV, not AUXO, not CAM): the rows' slots 9 and 10 -- the reverse
+// walk's sums of |per-pixel term of dL/dmean x, y| -- leave as dl_dmeans2d_abs [N, 3] (column 2 = 0): a live row's values,
+// zeros for the others through the block-wide clear, exactly as dL/dcolour.  Plain 12-byte stores like dL/dmeans2D's in this
+// form: the staged slice (STAGE) exists for running sums only, which this output does not come with.
 // WAVES: waves per SIMD the register allocator aims for (1 = its own choice: ~130 VGPRs, three waves).  Measured, 30 M
 // Gaussians, running sums / fresh gradients: default 374 / 736 us, 4 waves (128 VGPRs, no scratch) 391 / 865, 5 (spills)
 // 473 / 877, 6: 518 / 918 -- more resident workgroups make the scattered rows' traffic worse, not better.  A band view
@@ -369,7 +377,7 @@ LR_DEV void lr_pbwd_live_row(const LrView& v, int i, const float* means, const f
 // sink's kernel exists in both forms and band views launch the second (unless they take the compact-list form below, the
 // default; the current compiler spills 10 VGPRs in it, 22 before the staged slice: profiles/chain_rule_dmeans2d_lines.md).
 template <bool ACCUMULATE, bool TOUCHED, bool COV, bool AOS, bool SINKROWS = false, int WAVES = 1, bool AUXO = false,
-          bool CAM = false>
+          bool CAM = false, bool ABSO = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES)))
 lr_project_bwd_kernel(LrView v, int N, const float* __restrict__ means, const float* __restrict__ scales,
                       const float* __restrict__ rots, const int* __restrict__ radii,
@@ -378,7 +386,8 @@ lr_project_bwd_kernel(LrView v, int N, const float* __restrict__ means, const fl
                       float* __restrict__ o_col,
                       const float* __restrict__ pw, float* __restrict__ g_means3d, float* __restrict__ g_scales,
                       float* __restrict__ g_rots, int clear_inside, float* __restrict__ o_aux = nullptr,
-                      float* __restrict__ cam_out = nullptr) {
+                      float* __restrict__ cam_out = nullptr, float* __restrict__ o_abs = nullptr) {
+  static_assert(!ABSO || (AOS && !ACCUMULATE && !COV && !SINKROWS && !AUXO && !CAM), "absolute sums: fresh gradients from the accumulator rows only, no aux, no camera sums");
   static_assert(!CAM || (!ACCUMULATE && !COV && !SINKROWS && !AUXO), "camera sums: fresh gradients, scales / rotations, no aux");
   static_assert(!AUXO || (AOS && !ACCUMULATE && !COV && !SINKROWS), "dL/daux_colors: fresh gradients from the accumulator rows only");
   __shared__ uint32_t live_list[LR_PBWD_ROWS];
@@ -442,6 +451,7 @@ lr_project_bwd_kernel(LrView v, int N, const float* __restrict__ means, const fl
         // pass below (three store instructions covering a third of every line each)
         clear(o_opac + (size_t)base, rows_here); clear(o_col + 3 * (size_t)base, 3 * rows_here);
         if (AUXO) clear(o_aux + 3 * (size_t)base, 3 * rows_here);
+        if (ABSO) clear(o_abs + 3 * (size_t)base, 3 * rows_here);
         clear(g_means3d + 3 * (size_t)base, 3 * rows_here);
         if (COV) {
           clear(v.g_cov3d + 6 * (size_t)base, 6 * rows_here);
@@ -505,9 +515,9 @@ lr_project_bwd_kernel(LrView v, int N, const float* __restrict__ means, const fl
     for (int c = 0; c < LR_CAM_SUMS; c++) cam[c] = 0.f;
   }
   for (uint32_t j = (uint32_t)tid; j < n; j += 256u)
-    lr_pbwd_live_row<ACCUMULATE, COV, AOS, SINKROWS, AUXO, CAM>(v, (int)live_list[j], means, scales, rots, g_mean2d, g_conic, rows,
-                                                                o_mean2d, o_opac, o_col, g_means3d, g_scales, g_rots,
-                                                                STAGE ? m2d_slice : nullptr, base, staged, o_aux, cam);
+    lr_pbwd_live_row<ACCUMULATE, COV, AOS, SINKROWS, AUXO, CAM, ABSO>(v, (int)live_list[j], means, scales, rots, g_mean2d, g_conic, rows,
+                                                                      o_mean2d, o_opac, o_col, g_means3d, g_scales, g_rots,
+                                                                      STAGE ? m2d_slice : nullptr, base, staged, o_aux, cam, o_abs);
   if (CAM && n == 0u) {   // (most workgroups of a large view: no live row, nothing to reduce)
     if (tid < LR_CAM_SUMS) cam_out[(size_t)blockIdx.x * LR_CAM_SUMS + tid] = 0.f;
   } else if (CAM) {
@@ -705,7 +715,8 @@ void lr_launch_project_bwd(const LrView& v, int N, const float* means, const flo
                            const int* radii, const float* g_mean2d, const float* g_conic, const float* rows,
                            float* o_mean2d, float* o_opac, float* o_col, const float* pw,
                            float* g_means3d, float* g_scales, float* g_rots, bool accumulate, bool sink_rows,
-                           bool big_input, hipStream_t s, float* o_aux, float* cam_partials, float* cam_dv, float* cam_dp) {
+                           bool big_input, hipStream_t s, float* o_aux, float* cam_partials, float* cam_dv, float* cam_dp,
+                           float* o_abs) {
   if (N <= 0) return;
   lr_prof_begin(LRK_PROJECT_BWD, s);
   const dim3 grid((N + LR_PBWD_ROWS - 1) / LR_PBWD_ROWS), block(256);
@@ -728,6 +739,18 @@ void lr_launch_project_bwd(const LrView& v, int N, const float* means, const flo
     else
       hipLaunchKernelGGL((lr_project_bwd_kernel<false, false, false, true, false, 1, true>), grid, block, 0, s, v, N, means, scales,
                          rots, radii, g_mean2d, g_conic, rows4, o_mean2d, o_opac, o_col, pw, g_means3d, g_scales, g_rots, 1, o_aux);
+    lr_prof_end(LRK_PROJECT_BWD, s);
+    return;
+  }
+  if (o_abs) {   // (lograst_backward_abs checked: rows, fresh gradients, no cov3d_precomp, whole image; every output cleared inside)
+    if (pw)
+      hipLaunchKernelGGL((lr_project_bwd_kernel<false, true, false, true, false, 1, false, false, true>), grid, block, 0, s, v, N,
+                         means, scales, rots, radii, g_mean2d, g_conic, rows4, o_mean2d, o_opac, o_col, pw, g_means3d, g_scales,
+                         g_rots, 1, nullptr, nullptr, o_abs);
+    else
+      hipLaunchKernelGGL((lr_project_bwd_kernel<false, false, false, true, false, 1, false, false, true>), grid, block, 0, s, v, N,
+                         means, scales, rots, radii, g_mean2d, g_conic, rows4, o_mean2d, o_opac, o_col, pw, g_means3d, g_scales,
+                         g_rots, 1, nullptr, nullptr, o_abs);
     lr_prof_end(LRK_PROJECT_BWD, s);
     return;
   }

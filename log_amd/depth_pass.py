@@ -97,6 +97,9 @@ class _RasterizerProxy:
             return "tile_rows band"
         if _r._grad_sink is not None:
             return "accumulate_grads_into"
+        abs_own = getattr(self._rast, "abs_grad", None)
+        if _r._abs_grad_on() if abs_own is None else abs_own:
+            return "abs_grad"     # (no abs form of the aux backward: both calls are real, their abs sums add on the shared means2D)
         wvt = self._camera.get("world_view_transform") if hasattr(self._camera, "get") else None
         if not torch.is_tensor(wvt) or wvt.device != m.device:
             return "the camera's world_view_transform is not on the tensors' device"

@@ -509,6 +509,49 @@ class tile_rows:
         return False
 
 
+# ---- abs-grad: the absolute screen-space sums of the reverse walk (opt-in; extension) ---------------------------------------
+# dL/dmeans2D is a signed sum over pixels whose terms are odd around the splat centre: for a large splat inside the image they
+# cancel, and LoG's split decision (Counter.get_gradmean against split_grad_thres) reads the norm of what is left.  With abs-grad
+# on, the backward of a call takes lograst_backward_abs and leaves ``means2D.absgrad`` [N, 3]: the sums of the ABSOLUTE per-pixel
+# terms (the AbsGS statistic; gsplat's ``absgrad``).  Off by default, everywhere.
+_abs_grad_default = False
+_abs_grad_local = threading.local()
+_ABS_GRAD = object()      # the marker GaussianRasterizer.forward appends to the autograd function's arguments when it is on
+
+
+def set_abs_grad(enabled):
+    """Process-wide switch (default False).  True: every rasterizer backward also sums the absolute values of the per-pixel
+    terms of dL/dmeans2D and leaves them as ``means2D.absgrad`` (fp32 [N, 3] on means2D's device; column 2 is 0): set by the
+    first backward through that ``means2D`` object, ADDED to by later ones -- as ``.grad`` accumulates.  All returned
+    gradients are the plain backward's.  Not with aux_colors, camera gradients, cov3D_precomp, a ``tile_rows`` band or
+    ``accumulate_grads_into`` (ValueError); the in-place leaf route (``set_inplace_leaf_grads``) is not taken for such a call.
+    -> the previous setting."""
+    global _abs_grad_default
+    prev, _abs_grad_default = _abs_grad_default, bool(enabled)
+    return prev
+
+
+def _abs_grad_on():
+    local = getattr(_abs_grad_local, "on", None)
+    return _abs_grad_default if local is None else local
+
+
+class abs_grad:
+    """``with abs_grad(True): ...`` switches abs-grad on (or off) for the rasterizer calls of this thread inside the block."""
+
+    def __init__(self, enabled=True):
+        self.on = bool(enabled)
+
+    def __enter__(self):
+        self.prev = getattr(_abs_grad_local, "on", None)
+        _abs_grad_local.on = self.on
+        return self
+
+    def __exit__(self, *exc):
+        _abs_grad_local.on = self.prev
+        return False
+
+
 def _refuse_camera_with(sink=False, cov3D=False, band=False, aux=False):
     """The one list of what camera gradients (dL/dviewmatrix, dL/dprojmatrix) cannot be combined with: each is a follow-up,
     not a silent zero."""
@@ -520,6 +563,20 @@ def _refuse_camera_with(sink=False, cov3D=False, band=False, aux=False):
         raise ValueError("camera gradients cannot be combined with a tile_rows band (whole images only)")
     if aux:
         raise ValueError("camera gradients cannot be combined with aux_colors (no camera form of the aux backward)")
+
+
+def _refuse_abs_grad_with(sink=False, cov3D=False, band=False, aux=False, camera=False):
+    """The one list of what abs-grad (the absolute screen-space sums, ``means2D.absgrad``) cannot be combined with."""
+    if aux:
+        raise ValueError("abs_grad cannot be combined with aux_colors (no abs form of the aux backward)")
+    if camera:
+        raise ValueError("abs_grad cannot be combined with camera gradients (a viewmatrix / projmatrix that requires grad)")
+    if cov3D:
+        raise ValueError("abs_grad cannot be combined with cov3D_precomp (pass scales / rotations)")
+    if band:
+        raise ValueError("abs_grad cannot be combined with a tile_rows band (whole images only)")
+    if sink:
+        raise ValueError("abs_grad cannot be combined with accumulate_grads_into (it comes with fresh gradients)")
 
 
 class HipBackend:
@@ -770,18 +827,28 @@ class HipBackend:
         (The method autograd looks for: a backend without it has no camera gradients.)"""
         return self.backward(rs, flavour, use_filter, means3D, scales, rotations, saved, grad_image, camera=True)
 
+    def backward_abs(self, rs, flavour, use_filter, means3D, scales, rotations, saved, grad_image):
+        """backward() with the absolute screen-space sums: -> its six fresh gradients, then absgrad [N, 3] fp32 (columns 0, 1:
+        the sums over pixels of |per-pixel term of dL/dmeans2D x, y|; column 2: 0) -- lograst_backward_abs.
+        (The method autograd looks for: a backend without it has no abs-grad.)"""
+        return self.backward(rs, flavour, use_filter, means3D, scales, rotations, saved, grad_image, _abs=True)
+
     def backward(self, rs, flavour, use_filter, means3D, scales, rotations, saved, grad_image, sink=None, cov3D=None,
-                 _aux=None, camera=False):
+                 _aux=None, camera=False, _abs=False):
         """sink: optional dict of running-sum tensors (means3D, scales, rotations, opacities, colors) that this call
         adds into (LOGRAST_BWD_ACCUMULATE); the corresponding returned gradients are then None.
         cov3D (the forward's cov3D_precomp; no sink): the last two results are (dL/dcov3D [N, 6], None).
         _aux: backward_aux's (dL/daux_image,) (the body is this one; fresh gradients only).
         camera: two more results behind the six, dL/dviewmatrix and dL/dprojmatrix (fresh fp32 [4, 4] each, summed inside the
-        chain-rule launch: lograst_backward_camera).  Fresh gradients, scales / rotations, whole images, no aux channels."""
+        chain-rule launch: lograst_backward_camera).  Fresh gradients, scales / rotations, whole images, no aux channels.
+        _abs: backward_abs's switch (one more result behind the six: absgrad [N, 3]); the same restrictions."""
         device = means3D.device
         L = self.require(device)
         N = means3D.shape[0]
         aux = _aux is not None
+        if _abs:
+            _refuse_abs_grad_with(sink=sink is not None, cov3D=cov3D is not None, band=tuple(saved["tile_rows"]) != (0, 0),
+                                  aux=aux or saved.get("aux_colors") is not None, camera=camera)
         if camera:
             _refuse_camera_with(sink=sink is not None, cov3D=cov3D is not None, band=tuple(saved["tile_rows"]) != (0, 0), aux=aux)
         if aux and (sink is not None or cov3D is not None):
@@ -850,7 +917,11 @@ class HipBackend:
                 _ptr(pw), flags)
         g_cam = ()
         with torch.cuda.device(device):
-            if camera:
+            if _abs:
+                abs_buf = torch.empty(max(N, 1), 3, **f32)         # (never a NULL pointer: the entry point refuses one)
+                g_cam = (abs_buf[:N],)
+                _lib.check(L.lograst_backward_abs(*args, ctypes.c_void_p(abs_buf.data_ptr()), _stream_ptr(device)))
+            elif camera:
                 g_cam, scratch = self._camera_outputs(L, N, device)
                 _lib.check(L.lograst_backward_camera(*args, _ptr(g_cam[0]), _ptr(g_cam[1]), _ptr(scratch), 4 * scratch.numel(),
                                                      _stream_ptr(device)))
@@ -1333,7 +1404,17 @@ class _RasterizeGaussians(torch.autograd.Function):
         same walk and differentiated by the same reverse walk (HipBackend.forward_aux / backward_aux).
         camera: absent, or (rs.viewmatrix, rs.projmatrix) when one of them requires grad (GaussianRasterizer.forward passes
         them then, so that autograd sees them as inputs): the backward returns dL/dviewmatrix / dL/dprojmatrix for those that do
-        (HipBackend.backward_camera).  The values the kernels read are rs's, as always."""
+        (HipBackend.backward_camera).  The values the kernels read are rs's, as always.
+        Behind them, only while abs-grad is on: the marker _ABS_GRAD -- the backward then takes HipBackend.backward_abs and
+        leaves / adds to ``means2D.absgrad``."""
+        ctx.abs_grad = bool(camera) and camera[-1] is _ABS_GRAD
+        if ctx.abs_grad:
+            camera = camera[:-1]
+            _refuse_abs_grad_with(sink=_grad_sink is not None, cov3D=cov3D is not None, band=_tile_rows.get() != (0, 0),
+                                  aux=aux_colors is not None, camera=bool(camera))
+            if not hasattr(_backend, "backward_abs"):
+                raise _lib.LograstError("this backend has no backward_abs: abs_grad is not available")
+            ctx.abs_target = means2D      # (the caller's object: the backward hangs .absgrad on it)
         ctx.camera = len(camera) == 2
         if ctx.camera:
             _refuse_camera_with(sink=_grad_sink is not None, cov3D=cov3D is not None, band=_tile_rows.get() != (0, 0),
@@ -1422,7 +1503,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         # an in-place change of that output between forward and backward is refused, like autograd does for saved tensors
         ctx.radii, ctx.pw, ctx.pw_version = radii, pw, pw._version if pw is not None else None
         ctx.leaves = ((means3D, colors, opacities, scales, rotations)
-                      if (sh is None and cov is None and ax is None and not ctx.camera) else None)
+                      if (sh is None and cov is None and ax is None and not ctx.camera and not ctx.abs_grad) else None)
         ctx.sh = (sh, clamped)
         ctx.aux = ax is not None
         # the reverse walk reads aux_colors again (the RGB colours sit in the records, a copy): an in-place change of the
@@ -1443,7 +1524,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         grad_aux = unused[-1] if ctx.aux else None   # (the aux image is the last output)
         if grad_image is None and grad_aux is None:   # no gradient reached an image: nothing flows on, and no visibility is published
             _backward_view.cur = None
-            return (None,) * (15 if ctx.camera else 13)
+            return (None,) * ((15 if ctx.camera else 13) + (1 if ctx.abs_grad else 0))
         # which view's backward is running: nodes further down the same graph (log_amd.get_all's fused step) take the
         # visibility of THIS render from here (the rasterizer's node runs before the nodes that produced its inputs)
         _publish_backward_view(ctx.radii, m)
@@ -1463,6 +1544,8 @@ class _RasterizeGaussians(torch.autograd.Function):
             _refuse_camera_with(sink=sink is not None)
         if ctx.aux and sink is not None:
             raise ValueError("aux_colors cannot be combined with accumulate_grads_into (its backward returns fresh gradients)")
+        if ctx.abs_grad:
+            _refuse_abs_grad_with(sink=sink is not None)
         if sink is None and ctx.leaves is not None and (   # (leaves: None under cov3D_precomp or native SH)
                 _inplace_leaf_grads or all(getattr(t, _INPLACE_TAG, False) for t in ctx.leaves if t is not None)):
             sink = _leaf_grad_sink(ctx.leaves, m.device)
@@ -1491,6 +1574,17 @@ class _RasterizeGaussians(torch.autograd.Function):
                                                                                 ctx.saved, grad_image)
             g_cam = tuple(g.reshape(shape).to(dev) if need else None
                           for g, need, (shape, dev) in zip((g_v, g_p), ctx.needs_input_grad[13:15], ctx.camera_like))
+        elif ctx.abs_grad:   # the plain backward's gradients, and the absolute sums onto the caller's means2D
+            g_m3, g_m2, g_c, g_o, g_s, g_r, g_abs = _backend.backward_abs(ctx.rs, ctx.flavour, ctx.use_filter, m, s, r, ctx.saved,
+                                                                          grad_image)
+            target, g_abs = ctx.abs_target, g_abs.reshape(m2_shape).to(ctx.abs_target.device)
+            with torch.no_grad():
+                old = getattr(target, "absgrad", None)
+                if old is None:
+                    target.absgrad = g_abs
+                else:
+                    old.add_(g_abs)
+            g_cam = (None,)               # (the marker's slot)
         elif ctx.aux:   # both images through one reverse walk and one chain rule: means2D gets the one summed gradient
             g_m3, g_m2, g_c, g_o, g_s, g_r, g_aux = _backend.backward_aux(ctx.rs, ctx.flavour, ctx.use_filter, m, s, r, ctx.saved,
                                                                           grad_image, grad_aux)
@@ -1514,12 +1608,15 @@ class _RasterizeGaussians(torch.autograd.Function):
 class GaussianRasterizer(nn.Module):
     FLAVOUR = WODILATE
 
-    def __init__(self, raster_settings, walk_form=None):
+    def __init__(self, raster_settings, walk_form=None, abs_grad=None):
         """walk_form (extension; the third-party packages take raster_settings only): pin the compositing kernels' form
-        for this object's calls -- 'rows' / 'quadrant' / None (decided per call); see ``log_amd.rasterizer.walk_form``."""
+        for this object's calls -- 'rows' / 'quadrant' / None (decided per call); see ``log_amd.rasterizer.walk_form``.
+        abs_grad (extension): True / False switches abs-grad on / off for this object's calls, None (default) leaves it to
+        ``set_abs_grad`` / ``with abs_grad(...)``; see ``log_amd.rasterizer.set_abs_grad``."""
         super().__init__()
         self.raster_settings = raster_settings
         self.walk_form = walk_form
+        self.abs_grad = None if abs_grad is None else bool(abs_grad)
         _form_code(walk_form)
 
     def markVisible(self, positions):
@@ -1588,6 +1685,8 @@ class GaussianRasterizer(nn.Module):
                 camera = (rs.viewmatrix, rs.projmatrix)
             else:
                 camera = ()
+            if (_abs_grad_on() if self.abs_grad is None else self.abs_grad) and torch.is_grad_enabled():
+                camera = camera + (_ABS_GRAD,)   # (off: the call below is the parent's, argument for argument)
             ret = _RasterizeGaussians.apply(means3D, means2D, colors_precomp, shs, opacities, scales, rotations,
                                             rs, flavour, use_filter, cov3D_precomp, slot, aux_colors, *camera)
         if flavour.extras:
