@@ -324,7 +324,8 @@ int lograst_stream_copy(void* dst, const void* src, size_t bytes, int32_t blocks
  * aligned.  lograst_pack_rows writes one SEGMENT per group, back to back, each lograst_sparse_segment_floats(kmax) floats:
  * header [16] (word 0: how many rows with a non-zero entry the group holds), values [kmax][16] (those rows, in no
  * particular order), index [roundup(kmax, 16)] (int32: the row's index inside its group).  Rows beyond kmax are dropped
- * and *overflow (a device word, OR-ed; may be NULL) is raised.  Equal-sized segments: an all-to-all / all-gather with
+ * and *overflow (a device word, OR-ed; may be NULL) is raised.  Value rows and index words j >= min(count, kmax) of a
+ * segment are unspecified: nothing reads them.  Equal-sized segments: an all-to-all / all-gather with
  * equal splits moves them.  lograst_unpack_rows: for every segment s and every row j < min(count_s, kmax):
  *   atomic != 0:  dest[index][0..15] += values            (all segments into the same rows_per_group rows.  Despite the
  *                 argument's name no float atomics are involved since round 5: the segments are added one after the
@@ -773,7 +774,8 @@ int lograst_densify_src_rows(int32_t p, int32_t children, int32_t remove_split, 
 
 /* lograst_densify_move_rows: dst[d] = src[src_row[d]] for up to 8 keys in one launch, 16-byte stores throughout and
  * 16-byte loads where the row size allows.  Rows d >= num_keep follow child_mode.  dst must be 16-byte aligned and src
- * aligned to elem_size; both contiguous. */
+ * aligned to elem_size; both contiguous.  Rows d >= num_keep of a LOGRAST_MOVE_SKIP key are not written here: they are
+ * unspecified until the kernel that owns the children has run. */
 #define LOGRAST_MOVE_COPY_PARENT 0
 #define LOGRAST_MOVE_ZERO 1
 #define LOGRAST_MOVE_SKIP 2      /* another kernel writes the children (lograst_densify_split_uniform) */

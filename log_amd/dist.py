@@ -112,7 +112,7 @@ def _reduce_scatter(out, inp, group=None):
 def _all_gather(out, inp, group=None):
     """out[world * numel] = the ranks' `inp` in rank order."""
     if dist.get_backend(group) == "gloo":
-        parts = [torch.empty_like(inp) for _ in range(dist.get_world_size(group))]
+        parts = [torch.empty(inp.shape, dtype=inp.dtype, device=inp.device) for _ in range(dist.get_world_size(group))]
         dist.all_gather(parts, inp.contiguous(), group=group)
         out.copy_(torch.cat(parts))
     else:
@@ -255,7 +255,7 @@ def _all_to_all(out, inp, group=None):
     inp = inp.contiguous()
     if dist.get_backend(group) == "gloo" and inp.is_cuda:
         world, rank = dist.get_world_size(group), dist.get_rank(group)
-        parts = [torch.empty_like(inp) for _ in range(world)]
+        parts = [torch.empty(inp.shape, dtype=inp.dtype, device=inp.device) for _ in range(world)]
         dist.all_gather(parts, inp, group=group)
         n = inp.numel() // world
         out.copy_(torch.cat([p[rank * n:(rank + 1) * n] for p in parts]))
@@ -562,7 +562,7 @@ class GradientBucket(_Flat):
             hint.record_stream(torch.cuda.current_stream(hint.device))      # (read here, possibly on a side stream)
         packed, self.sparse_overflow = _pack_segments(rows, kmax, clear=clear, hint=hint)
         self.sparse_kmax = kmax
-        recv = torch.empty_like(packed)
+        recv = torch.empty(packed.shape, dtype=packed.dtype, device=packed.device)
         _all_to_all(recv, packed, group)
         shard = into["rows"] if into is not None else torch.zeros(self.Pr, ROW_FLOATS, dtype=torch.float32, device=self.flat.device)
         out = {"rows": _unpack_segments(shard, recv, self.world, kmax)}
@@ -962,9 +962,9 @@ def gather_bands(image, rank, world, group=None):
     b, e = rows[rank]
     mine = torch.zeros(C, hmax, W, dtype=image.dtype, device=image.device)
     mine[:, :e - b] = image[:, b:e]
-    parts = [torch.empty_like(mine) for _ in range(world)]
+    parts = [torch.empty(mine.shape, dtype=mine.dtype, device=mine.device) for _ in range(world)]
     dist.all_gather(parts, mine, group=group)
-    out = torch.empty_like(image)
+    out = torch.empty(image.shape, dtype=image.dtype, device=image.device)
     for (rb, re), part in zip(rows, parts):
         out[:, rb:re] = part[:, :re - rb]
     return out
