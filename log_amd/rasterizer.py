@@ -909,7 +909,12 @@ class HipBackend:
                                                   _ptr(g_means3D), _ptr(g_scales), _ptr(g_rot), _ptr(pw), flags,
                                                   _stream_ptr(device)))
             del keep
+            # test introspection only: dL/dconic per image, [N, 4] (A, B, C, 0) each -- slots 2-4 and 12-14 of the rows
             self.last_conic_grad = None
+            self.last_aux_conic_grads = None
+            if _debug_keep and N:
+                rows = acc.view(N, need)
+                self.last_aux_conic_grads = tuple(torch.cat([rows[:, a:a + 3], acc.new_zeros(N, 1)], dim=1) for a in (2, 12))
             return g_means3D, g_means2D, g_colors, g_opac, g_scales, g_rot, g["aux"]
         args = (ctypes.byref(view), N, _ptr(means3D), _ptr(scales), _ptr(rotations), _ptr(saved["radii"]), _ptr(saved["geom"]),
                 _ptr(saved["state"]), _ptr(saved["plist"]), _ptr(saved["final_T"]), _ptr(saved["n_contrib"]), _ptr(grad_image),

@@ -196,8 +196,9 @@ def instance_support(view, fwd):
     return flags[:fwd["I"]]
 
 
-def backward(view, fwd, dL_dimage):
-    """Full backward for a forward() result.  Returns grads dict."""
+def backward(view, fwd, dL_dimage, abs_sums=False):
+    """Full backward for a forward() result.  Returns grads dict (abs_sums: + "absgrad" [N, 2], the absolute sums of
+    lograst_backward_abs from the same fp32 addends)."""
     means, scales, rots, opac, colors = fwd["inputs"]
     N = fwd["N"]
     dL = _f32(dL_dimage)
@@ -212,9 +213,15 @@ def backward(view, fwd, dL_dimage):
     L = lib()
     rec = np.ascontiguousarray(fwd["rec"]) if N else np.zeros((1, REC), np.float32)
     plist = fwd["point_list"] if fwd["I"] else np.zeros(1, np.uint32)
-    L.ora_blend_bwd(ctypes.byref(view), ctypes.c_int32(N), _p(rec), _p(fwd["tile_offsets"]), _p(plist),
-                    _p(fwd["final_T"]), _p(fwd["n_contrib"]), _p(dL), _p(g_mean2d), _p(g_conic), _p(g_opac),
-                    _p(g_col))
+    g_am = np.zeros((n, 2), np.float32) if abs_sums else None
+    if abs_sums:
+        L.ora_blend_bwd_abs(ctypes.byref(view), ctypes.c_int32(N), _p(rec), _p(fwd["tile_offsets"]), _p(plist),
+                            _p(fwd["final_T"]), _p(fwd["n_contrib"]), _p(dL), _p(g_mean2d), _p(g_conic), _p(g_opac),
+                            _p(g_col), _p(g_am))
+    else:
+        L.ora_blend_bwd(ctypes.byref(view), ctypes.c_int32(N), _p(rec), _p(fwd["tile_offsets"]), _p(plist),
+                        _p(fwd["final_T"]), _p(fwd["n_contrib"]), _p(dL), _p(g_mean2d), _p(g_conic), _p(g_opac),
+                        _p(g_col))
     cov3d = fwd.get("cov3d")
     g_cov = np.zeros((n, 6), np.float32) if cov3d is not None else None
     L.ora_project_bwd(ctypes.byref(view), ctypes.c_int32(N), _p(means), _p(scales), _p(rots),
@@ -224,14 +231,46 @@ def backward(view, fwd, dL_dimage):
                opacities=g_opac[:N].reshape(-1, 1), colors=g_col[:N], conic=g_conic[:N])
     if cov3d is not None:
         out["cov3D"] = g_cov[:N]
+    if abs_sums:
+        out["absgrad"] = g_am[:N]
     return out
 
 
-def backward_f64(view, fwd, dL_dimage, cond=True, pert=1e-7, trials=3):
+def set_threads(n):
+    """OpenMP threads of the oracle's calls from now on (0 / None: unchanged) -> the count before.  Two thread counts are two
+    orders of the reverse walk's commits."""
+    return int(lib().ora_set_threads(ctypes.c_int32(int(n or 0))))
+
+
+def backward_alt(view, fwd, dL_dimage, abs_sums=False):
+    """The reverse walk of backward() restated with the freedoms the HIP kernels take (C: ora_blend_bwd_alt): reciprocal and
+    multiply, fused multiply-adds, entries in pairs, the 4x4 block's tree, tiles in reverse.  Returns the walk's four keys
+    (+ "absgrad" [N, 2] with abs_sums).  Calibrates tests/gpu_util.py's WALK_ROW_FLOOR; nothing else."""
+    N = fwd["N"]
+    dL = _f32(dL_dimage)
+    n = max(N, 1)
+    g_mean2d, g_conic = np.zeros((n, 3), np.float32), np.zeros((n, 4), np.float32)
+    g_opac, g_col = np.zeros(n, np.float32), np.zeros((n, 3), np.float32)
+    g_am = np.zeros((n, 2), np.float32) if abs_sums else None
+    rec = np.ascontiguousarray(fwd["rec"]) if N else np.zeros((1, REC), np.float32)
+    plist = fwd["point_list"] if fwd["I"] else np.zeros(1, np.uint32)
+    lib().ora_blend_bwd_alt(ctypes.byref(view), ctypes.c_int32(N), _p(rec), _p(fwd["tile_offsets"]), _p(plist),
+                            _p(fwd["final_T"]), _p(fwd["n_contrib"]), _p(dL), _p(g_mean2d), _p(g_conic), _p(g_opac),
+                            _p(g_col), _p(g_am) if abs_sums else None)
+    out = dict(means2D=g_mean2d[:N], opacities=g_opac[:N].reshape(-1, 1), colors=g_col[:N], conic=g_conic[:N])
+    if abs_sums:
+        out["absgrad"] = g_am[:N]
+    return out
+
+
+def backward_f64(view, fwd, dL_dimage, cond=True, pert=1e-7, trials=3, abs_sums=False):
     """The float64 twin of backward() at full size (C: ora64_blend_bwd + ora64_project_bwd): every value in double, every
     decision the fp32 forward's.  Returns the same keys as backward() as float64 arrays, plus (cond=True) "cond":
     float64[N, 3] = how much the chain rule amplifies a relative perturbation of its inputs, for the means3D / scales /
-    rotations row of every Gaussian (see the C header).  Not available with cov3D_precomp."""
+    rotations row of every Gaussian (see the C header).  Not available with cov3D_precomp.
+    Always: "walk_unit" float64[N, 9] -- the error unit of each of the reverse walk's nine sums, in the slot order of the
+    kernels' accumulator row (0-1 mean, 2-4 conic, 5 opacity, 6-8 colour; C: ora64_blend_bwd_impl); abs_sums=True: [N, 11]
+    with the two absolute sums' units, and "absgrad" float64[N, 2], the sums themselves."""
     assert fwd.get("cov3d") is None, "the float64 twin covers the scales / rotations path"
     means, scales, rots, opac, colors = fwd["inputs"]
     N = fwd["N"]
@@ -245,14 +284,21 @@ def backward_f64(view, fwd, dL_dimage, cond=True, pert=1e-7, trials=3):
     L = lib()
     rec = np.ascontiguousarray(fwd["rec"]) if N else np.zeros((1, REC), np.float32)
     plist = fwd["point_list"] if fwd["I"] else np.zeros(1, np.uint32)
-    L.ora64_blend_bwd(ctypes.byref(view), ctypes.c_int32(N), _p(rec), _p(fwd["tile_offsets"]), _p(plist),
-                      _p(fwd["n_contrib"]), _p(dL), _p(g_mean2d), _p(g_conic), _p(g_opac), _p(g_col),
-                      _p(g_abs) if cond else None)
+    cols = 11 if abs_sums else 9
+    unit = z(n, cols)
+    g_am = z(n, 2) if abs_sums else None
+    rc = L.ora64_blend_bwd_unit(ctypes.byref(view), ctypes.c_int32(N), _p(rec), _p(fwd["tile_offsets"]), _p(plist),
+                                _p(fwd["n_contrib"]), _p(dL), _p(g_mean2d), _p(g_conic), _p(g_opac), _p(g_col),
+                                _p(g_abs) if cond else None, _p(unit), ctypes.c_int32(cols),
+                                _p(g_am) if abs_sums else None)
+    assert rc == 0
     L.ora64_project_bwd(ctypes.byref(view), ctypes.c_int32(N), _p(means), _p(scales), _p(rots), _p(fwd["radii"]),
                         _p(g_mean2d), _p(g_conic), _p(g_abs) if cond else None, _p(g_means), _p(g_scales), _p(g_rots),
                         _p(cnd) if cond else None, ctypes.c_double(pert), ctypes.c_int32(trials))
     out = dict(means3D=g_means[:N], means2D=g_mean2d[:N], scales=g_scales[:N], rotations=g_rots[:N],
-               opacities=g_opac[:N].reshape(-1, 1), colors=g_col[:N], conic=g_conic[:N])
+               opacities=g_opac[:N].reshape(-1, 1), colors=g_col[:N], conic=g_conic[:N], walk_unit=unit[:N])
+    if abs_sums:
+        out["absgrad"] = g_am[:N]
     if cond:
         out["cond"] = cnd[:N]
         # the fp32 chain rule (ora_project_bwd: the op sequence the HIP kernel shares) on the float64 sums rounded to fp32:

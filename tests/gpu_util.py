@@ -388,7 +388,8 @@ def compare_forward(hf, of):
 
 
 # ---- end-to-end gradients anchored on the float64 twin (oracle.backward_f64) -----------------------------------------
-# BASELINE.json: "gradients within 1e-4 relative L2".  The reverse walk's outputs meet that on every row.  Behind the
+# BASELINE.json: "gradients within 1e-4 relative L2".  The reverse walk's outputs meet that over the whole array (asserted
+# below as an aggregate), and are held row by row, slot by slot, by the rule of walk_row_stats further down.  Behind the
 # per-Gaussian chain rule a degenerate Gaussian (pancake: one scale far below the others; needle: two) loses digits in
 # ANY fp32 evaluation.  The float64 twin quantifies that per row, as a relative scale
 #     s_i = 6e-8 * cond_i  +  |chain32_i - f64_i| / |f64_i|
@@ -420,9 +421,85 @@ def row_units(g64, k, j):
     return unit, (y > 0) & (unit <= COND_BOUND * EPS32 * y)
 
 
+# ---- the reverse walk's sums, row by row (oracle.backward_f64: "walk_unit") ---------------------------------------------
+# An aggregate relative L2 weights every row by the size of its gradient: a lost commit deep in a list, where T is small, a
+# wrong lane-to-slot route, a relative error of 1e-3 on a few rows do not move it.  So for EVERY Gaussian i and EVERY slot k of
+# the kernels' accumulator row (0-1 mean x y, 2-4 conic A B C, 5 opacity, 6-8 colour r g b, 9-10 the absolute sums):
+#     |hip - f64|  <=  2 |oracle - f64|  +  WALK_ROW_FLOOR * 6e-8 * walk_unit[i, k]
+# walk_unit: the float64 twin's sum of the magnitudes of the addends' own terms, each weighted by the forward error factor of
+# its pixel (oracle/lograst_oracle.c: ora64_blend_bwd_impl).  Where walk_unit is 0 nothing contributed and the device value
+# is exactly 0; no device value is NaN or infinite.
+# WALK_ROW_FLOOR is MEASURED on the CPU references alone, never on a device result: the largest
+#     (|alt - f64| - 2 |oracle - f64|) / (6e-8 walk_unit)
+# of oracle.backward_alt (the fp32 walk with the kernels' freedoms: reciprocal, fma, pairs, block tree, reverse tiles) against
+# oracle.backward, each run with 1 and with 16 OpenMP threads, over every scene of tests/walk_rows_scenes.py -- 5.37, on
+# tie33-8193 (profiles/walk_rows_tests.md; tests/test_walk_rows_cpu.py measures it again on every run) -- times 4 = 21.5 (the device's commit order is not reproducible and its two
+# forms' trees differ), rounded up to a power of two: 32.  Capped by the chain rule's ROW_FLOOR (64).
+WALK_ROW_FLOOR = 32.0
+WALK_FLOOR_MEASURED = 5.37
+WALK_SLOTS = (("means2D", 0), ("means2D", 1), ("conic", 0), ("conic", 1), ("conic", 2), ("opacities", 0), ("colors", 0),
+              ("colors", 1), ("colors", 2), ("absgrad", 0), ("absgrad", 1))
+WALK_SLOT_NAMES = ("mean x", "mean y", "conic A", "conic B", "conic C", "opacity", "colour r", "colour g", "colour b",
+                   "|mean x|", "|mean y|")
+
+
+def walk_matrix(g, cols=9):
+    """[N, cols] float64: the walk's sums of a gradient dict in slot order."""
+    n = len(g["colors"])
+    return np.stack([np.asarray(g[k], np.float64).reshape(n, -1)[:, j] for k, j in WALK_SLOTS[:cols]], 1) if n \
+        else np.zeros((0, cols))
+
+
+def walk_row_stats(hg, og, g64, floor=None):
+    """The rule above for every (row, slot) -> statistics.  Slots 9-10 take part when all three carry "absgrad" (and the
+    twin's unit has their columns)."""
+    floor = WALK_ROW_FLOOR if floor is None else floor
+    unit = np.asarray(g64["walk_unit"], np.float64)
+    cols = 11 if (unit.shape[1] >= 11 and all("absgrad" in g for g in (hg, og, g64))) else 9
+    unit = unit[:, :cols]
+    h, o, r = walk_matrix(hg, cols), walk_matrix(og, cols), walk_matrix(g64, cols)
+    finite = np.isfinite(h)
+    eh = np.where(finite, np.abs(np.where(finite, h, 0.0) - r), np.inf)
+    eo = np.abs(o - r)
+    u = EPS32 * unit
+    live = unit > 0
+    su = np.where(live, u, 1.0)
+    excess = np.where(live, (eh - 2.0 * eo) / su, 0.0)
+    bound = 2.0 * eo + floor * u
+    bad = live & ~(eh <= bound)
+    held = live & (bound <= 1e-3 * np.abs(r))
+    q = lambda a: [float(x) for x in np.quantile(a[live], [0.5, 0.99, 1.0])] if live.any() else [0.0, 0.0, 0.0]
+    st = dict(rows=int(len(unit)), slots=cols, live=int(live.sum()), floor=float(floor), violations=int(bad.sum()),
+              nonfinite=int((~finite).sum()), zero_unit_nonzero=int((~live & (h != 0)).sum()),
+              hip_err_units_q50_q99_max=q(np.where(live, eh / su, 0.0)), oracle_err_units_q50_q99_max=q(np.where(live, eo / su, 0.0)),
+              worst_excess_units=float(excess.max()) if live.any() else 0.0,
+              held_3_digits=float(held.sum() / max(int(live.sum()), 1)),
+              violations_by_slot={WALK_SLOT_NAMES[k]: int(bad[:, k].sum()) for k in range(cols) if bad[:, k].any()})
+    if live.any():
+        i, k = np.unravel_index(int(np.argmax(excess)), excess.shape)
+        st["worst"] = dict(row=int(i), slot=int(k), name=WALK_SLOT_NAMES[k], hip=float(h[i, k]), oracle=float(o[i, k]),
+                           f64=float(r[i, k]), unit=float(unit[i, k]))
+    return st
+
+
+def assert_walk_rows(st, name=None):
+    """The row-by-row rule on the statistics of walk_row_stats; `name`: also dump them as <name>.walk_rows.json where
+    assert_gradients_anchored dumps its own (the one place that knows the directory)."""
+    if name:
+        assert_gradients_anchored(st, name=name + ".walk_rows", dump_only=True)
+    print("WALKROWS " + (name or "") + " live %d  hip q50/q99/max %s  oracle %s  worst excess %.2f units  held to 3 digits %.3f"
+          % (st["live"], ["%.2f" % x for x in st["hip_err_units_q50_q99_max"]],
+             ["%.2f" % x for x in st["oracle_err_units_q50_q99_max"]], st["worst_excess_units"], st["held_3_digits"]))
+    assert st["nonfinite"] == 0, st
+    assert st["zero_unit_nonzero"] == 0, st
+    assert st["violations"] == 0, st
+
+
 def gradient_anchor_stats(hg, og, g64):
     st = {}
     f64 = np.float64
+    if "walk_unit" in g64:   # (a twin put together by hand -- tools/fuzz_parity.py's cov3D one -- has no units of the walk)
+        st["walk_rows"] = walk_row_stats(hg, og, g64)
     for k in ("means2D", "conic", "opacities", "colors"):
         ref = g64[k].reshape(len(g64[k]), -1)
         nr = max(float(np.linalg.norm(ref)), 1e-300)
@@ -460,7 +537,7 @@ def gradient_anchor_stats(hg, og, g64):
     return st
 
 
-def assert_gradients_anchored(st, tol=1e-4, max_excluded=0.06, name=None, all_rows_tol=None):
+def assert_gradients_anchored(st, tol=1e-4, max_excluded=0.06, name=None, all_rows_tol=None, dump_only=False):
     """The four claims above; `name`: also dump the statistics to gpurun_out/parity_stats/<name>.json (best effort).
     all_rows_tol: additionally the PLAIN criterion of BASELINE.json's north_star -- relative L2 over ALL rows, no row
     excluded, no conditioning -- for dL/dmeans3D, dL/dscales, dL/drotations end to end: HIP against the float64 twin AND
@@ -477,6 +554,9 @@ def assert_gradients_anchored(st, tol=1e-4, max_excluded=0.06, name=None, all_ro
                 json.dump(st, f, indent=1)
         except OSError:
             pass
+    if dump_only:            # (assert_walk_rows: the dump alone, under its own name)
+        return
+    assert_walk_rows(st["walk_rows"], name=name)   # (oracle.backward_f64 always brings the units: no twin without them here)
     # the reverse walk's outputs against the float64 twin: within the tolerance, or -- where the fp32 forward's own
     # evaluation error (alpha of a sharp splat; 1 / (1 - alpha) of a near-opaque one) already separates ANY fp32 reverse walk
     # from the float64 one by more than that (one C2 view with random opacities: 1.7e-4 for HIP and oracle alike) -- no

@@ -54,6 +54,7 @@ def _two_sided(n, rng):
 def depths(L, pattern, rng):
     """-> float32[L].
     spread   2 + 1e-4 * permutation: all distinct.
+    offc     the depths of `spread`; the scene differs (one_tile: every centre (+0.3, -0.2) px off a pixel).
     flat     one depth: the order is the id order.
     tie<k>   one isolated group of exactly k equal depths (2.5) in the gap of an evenly spread rest: the group has a bucket of
              any linear map to itself.  32 / 33: a bucket holds LR_BUCKET_MAX keys and not one more.  8 / 9 (streamed lists,
@@ -65,7 +66,7 @@ def depths(L, pattern, rng):
              clusters begin a quarter of a cell behind a cell's edge: no cell holds a sliver of a group -- a few dozen keys
              for which the sample earns the cell a handful of buckets, all in one of them -- whatever the sample.
     strays   99.5 % in [2, 2.001], the rest uniform in [1, 4] (a surface seen head-on plus strays)."""
-    if pattern == "spread":
+    if pattern in ("spread", "offc"):
         z = 2.0 + 1e-4 * rng.permutation(L)
     elif pattern == "flat":
         z = np.full(L, 2.5)
@@ -119,15 +120,31 @@ def _cat(parts):
     return {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
 
 
-def _tile_list(tile, z32, opacity, rng):
+OFF_CENTRE = (0.3, -0.2)                      # `offc`: where every centre lies relative to its pixel ...
+OFF_JITTER = 0.05                             # ... give or take this much: no two splats have the same alpha at a pixel
+
+
+def _tile_list(tile, z32, opacity, rng, off_centre=None):
     """len(z32) splats inside `tile`; the one that sorts LAST (largest depth, then largest id) sits exactly on the tile's
-    pixel (8, 8), so that pixel's walk reaches the end of the list if it never stops."""
+    pixel (8, 8), so that pixel's walk reaches the end of the list if it never stops.
+    off_centre=(ox, oy): every centre, the last one's included, lies (ox, oy) px off one of the pixels 5 ... 11, give or take
+    OFF_JITTER: no pixel has dx = 0 or dy = 0 to any splat, so no addend of dL/dmean or dL/dconic is zero by construction.
+    (The jitter: with hundreds of splats on EXACTLY one centre a pixel sees the same alpha hundreds of times over, and a
+    transmittance rebuilt by reciprocal-and-multiply then repeats one rounding error of 1 / (1 - alpha) at every step, in one
+    direction -- a scene made of copies, profiles/walk_rows_tests.md.)"""
     n = len(z32)
     x0, y0 = 16 * (tile % GX), 16 * (tile // GX)
-    u, v = x0 + rng.uniform(4.5, 11.5, n), y0 + rng.uniform(4.5, 11.5, n)
+    if off_centre is None:
+        u, v = x0 + rng.uniform(4.5, 11.5, n), y0 + rng.uniform(4.5, 11.5, n)
+    else:
+        u = x0 + rng.integers(5, 12, n).astype(np.float64) + off_centre[0] + rng.uniform(-OFF_JITTER, OFF_JITTER, n)
+        v = y0 + rng.integers(5, 12, n).astype(np.float64) + off_centre[1] + rng.uniform(-OFF_JITTER, OFF_JITTER, n)
     if n:
         last = np.lexsort((np.arange(n), z32.view(np.uint32)))[-1]
         u[last], v[last] = x0 + 8.0, y0 + 8.0
+        if off_centre is not None:
+            u[last] += off_centre[0]
+            v[last] += off_centre[1]
     return _splats(u, v, z32, SIGMA_PX, opacity, rng)
 
 
@@ -144,7 +161,7 @@ def one_tile(L, pattern, opacity=None, front=None, beg=37, seed=0):
     assert front in (None, "closed") and L >= nf and beg >= 4 * nf
     n0 = beg - 4 * nf
     parts = [_tile_list(0, depths(n0, "spread", rng), open_opacity(n0 + nf), rng),
-             _tile_list(MAIN_TILE, depths(L - nf, pattern, rng), opacity, rng)]
+             _tile_list(MAIN_TILE, depths(L - nf, pattern, rng), opacity, rng, OFF_CENTRE if pattern == "offc" else None)]
     lens = [n0 + nf, nf, nf, nf, L, nf]
     if nf:
         parts.append(_splats(np.full(nf, 24.0), np.full(nf, 24.0), np.array([0.5, 0.51, 0.52], np.float32)[:nf], 60.0, 0.999, rng))
@@ -258,6 +275,7 @@ def regime_streamed(z):
 
 LENGTHS = [1, 8, 9, 32, 33, 63, 64, 65, 127, 128, 129, 1023, 1024, 1025, 4095, 4096, 4097, 7680, 7681, 7744, 8191, 8192,
            8193, 16384, 16385, 24577]
+OFFC_LENGTHS = [65, 4097, 7681, 8193]
 STREAMED_CELLS = 8193                                        # the `cells` list of the streamed class
 
 
@@ -287,6 +305,9 @@ def _cases():
     # every pixel stops at once: the tail of a list left at its first window is never asked for
     # (`spread` only: the front splats' depth, if sampled, moves the range a `cells` list is laid out for)
     out += [Case(L, "spread", "linear", 1, front="closed") for L in (7681, 8193, 20000)]
+    # `spread` with every centre off its pixel: a partial second chunk, just past LONG_LIST, just past LONG_WIN, a tail that is
+    # ordered on demand -- with all nine of the reverse walk's sums live on (nearly) every entry
+    out += [Case(L, "offc", "linear", 1) for L in OFFC_LENGTHS]
     return out
 
 

@@ -8,7 +8,8 @@ summed by the reverse walk next to the signed sums that are dL/dmeans2D, and lef
   ``oracle/torch_oracle.render``: tests/test_abs_grad_cpu.py).  Relative L2 of ``absgrad[:, :2]`` <= GRAD_TOL = 1e-4
   (BASELINE.json's gradient tolerance).  A scene is admissible only if the SIGNED dL/dmeans2D of the same backward meets the
   same bound against the same restatement -- asserted in the same test, so that a miss caused by fp32-versus-float64
-  contribution decisions shows as the scene's fault.  The worst per-row relative error is printed, with no bound of its own.
+  contribution decisions shows as the scene's fault.  Row by row, all eleven sums of the abs backward -- slots 9 and 10 are
+  the absolute ones -- are held against the oracle's float64 twin by the rule of gpu_util.assert_walk_rows.
 * Exact relations, every case: column 2 is zero; rows with radii == 0 or point_weight == 0 are zero; finite and >= 0; and
   |grad[g, c]| <= absgrad[g, c] (1 + 2 H W 2^-24): the triangle inequality plus the worst-case error of an fp32 sum of at
   most H W addends in any order (gamma_n <= n u / (1 - n u) on each side, u = 2^-24; the addends are the same fp32 numbers on
@@ -153,7 +154,20 @@ def _check(cam, sc, package="wodilate", forms=("rows", "quadrant"), **kw):
 
 # ---- against float64 ------------------------------------------------------------------------------------------------------
 
-def _against_float64(cam, sc, package, form):
+def _walk_rows(oracle_mod, a, cam, sc, flavour, name):
+    """Every row, all eleven slots: |hip - f64| <= 2 |oracle - f64| + WALK_ROW_FLOOR * 6e-8 * unit (gpu_util.walk_row_stats)."""
+    import gpu_util as G
+    v, of = G.oracle_forward(oracle_mod, cam, sc, BG, flavour=flavour)
+    og = oracle_mod.backward(v, of, a.w, abs_sums=True)
+    g64 = oracle_mod.backward_f64(v, of, a.w, cond=False, abs_sums=True)
+    g = a.grads()
+    hg = dict(means2D=g["means2D"], conic=g["conic"], opacities=g["opacity"].reshape(-1, 1), colors=g["colors"], absgrad=a.absgrad[:, :2])
+    st = G.walk_row_stats(hg, og, g64)
+    assert st["slots"] == 11 and st["live"] > 0
+    G.assert_walk_rows(st, name=name)
+
+
+def _against_float64(cam, sc, package, form, oracle_mod=None, name=None):
     from log_amd import rasterizer as R
     a = Run(cam, sc, True, package, form=form)
     assert a.bwd_form == form
@@ -166,21 +180,22 @@ def _against_float64(cam, sc, package, form):
     print("%s %s: signed dL/dmeans2D vs float64 %.3g, absgrad vs float64 %.3g, worst row %.3g" % (package, form, signed, absolute, worst))
     assert signed <= GRAD_TOL, ("the scene is not admissible: its signed gradient misses the bound", signed)
     assert absolute <= GRAD_TOL, absolute
+    _walk_rows(oracle_mod, a, cam, sc, R.WODILATE if package == "wodilate" else R.UPSTREAM, name)
 
 
 @pytest.mark.parametrize("form", ["rows", "quadrant"])
 @pytest.mark.parametrize("package", ["wodilate", "upstream"])
 @pytest.mark.parametrize("shape", [(16, 16), (37, 21), (64, 48)])
-def test_against_float64_shapes_both_packages(shape, package, form):
+def test_against_float64_shapes_both_packages(oracle_mod, shape, package, form):
     W, H = shape
     cam, sc = small_case(n=400, W=W, H=H, focal=1.1 * W, seed=2, smax=0.1)
-    _against_float64(cam, sc, package, form)
+    _against_float64(cam, sc, package, form, oracle_mod, "abs_%dx%d_%s_%s" % (W, H, package, form))
 
 
 @pytest.mark.parametrize("form", ["rows", "quadrant"])
-def test_against_float64_ragged_scene(form):
+def test_against_float64_ragged_scene(oracle_mod, form):
     cam, sc = _ragged()
-    _against_float64(cam, sc, "wodilate", form)
+    _against_float64(cam, sc, "wodilate", form, oracle_mod, "abs_ragged_" + form)
 
 
 # ---- same sums, another order ---------------------------------------------------------------------------------------------

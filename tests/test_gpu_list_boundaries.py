@@ -49,7 +49,8 @@ def _same_bits(a, b):
 
 def _assert_gradients(name, g, og, g64):
     """Against the fp32 oracle: rel-L2 < GRAD_TOL.  Against the float64 twin: the rule of gpu_util.assert_gradients_anchored
-    for the reverse walk's outputs -- within the tolerance, or no further from it than 1.25 x the fp32 oracle's own distance."""
+    for the reverse walk's outputs -- within the tolerance, or no further from it than 1.25 x the fp32 oracle's own distance --
+    and gpu_util.assert_walk_rows for every row and slot of them."""
     assert g["bwd_masks"]
     fig = {}
     for k in WALK:
@@ -59,6 +60,9 @@ def _assert_gradients(name, g, og, g64):
     for k, (e, e64, o64) in fig.items():
         assert e < GRAD_TOL, (k, e)
         assert e64 <= max(1e-4, 1.25 * o64), (k, e64, o64)
+    # ... and row by row, slot by slot (gpu_util.walk_row_stats): an aggregate does not see one entry of 8193
+    import gpu_util as G
+    G.assert_walk_rows(G.walk_row_stats(g, og, g64), name="list_" + name)
 
 
 def _reference(oracle_mod, G, cam, sc):

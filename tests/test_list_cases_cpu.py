@@ -86,6 +86,28 @@ def test_declared_regime(oracle_mod, case):
         assert all(r[1] == case.tie for r in seen), seen                          # the group is a bucket of its own, and the largest
 
 
+@pytest.mark.parametrize("L", LC.OFFC_LENGTHS)
+def test_off_centre_lists_have_live_mean_and_conic_sums(oracle_mod, L):
+    """The `offc` family exists so that the long-list regimes exercise ALL nine sums of the reverse walk: at least 99 % of the
+    main list's entries have a non-zero dL/dmeans2D and a non-zero dL/dconic row in the float64 twin (one tile, declared
+    regime: test_case_is_what_it_declares / test_declared_regime above, through LC.CASES)."""
+    case = LC.BY_ID["offc-%d" % L]
+    assert case.regime == "linear" and case.open
+    sc, lens, of = _forward(oracle_mod, case.id, case.scene)
+    assert np.diff(of["tile_offsets"].astype(np.int64)).tolist() == lens      # each splat in ONE tile's list
+    ids, _ = _main_depths(of, lens)
+    cx, cy = of["rec"][ids, 0].astype(np.float64), of["rec"][ids, 1].astype(np.float64)
+    ox, oy = LC.OFF_CENTRE
+    tol = LC.OFF_JITTER + 1e-4                                                   # every centre off its pixel on both axes
+    assert np.abs((cx - np.floor(cx)) - ox).max() < tol and np.abs((cy - np.floor(cy)) - (1.0 + oy)).max() < tol
+    dL = np.random.default_rng(4).standard_normal(of["image"].shape).astype(np.float32)
+    g64 = oracle_mod.backward_f64(oracle_view(oracle_mod, LC.camera(), BG), of, dL, cond=False)
+    mean_live = (g64["means2D"][ids, :2] != 0).all(axis=1)
+    conic_live = (g64["conic"][ids, :3] != 0).all(axis=1)
+    print(case.id, "live mean rows %.4f, live conic rows %.4f" % (mean_live.mean(), conic_live.mean()))
+    assert mean_live.mean() >= 0.99 and conic_live.mean() >= 0.99
+
+
 def test_every_size_class_has_every_regime():
     have = {(c.size_class, c.regime) for c in LC.CASES if c.open}
     for cls in ("small", "lds", "streamed"):

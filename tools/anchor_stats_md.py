@@ -10,6 +10,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tag = sys.argv[1] if len(sys.argv) > 1 else "r03"
 note = sys.argv[2] if len(sys.argv) > 2 else "the round's last full `pytest -m gpu` run"
 files = sorted(glob.glob(os.path.join(ROOT, "gpurun_out", "parity_stats", "*.json")))
+files = [f for f in files if not f.endswith(".walk_rows.json")]   # (the reverse walk's row statistics: tests/gpu_util.py, assert_walk_rows)
 out = ["# End-to-end gradients against the float64 twin (MI355X, `pytest -m gpu`, default kernels)", "",
        "Source: `tests/gpu_util.py::gradient_anchor_stats`, dumped by every full-size / case test of `tests/test_gpu_scale.py` and",
        "`tests/test_gpu_parity.py` (%s; this table: `python tools/anchor_stats_md.py %s`).  Per chain-rule output: rows the" % (note, tag),
