@@ -1060,8 +1060,15 @@ lr_blend_bwd_rows_kernel(LrView v, const float4* __restrict__ geom, const uint32
 // (row, Gaussian) visit (row maximum by four DPP steps), and the Gaussian's accumulator row is cleared by the row's
 // first four lanes.
 template <bool EXTRAS>
-// 5 waves per SIMD: with the unconditional prefetch loads the allocator's own choice is 102 VGPRs (4 waves); 96 fit
-// without a spill (round 6)
+// 5 waves per SIMD (4 measured slower); with the unconditional prefetch loads the allocator's own choice is 4.  At 5 the
+// kernel fits only with the wave index in an SGPR (`wq` below: readfirstlane -- the compiler cannot see that
+// threadIdx.x >> 6 is wave-uniform).  With it the quadrant origin, the wave's LDS bases (stage, mask buffer, row maxima),
+// the mask slot pointer and the chunk bookkeeping (mcount, mfirst) are scalar: 94 VGPRs (EXTRAS; 89 without), no scratch.
+// With the index in a VGPR the allocator took all 96 and spilled ten values of loop invariants (the block bounds'
+// +-0.01 / +3 / +7 forms among them; 36 B of scratch per lane).  Scratch accesses count in vmcnt, so every reload in the
+// chunk prologue's block tests drew an s_waitcnt vmcnt(0) right behind the gather of the next chunk: the prefetch this
+// loop is built around drained once per chunk and wave.  Now the only vmcnt wait inside the chunk loop is its hand-over
+// (g0_n ... -> g0 ...).  tests/test_kernel_resources_cpu.py holds the resource numbers; profiles/fwd_rows_prefetch.md.
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5)))
 lr_blend_fwd_rows_kernel(LrView v, const float4* __restrict__ geom, const uint32_t* __restrict__ state,
                          uint32_t tiles, const uint32_t* __restrict__ plist, uint32_t capacity,
@@ -1080,7 +1087,8 @@ lr_blend_fwd_rows_kernel(LrView v, const float4* __restrict__ geom, const uint32
   uint32_t beg = offsets[tile];
   uint32_t end = offsets[tile + 1], first;
   bool clamped;
-  const int lane = threadIdx.x & 63, wq = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63;
+  const int wq = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);   // the wave's index, scalar (above: no scratch)
   // Hit masks for the reverse walk: collected in LDS (64 chunks x 4 block masks per wave) and written out in bursts -- when
   // the buffer is full and after the walk.  A store per chunk, straight from the loop, cost the kernel 60-90 us at 30 M
   // (544 -> 602-632): gfx9 counts loads and stores in ONE counter (vmcnt) and they return out of order with each other, so
