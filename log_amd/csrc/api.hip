@@ -425,14 +425,17 @@ static LrCompositePlan lr_composite_plan(const LrView& v, const LrPlan& p, const
 // the first window, open[] keeps the bits).
 static void lr_composite(const LrView& v, const LrPlan& p, const LrForwardArgs& a, const void* geom, const LrCompositePlan& c,
                          uint32_t* st, bool sort_rest, hipStream_t s) {
-  float* const zrows = c.touched_only ? a.bwd_scratch : nullptr;
-  lr_launch_blend_fwd(v, geom, st, p.tiles, a.point_list, a.capacity, a.image, a.final_t, a.n_contrib, a.point_id_pixel,
-                      a.point_weight_pixel, a.point_weight, zrows, p.big_input ? 1 : 0, c.lazy, v.masks, s, a.aux_colors, a.aux_image);
+  LrBlendFwdArgs b = {};
+  b.geom = geom; b.state = st; b.tiles = p.tiles; b.plist = a.point_list; b.capacity = a.capacity;
+  b.image = a.image; b.final_T = a.final_t; b.n_contrib = a.n_contrib; b.pid = a.point_id_pixel; b.pwp = a.point_weight_pixel;
+  b.pw = a.point_weight; b.zero_conic = c.touched_only ? a.bwd_scratch : nullptr; b.big_input = p.big_input ? 1 : 0;
+  b.lazy = c.lazy; b.masks = v.masks; b.aux_colors = a.aux_colors; b.aux_image = a.aux_image;
+  lr_launch_blend_fwd(v, b, s);
   if (c.lazy) {
     lr_prof_begin(LRK_LAZY_TAIL, s);
     if (sort_rest) lr_launch_sort_rest(st, p.tiles, a.keys, a.point_list, a.capacity, a.max_tile_len, 2, s);
-    lr_launch_blend_fwd(v, geom, st, p.tiles, a.point_list, a.capacity, a.image, a.final_t, a.n_contrib, a.point_id_pixel,
-                        a.point_weight_pixel, a.point_weight, zrows, p.big_input ? 1 : 0, 2, v.masks, s, a.aux_colors, a.aux_image);
+    b.lazy = 2;   // the pass of the waves that parked
+    lr_launch_blend_fwd(v, b, s);
     lr_prof_end(LRK_LAZY_TAIL, s);
   }
 }
@@ -856,21 +859,48 @@ int lograst_read_state(const void* tile_state, uint32_t* num_instances_host, uin
   return LOGRAST_OK;
 }
 
-// What lograst_backward_aux has on top of lograst_backward (aux.on = 0: the plain backward).
-struct LrBackwardAux { int on; const float* aux_colors; const float* dl_daux_image; int32_t bwd_row_floats; float* dl_daux_colors; };
+// What lograst_backward_aux has on top of lograst_backward.
+struct LrAuxGrads { const float *aux_colors, *dl_daux_image; int32_t bwd_row_floats; float* dl_daux_colors; };
 // What the *_camera entry points have on top: dL/dviewmatrix and dL/dprojmatrix [4, 4] and the chain rule's partials scratch.
-struct LrBackwardCam { int on; float* dl_dview; float* dl_dproj; void* scratch; size_t scratch_bytes; };
-// What lograst_backward_abs has on top: dl_dmeans2d_abs [n, 3].
-struct LrBackwardAbs { int on; float* dl_dmeans2d_abs; };
-// Their own argument errors, before any launch; *done: n == 0, the two gradients are zeros and nothing else is to do.
-static int lr_check_camera(const LrView& v, int32_t n, int32_t flags, const LrBackwardCam& cam, hipStream_t s, bool* done) {
+struct LrCameraOut { float *dl_dview, *dl_dproj; void* scratch; size_t scratch_bytes; };
+// What the four backward entry points share: the parameters of lograst_backward (include/lograst.h), in its order, so that an
+// entry point fills it with one braced list; then which entry point it is and what it has on top (NULL / 0: off).
+enum LrBackwardExtra { LR_BWD_PLAIN = 0, LR_BWD_AUX, LR_BWD_CAMERA, LR_BWD_ABS };
+struct LrBackwardArgs {
+  const lograst_view* view; int32_t n;
+  const float *means3d, *scales, *rotations; const int32_t* radii; const void *geom, *tile_state; const uint32_t* point_list;
+  const float* final_t; const int32_t* n_contrib; const float* dl_dimage;
+  float *dl_dmeans2d, *bwd_rows, *dl_dopacities, *dl_dcolors, *dl_dmeans3d, *dl_dscales, *dl_drotations;
+  const float* point_weight; int32_t flags; void* stream;
+  LrBackwardExtra extra;
+  LrAuxGrads aux;           // lograst_backward_aux
+  LrCameraOut cam;          // lograst_backward_camera
+  float* dl_dmeans2d_abs;   // lograst_backward_abs: [n, 3]
+};
+// lograst_project_backward's parameters in its order, and the camera form's on top.
+struct LrProjectBackwardArgs {
+  const lograst_view* view; int32_t n;
+  const float *means3d, *scales, *rotations; const int32_t* radii; const float *dl_dmeans2d, *dl_dconic;
+  float *dl_dmeans3d, *dl_dscales, *dl_drotations; void* stream;
+  bool camera; LrCameraOut cam;
+};
+
+// What the extras refuse alike -- running sums, the cov3d_precomp form, a band view -- each in the caller's words (NULL: that
+// one is not this call's to refuse here).
+static int lr_refuse_forms(const LrView& v, int32_t flags, const char* sums, const char* cov3d, const char* band) {
+  if (sums && (flags & (LOGRAST_BWD_ACCUMULATE | LOGRAST_BWD_ACCUMULATE_ROWS))) return lr_fail(LOGRAST_ERR_ARG, sums);
+  if (cov3d && v.cov3d) return lr_fail(LOGRAST_ERR_ARG, cov3d);
+  if (band && (v.ty0 != 0 || v.ty1 != v.gy)) return lr_fail(LOGRAST_ERR_ARG, band);
+  return LOGRAST_OK;
+}
+// The camera form's own argument errors, before any launch; *done: n == 0, the two gradients are zeros and nothing else is to do.
+static int lr_check_camera(const LrView& v, int32_t n, int32_t flags, const LrCameraOut& cam, hipStream_t s, bool* done) {
   *done = false;
   if (!cam.dl_dview || !cam.dl_dproj) return lr_fail(LOGRAST_ERR_ARG, "dl_dviewmatrix / dl_dprojmatrix are NULL");
-  if (flags & (LOGRAST_BWD_ACCUMULATE | LOGRAST_BWD_ACCUMULATE_ROWS))
-    return lr_fail(LOGRAST_ERR_ARG, "camera gradients come with fresh gradients only (no LOGRAST_BWD_ACCUMULATE / _ROWS form)");
-  if (v.cov3d) return lr_fail(LOGRAST_ERR_ARG, "camera gradients have no cov3d_precomp form");
-  if (v.ty0 != 0 || v.ty1 != v.gy)
-    return lr_fail(LOGRAST_ERR_ARG, "camera gradients are summed over whole images only (tile_row_begin / tile_row_end)");
+  if (int rc = lr_refuse_forms(v, flags, "camera gradients come with fresh gradients only (no LOGRAST_BWD_ACCUMULATE / _ROWS form)",
+                               "camera gradients have no cov3d_precomp form",
+                               "camera gradients are summed over whole images only (tile_row_begin / tile_row_end)"))
+    return rc;
   if (n < 0) return lr_fail(LOGRAST_ERR_ARG, "negative Gaussian count");
   if (n == 0) {
     LR_HIP(hipMemsetAsync(cam.dl_dview, 0, 16 * sizeof(float), s));
@@ -884,85 +914,84 @@ static int lr_check_camera(const LrView& v, int32_t n, int32_t flags, const LrBa
   return LOGRAST_OK;
 }
 // The one backward body behind lograst_backward, lograst_backward_aux, lograst_backward_camera and lograst_backward_abs.
-static int lr_backward(const lograst_view* view, int32_t n, const float* means3d, const float* scales,
-                       const float* rotations, const int32_t* radii, const void* geom, const void* tile_state,
-                       const uint32_t* point_list, const float* final_t, const int32_t* n_contrib,
-                       const float* dl_dimage, float* dl_dmeans2d, float* bwd_rows, float* dl_dopacities,
-                       float* dl_dcolors, float* dl_dmeans3d, float* dl_dscales, float* dl_drotations,
-                       const float* point_weight, int32_t flags, void* stream, const LrBackwardAux& aux,
-                       const LrBackwardCam& cam = LrBackwardCam{0, nullptr, nullptr, nullptr, 0},
-                       const LrBackwardAbs& ab = LrBackwardAbs{0, nullptr}) {
-  float* const dl_dconic = bwd_rows;   // (the fourth gradient argument: since version 3 the n x 16 accumulator rows)
+static int lr_backward(const LrBackwardArgs& a) {
+  const int32_t n = a.n, flags = a.flags;
+  float* const dl_dconic = a.bwd_rows;   // (the fourth gradient argument: since version 3 the n x 16 accumulator rows)
+  const bool aux = a.extra == LR_BWD_AUX, camera = a.extra == LR_BWD_CAMERA, abs_sums = a.extra == LR_BWD_ABS;
+  hipStream_t s = (hipStream_t)a.stream;
   g_prof_call++;
   LrView v;
-  int rc = lr_make_view(view, &v);
+  int rc = lr_make_view(a.view, &v);
   if (rc) return rc;
-  if (cam.on) {
+  if (camera) {
     bool done;
-    if ((rc = lr_check_camera(v, n, flags, cam, (hipStream_t)stream, &done)) || done) return rc;
+    if ((rc = lr_check_camera(v, n, flags, a.cam, s, &done)) || done) return rc;
   }
-  if (ab.on) {   // (the abs form's own argument errors: before anything else of the call, n == 0 included)
-    if (!ab.dl_dmeans2d_abs) return lr_fail(LOGRAST_ERR_ARG, "dl_dmeans2d_abs is NULL");
-    if (flags & (LOGRAST_BWD_ACCUMULATE | LOGRAST_BWD_ACCUMULATE_ROWS))
-      return lr_fail(LOGRAST_ERR_ARG, "lograst_backward_abs writes fresh gradients (no LOGRAST_BWD_ACCUMULATE / _ROWS form)");
-    if (v.cov3d) return lr_fail(LOGRAST_ERR_ARG, "lograst_backward_abs has no cov3d_precomp form");
-    if (v.ty0 != 0 || v.ty1 != v.gy)
-      return lr_fail(LOGRAST_ERR_ARG, "lograst_backward_abs: whole images only (tile_row_begin / tile_row_end)");
+  if (abs_sums) {   // (the abs form's own argument errors: before anything else of the call, n == 0 included)
+    if (!a.dl_dmeans2d_abs) return lr_fail(LOGRAST_ERR_ARG, "dl_dmeans2d_abs is NULL");
+    if ((rc = lr_refuse_forms(v, flags, "lograst_backward_abs writes fresh gradients (no LOGRAST_BWD_ACCUMULATE / _ROWS form)",
+                              "lograst_backward_abs has no cov3d_precomp form",
+                              "lograst_backward_abs: whole images only (tile_row_begin / tile_row_end)")))
+      return rc;
   }
   if (n < 0) return lr_fail(LOGRAST_ERR_ARG, "negative Gaussian count");
   if (n == 0) return LOGRAST_OK;
   const bool sink_rows = (flags & LOGRAST_BWD_ACCUMULATE_ROWS) != 0;
-  if (aux.on) {   // (before anything else of the call: the aux form's own argument errors)
+  if (aux) {   // (before anything else of the call: the aux form's own argument errors; band and cov3d in the forward's words)
     if ((rc = lr_check_aux_view(v))) return rc;
-    if (!aux.aux_colors || !aux.dl_daux_colors) return lr_fail(LOGRAST_ERR_ARG, "aux_colors / dl_daux_colors are NULL");
-    if (!dl_dimage && !aux.dl_daux_image) return lr_fail(LOGRAST_ERR_ARG, "dl_dimage and dl_daux_image are both NULL");
-    if (aux.bwd_row_floats != LOGRAST_BWD_ROW_FLOATS)
+    if (!a.aux.aux_colors || !a.aux.dl_daux_colors) return lr_fail(LOGRAST_ERR_ARG, "aux_colors / dl_daux_colors are NULL");
+    if (!a.dl_dimage && !a.aux.dl_daux_image) return lr_fail(LOGRAST_ERR_ARG, "dl_dimage and dl_daux_image are both NULL");
+    if (a.aux.bwd_row_floats != LOGRAST_BWD_ROW_FLOATS)
       return lr_fail(LOGRAST_ERR_ARG, "bwd_rows must hold LOGRAST_BWD_ROW_FLOATS (16) floats per Gaussian (dL/daux_colors: slots 9..11)");
-    if (flags & (LOGRAST_BWD_ACCUMULATE | LOGRAST_BWD_ACCUMULATE_ROWS))
-      return lr_fail(LOGRAST_ERR_ARG, "lograst_backward_aux writes fresh gradients (no LOGRAST_BWD_ACCUMULATE / _ROWS form)");
+    if ((rc = lr_refuse_forms(v, flags, "lograst_backward_aux writes fresh gradients (no LOGRAST_BWD_ACCUMULATE / _ROWS form)",
+                              nullptr, nullptr)))
+      return rc;
   }
-  if (!means3d || !radii || !geom || !tile_state || !final_t || !n_contrib || (!aux.on && !dl_dimage) ||
-      !dl_dmeans2d || !dl_dconic || !dl_dmeans3d || (!sink_rows && (!dl_dopacities || !dl_dcolors)))
+  if (!a.means3d || !a.radii || !a.geom || !a.tile_state || !a.final_t || !a.n_contrib || (!aux && !a.dl_dimage) ||
+      !a.dl_dmeans2d || !dl_dconic || !a.dl_dmeans3d || (!sink_rows && (!a.dl_dopacities || !a.dl_dcolors)))
     return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
   if (sink_rows) {   // dl_dmeans3d = the caller's [n][LOGRAST_GRAD_ROW_FLOATS] running sums; the other four are not used
     if (v.cov3d) return lr_fail(LOGRAST_ERR_ARG, "LOGRAST_BWD_ACCUMULATE_ROWS has no cov3d_precomp form");
-    if (!scales || !rotations) return lr_fail(LOGRAST_ERR_ARG, "scales / rotations are NULL");
-    if (reinterpret_cast<uintptr_t>(dl_dmeans3d) & 63u)
+    if (!a.scales || !a.rotations) return lr_fail(LOGRAST_ERR_ARG, "scales / rotations are NULL");
+    if (reinterpret_cast<uintptr_t>(a.dl_dmeans3d) & 63u)
       return lr_fail(LOGRAST_ERR_ARG, "LOGRAST_BWD_ACCUMULATE_ROWS: the gradient rows must be 64-byte aligned");
-    if (reinterpret_cast<uintptr_t>(rotations) & 15u) return lr_fail(LOGRAST_ERR_ARG, "rotations must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(a.rotations) & 15u) return lr_fail(LOGRAST_ERR_ARG, "rotations must be 16-byte aligned");
   } else {
-    rc = lr_check_cov_args(v, scales, rotations, dl_dscales, dl_drotations);
+    rc = lr_check_cov_args(v, a.scales, a.rotations, a.dl_dscales, a.dl_drotations);
     if (rc) return rc;
-    if ((reinterpret_cast<uintptr_t>(rotations) | reinterpret_cast<uintptr_t>(dl_drotations)) & 15u)
+    if ((reinterpret_cast<uintptr_t>(a.rotations) | reinterpret_cast<uintptr_t>(a.dl_drotations)) & 15u)
       return lr_fail(LOGRAST_ERR_ARG, "rotations / dl_drotations must be 16-byte aligned");
   }
-  if (reinterpret_cast<uintptr_t>(bwd_rows) & 63u)
+  if (reinterpret_cast<uintptr_t>(a.bwd_rows) & 63u)
     return lr_fail(LOGRAST_ERR_ARG, "bwd_rows must be 64-byte aligned (one accumulator row per line)");
-  hipStream_t s = (hipStream_t)stream;
-  uint32_t tiles = (uint32_t)(v.gx * v.gy);
-  const uint32_t* st = reinterpret_cast<const uint32_t*>(tile_state);
-  const bool accumulate = (flags & LOGRAST_BWD_ACCUMULATE) != 0 || sink_rows;
-  if ((flags & LOGRAST_BWD_CONIC_TOUCHED_ONLY) && !point_weight)
+  if ((flags & LOGRAST_BWD_CONIC_TOUCHED_ONLY) && !a.point_weight)
     return lr_fail(LOGRAST_ERR_ARG, "LOGRAST_BWD_CONIC_TOUCHED_ONLY needs point_weight");
   // A forward with extras on a large input clears the dL/dconic rows of contributing Gaussians only (lr_stage2:
   // touched_only); the chain rule must then skip the others, which it does exactly when it is handed point_weight.
   const bool big_input = lr_big_input(n);
-  if ((flags & LOGRAST_BWD_SCRATCH_ZEROED) && v.extras && big_input && !point_weight)
+  if ((flags & LOGRAST_BWD_SCRATCH_ZEROED) && v.extras && big_input && !a.point_weight)
     return lr_fail(LOGRAST_ERR_ARG, "LOGRAST_BWD_SCRATCH_ZEROED after a forward with view.extras and n >= "
                                     "LOGRAST_HELPER_MIN_N: dL/dconic is cleared for contributing Gaussians only, pass "
                                     "point_weight (+ LOGRAST_BWD_CONIC_TOUCHED_ONLY)");
   if (!(flags & LOGRAST_BWD_SCRATCH_ZEROED))
     LR_HIP(hipMemsetAsync(dl_dconic, 0, sizeof(float) * LOGRAST_BWD_ROW_FLOATS * (size_t)n, s));
-  // capacity check is a forward concern: a list that rendered is by construction within capacity
-  lr_launch_blend_bwd(v, geom, st, tiles, point_list, 0xffffffffu, final_t, n_contrib, dl_dimage, dl_dconic,
-                      big_input ? 1 : 0, v.masks, s, aux.on ? aux.aux_colors : nullptr, aux.on ? aux.dl_daux_image : nullptr,
-                      ab.on != 0);
+  LrBlendBwdArgs w = {};
+  w.geom = a.geom; w.state = reinterpret_cast<const uint32_t*>(a.tile_state); w.tiles = (uint32_t)(v.gx * v.gy);
+  w.plist = a.point_list; w.capacity = 0xffffffffu;   // capacity check is a forward concern: a list that rendered is by construction within capacity
+  w.final_T = a.final_t; w.n_contrib = a.n_contrib; w.dL_dimage = a.dl_dimage; w.acc_rows = dl_dconic;
+  w.big_input = big_input ? 1 : 0; w.masks = v.masks; w.aux_colors = a.aux.aux_colors; w.dL_daux = a.aux.dl_daux_image;
+  w.abs_sums = abs_sums;
+  lr_launch_blend_bwd(v, w, s);
   // the chain rule reads every live Gaussian's accumulator row and hands out the separate outputs: dL/dmeans2D (written
   // for all rows), dL/dopacities and dL/dcolors (written, or added to the caller's running sums)
-  lr_launch_project_bwd(v, n, means3d, scales, rotations, radii, nullptr, nullptr, dl_dconic, dl_dmeans2d, dl_dopacities,
-                        dl_dcolors, point_weight, dl_dmeans3d, dl_dscales, dl_drotations, accumulate, sink_rows, big_input, s,
-                        aux.on ? aux.dl_daux_colors : nullptr, cam.on ? static_cast<float*>(cam.scratch) : nullptr, cam.dl_dview,
-                        cam.dl_dproj, ab.on ? ab.dl_dmeans2d_abs : nullptr);
+  LrProjectBwdArgs c = {};
+  c.N = n; c.means = a.means3d; c.scales = a.scales; c.rots = a.rotations; c.radii = a.radii; c.rows = dl_dconic;
+  c.o_mean2d = a.dl_dmeans2d; c.o_opac = a.dl_dopacities; c.o_col = a.dl_dcolors; c.pw = a.point_weight;
+  c.g_means3d = a.dl_dmeans3d; c.g_scales = a.dl_dscales; c.g_rots = a.dl_drotations;
+  c.accumulate = (flags & LOGRAST_BWD_ACCUMULATE) != 0 || sink_rows; c.sink_rows = sink_rows; c.big_input = big_input;
+  c.o_aux = a.aux.dl_daux_colors; c.o_abs = a.dl_dmeans2d_abs;   // (NULL but for their entry point, like the camera's three)
+  c.cam_partials = static_cast<float*>(a.cam.scratch); c.cam_dv = a.cam.dl_dview; c.cam_dp = a.cam.dl_dproj;
+  lr_launch_project_bwd(v, c, s);
   LR_HIP(hipGetLastError());
   return LOGRAST_OK;
 }
@@ -972,9 +1001,9 @@ int lograst_backward(const lograst_view* view, int32_t n, const float* means3d, 
                      const float* dl_dimage, float* dl_dmeans2d, float* bwd_rows, float* dl_dopacities,
                      float* dl_dcolors, float* dl_dmeans3d, float* dl_dscales, float* dl_drotations,
                      const float* point_weight, int32_t flags, void* stream) {
-  return lr_backward(view, n, means3d, scales, rotations, radii, geom, tile_state, point_list, final_t, n_contrib, dl_dimage,
-                     dl_dmeans2d, bwd_rows, dl_dopacities, dl_dcolors, dl_dmeans3d, dl_dscales, dl_drotations, point_weight,
-                     flags, stream, LrBackwardAux{0, nullptr, nullptr, 0, nullptr});
+  return lr_backward({view, n, means3d, scales, rotations, radii, geom, tile_state, point_list, final_t, n_contrib, dl_dimage,
+                      dl_dmeans2d, bwd_rows, dl_dopacities, dl_dcolors, dl_dmeans3d, dl_dscales, dl_drotations, point_weight,
+                      flags, stream});
 }
 int lograst_backward_aux(const lograst_view* view, int32_t n, const float* means3d, const float* scales,
                          const float* rotations, const int32_t* radii, const void* geom, const void* tile_state,
@@ -983,9 +1012,9 @@ int lograst_backward_aux(const lograst_view* view, int32_t n, const float* means
                          float* bwd_rows, int32_t bwd_row_floats, float* dl_dopacities, float* dl_dcolors,
                          float* dl_daux_colors, float* dl_dmeans3d, float* dl_dscales, float* dl_drotations,
                          const float* point_weight, int32_t flags, void* stream) {
-  return lr_backward(view, n, means3d, scales, rotations, radii, geom, tile_state, point_list, final_t, n_contrib, dl_dimage,
-                     dl_dmeans2d, bwd_rows, dl_dopacities, dl_dcolors, dl_dmeans3d, dl_dscales, dl_drotations, point_weight,
-                     flags, stream, LrBackwardAux{1, aux_colors, dl_daux_image, bwd_row_floats, dl_daux_colors});
+  return lr_backward({view, n, means3d, scales, rotations, radii, geom, tile_state, point_list, final_t, n_contrib, dl_dimage,
+                      dl_dmeans2d, bwd_rows, dl_dopacities, dl_dcolors, dl_dmeans3d, dl_dscales, dl_drotations, point_weight,
+                      flags, stream, LR_BWD_AUX, {aux_colors, dl_daux_image, bwd_row_floats, dl_daux_colors}});
 }
 
 int lograst_backward_camera(const lograst_view* view, int32_t n, const float* means3d, const float* scales,
@@ -995,10 +1024,9 @@ int lograst_backward_camera(const lograst_view* view, int32_t n, const float* me
                             float* dl_dcolors, float* dl_dmeans3d, float* dl_dscales, float* dl_drotations,
                             const float* point_weight, int32_t flags, float* dl_dviewmatrix, float* dl_dprojmatrix,
                             void* camera_scratch, size_t camera_scratch_bytes, void* stream) {
-  return lr_backward(view, n, means3d, scales, rotations, radii, geom, tile_state, point_list, final_t, n_contrib, dl_dimage,
-                     dl_dmeans2d, bwd_rows, dl_dopacities, dl_dcolors, dl_dmeans3d, dl_dscales, dl_drotations, point_weight,
-                     flags, stream, LrBackwardAux{0, nullptr, nullptr, 0, nullptr},
-                     LrBackwardCam{1, dl_dviewmatrix, dl_dprojmatrix, camera_scratch, camera_scratch_bytes});
+  return lr_backward({view, n, means3d, scales, rotations, radii, geom, tile_state, point_list, final_t, n_contrib, dl_dimage,
+                      dl_dmeans2d, bwd_rows, dl_dopacities, dl_dcolors, dl_dmeans3d, dl_dscales, dl_drotations, point_weight,
+                      flags, stream, LR_BWD_CAMERA, {}, {dl_dviewmatrix, dl_dprojmatrix, camera_scratch, camera_scratch_bytes}});
 }
 size_t lograst_camera_scratch_bytes(int32_t n) { return lr_camera_scratch_bytes(n); }
 
@@ -1008,37 +1036,37 @@ int lograst_backward_abs(const lograst_view* view, int32_t n, const float* means
                          const float* dl_dimage, float* dl_dmeans2d, float* bwd_rows, float* dl_dopacities,
                          float* dl_dcolors, float* dl_dmeans3d, float* dl_dscales, float* dl_drotations,
                          const float* point_weight, int32_t flags, float* dl_dmeans2d_abs, void* stream) {
-  return lr_backward(view, n, means3d, scales, rotations, radii, geom, tile_state, point_list, final_t, n_contrib, dl_dimage,
-                     dl_dmeans2d, bwd_rows, dl_dopacities, dl_dcolors, dl_dmeans3d, dl_dscales, dl_drotations, point_weight,
-                     flags, stream, LrBackwardAux{0, nullptr, nullptr, 0, nullptr}, LrBackwardCam{0, nullptr, nullptr, nullptr, 0},
-                     LrBackwardAbs{1, dl_dmeans2d_abs});
+  return lr_backward({view, n, means3d, scales, rotations, radii, geom, tile_state, point_list, final_t, n_contrib, dl_dimage,
+                      dl_dmeans2d, bwd_rows, dl_dopacities, dl_dcolors, dl_dmeans3d, dl_dscales, dl_drotations, point_weight,
+                      flags, stream, LR_BWD_ABS, {}, {}, dl_dmeans2d_abs});
 }
 
 // The one body behind lograst_project_backward and lograst_project_backward_camera.
-static int lr_project_backward(const lograst_view* view, int32_t n, const float* means3d, const float* scales,
-                               const float* rotations, const int32_t* radii, const float* dl_dmeans2d,
-                               const float* dl_dconic, float* dl_dmeans3d, float* dl_dscales,
-                               float* dl_drotations, void* stream, const LrBackwardCam& cam) {
+static int lr_project_backward(const LrProjectBackwardArgs& a) {
+  hipStream_t s = (hipStream_t)a.stream;
   g_prof_call++;
   LrView v;
-  int rc = lr_make_view(view, &v);
+  int rc = lr_make_view(a.view, &v);
   if (rc) return rc;
-  if (cam.on) {
+  if (a.camera) {
     bool done;
-    if ((rc = lr_check_camera(v, n, 0, cam, (hipStream_t)stream, &done)) || done) return rc;
+    if ((rc = lr_check_camera(v, a.n, 0, a.cam, s, &done)) || done) return rc;
   }
-  if (n < 0) return lr_fail(LOGRAST_ERR_ARG, "negative Gaussian count");
-  if (n == 0) return LOGRAST_OK;
-  if (!means3d || !radii || !dl_dmeans2d || !dl_dconic || !dl_dmeans3d)
+  if (a.n < 0) return lr_fail(LOGRAST_ERR_ARG, "negative Gaussian count");
+  if (a.n == 0) return LOGRAST_OK;
+  if (!a.means3d || !a.radii || !a.dl_dmeans2d || !a.dl_dconic || !a.dl_dmeans3d)
     return lr_fail(LOGRAST_ERR_ARG, "NULL pointer");
-  rc = lr_check_cov_args(v, scales, rotations, dl_dscales, dl_drotations);
+  rc = lr_check_cov_args(v, a.scales, a.rotations, a.dl_dscales, a.dl_drotations);
   if (rc) return rc;
-  if ((reinterpret_cast<uintptr_t>(dl_dconic) | reinterpret_cast<uintptr_t>(rotations) |
-       reinterpret_cast<uintptr_t>(dl_drotations)) & 15u)
+  if ((reinterpret_cast<uintptr_t>(a.dl_dconic) | reinterpret_cast<uintptr_t>(a.rotations) |
+       reinterpret_cast<uintptr_t>(a.dl_drotations)) & 15u)
     return lr_fail(LOGRAST_ERR_ARG, "rotations / dl_dconic / dl_drotations must be 16-byte aligned");
-  lr_launch_project_bwd(v, n, means3d, scales, rotations, radii, dl_dmeans2d, dl_dconic, nullptr, nullptr, nullptr,
-                        nullptr, nullptr, dl_dmeans3d, dl_dscales, dl_drotations, false, false, false, (hipStream_t)stream,
-                        nullptr, cam.on ? static_cast<float*>(cam.scratch) : nullptr, cam.dl_dview, cam.dl_dproj);
+  LrProjectBwdArgs c = {};
+  c.N = a.n; c.means = a.means3d; c.scales = a.scales; c.rots = a.rotations; c.radii = a.radii;
+  c.g_mean2d = a.dl_dmeans2d; c.g_conic = a.dl_dconic;
+  c.g_means3d = a.dl_dmeans3d; c.g_scales = a.dl_dscales; c.g_rots = a.dl_drotations;
+  c.cam_partials = static_cast<float*>(a.cam.scratch); c.cam_dv = a.cam.dl_dview; c.cam_dp = a.cam.dl_dproj;   // (NULL without camera)
+  lr_launch_project_bwd(v, c, s);
   LR_HIP(hipGetLastError());
   return LOGRAST_OK;
 }
@@ -1046,16 +1074,16 @@ int lograst_project_backward(const lograst_view* view, int32_t n, const float* m
                              const float* rotations, const int32_t* radii, const float* dl_dmeans2d,
                              const float* dl_dconic, float* dl_dmeans3d, float* dl_dscales,
                              float* dl_drotations, void* stream) {
-  return lr_project_backward(view, n, means3d, scales, rotations, radii, dl_dmeans2d, dl_dconic, dl_dmeans3d, dl_dscales,
-                             dl_drotations, stream, LrBackwardCam{0, nullptr, nullptr, nullptr, 0});
+  return lr_project_backward({view, n, means3d, scales, rotations, radii, dl_dmeans2d, dl_dconic, dl_dmeans3d, dl_dscales,
+                              dl_drotations, stream});
 }
 int lograst_project_backward_camera(const lograst_view* view, int32_t n, const float* means3d, const float* scales,
                                     const float* rotations, const int32_t* radii, const float* dl_dmeans2d,
                                     const float* dl_dconic, float* dl_dmeans3d, float* dl_dscales, float* dl_drotations,
                                     float* dl_dviewmatrix, float* dl_dprojmatrix, void* camera_scratch,
                                     size_t camera_scratch_bytes, void* stream) {
-  return lr_project_backward(view, n, means3d, scales, rotations, radii, dl_dmeans2d, dl_dconic, dl_dmeans3d, dl_dscales,
-                             dl_drotations, stream, LrBackwardCam{1, dl_dviewmatrix, dl_dprojmatrix, camera_scratch, camera_scratch_bytes});
+  return lr_project_backward({view, n, means3d, scales, rotations, radii, dl_dmeans2d, dl_dconic, dl_dmeans3d, dl_dscales,
+                              dl_drotations, stream, true, {dl_dviewmatrix, dl_dprojmatrix, camera_scratch, camera_scratch_bytes}});
 }
 
 size_t lograst_knn_scratch_bytes(int32_t p) { return lr_knn_scratch_bytes(p); }

@@ -1310,100 +1310,74 @@ int lr_blend_bwd_form(const LrView& v, int big_input) {
   return rows ? (int)LR_MASK_FORM_ROWS : (int)LR_MASK_FORM_QUAD;
 }
 
-void lr_launch_blend_fwd(const LrView& v, const void* geom, const uint32_t* state, uint32_t tiles,
-                         const uint32_t* plist, uint32_t capacity, float* image, float* final_T, int* n_contrib,
-                         int* pid, float* pwp, float* pw, float* zero_conic, int big_input, int lazy, uint64_t* masks,
-                         hipStream_t s, const float* aux_colors, float* aux_image) {
-  uint32_t* const hdr_w = const_cast<uint32_t*>(state);     // (header word LR_HDR_MASKS: which form left hit masks)
-  uint32_t* const lazy_state = lazy ? const_cast<uint32_t*>(state) : nullptr;   // (the tile state once more, writable: open[] and header word LR_HDR_OPEN are all a compositing kernel writes there)
+void lr_launch_blend_fwd(const LrView& v, const LrBlendFwdArgs& a, hipStream_t s) {
+  uint32_t* const hdr_w = const_cast<uint32_t*>(a.state);   // (header word LR_HDR_MASKS: which form left hit masks)
+  uint32_t* const lazy_state = a.lazy ? const_cast<uint32_t*>(a.state) : nullptr;   // (the tile state once more, writable: open[] and header word LR_HDR_OPEN are all a compositing kernel writes there)
   int xcd_mode = lr_knob(LRKNOB_XCD_MODE);
   // LOGRAST_FWD_ROWS: 1 = row-split form (lr_blend_fwd_rows_kernel), 0 = one quadrant per wave, 2 (default) = the caller's
   // hint (lograst_view.walk_form), quadrant without one.  Measured, MI355X: 30 M tiny splats 706 -> 658 us (random
   // opacities 1267 -> 1188); C2's 1 M 174 -> 193; a tree-ordered heavy-tailed view 278 -> 347.
-  const int rows = !aux_image && lr_blend_fwd_form(v) == (int)LR_MASK_FORM_ROWS;   // (aux channels: quadrant kernels only)
+  const bool aux = a.aux_image != nullptr;
+  const bool rows = !aux && lr_blend_fwd_form(v) == (int)LR_MASK_FORM_ROWS;   // (aux channels: quadrant kernels only)
+  const bool extras = v.extras != 0;
+  // The choice, [!extras] each.  (The tables name the kernels in the order in which they have always been instantiated, the
+  // one with extras first: that is the order of the device code, which tools/device_asm_digest.py holds still.)
+  static constexpr decltype(&lr_blend_fwd_kernel<true, true>) aux_kernel[2] = {lr_blend_fwd_kernel<true, true>, lr_blend_fwd_kernel<false, true>};
+  static constexpr decltype(&lr_blend_fwd_rows_kernel<true>) rows_kernel[2] = {lr_blend_fwd_rows_kernel<true>, lr_blend_fwd_rows_kernel<false>};
+  static constexpr decltype(&lr_blend_fwd_kernel<true>) quad_kernel[2] = {lr_blend_fwd_kernel<true>, lr_blend_fwd_kernel<false>};
   const int fwd_block_test = lr_knob(LRKNOB_FWD_BLOCK_TEST);
   const int exact_masks = lr_knob(LRKNOB_HIT_MASKS) != 2;   // row-split form: hit masks = contributions (2: support ballots)
   // Both forward kernels still take `cull` (always 1: the support tests run) as a run-time argument.  With the tests
   // unconditional the register allocation of the row-split kernel changed (one more value in scratch) and the forward
   // measured 1-3 % slower on the 30 M view (quadrant form: 0.6 %).
-  uint32_t grid = lr_blend_grid(tiles, v.gx, v.gy, xcd_mode);
-  if (lazy == 2) {   // only streamed lists can be open: in the scan's longest-first order they sit in front of every shorter one
+  uint32_t grid = lr_blend_grid(a.tiles, v.gx, v.gy, xcd_mode);
+  if (a.lazy == 2) {   // only streamed lists can be open: in the scan's longest-first order they sit in front of every shorter one
     xcd_mode = 3;
-    grid = min(tiles, capacity / (uint32_t)LR_LONG_LIST + 1u);
+    grid = min(a.tiles, a.capacity / (uint32_t)LR_LONG_LIST + 1u);
   }
-  const float4* g4 = reinterpret_cast<const float4*>(geom);
-  float4* z4 = reinterpret_cast<float4*>(zero_conic);
-  if (lazy != 2) lr_prof_begin(LRK_BLEND_FWD, s);           // (the second pass is timed by its caller, with the sort of the tails)
-  if (aux_image) {
-    if (v.extras)
-      hipLaunchKernelGGL((lr_blend_fwd_kernel<true, true>), dim3(grid), dim3(256), 0, s, v, g4, state, tiles, plist, capacity,
-                         image, final_T, n_contrib, pid, pwp, pw, z4, xcd_mode, 1, lazy_state, lazy, masks, hdr_w, aux_colors, aux_image);
-    else
-      hipLaunchKernelGGL((lr_blend_fwd_kernel<false, true>), dim3(grid), dim3(256), 0, s, v, g4, state, tiles, plist, capacity,
-                         image, final_T, n_contrib, pid, pwp, pw, z4, xcd_mode, 1, lazy_state, lazy, masks, hdr_w, aux_colors, aux_image);
-  } else if (rows) {
-    if (v.extras)
-      hipLaunchKernelGGL(lr_blend_fwd_rows_kernel<true>, dim3(grid), dim3(256), 0, s, v, g4, state, tiles, plist, capacity,
-                         image, final_T, n_contrib, pid, pwp, pw, z4, xcd_mode, 1, lazy_state, lazy, masks, hdr_w, fwd_block_test, exact_masks);
-    else
-      hipLaunchKernelGGL(lr_blend_fwd_rows_kernel<false>, dim3(grid), dim3(256), 0, s, v, g4, state, tiles, plist, capacity,
-                         image, final_T, n_contrib, pid, pwp, pw, z4, xcd_mode, 1, lazy_state, lazy, masks, hdr_w, fwd_block_test, exact_masks);
-  } else {
-    if (v.extras)
-      hipLaunchKernelGGL(lr_blend_fwd_kernel<true>, dim3(grid), dim3(256), 0, s, v, g4, state, tiles, plist, capacity,
-                         image, final_T, n_contrib, pid, pwp, pw, z4, xcd_mode, 1, lazy_state, lazy, masks, hdr_w, nullptr, nullptr);
-    else
-      hipLaunchKernelGGL(lr_blend_fwd_kernel<false>, dim3(grid), dim3(256), 0, s, v, g4, state, tiles, plist, capacity,
-                         image, final_T, n_contrib, pid, pwp, pw, z4, xcd_mode, 1, lazy_state, lazy, masks, hdr_w, nullptr, nullptr);
-  }
-  if (lazy != 2) lr_prof_end(LRK_BLEND_FWD, s);
+  const float4* g4 = reinterpret_cast<const float4*>(a.geom);
+  float4* z4 = reinterpret_cast<float4*>(a.zero_conic);
+  if (a.lazy != 2) lr_prof_begin(LRK_BLEND_FWD, s);         // (the second pass is timed by its caller, with the sort of the tails)
+  if (rows)
+    hipLaunchKernelGGL(rows_kernel[!extras], dim3(grid), dim3(256), 0, s, v, g4, a.state, a.tiles, a.plist, a.capacity, a.image,
+                       a.final_T, a.n_contrib, a.pid, a.pwp, a.pw, z4, xcd_mode, 1, lazy_state, a.lazy, a.masks, hdr_w,
+                       fwd_block_test, exact_masks);
+  else
+    hipLaunchKernelGGL((aux ? aux_kernel : quad_kernel)[!extras], dim3(grid), dim3(256), 0, s, v, g4, a.state, a.tiles, a.plist, a.capacity,
+                       a.image, a.final_T, a.n_contrib, a.pid, a.pwp, a.pw, z4, xcd_mode, 1, lazy_state, a.lazy, a.masks, hdr_w,
+                       aux ? a.aux_colors : nullptr, a.aux_image);
+  if (a.lazy != 2) lr_prof_end(LRK_BLEND_FWD, s);
 }
 
-void lr_launch_blend_bwd(const LrView& v, const void* geom, const uint32_t* state, uint32_t tiles,
-                         const uint32_t* plist, uint32_t capacity, const float* final_T, const int* n_contrib,
-                         const float* dL_dimage, float* acc_rows, int big_input, const uint64_t* masks, hipStream_t s,
-                         const float* aux_colors, const float* dL_daux, bool abs_sums) {
+void lr_launch_blend_bwd(const LrView& v, const LrBlendBwdArgs& a, hipStream_t s) {
   const int xcd_mode = lr_knob(LRKNOB_XCD_MODE);
-  uint32_t grid = lr_blend_grid(tiles, v.gx, v.gy, xcd_mode);
+  const uint32_t grid = lr_blend_grid(a.tiles, v.gx, v.gy, xcd_mode);
   // LOGRAST_BWD_ROWS=1: the row-split form (the four 16-lane rows of a wave walk their own 4x4 blocks); 0: one
   // (Gaussian, quadrant) pair per visit; 2 (default): the caller's hint (lograst_view.walk_form: row-split for views of
   // tiny splats, few tile instances per Gaussian), else row-split on large inputs.  Measured, MI355X: 30 M tiny splats
   // 949 -> 700 us, with random opacities 1768 -> 1259; C2's 1 M 292 -> 307; a tree-ordered heavy-tailed view 448 -> 579.
-  const int rows = !aux_colors && lr_blend_bwd_form(v, big_input) == (int)LR_MASK_FORM_ROWS;   // (aux channels: quadrant kernels only)
-  const int block_test = lr_knob(LRKNOB_BWD_BLOCK_TEST);
-  lr_prof_begin(LRK_BLEND_BWD, s);
+  const bool aux = a.aux_colors != nullptr;
+  const bool rows = !aux && lr_blend_bwd_form(v, a.big_input) == (int)LR_MASK_FORM_ROWS;   // (aux channels: quadrant kernels only)
   // the forward's hit masks serve a reverse walk of the SAME form only (v.mask_form: what the caller says its forward launched)
-  const bool use_masks = masks != nullptr && v.mask_form == (rows ? (int)LR_MASK_FORM_ROWS : (int)LR_MASK_FORM_QUAD);
-  const float4* g4 = reinterpret_cast<const float4*>(geom);
-  if (aux_colors && use_masks)
-    hipLaunchKernelGGL((lr_blend_bwd_kernel<true, true>), dim3(grid), dim3(256), 0, s, v, g4, state, tiles, plist, capacity,
-                       final_T, n_contrib, dL_dimage, acc_rows, xcd_mode, masks, aux_colors, dL_daux);
-  else if (aux_colors)
-    hipLaunchKernelGGL((lr_blend_bwd_kernel<false, true>), dim3(grid), dim3(256), 0, s, v, g4, state, tiles, plist, capacity,
-                       final_T, n_contrib, dL_dimage, acc_rows, xcd_mode, masks, aux_colors, dL_daux);
-  else if (abs_sums && rows && use_masks)   // (lograst_backward_abs: the same four choices, slots 9 and 10 summed too)
-    hipLaunchKernelGGL((lr_blend_bwd_rows_kernel<true, true>), dim3(grid), dim3(256), 0, s, v, g4, state, tiles, plist, capacity,
-                       final_T, n_contrib, dL_dimage, acc_rows, xcd_mode, block_test, masks);
-  else if (abs_sums && rows)
-    hipLaunchKernelGGL((lr_blend_bwd_rows_kernel<false, true>), dim3(grid), dim3(256), 0, s, v, g4, state, tiles, plist, capacity,
-                       final_T, n_contrib, dL_dimage, acc_rows, xcd_mode, block_test, masks);
-  else if (abs_sums && use_masks)
-    hipLaunchKernelGGL((lr_blend_bwd_kernel<true, false, true>), dim3(grid), dim3(256), 0, s, v, g4, state, tiles, plist, capacity,
-                       final_T, n_contrib, dL_dimage, acc_rows, xcd_mode, masks, nullptr, nullptr);
-  else if (abs_sums)
-    hipLaunchKernelGGL((lr_blend_bwd_kernel<false, false, true>), dim3(grid), dim3(256), 0, s, v, g4, state, tiles, plist, capacity,
-                       final_T, n_contrib, dL_dimage, acc_rows, xcd_mode, masks, nullptr, nullptr);
-  else if (rows && use_masks)
-    hipLaunchKernelGGL(lr_blend_bwd_rows_kernel<true>, dim3(grid), dim3(256), 0, s, v, g4, state, tiles, plist, capacity,
-                       final_T, n_contrib, dL_dimage, acc_rows, xcd_mode, block_test, masks);
-  else if (rows)
-    hipLaunchKernelGGL(lr_blend_bwd_rows_kernel<false>, dim3(grid), dim3(256), 0, s, v, g4, state, tiles, plist, capacity,
-                       final_T, n_contrib, dL_dimage, acc_rows, xcd_mode, block_test, masks);
-  else if (use_masks)
-    hipLaunchKernelGGL(lr_blend_bwd_kernel<true>, dim3(grid), dim3(256), 0, s, v, g4, state, tiles, plist, capacity,
-                       final_T, n_contrib, dL_dimage, acc_rows, xcd_mode, masks, nullptr, nullptr);
+  const bool use_masks = a.masks != nullptr && v.mask_form == (rows ? (int)LR_MASK_FORM_ROWS : (int)LR_MASK_FORM_QUAD);
+  // The choice, [!use_masks] each (order of the tables and in them: see lr_launch_blend_fwd).  lograst_backward_abs: the same
+  // four choices as the plain walk, slots 9 and 10 summed too.
+  typedef decltype(&lr_blend_bwd_kernel<true, true>) Quad;
+  typedef decltype(&lr_blend_bwd_rows_kernel<true, true>) Rows;
+  static constexpr Quad aux_kernel[2] = {lr_blend_bwd_kernel<true, true>, lr_blend_bwd_kernel<false, true>};
+  static constexpr Rows abs_rows_kernel[2] = {lr_blend_bwd_rows_kernel<true, true>, lr_blend_bwd_rows_kernel<false, true>};
+  static constexpr Quad abs_quad_kernel[2] = {lr_blend_bwd_kernel<true, false, true>, lr_blend_bwd_kernel<false, false, true>};
+  static constexpr Rows rows_kernel[2] = {lr_blend_bwd_rows_kernel<true>, lr_blend_bwd_rows_kernel<false>};
+  static constexpr Quad quad_kernel[2] = {lr_blend_bwd_kernel<true>, lr_blend_bwd_kernel<false>};
+  const int block_test = lr_knob(LRKNOB_BWD_BLOCK_TEST);
+  const float4* g4 = reinterpret_cast<const float4*>(a.geom);
+  lr_prof_begin(LRK_BLEND_BWD, s);
+  if (rows)
+    hipLaunchKernelGGL((a.abs_sums ? abs_rows_kernel : rows_kernel)[!use_masks], dim3(grid), dim3(256), 0, s, v, g4, a.state, a.tiles,
+                       a.plist, a.capacity, a.final_T, a.n_contrib, a.dL_dimage, a.acc_rows, xcd_mode, block_test, a.masks);
   else
-    hipLaunchKernelGGL(lr_blend_bwd_kernel<false>, dim3(grid), dim3(256), 0, s, v, g4, state, tiles, plist, capacity,
-                       final_T, n_contrib, dL_dimage, acc_rows, xcd_mode, masks, nullptr, nullptr);
+    hipLaunchKernelGGL((aux ? aux_kernel : a.abs_sums ? abs_quad_kernel : quad_kernel)[!use_masks], dim3(grid), dim3(256), 0, s, v, g4,
+                       a.state, a.tiles, a.plist, a.capacity, a.final_T, a.n_contrib, a.dL_dimage, a.acc_rows, xcd_mode, a.masks,
+                       a.aux_colors, aux ? a.dL_daux : nullptr);
   lr_prof_end(LRK_BLEND_BWD, s);
 }

@@ -36,28 +36,39 @@ void lr_launch_sort_rest(uint32_t* state, uint32_t tiles, uint64_t* keys, uint32
 void lr_launch_ordered_lengths(const uint32_t* state, uint32_t tiles, uint32_t* out, hipStream_t s);
 
 // blend.hip
-void lr_launch_blend_fwd(const LrView& v, const void* geom, const uint32_t* state, uint32_t tiles,
-                         const uint32_t* plist, uint32_t capacity, float* image, float* final_T, int* n_contrib,
-                         int* pid, float* pwp, float* pw, float* zero_conic, int big_input, int lazy, uint64_t* masks,
-                         hipStream_t s, const float* aux_colors = nullptr, float* aux_image = nullptr);   // aux: quadrant form, whatever the view says
+// The launchers' arguments as records: a call site names every field it sets, and the ones it leaves out are NULL / 0 = off.
+struct LrBlendFwdArgs {
+  const void* geom; const uint32_t* state; uint32_t tiles; const uint32_t* plist; uint32_t capacity;
+  float *image, *final_T; int *n_contrib, *pid; float *pwp, *pw;
+  float* zero_conic;            // the accumulator rows the kernel clears as it meets them, or NULL
+  int big_input, lazy; uint64_t* masks;
+  const float* aux_colors; float* aux_image;   // aux: quadrant form, whatever the view says
+};
+void lr_launch_blend_fwd(const LrView& v, const LrBlendFwdArgs& a, hipStream_t s);
 int lr_blend_fwd_form(const LrView& v);
 int lr_blend_bwd_form(const LrView& v, int big_input);
-void lr_launch_blend_bwd(const LrView& v, const void* geom, const uint32_t* state, uint32_t tiles,
-                         const uint32_t* plist, uint32_t capacity, const float* final_T, const int* n_contrib,
-                         const float* dL_dimage, float* acc_rows, int big_input, const uint64_t* masks, hipStream_t s,
-                         const float* aux_colors = nullptr, const float* dL_daux = nullptr,   // aux: quadrant form; either gradient may be NULL
-                         bool abs_sums = false);   // abs_sums (no aux): |per-pixel terms of dL/dmean x, y| summed into the rows' slots 9, 10
+struct LrBlendBwdArgs {
+  const void* geom; const uint32_t* state; uint32_t tiles; const uint32_t* plist; uint32_t capacity;
+  const float* final_T; const int* n_contrib; const float* dL_dimage; float* acc_rows; int big_input; const uint64_t* masks;
+  const float *aux_colors, *dL_daux;   // aux: quadrant form; either gradient may be NULL
+  bool abs_sums;                       // (no aux): |per-pixel terms of dL/dmean x, y| summed into the rows' slots 9, 10
+};
+void lr_launch_blend_bwd(const LrView& v, const LrBlendBwdArgs& a, hipStream_t s);
 
 // project_bwd.hip
-// rows != NULL: the 64-byte accumulator rows of lograst_backward (+ its three separate outputs); NULL: g_mean2d / g_conic.
-// big_input: the caller's large-input predicate (n >= LOGRAST_HELPER_MIN_N); only looked at when rows != NULL.
-void lr_launch_project_bwd(const LrView& v, int N, const float* means, const float* scales, const float* rots,
-                           const int* radii, const float* g_mean2d, const float* g_conic, const float* rows,
-                           float* o_mean2d, float* o_opac, float* o_col, const float* pw,
-                           float* g_means3d, float* g_scales, float* g_rots, bool accumulate, bool sink_rows,
-                           bool big_input, hipStream_t s, float* o_aux = nullptr,
-                           float* cam_partials = nullptr, float* cam_dv = nullptr, float* cam_dp = nullptr,   // o_aux: dL/daux_colors [N, 3] out of the rows' slots 9..11 (fresh gradients, no cov3d)
-                           float* o_abs = nullptr);   // o_abs: dl_dmeans2d_abs [N, 3] out of the rows' slots 9, 10 (fresh gradients, no cov3d, no o_aux, no camera sums)
+struct LrProjectBwdArgs {
+  int N; const float *means, *scales, *rots; const int* radii;
+  const float *g_mean2d, *g_conic;   // lograst_project_backward's inputs, or
+  const float* rows;                 // the 64-byte accumulator rows of lograst_backward (+ its three separate outputs)
+  float *o_mean2d, *o_opac, *o_col; const float* pw;
+  float *g_means3d, *g_scales, *g_rots;
+  bool accumulate, sink_rows;
+  bool big_input;                    // the caller's large-input predicate (n >= LOGRAST_HELPER_MIN_N); only looked at with rows
+  float* o_aux;                      // dL/daux_colors [N, 3] out of the rows' slots 9..11 (fresh gradients, no cov3d)
+  float *cam_partials, *cam_dv, *cam_dp;   // the camera sums (below; fresh gradients, no cov3d, no o_aux)
+  float* o_abs;                      // dl_dmeans2d_abs [N, 3] out of the rows' slots 9, 10 (fresh gradients, no cov3d, no o_aux, no camera sums)
+};
+void lr_launch_project_bwd(const LrView& v, const LrProjectBwdArgs& a, hipStream_t s);
 
 // cam_partials (+ cam_dv, cam_dp [4, 4]): the camera sums -- one row of 24 partials per workgroup of the chain rule, then
 // dL/dviewmatrix / dL/dprojmatrix by a finishing kernel; lr_camera_scratch_bytes(N) bytes (fresh gradients, no cov3d, no o_aux)

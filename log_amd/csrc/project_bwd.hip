@@ -711,49 +711,14 @@ static void lr_launch_camera_finish(float* partials, int N, float* dV, float* dP
   if (B > 1) hipLaunchKernelGGL(lr_camera_total_kernel, dim3(1), dim3(64), 0, s, stage, B, dV, dP);
 }
 
-void lr_launch_project_bwd(const LrView& v, int N, const float* means, const float* scales, const float* rots,
-                           const int* radii, const float* g_mean2d, const float* g_conic, const float* rows,
-                           float* o_mean2d, float* o_opac, float* o_col, const float* pw,
-                           float* g_means3d, float* g_scales, float* g_rots, bool accumulate, bool sink_rows,
-                           bool big_input, hipStream_t s, float* o_aux, float* cam_partials, float* cam_dv, float* cam_dp,
-                           float* o_abs) {
+void lr_launch_project_bwd(const LrView& v, const LrProjectBwdArgs& a, hipStream_t s) {
+  const int N = a.N;
   if (N <= 0) return;
-  lr_prof_begin(LRK_PROJECT_BWD, s);
-  const dim3 grid((N + LR_PBWD_ROWS - 1) / LR_PBWD_ROWS), block(256);
-  const float4* rows4 = reinterpret_cast<const float4*>(rows);
-  if (cam_partials) {   // (the *_camera entry points checked: fresh gradients, no cov3d_precomp, whole image, no aux; cleared inside)
-#define LR_PBWD_CAM(T, O) hipLaunchKernelGGL((lr_project_bwd_kernel<false, T, false, O, false, 3, false, true>), grid, block, 0, s, \
-                                             v, N, means, scales, rots, radii, g_mean2d, g_conic, rows4, o_mean2d, o_opac,      \
-                                             o_col, pw, g_means3d, g_scales, g_rots, 1, nullptr, cam_partials)
-    if (rows) { if (pw) LR_PBWD_CAM(true, true); else LR_PBWD_CAM(false, true); }
-    else { if (pw) LR_PBWD_CAM(true, false); else LR_PBWD_CAM(false, false); }
-#undef LR_PBWD_CAM
-    lr_launch_camera_finish(cam_partials, N, cam_dv, cam_dp, s);
-    lr_prof_end(LRK_PROJECT_BWD, s);
-    return;
-  }
-  if (o_aux) {   // (lograst_backward_aux checked: rows, fresh gradients, no cov3d_precomp; every output cleared inside)
-    if (pw)
-      hipLaunchKernelGGL((lr_project_bwd_kernel<false, true, false, true, false, 1, true>), grid, block, 0, s, v, N, means, scales,
-                         rots, radii, g_mean2d, g_conic, rows4, o_mean2d, o_opac, o_col, pw, g_means3d, g_scales, g_rots, 1, o_aux);
-    else
-      hipLaunchKernelGGL((lr_project_bwd_kernel<false, false, false, true, false, 1, true>), grid, block, 0, s, v, N, means, scales,
-                         rots, radii, g_mean2d, g_conic, rows4, o_mean2d, o_opac, o_col, pw, g_means3d, g_scales, g_rots, 1, o_aux);
-    lr_prof_end(LRK_PROJECT_BWD, s);
-    return;
-  }
-  if (o_abs) {   // (lograst_backward_abs checked: rows, fresh gradients, no cov3d_precomp, whole image; every output cleared inside)
-    if (pw)
-      hipLaunchKernelGGL((lr_project_bwd_kernel<false, true, false, true, false, 1, false, false, true>), grid, block, 0, s, v, N,
-                         means, scales, rots, radii, g_mean2d, g_conic, rows4, o_mean2d, o_opac, o_col, pw, g_means3d, g_scales,
-                         g_rots, 1, nullptr, nullptr, o_abs);
-    else
-      hipLaunchKernelGGL((lr_project_bwd_kernel<false, false, false, true, false, 1, false, false, true>), grid, block, 0, s, v, N,
-                         means, scales, rots, radii, g_mean2d, g_conic, rows4, o_mean2d, o_opac, o_col, pw, g_means3d, g_scales,
-                         g_rots, 1, nullptr, nullptr, o_abs);
-    lr_prof_end(LRK_PROJECT_BWD, s);
-    return;
-  }
+  // What the call is, in one place.  The extras' entry points checked: fresh gradients, no cov3d_precomp, whole image, one
+  // extra at a time (aux and abs: rows), so every output is cleared inside for them.
+  const bool touched = a.pw != nullptr, aos = a.rows != nullptr, cov = v.cov3d != nullptr;
+  const bool cam = a.cam_partials != nullptr, auxo = a.o_aux != nullptr, abso = a.o_abs != nullptr;
+  const bool band_view = v.ty0 > 0 || v.ty1 < v.gy;
   // dL/dmeans2D is a per-view output, defined for every row.  When the other gradients are running sums (nothing else is
   // written for a dead row) and the input is large (clear_inside == 0), the kernel's workgroups neither clear their slice
   // between their flag reads and their barrier nor overwrite live rows with 12-byte stores: the slice is staged in LDS and
@@ -762,7 +727,7 @@ void lr_launch_project_bwd(const LrView& v, int N, const float* means, const flo
   // stores; a band view of 100 M rows 1040 -> 730 us against clearing inside, with the radii read gone).  With fresh
   // gradients (every output zeroed for every dead row: 68 bytes per row) a separate zero pass LOSES (30 M: 763 -> 858 us):
   // cleared inside.
-  const int clear_inside = (rows && (accumulate || sink_rows) && big_input) ? 0 : 1;
+  const int clear_inside = (aos && (a.accumulate || a.sink_rows) && a.big_input) ? 0 : 1;
   // Large inputs, running sums, the forward's point_weight at hand, no cov3d_precomp: the live rows through a compact list
   // (see lr_pbwd_compact_kernel) -- on BAND views, where a per cent of the rows is live and the one-kernel form is nearly
   // all flag pass (100 M rows, band 3 of 8: 929 -> 490 us).  On full views the chain rule is bound by its scattered lines
@@ -770,45 +735,48 @@ void lr_launch_project_bwd(const LrView& v, int N, const float* means, const flo
   // 7.5 % (trained-like) 451 / 481, 14 % (opacity = rand) 690 / 610 -- not worth a second form there.
   // LOGRAST_PBWD_LIST: 0 never, 1 band views (default), 2 always.
   const int list_knob = lr_knob(LRKNOB_PBWD_LIST);
-  const bool band_view = v.ty0 > 0 || v.ty1 < v.gy;
-  if ((list_knob == 2 || (list_knob == 1 && band_view)) && !clear_inside && pw && !v.cov3d && N >= 8) {
-    lr_launch_zero_floats(o_mean2d, 3 * (size_t)N, s);
+  const bool list = (list_knob == 2 || (list_knob == 1 && band_view)) && !clear_inside && touched && !cov && N >= 8;
+  // The one-kernel form's choice; template arguments <ACCUMULATE, TOUCHED, COV, AOS, SINKROWS, WAVES, AUXO, CAM, ABSO>.  (The
+  // tables name the kernels in the order in which they have always been instantiated, "true" first: that is the order of the
+  // device code, which tools/device_asm_digest.py holds still.  So an entry's index is [!flag].)
+#define LR_K(...) lr_project_bwd_kernel<__VA_ARGS__>
+  typedef decltype(&LR_K(false, true, false, true, false, 3, false, true)) Kernel;
+  static constexpr Kernel cam_kernel[2][2] = {   // [!aos][!touched]
+      {LR_K(false, true, false, true, false, 3, false, true), LR_K(false, false, false, true, false, 3, false, true)},
+      {LR_K(false, true, false, false, false, 3, false, true), LR_K(false, false, false, false, false, 3, false, true)}};
+  static constexpr Kernel aux_kernel[2] = {LR_K(false, true, false, true, false, 1, true),   // [!touched]
+                                           LR_K(false, false, false, true, false, 1, true)};
+  static constexpr Kernel abs_kernel[2] = {LR_K(false, true, false, true, false, 1, false, false, true),   // [!touched]
+                                           LR_K(false, false, false, true, false, 1, false, false, true)};
+  static constexpr decltype(&lr_pbwd_list_kernel<true, true>) list_kernel[2] = {lr_pbwd_list_kernel<true, true>,   // [!sink_rows]
+                                                                                   lr_pbwd_list_kernel<true, false>};
+  static constexpr Kernel sink_kernel[3] = {LR_K(true, true, false, true, true, 4),   // [0] touched, band view: the four-wave form (WAVES, above)
+                                            LR_K(true, true, false, true, true),      // [1] touched, whole view
+                                            LR_K(true, false, false, true, true)};    // [2] no point_weight
+  static constexpr Kernel plain_kernel[2][2][2][2] = {   // [!accumulate][!touched][!cov][!aos]
+      {{{LR_K(true, true, true, true), LR_K(true, true, true, false)}, {LR_K(true, true, false, true), LR_K(true, true, false, false)}},
+       {{LR_K(true, false, true, true), LR_K(true, false, true, false)}, {LR_K(true, false, false, true), LR_K(true, false, false, false)}}},
+      {{{LR_K(false, true, true, true), LR_K(false, true, true, false)}, {LR_K(false, true, false, true), LR_K(false, true, false, false)}},
+       {{LR_K(false, false, true, true), LR_K(false, false, true, false)}, {LR_K(false, false, false, true), LR_K(false, false, false, false)}}}};
+#undef LR_K
+  const Kernel kernel = cam ? cam_kernel[!aos][!touched] : auxo ? aux_kernel[!touched] : abso ? abs_kernel[!touched]
+                        : a.sink_rows ? sink_kernel[!touched ? 2 : band_view ? 0 : 1]   // (lograst_backward checked: rows != NULL, no cov3d)
+                                      : plain_kernel[!a.accumulate][!touched][!cov][!aos];
+  const dim3 grid((N + LR_PBWD_ROWS - 1) / LR_PBWD_ROWS), block(256);
+  const float4* rows4 = reinterpret_cast<const float4*>(a.rows);
+  lr_prof_begin(LRK_PROJECT_BWD, s);
+  if (list) {
+    lr_launch_zero_floats(a.o_mean2d, 3 * (size_t)N, s);
     float4* rows_w = const_cast<float4*>(rows4);   // (the accumulator rows are the caller's scratch: slots 12-15 are this path's)
     lr_launch_zero_words(reinterpret_cast<uint32_t*>(rows_w + 3), 4, s);
-    hipLaunchKernelGGL(lr_pbwd_compact_kernel, dim3((N + LR_PBWD_CHUNK - 1) / LR_PBWD_CHUNK), dim3(1024), 0, s, pw, N, rows_w);
-    const dim3 lgrid(2048);
-    if (sink_rows)
-      hipLaunchKernelGGL((lr_pbwd_list_kernel<true, true>), lgrid, block, 0, s, v, N, means, scales, rots, rows_w, o_mean2d,
-                         o_opac, o_col, g_means3d, g_scales, g_rots);
-    else
-      hipLaunchKernelGGL((lr_pbwd_list_kernel<true, false>), lgrid, block, 0, s, v, N, means, scales, rots, rows_w, o_mean2d,
-                         o_opac, o_col, g_means3d, g_scales, g_rots);
-    lr_prof_end(LRK_PROJECT_BWD, s);
-    return;
+    hipLaunchKernelGGL(lr_pbwd_compact_kernel, dim3((N + LR_PBWD_CHUNK - 1) / LR_PBWD_CHUNK), dim3(1024), 0, s, a.pw, N, rows_w);
+    hipLaunchKernelGGL(list_kernel[!a.sink_rows], dim3(2048), block, 0, s, v, N, a.means, a.scales, a.rots, rows_w, a.o_mean2d,
+                       a.o_opac, a.o_col, a.g_means3d, a.g_scales, a.g_rots);
+  } else {
+    hipLaunchKernelGGL(kernel, grid, block, 0, s, v, N, a.means, a.scales, a.rots, a.radii, a.g_mean2d, a.g_conic, rows4,
+                       a.o_mean2d, a.o_opac, a.o_col, a.pw, a.g_means3d, a.g_scales, a.g_rots, clear_inside, a.o_aux,
+                       a.cam_partials, a.o_abs);
+    if (cam) lr_launch_camera_finish(a.cam_partials, N, a.cam_dv, a.cam_dp, s);
   }
-  if (sink_rows) {   // (lograst_backward checked: rows != NULL, no cov3d)
-    const bool band = v.ty0 > 0 || v.ty1 < v.gy;
-    if (pw && band)
-      hipLaunchKernelGGL((lr_project_bwd_kernel<true, true, false, true, true, 4>), grid, block, 0, s, v, N, means, scales, rots,
-                         radii, g_mean2d, g_conic, rows4, o_mean2d, o_opac, o_col, pw, g_means3d, g_scales, g_rots, clear_inside, nullptr);
-    else if (pw)
-      hipLaunchKernelGGL((lr_project_bwd_kernel<true, true, false, true, true>), grid, block, 0, s, v, N, means, scales, rots,
-                         radii, g_mean2d, g_conic, rows4, o_mean2d, o_opac, o_col, pw, g_means3d, g_scales, g_rots, clear_inside, nullptr);
-    else
-      hipLaunchKernelGGL((lr_project_bwd_kernel<true, false, false, true, true>), grid, block, 0, s, v, N, means, scales, rots,
-                         radii, g_mean2d, g_conic, rows4, o_mean2d, o_opac, o_col, pw, g_means3d, g_scales, g_rots, clear_inside, nullptr);
-    lr_prof_end(LRK_PROJECT_BWD, s);
-    return;
-  }
-#define LR_PBWD2(A, T, C, O) hipLaunchKernelGGL((lr_project_bwd_kernel<A, T, C, O>), grid, block, 0, s, v, N, means, scales, \
-                                                rots, radii, g_mean2d, g_conic, rows4, o_mean2d, o_opac, o_col, pw,       \
-                                                g_means3d, g_scales, g_rots, clear_inside, nullptr)
-#define LR_PBWD(A, T, C) do { if (rows) LR_PBWD2(A, T, C, true); else LR_PBWD2(A, T, C, false); } while (0)
-#define LR_PBWD_C(A, T) do { if (v.cov3d) LR_PBWD(A, T, true); else LR_PBWD(A, T, false); } while (0)
-  if (accumulate) { if (pw) LR_PBWD_C(true, true); else LR_PBWD_C(true, false); }
-  else { if (pw) LR_PBWD_C(false, true); else LR_PBWD_C(false, false); }
-#undef LR_PBWD_C
-#undef LR_PBWD
-#undef LR_PBWD2
   lr_prof_end(LRK_PROJECT_BWD, s);
 }

@@ -19,6 +19,7 @@ All arithmetic runs in hand-written HIP kernels (log_amd/csrc) through the C ABI
 """
 import contextlib
 import ctypes
+import functools
 import math
 import threading
 from typing import NamedTuple
@@ -552,32 +553,33 @@ class abs_grad:
         return False
 
 
-def _refuse_camera_with(sink=False, cov3D=False, band=False, aux=False):
-    """The one list of what camera gradients (dL/dviewmatrix, dL/dprojmatrix) cannot be combined with: each is a follow-up,
-    not a silent zero."""
-    if sink:
-        raise ValueError("camera gradients cannot be combined with accumulate_grads_into (they come with fresh gradients)")
-    if cov3D:
-        raise ValueError("camera gradients cannot be combined with cov3D_precomp (pass scales / rotations)")
-    if band:
-        raise ValueError("camera gradients cannot be combined with a tile_rows band (whole images only)")
-    if aux:
-        raise ValueError("camera gradients cannot be combined with aux_colors (no camera form of the aux backward)")
+# What each extra of the backward -- aux channels, camera gradients (dL/dviewmatrix, dL/dprojmatrix), abs-grad (the absolute
+# screen-space sums, ``means2D.absgrad``) -- cannot be combined with, in the order in which a call with several of them hears
+# about it: each is a follow-up, not a silent zero.
+_EXTRA_REFUSES = {
+    "aux": (("cov3D", "aux_colors cannot be combined with cov3D_precomp (pass scales / rotations)"),
+            ("band", "aux_colors cannot be combined with a tile_rows band (whole images only)"),
+            ("sink", "aux_colors cannot be combined with accumulate_grads_into (its backward returns fresh gradients)")),
+    "camera": (("sink", "camera gradients cannot be combined with accumulate_grads_into (they come with fresh gradients)"),
+               ("cov3D", "camera gradients cannot be combined with cov3D_precomp (pass scales / rotations)"),
+               ("band", "camera gradients cannot be combined with a tile_rows band (whole images only)"),
+               ("aux", "camera gradients cannot be combined with aux_colors (no camera form of the aux backward)")),
+    "abs": (("aux", "abs_grad cannot be combined with aux_colors (no abs form of the aux backward)"),
+            ("camera", "abs_grad cannot be combined with camera gradients (a viewmatrix / projmatrix that requires grad)"),
+            ("cov3D", "abs_grad cannot be combined with cov3D_precomp (pass scales / rotations)"),
+            ("band", "abs_grad cannot be combined with a tile_rows band (whole images only)"),
+            ("sink", "abs_grad cannot be combined with accumulate_grads_into (it comes with fresh gradients)")),
+}
 
 
-def _refuse_abs_grad_with(sink=False, cov3D=False, band=False, aux=False, camera=False):
-    """The one list of what abs-grad (the absolute screen-space sums, ``means2D.absgrad``) cannot be combined with."""
-    if aux:
-        raise ValueError("abs_grad cannot be combined with aux_colors (no abs form of the aux backward)")
-    if camera:
-        raise ValueError("abs_grad cannot be combined with camera gradients (a viewmatrix / projmatrix that requires grad)")
-    if cov3D:
-        raise ValueError("abs_grad cannot be combined with cov3D_precomp (pass scales / rotations)")
-    if band:
-        raise ValueError("abs_grad cannot be combined with a tile_rows band (whole images only)")
-    if sink:
-        raise ValueError("abs_grad cannot be combined with accumulate_grads_into (it comes with fresh gradients)")
+def _refuse_extra_with(extra, **present):
+    """Raise for the first entry of _EXTRA_REFUSES[extra] that the call has (sink=, cov3D=, band=, aux=, camera=: booleans)."""
+    for what, message in _EXTRA_REFUSES[extra]:
+        if present.get(what):
+            raise ValueError(message)
 
+
+_refuse_abs_grad_with = functools.partial(_refuse_extra_with, "abs")   # (the name tests/test_abs_grad_cpu.py reads the list by)
 
 class HipBackend:
     """Drives the kernels.  All buffers come from torch's caching allocator."""
@@ -846,11 +848,11 @@ class HipBackend:
         L = self.require(device)
         N = means3D.shape[0]
         aux = _aux is not None
+        has = dict(sink=sink is not None, cov3D=cov3D is not None, band=tuple(saved["tile_rows"]) != (0, 0))
         if _abs:
-            _refuse_abs_grad_with(sink=sink is not None, cov3D=cov3D is not None, band=tuple(saved["tile_rows"]) != (0, 0),
-                                  aux=aux or saved.get("aux_colors") is not None, camera=camera)
+            _refuse_extra_with("abs", aux=aux or saved.get("aux_colors") is not None, camera=camera, **has)
         if camera:
-            _refuse_camera_with(sink=sink is not None, cov3D=cov3D is not None, band=tuple(saved["tile_rows"]) != (0, 0), aux=aux)
+            _refuse_extra_with("camera", aux=aux, **has)
         if aux and (sink is not None or cov3D is not None):
             raise ValueError("backward_aux writes fresh gradients: no gradient sink, no cov3D_precomp")
         if not aux and saved.get("aux_colors") is not None:
@@ -899,55 +901,49 @@ class HipBackend:
             g_opac, g_colors = sink["opacities"], sink["colors"]
             g_means3D, g_scales, g_rot = sink["means3D"], sink["scales"], sink["rotations"]
             flags |= 2
-        if aux:
-            with torch.cuda.device(device):
-                _lib.check(L.lograst_backward_aux(ctypes.byref(view), N, _ptr(means3D), _ptr(scales), _ptr(rotations),
-                                                  _ptr(saved["radii"]), _ptr(saved["geom"]), _ptr(saved["state"]),
-                                                  _ptr(saved["plist"]), _ptr(saved["final_T"]), _ptr(saved["n_contrib"]),
-                                                  _ptr(saved["aux_colors"]), _ptr(grad_image), _ptr(grad_aux), _ptr(g_means2D),
-                                                  _ptr(g_conic), need, _ptr(g_opac), _ptr(g_colors), _ptr(g["aux"]),
-                                                  _ptr(g_means3D), _ptr(g_scales), _ptr(g_rot), _ptr(pw), flags,
-                                                  _stream_ptr(device)))
-            del keep
-            # test introspection only: dL/dconic per image, [N, 4] (A, B, C, 0) each -- slots 2-4 and 12-14 of the rows
-            self.last_conic_grad = None
-            self.last_aux_conic_grads = None
-            if _debug_keep and N:
-                rows = acc.view(N, need)
-                self.last_aux_conic_grads = tuple(torch.cat([rows[:, a:a + 3], acc.new_zeros(N, 1)], dim=1) for a in (2, 12))
-            return g_means3D, g_means2D, g_colors, g_opac, g_scales, g_rot, g["aux"]
-        args = (ctypes.byref(view), N, _ptr(means3D), _ptr(scales), _ptr(rotations), _ptr(saved["radii"]), _ptr(saved["geom"]),
+        # lograst_backward's arguments up to `flags`; each other entry point has its own behind them (include/lograst.h), but
+        # lograst_backward_aux, whose four sit among them
+        args = [ctypes.byref(view), N, _ptr(means3D), _ptr(scales), _ptr(rotations), _ptr(saved["radii"]), _ptr(saved["geom"]),
                 _ptr(saved["state"]), _ptr(saved["plist"]), _ptr(saved["final_T"]), _ptr(saved["n_contrib"]), _ptr(grad_image),
                 _ptr(g_means2D), _ptr(g_conic), _ptr(g_opac), _ptr(g_colors), _ptr(g_means3D), _ptr(g_scales), _ptr(g_rot),
-                _ptr(pw), flags)
-        g_cam = ()
+                _ptr(pw), flags]
+        entry, more, scratch = L.lograst_backward, (), None
         with torch.cuda.device(device):
-            if _abs:
+            if aux:
+                entry, more = L.lograst_backward_aux, (g["aux"],)
+                for at, value in ((11, _ptr(saved["aux_colors"])), (13, _ptr(grad_aux)), (16, need), (19, _ptr(g["aux"]))):
+                    args.insert(at, value)
+            elif _abs:
                 abs_buf = torch.empty(max(N, 1), 3, **f32)         # (never a NULL pointer: the entry point refuses one)
-                g_cam = (abs_buf[:N],)
-                _lib.check(L.lograst_backward_abs(*args, ctypes.c_void_p(abs_buf.data_ptr()), _stream_ptr(device)))
+                entry, more = L.lograst_backward_abs, (abs_buf[:N],)
+                args.append(ctypes.c_void_p(abs_buf.data_ptr()))
             elif camera:
-                g_cam, scratch = self._camera_outputs(L, N, device)
-                _lib.check(L.lograst_backward_camera(*args, _ptr(g_cam[0]), _ptr(g_cam[1]), _ptr(scratch), 4 * scratch.numel(),
-                                                     _stream_ptr(device)))
-            else:
-                _lib.check(L.lograst_backward(*args, _stream_ptr(device)))
-        del keep
-        # test introspection only: dL/dconic [N, 4] (A, B, C, 0) out of the accumulator rows
-        self.last_conic_grad = (torch.cat([acc.view(N, need)[:, 2:5], acc.new_zeros(N, 1)], dim=1)
-                                if _debug_keep and N else (acc.new_zeros(0, 4) if _debug_keep else None))
+                entry = L.lograst_backward_camera
+                more, tail, scratch = self._camera_outputs(L, N, device)
+                args.extend(tail)
+            _lib.check(entry(*args, _stream_ptr(device)))
+        del keep, scratch
+        # test introspection only: dL/dconic [N, 4] (A, B, C, 0) out of the accumulator rows -- slots 2-4, and with aux channels
+        # one per image: slots 2-4 and 12-14
+        conic = lambda at: torch.cat([acc.view(N, need)[:, at:at + 3], acc.new_zeros(N, 1)], dim=1)
+        if aux:
+            self.last_conic_grad = None
+            self.last_aux_conic_grads = (conic(2), conic(12)) if _debug_keep and N else None
+        else:
+            self.last_conic_grad = (conic(2) if N else acc.new_zeros(0, 4)) if _debug_keep else None
         if sink is not None:
             return None, g_means2D, None, None, None, None
         if cov3D is not None:
             return g_means3D, g_means2D, g_colors, g_opac, g_cov, None
-        return (g_means3D, g_means2D, g_colors, g_opac, g_scales, g_rot) + g_cam
+        return (g_means3D, g_means2D, g_colors, g_opac, g_scales, g_rot) + more
 
     @staticmethod
     def _camera_outputs(L, N, device):
-        """((dL/dviewmatrix, dL/dprojmatrix), the chain rule's partials scratch) for a *_camera call."""
+        """For a *_camera call: (dL/dviewmatrix, dL/dprojmatrix), the four arguments the entry point takes in front of the
+        stream, and the chain rule's partials scratch among them (to be held until the call is made)."""
         g = torch.empty(2, 4, 4, dtype=torch.float32, device=device)
         scratch = torch.empty(int(L.lograst_camera_scratch_bytes(N)) // 4, dtype=torch.float32, device=device)
-        return (g[0], g[1]), scratch
+        return (g[0], g[1]), (_ptr(g[0]), _ptr(g[1]), _ptr(scratch), 4 * scratch.numel()), scratch
 
     def sh_forward(self, means3D, campos, shs, degree):
         """Native `shs=` path (lograst_sh_forward): colours[N,3] and the clamp mask u8[N,3]."""
@@ -984,22 +980,21 @@ class HipBackend:
         L = self.require(device)
         N = means3D.shape[0]
         if camera:
-            _refuse_camera_with(cov3D=cov3D is not None, band=_tile_rows.get() != (0, 0))
+            _refuse_extra_with("camera", cov3D=cov3D is not None, band=_tile_rows.get() != (0, 0))
         g_cov = torch.empty(N, 6, dtype=torch.float32, device=device) if cov3D is not None else None
         view, keep = self.make_view(rs, flavour, use_filter, device, cov3D=cov3D, g_cov3D=g_cov)
         f32 = dict(dtype=torch.float32, device=device)
         g_means3D, g_scales, g_rot = torch.empty(N, 3, **f32), torch.empty(N, 3, **f32), torch.empty(N, 4, **f32)
-        args = (ctypes.byref(view), N, _ptr(means3D), _ptr(scales), _ptr(rotations), _ptr(radii), _ptr(g_means2D), _ptr(g_conic),
-                _ptr(g_means3D), _ptr(g_scales), _ptr(g_rot))
-        g_cam = ()
+        args = [ctypes.byref(view), N, _ptr(means3D), _ptr(scales), _ptr(rotations), _ptr(radii), _ptr(g_means2D), _ptr(g_conic),
+                _ptr(g_means3D), _ptr(g_scales), _ptr(g_rot)]
+        entry, g_cam, scratch = L.lograst_project_backward, (), None
         with torch.cuda.device(device):
             if camera:
-                g_cam, scratch = self._camera_outputs(L, N, device)
-                _lib.check(L.lograst_project_backward_camera(*args, _ptr(g_cam[0]), _ptr(g_cam[1]), _ptr(scratch),
-                                                             4 * scratch.numel(), _stream_ptr(device)))
-            else:
-                _lib.check(L.lograst_project_backward(*args, _stream_ptr(device)))
-        del keep
+                entry = L.lograst_project_backward_camera
+                g_cam, tail, scratch = self._camera_outputs(L, N, device)
+                args.extend(tail)
+            _lib.check(entry(*args, _stream_ptr(device)))
+        del keep, scratch
         if cov3D is not None:
             return g_means3D, g_cov, None
         return (g_means3D, g_scales, g_rot) + g_cam
@@ -1415,15 +1410,15 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.abs_grad = bool(camera) and camera[-1] is _ABS_GRAD
         if ctx.abs_grad:
             camera = camera[:-1]
-            _refuse_abs_grad_with(sink=_grad_sink is not None, cov3D=cov3D is not None, band=_tile_rows.get() != (0, 0),
-                                  aux=aux_colors is not None, camera=bool(camera))
+            _refuse_extra_with("abs", sink=_grad_sink is not None, cov3D=cov3D is not None, band=_tile_rows.get() != (0, 0),
+                               aux=aux_colors is not None, camera=bool(camera))
             if not hasattr(_backend, "backward_abs"):
                 raise _lib.LograstError("this backend has no backward_abs: abs_grad is not available")
             ctx.abs_target = means2D      # (the caller's object: the backward hangs .absgrad on it)
         ctx.camera = len(camera) == 2
         if ctx.camera:
-            _refuse_camera_with(sink=_grad_sink is not None, cov3D=cov3D is not None, band=_tile_rows.get() != (0, 0),
-                                aux=aux_colors is not None)
+            _refuse_extra_with("camera", sink=_grad_sink is not None, cov3D=cov3D is not None, band=_tile_rows.get() != (0, 0),
+                               aux=aux_colors is not None)
             if not hasattr(_backend, "backward_camera"):
                 raise _lib.LograstError("this backend has no backward_camera: camera gradients (viewmatrix / projmatrix with "
                                         "requires_grad) are not available")
@@ -1438,12 +1433,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         m = means3D.detach().to(torch.float32).contiguous()
         ax = None
         if aux_colors is not None:
-            if cov3D is not None:
-                raise ValueError("aux_colors cannot be combined with cov3D_precomp (pass scales / rotations)")
-            if _tile_rows.get() != (0, 0):
-                raise ValueError("aux_colors cannot be combined with a tile_rows band (whole images only)")
-            if _grad_sink is not None:
-                raise ValueError("aux_colors cannot be combined with accumulate_grads_into (its backward returns fresh gradients)")
+            _refuse_extra_with("aux", cov3D=cov3D is not None, band=_tile_rows.get() != (0, 0), sink=_grad_sink is not None)
             if not (hasattr(_backend, "forward_aux") and hasattr(_backend, "backward_aux")):
                 raise _lib.LograstError("this backend has no forward_aux / backward_aux: aux_colors is not available")
             ax = aux_colors.detach().to(torch.float32).contiguous()
@@ -1545,12 +1535,9 @@ class _RasterizeGaussians(torch.autograd.Function):
         # tensor per input (with native SH: the colour gradient into a scratch, from there into the running dL/dshs)
         n = m.shape[0]
         sink = _grad_sink if ctx.cov is None else None
-        if ctx.camera:
-            _refuse_camera_with(sink=sink is not None)
-        if ctx.aux and sink is not None:
-            raise ValueError("aux_colors cannot be combined with accumulate_grads_into (its backward returns fresh gradients)")
-        if ctx.abs_grad:
-            _refuse_abs_grad_with(sink=sink is not None)
+        for extra, on in (("camera", ctx.camera), ("aux", ctx.aux), ("abs", ctx.abs_grad)):
+            if on:
+                _refuse_extra_with(extra, sink=sink is not None)
         if sink is None and ctx.leaves is not None and (   # (leaves: None under cov3D_precomp or native SH)
                 _inplace_leaf_grads or all(getattr(t, _INPLACE_TAG, False) for t in ctx.leaves if t is not None)):
             sink = _leaf_grad_sink(ctx.leaves, m.device)
@@ -1572,17 +1559,26 @@ class _RasterizeGaussians(torch.autograd.Function):
                 sink = dict(sink, colors=torch.zeros(n, 3, dtype=torch.float32, device=m.device))
         else:
             sink = None   # (a sink without an "shs" entry under native SH: the gradients go back to autograd)
-        g_aux = None
+        # One call: the backend method of the extra this forward came with (camera: the chain-rule launch sums the camera
+        # terms too; abs-grad: the plain gradients and the absolute sums; aux: both images through one reverse walk and one
+        # chain rule, means2D gets the one summed gradient), else backward() -- the six gradients, then the extra's own.
+        base = (ctx.rs, ctx.flavour, ctx.use_filter, m, *((s, r) if ctx.cov is None else (None, None)), ctx.saved, grad_image)
+        if ctx.camera:
+            out = _backend.backward_camera(*base)
+        elif ctx.abs_grad:
+            out = _backend.backward_abs(*base)
+        elif ctx.aux:
+            out = _backend.backward_aux(*base, grad_aux)
+        else:
+            out = _backend.backward(*base, sink=sink, cov3D=ctx.cov)
+        (g_m3, g_m2, g_c, g_o, g_s, g_r), more = out[:6], out[6:]
+        g_aux = more[0] if ctx.aux else None
         g_cam = ()
-        if ctx.camera:   # the chain-rule launch sums the camera terms too; one that does not require grad gets None
-            g_m3, g_m2, g_c, g_o, g_s, g_r, g_v, g_p = _backend.backward_camera(ctx.rs, ctx.flavour, ctx.use_filter, m, s, r,
-                                                                                ctx.saved, grad_image)
+        if ctx.camera:   # a matrix that does not require grad gets None
             g_cam = tuple(g.reshape(shape).to(dev) if need else None
-                          for g, need, (shape, dev) in zip((g_v, g_p), ctx.needs_input_grad[13:15], ctx.camera_like))
-        elif ctx.abs_grad:   # the plain backward's gradients, and the absolute sums onto the caller's means2D
-            g_m3, g_m2, g_c, g_o, g_s, g_r, g_abs = _backend.backward_abs(ctx.rs, ctx.flavour, ctx.use_filter, m, s, r, ctx.saved,
-                                                                          grad_image)
-            target, g_abs = ctx.abs_target, g_abs.reshape(m2_shape).to(ctx.abs_target.device)
+                          for g, need, (shape, dev) in zip(more, ctx.needs_input_grad[13:15], ctx.camera_like))
+        elif ctx.abs_grad:   # the absolute sums go onto the caller's means2D
+            target, g_abs = ctx.abs_target, more[0].reshape(m2_shape).to(ctx.abs_target.device)
             with torch.no_grad():
                 old = getattr(target, "absgrad", None)
                 if old is None:
@@ -1590,13 +1586,6 @@ class _RasterizeGaussians(torch.autograd.Function):
                 else:
                     old.add_(g_abs)
             g_cam = (None,)               # (the marker's slot)
-        elif ctx.aux:   # both images through one reverse walk and one chain rule: means2D gets the one summed gradient
-            g_m3, g_m2, g_c, g_o, g_s, g_r, g_aux = _backend.backward_aux(ctx.rs, ctx.flavour, ctx.use_filter, m, s, r, ctx.saved,
-                                                                          grad_image, grad_aux)
-        else:
-            g_m3, g_m2, g_c, g_o, g_s, g_r = _backend.backward(ctx.rs, ctx.flavour, ctx.use_filter, m,
-                                                               *((s, r) if ctx.cov is None else (None, None)), ctx.saved,
-                                                               grad_image, sink=sink, cov3D=ctx.cov)
         g_sh = g_cov = None
         if ctx.cov is not None:   # (the backend's last two results are then (dL/dcov3D, None))
             g_cov, g_s = g_s, None
